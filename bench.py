@@ -2,6 +2,7 @@
 """bench.py — DeepSpeech2 CTC train-step throughput (utterances/sec) on MI355X, BASELINE.json metric.
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run)
+    python bench.py ... --dump-outputs DIR                 (+ what the last timed step computed, as DIR/<name>.npy: dump_outputs)
 
 A "step" = one full train step of the hot path on one synthetic batch already resident in HBM:
 forward, CTC, backward, (RCCL gradient all-reduce,) fused AdamW, loss.item() sync.
@@ -346,6 +347,41 @@ def cpu_baseline(rnn, H, L, C, tin, B, limit_s=300):
         return {"value": None, "unit": "utterances/sec", "cores": 0, "kind": "port", "sample": f"worker exceeded {limit_s}s"}
 
 
+DUMP_MAX_ELEMS = 1 << 16          # --dump-outputs: a larger tensor is written as a fixed, seeded sample of this many elements
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, model, loss_value):
+    """--dump-outputs DIR: what the last timed train step left to a caller of DeepSpeechTrainer.step, one DIR/<name>.npy per array:
+    loss.npy (float64, the step's loss value), param.<name>.npy (the updated weights), grad.<name>.npy (the step's gradient buffer that the
+    fused AdamW read: with N ranks the all-reduced sum) and buffer.<name>.npy (the BatchNorm running statistics), float32.  A tensor of more than DUMP_MAX_ELEMS
+    elements is written flat as the elements at DUMP_MAX_ELEMS sorted positions drawn by a generator seeded with the crc32 of its name:
+    the same positions in every run and every build, so that two builds can be compared array by array."""
+    import zlib
+    import numpy as np
+
+    def sample(name, t):
+        t = t.detach()
+        if t.numel() <= DUMP_MAX_ELEMS:
+            return t.float().cpu().numpy()
+        idx = np.random.default_rng(zlib.crc32(name.encode())).choice(t.numel(), DUMP_MAX_ELEMS, replace=False)
+        return t.reshape(-1)[torch.from_numpy(np.sort(idx)).to(t.device)].float().cpu().numpy()
+
+    grads = model._flat.tensors(model, grads=True)
+    arrays = {"loss": np.array([loss_value], dtype=np.float64)}
+    for n, p in model.named_parameters():
+        arrays["param." + n] = sample(n, p)
+        arrays["grad." + n] = sample(n, grads[n])
+    for n, b in model.named_buffers():
+        if b.is_floating_point():
+            arrays["buffer." + n] = sample(n, b)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes exceed {DUMP_MAX_BYTES}"
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def _make_trainer(workload, dtype, dev, world=1, rank=0):
     """(trainer, batches resident in HBM, (rnn, H, L, C, B, tin)) for a named workload, built exactly as main() builds the timed one."""
     from asr_amd import CTCLoss, DeepSpeech, FusedAdamW
@@ -603,7 +639,14 @@ def main():
     ap.add_argument("--ranks-on-one-gpu", action="store_true",
                     help="TEST MODE for the N > 1 code path on a 1-GPU box: every rank uses cuda:0 and the process group is gloo (RCCL cannot put "
                          "two ranks on one device) unless DS2_DIST_BACKEND says otherwise.  The line is labelled; it is not a scaling point.")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, updated weights, gradients, BatchNorm running "
+                         "statistics; large tensors as a fixed, seeded sample) as DIR/<name>.npy, rank 0 only")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup is not None and args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         return spawn_ranks(args.gpus)                   # `python bench.py --gpus N`: one rank per GPU under torch.distributed.run
@@ -734,6 +777,8 @@ def main():
         red.timing = None
     ms = dt / args.steps * 1e3
     utts = world * B * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, lv)
 
     # ---- roofline of the dominant kernels (the two recurrences): timed live with HIP events on torch's current stream, which is the
     # stream libds2hip launches on - inside the timed region (event pairs recorded above); a stand-alone probe only as a fallback.

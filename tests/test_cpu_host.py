@@ -626,3 +626,29 @@ def test_unidirectional_variant_matches_reference_golden():
     tr = DeepSpeechTrainer(model, torch.nn.CTCLoss(reduction="sum"), 1, None, torch.optim.AdamW(model.parameters()), None, None, "cpu", "cpu", False, None)
     with pytest.raises(NotImplementedError):
         tr.step((inputs, torch.from_numpy(targets), torch.from_numpy(pct.copy()), torch.from_numpy(tsz)))
+
+
+def test_bench_dump_outputs_writes_the_step_state_as_float_arrays(tmp_path):
+    """bench.py --dump-outputs: the loss, every parameter and its gradient and the float BatchNorm buffers as float32 / float64 .npy files
+    under the size cap; a tensor above bench.DUMP_MAX_ELEMS is written as a sample at positions that are the same in every run."""
+    import bench
+    m = make("gru", 128, 2, 7)                                          # rnns.0 weight_ih: 384 x 1312 elements, sampled
+    m._ensure_flat("cpu")
+    m._flat.flat_grad.copy_(torch.randn(m._flat.flat_grad.numel(), generator=torch.Generator().manual_seed(3)))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), m, 12.5)
+    names = sorted(os.listdir(tmp_path / "a"))
+    expect = ["loss.npy"] + [f"{k}.{n}.npy" for n, _ in m.named_parameters() for k in ("param", "grad")]
+    expect += [f"buffer.{n}.npy" for n, b in m.named_buffers() if b.is_floating_point()]
+    assert names == sorted(expect) and sorted(os.listdir(tmp_path / "b")) == names
+    a = {f[:-4]: np.load(tmp_path / "a" / f) for f in names}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values()) and sum(v.nbytes for v in a.values()) <= bench.DUMP_MAX_BYTES
+    assert all(np.array_equal(a[f[:-4]], np.load(tmp_path / "b" / f)) for f in names)
+    assert a["loss"].dtype == np.float64 and a["loss"].tolist() == [12.5]
+    grads = m._flat.tensors(m, grads=True)
+    for n, p in m.named_parameters():
+        if p.numel() <= bench.DUMP_MAX_ELEMS:
+            assert np.array_equal(a["param." + n], p.detach().numpy()) and np.array_equal(a["grad." + n], grads[n].numpy()), n
+        else:
+            assert a["param." + n].shape == a["grad." + n].shape == (bench.DUMP_MAX_ELEMS,), n
+            assert np.isin(a["grad." + n], grads[n].numpy()).all(), n
