@@ -1,5 +1,6 @@
-// Bidirectional GRU / LSTM recurrence (fp32), padded + masked formulation of
-// pack_padded_sequence -> aten::gru/lstm -> pad_packed_sequence (blocks.py:87-89) and its backward.
+// Bidirectional GRU / LSTM / tanh-RNN recurrence (fp32), padded + masked formulation of
+// pack_padded_sequence -> aten::gru/lstm/rnn_tanh -> pad_packed_sequence (blocks.py:87-89) and its backward.
+// G = gates per hidden unit: 3 GRU, 4 LSTM, 1 the Elman cell of nn.RNN (tanh) — every G = 1 difference is an `if constexpr (G == 1)` arm.
 //
 // The input projections X W_ih^T + b_ih for all t and both directions are one big MFMA GEMM
 // (gemm.hip); this file is the strictly sequential part, in two kernel families with bit-identical results:
@@ -26,7 +27,7 @@
 //     them (ping-pong buffer), next to the plain-layout copies the big GEMMs consume.
 //
 // Saved for backward (in place of the x-projections): activated gates; aux = W_hn h + b_hn (GRU)
-// or the cell state c (LSTM); h per direction.  Rows t >= len[b] hold zeros everywhere, which is
+// or the cell state c (LSTM); h per direction.  The tanh cell saves h alone: d pre = (dy + dh_carry)(1 - h^2) needs nothing else.  Rows t >= len[b] hold zeros everywhere, which is
 // what makes the reverse direction start at each sample's own last frame.
 #include "common.h"
 #include "permlane.h"
@@ -380,7 +381,9 @@ __global__ __launch_bounds__(NW * 64) void rnn_fwd_step_kernel(const float* pk, 
     float* ho = a.hbuf + rowH[i];
     float* ax = a.aux + rowH[i];
     if (!(t < plen[i])) {
-      if (a.gates_bf) {
+      if constexpr (G == 1) {
+        // tanh cell: backward needs h alone (hbuf); no gate record, nothing in gx / aux
+      } else if (a.gates_bf) {
         __builtin_nontemporal_store(bf16x4_{(__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f}, reinterpret_cast<bf16x4_*>(a.gates_bf) + rowH[i]);
         if (G == 4) stnt(ax, 0.f);
       } else {
@@ -407,7 +410,9 @@ __global__ __launch_bounds__(NW * 64) void rnn_fwd_step_kernel(const float* pk, 
     RNN_TRACE(s, 7);                                   // epilogue operands (gate pre-activations, bias, h_prev) have landed
 #endif
     float hnew;
-    if constexpr (G == 3) {
+    if constexpr (G == 1) {
+      hnew = tanhf_(pgx[i][0] + gh[0]);                 // Elman cell, tanh: h_t = tanh(x W_ih^T + b_ih + h W_hh^T + b_hh)
+    } else if constexpr (G == 3) {
       const float r = sigmoidf_(pgx[i][0] + gh[0]);
       const float z = sigmoidf_(pgx[i][1] + gh[1]);
       const float n = tanhf_(__builtin_fmaf(r, gh[2], pgx[i][2]));      // explicit fma: the persistent kernel must contract identically
@@ -731,7 +736,9 @@ __global__ __launch_bounds__(NW * 64) void rnn_fwd_persistent_kernel(RnnArgs a, 
   // saved-for-backward outputs of one time step
   auto store_outputs = [&](long long fH, long long fG, const float (&og)[4], float oaux, float oh, bool live) {
     if (!pact) return;
-    if (a.gates_bf) {
+    if constexpr (G == 1) {
+      // tanh cell: h is the whole saved-for-backward state
+    } else if (a.gates_bf) {
       __builtin_nontemporal_store(bf16x4_{(__bf16)og[0], (__bf16)og[1], (__bf16)og[2], (__bf16)og[3]}, reinterpret_cast<bf16x4_*>(a.gates_bf) + fH);
       if (G == 4) a.aux[fH] = oaux;
     } else {
@@ -908,7 +915,9 @@ __global__ __launch_bounds__(NW * 64) void rnn_fwd_persistent_kernel(RnnArgs a, 
         for (int w = 0; w < NW; ++w) sum += red[s & 1][w][sub * G + g][src_lane][red_reg];
         gh[g] = sum + pb[g];
       }
-      if constexpr (G == 3) {
+      if constexpr (G == 1) {
+        hnew = tanhf_(pgx[0] + gh[0]);                  // (no state but h: pprev stays unused)
+      } else if constexpr (G == 3) {
         const float r = sigmoidf_(pgx[0] + gh[0]);
         const float z = sigmoidf_(pgx[1] + gh[1]);
         const float n = tanhf_(__builtin_fmaf(r, gh[2], pgx[2]));
@@ -996,6 +1005,11 @@ __device__ __forceinline__ void lstm_bwd_point(float dh, float dcar_in, float ig
   dgh[3] = dh * tc * og * (1.f - og);
   carry = dc * fg;
 }
+// tanh cell: d(pre-activation) = (dy + dh_carry) (1 - h^2); it is dGx and the (single-gate) row of dGh at once, and db_ih = db_hh = its sum
+__device__ __forceinline__ float tanh_bwd_point(float dh, float h) {
+#pragma clang fp contract(off)
+  return dh * (1.f - h * h);
+}
 
 // ------------------------------------------------------------------------------------------
 // backward step (same grid mapping).  carry[b][j] = sum_k dGh[tq][b][k] * W_hh[k][j]
@@ -1054,7 +1068,9 @@ __global__ __launch_bounds__(NW * 64) void rnn_bwd_step_kernel(const float* pk, 
 #pragma unroll
       for (int g = 0; g < G; ++g) pg[i][g] = 0.f;
       if (pact[i]) {
-        if (gates_bf) {                                   // packed record: one 8-byte load (wave-uniform choice, preloaded pointer)
+        if constexpr (G == 1) {
+          pax[i] = ldnt(auxbase + rowH[i]);               // tanh cell: auxbase is hbuf (launch_steps), pax = h_t; gx is output only
+        } else if (gates_bf) {                            // packed record: one 8-byte load (wave-uniform choice, preloaded pointer)
           const bf16x4_ rec = __builtin_nontemporal_load(reinterpret_cast<const bf16x4_*>(gates_bf) + rowH[i]);
           pg[i][0] = (float)rec[0]; pg[i][1] = (float)rec[1]; pg[i][2] = (float)rec[2];
           if (G == 3) pax[i] = (float)rec[3];
@@ -1128,12 +1144,15 @@ __global__ __launch_bounds__(NW * 64) void rnn_bwd_step_kernel(const float* pk, 
 #pragma unroll
       for (int g = 0; g < G; ++g) { dgx_store(gx, gb, g * H, 0.f); dgh[g] = 0.f; }
       if (G == 3) stnt(ax, 0.f);
-      *dco = 0.f;
+      if constexpr (G != 1) *dco = 0.f;                   // (the tanh cell has no elementwise carry)
     } else {
       float carry = 0.f;
 #pragma unroll
       for (int w = 0; w < NW; ++w) carry += red[w][sub][src_lane][reg];
-      if constexpr (G == 3) {
+      if constexpr (G == 1) {
+        dgh[0] = tanh_bwd_point(pdy[i] + carry, pax[i]);
+        dgx_store(gx, gb, 0, dgh[0]);
+      } else if constexpr (G == 3) {
         const float dh = pdy[i] + carry + pdc[i];
         float dpn, car;
         gru_bwd_point(dh, pg[i][0], pg[i][1], pg[i][2], pax[i], pprev[i], dgh, dpn, car);
@@ -1211,7 +1230,7 @@ __global__ __launch_bounds__(NW * 64) void rnn_bwd_persistent_kernel(RnnArgs a, 
   const int src_lane = (brow >> 2) * 16 + jl, reg = brow & 3;
   const int red_sw = (lane >> 3) & 1, red_reg = (reg + 2 * ((jl >> 3) & 1)) & 3;      // conflict-free dword reads of the partial sums (see forward)
   const int plen = pact ? a.lens[b] : 0;
-  const __bf16* gates_bf = a.gates_bf;
+  const __bf16* gates_bf = G == 1 ? nullptr : a.gates_bf;                    // (the tanh cell has no gate record)
   float dcar = 0.f;                                                           // GRU dh*z / LSTM dc*f of the step before (own pair)
 
   // operands of the gate-derivative math for one time step: independent of the recurrence, so they are fetched one step ahead
@@ -1223,6 +1242,11 @@ __global__ __launch_bounds__(NW * 64) void rnn_bwd_persistent_kernel(RnnArgs a, 
     if (!pact) return o;
     const int t = dir == 0 ? T - 1 - step : step;
     const long long rowH = (((long long)t * B + b) * 2 + dir) * H + j;
+    if constexpr (G == 1) {                               // tanh cell: h_t is all the derivative needs
+      o.g0 = ldnt(a.hbuf + rowH);
+      o.dy = ldnt(&a.dy[((long long)t * B + b) * lddy + j]);
+      return o;
+    }
     if (gates_bf) {                                       // packed 8-byte record (bf16 training path)
       o.rec = __builtin_nontemporal_load(reinterpret_cast<const bf16x4_*>(gates_bf) + rowH);
       if (G == 4) o.ax = ldnt(a.aux + rowH);
@@ -1384,7 +1408,9 @@ __global__ __launch_bounds__(NW * 64) void rnn_bwd_persistent_kernel(RnnArgs a, 
       float carry = 0.f;
 #pragma unroll
       for (int w = 0; w < NW; ++w) carry += red[s & 1][w][sub][src_lane][red_reg];
-      if constexpr (G == 3) {
+      if constexpr (G == 1) {
+        dgh[0] = dgx[0] = tanh_bwd_point(cur.dy + carry, cur.g0);
+      } else if constexpr (G == 3) {
         const float dh = cur.dy + carry + dcar;
         float dpn;
         gru_bwd_point(dh, cur.g0, cur.g1, cur.g2, cur.g3, cur.prev, dgh, dpn, dcar);
@@ -1427,7 +1453,7 @@ __global__ __launch_bounds__(NW * 64) void rnn_bwd_persistent_kernel(RnnArgs a, 
   if (a.bsum && pact) {
     float* o = a.bsum + (((long long)b * 2 + dir) * 4) * H + j;
 #pragma unroll
-    for (int g = 0; g < 4; ++g) o[g * H] = bs[g];
+    for (int g = 0; g < (G == 1 ? 1 : 4); ++g) o[g * H] = bs[g];   // (tanh cell: slot 0 only, the one rnn_bias_finalize_kernel reads)
   }
   PTRACE_DUMP(1);
 }
@@ -1600,6 +1626,11 @@ int try_launch_persistent_fwd(RnnArgs a, hipStream_t st) {
   // way.  So: 16 batch rows x 32 units per workgroup where the registers allow it (W_hh fragments ncw * 2G + operand ncw lane vectors of
   // 4 VGPRs) and the alternative would be a 32-row tile; else the step kernels' 16|32 rows x 16 units (with 16-row tiles the gather
   // is the same size either way and twice as many, half as big workgroups measured slightly faster).
+  // Tanh cell (G = 1): the register budget never binds (W_hh fragments ncw * NS lane vectors: 8 = 32 VGPRs at H = 1024, against 24 for the
+  // GRU), so the limit is the kernel's one (batch row, unit) pair per thread = 512 pairs per workgroup, i.e. 16 x 32 or 32 x 16 — a wider
+  // slice would need a second pair per thread.  Between those two the exchange decides exactly as for G = 3 / 4 (the gather of a 16-row
+  // tile is H wide either way; 16 x 32 halves the producers and is what lets a group fit one XCD), so G = 1 takes the same rule below:
+  // at c3's shape (H = 1024, B = 64) that is 16 x 32, 8 groups of 32 workgroups on 256 CUs.
   int mb = 1, ns = 2;
   const bool ns2_ok = (nsl % 2) == 0 && ncw * NPL * (2 * G + 1) * 4 <= RLIM && (long long)(nsl / 2) * ceil_div(a.B, 16) * 2 <= cu_count();
   // ... and 16 x 32 also where 16 x 16 would be chosen but only the wider slice lets an exchange group fit one XCD (L2-local exchange;
@@ -1660,12 +1691,15 @@ int try_launch_persistent_bwd(RnnArgs a, hipStream_t st) {
   static const char* env = getenv("DS2_RNN_PERSISTENT");
   if ((env && env[0] == '0') || (a.dbg & ~128)) return 0;
   // buffers: either the bf16 training path's (packed gate records in, bf16 dGx out) or the plain ones (gates in gx, dGx in place)
-  if (!((a.gates_bf && a.dgx_bf) || (!a.gates_bf && !a.dgx_bf && a.gx))) return 0;
+  // (tanh cell: no gate record either way — h comes from hbuf; dGx goes to the bf16 buffer if given, else into gx)
+  if (G == 1 ? !(a.dgx_bf || a.gx) : !((a.gates_bf && a.dgx_bf) || (!a.gates_bf && !a.dgx_bf && a.gx))) return 0;
   if ((a.H % 16) != 0 || a.T < 2 || !persist_allowed(a.hctx, true)) return 0;
   int mb = pick_mb(a.B, a.H);
   const int nsl = a.H / 16;
   const int nchb = ceil_div(G * a.H, kchunk<BF>());
-  const int q = BF ? 3 : 6;                                           // instantiated chunks per wave: bf16 3, 6, 9, 12 ; fp32 6, 12, 18
+  // instantiated chunks per wave: bf16 3, 6, 9, 12 ; fp32 6, 12, 18.  Tanh cell: the product dGh W_hh has K = H, the forward's shape, and
+  // takes the forward's set (bf16 1-5, fp32 2, 4, 6, 8) — rounding 4 chunks up to 6 would issue a third of the MFMAs on zeros at H = 1024
+  const int q = G == 1 ? (BF ? 1 : 2) : (BF ? 3 : 6);
   const int ncw = ceil_div(ceil_div(nchb, NW), q) * q;
   int ns = (mb == 2 && (nsl % 2) == 0) ? 2 : 1;                       // same tile choice as the step kernels ...
   // ... and 16 rows x 32 units also where that is what lets an exchange group fit one XCD (L2-local exchange)
@@ -1695,7 +1729,19 @@ int try_launch_persistent_bwd(RnnArgs a, hipStream_t st) {
       return 0;                                                                                                                     \
   } while (0)
 #define DS2_PBCASE(NCW_) case NCW_: if (ns == 2) DS2_PB(1, 2, NCW_); else if (mb == 2) DS2_PB(2, 1, NCW_); else DS2_PB(1, 1, NCW_); break;
-  if constexpr (BF) {
+  if constexpr (G == 1) {
+    if constexpr (BF) {
+      switch (ncw) {
+        DS2_PBCASE(1) DS2_PBCASE(2) DS2_PBCASE(3) DS2_PBCASE(4) DS2_PBCASE(5)
+        default: return 0;
+      }
+    } else {
+      switch (ncw) {
+        DS2_PBCASE(2) DS2_PBCASE(4) DS2_PBCASE(6) DS2_PBCASE(8)
+        default: return 0;
+      }
+    }
+  } else if constexpr (BF) {
     switch (ncw) {
       DS2_PBCASE(3) DS2_PBCASE(6) DS2_PBCASE(9) DS2_PBCASE(12)
       default: return 0;
@@ -1727,6 +1773,11 @@ __device__ __forceinline__ void store16_base(const char* base, unsigned off, u32
 #include "rnn_bwd_ksplit.h"
 #include "rnn_fwd_u10.h"
 
+// The K-split backward and the 10-unit-slice forward exist for G = 3 / 4 only: the K-split kernel gathers H-wide partial dh instead of the
+// G*H-wide dGh — at G = 1 those are the same size — and the tanh cell's W_hh slice fits the 16-unit persistent kernels at every H they take.
+inline bool ksplit_avail(int gates, int H) { return gates != 1 && ksplit_shape_ok(H); }
+inline bool u10_avail(int gates, int H) { return gates != 1 && u10_shape_ok(H); }
+
 template <int G, bool BF, bool SP = false>
 int launch_steps(bool bwd, RnnArgs a, hipStream_t st) {
   a.dbg = a.hctx ? a.hctx->debug_flags : 0;
@@ -1747,7 +1798,8 @@ int launch_steps(bool bwd, RnnArgs a, hipStream_t st) {
   const int T_B = a.T | (a.B << 16);
   const float* pk = a.pk;
   const float* wp = a.wp;
-  const float* prev = G == 3 ? a.hbuf : a.aux;                      // previous hidden (GRU) / cell (LSTM) state
+  const float* prev = G == 4 ? a.aux : a.hbuf;                      // previous hidden (GRU; unused by the tanh cell) / cell (LSTM) state
+  float* auxb = G == 1 ? a.hbuf : a.aux;                             // backward: the tanh cell reads h_t in aux's place (it has no aux)
   for (int s = 0; s < a.T; ++s) {
     const int s_H = s | (a.H << 16);
     if (!bwd) {
@@ -1755,9 +1807,9 @@ int launch_steps(bool bwd, RnnArgs a, hipStream_t st) {
       else if (mb == 2) hipLaunchKernelGGL((rnn_fwd_step_kernel<G, 2, 1, BF>), grid, block, 0, st, pk, wp, a.gx, prev, a.bhh, s_H, T_B, packed, a);
       else hipLaunchKernelGGL((rnn_fwd_step_kernel<G, 1, 1, BF>), grid, block, 0, st, pk, wp, a.gx, prev, a.bhh, s_H, T_B, packed, a);
     } else {
-      if (ns == 2) hipLaunchKernelGGL((rnn_bwd_step_kernel<G, 1, 2, BF, SP>), grid, block, 0, st, pk, wp, gx_or_rec, a.aux, a.dy, s_H, T_B, packed, a.lddy, a);
-      else if (mb == 2) hipLaunchKernelGGL((rnn_bwd_step_kernel<G, 2, 1, BF, SP>), grid, block, 0, st, pk, wp, gx_or_rec, a.aux, a.dy, s_H, T_B, packed, a.lddy, a);
-      else hipLaunchKernelGGL((rnn_bwd_step_kernel<G, 1, 1, BF, SP>), grid, block, 0, st, pk, wp, gx_or_rec, a.aux, a.dy, s_H, T_B, packed, a.lddy, a);
+      if (ns == 2) hipLaunchKernelGGL((rnn_bwd_step_kernel<G, 1, 2, BF, SP>), grid, block, 0, st, pk, wp, gx_or_rec, auxb, a.dy, s_H, T_B, packed, a.lddy, a);
+      else if (mb == 2) hipLaunchKernelGGL((rnn_bwd_step_kernel<G, 2, 1, BF, SP>), grid, block, 0, st, pk, wp, gx_or_rec, auxb, a.dy, s_H, T_B, packed, a.lddy, a);
+      else hipLaunchKernelGGL((rnn_bwd_step_kernel<G, 1, 1, BF, SP>), grid, block, 0, st, pk, wp, gx_or_rec, auxb, a.dy, s_H, T_B, packed, a.lddy, a);
     }
   }
   hipError_t e = hipGetLastError();
@@ -1772,7 +1824,7 @@ size_t pk_floats(int B, int H, int kdim, int bf16) {   // size in 4-byte units (
 
 template <bool BF>
 int dispatch(int gates, bool bwd, const RnnArgs& a, hipStream_t st) {
-  return gates == 3 ? launch_steps<3, BF>(bwd, a, st) : launch_steps<4, BF>(bwd, a, st);
+  return gates == 1 ? launch_steps<1, BF>(bwd, a, st) : gates == 3 ? launch_steps<3, BF>(bwd, a, st) : launch_steps<4, BF>(bwd, a, st);
 }
 
 }  // namespace
@@ -1784,7 +1836,7 @@ extern "C" size_t ds2_rnn_packed_bytes(int gates, int H, int which, int bf16) {
   // bf16 = 2 (fp32 mode, split recurrences): [fp32 | hi | lo] and, forward operand of shapes the 10-unit-slice kernel exists for, [u10 hi | u10 lo]
   if (bf16 == 2)
     return ds2_rnn_packed_bytes(gates, H, which, 0) + 2 * ds2_rnn_packed_bytes(gates, H, which, 1) +
-           ((which == 0 && u10_shape_ok(H)) ? 2 * u10_plane_bytes(gates, H) : 0);
+           ((which == 0 && u10_avail(gates, H)) ? 2 * u10_plane_bytes(gates, H) : 0);
   const int kc = bf16 ? 32 : 16;
   return (which == 0 ? 2 * nsl * gates * ceil_div(H, kc) : 2 * nsl * ceil_div(gates * H, kc)) * 1024;
 }
@@ -1792,7 +1844,7 @@ extern "C" size_t ds2_rnn_packed_bytes(int gates, int H, int which, int bf16) {
 // Re-pack W_hh = [weight_hh_l0 ; weight_hh_l0_reverse] (2, G*H, H) fp32 into MFMA-fragment order, as fp32 (bf16 = 0) or
 // bf16 (bf16 = 1) fragments (call after every optimizer step / load_state_dict).
 extern "C" int ds2_rnn_pack_whh(int gates, const float* whh, void* wp_fwd, void* wp_bwd, int H, int bf16, void* stream) {
-  DS2_REQUIRE(gates == 3 || gates == 4, "ds2_rnn_pack_whh: gates must be 3 or 4");
+  DS2_REQUIRE(gates == 1 || gates == 3 || gates == 4, "ds2_rnn_pack_whh: gates must be 1, 3 or 4");
   DS2_REQUIRE(whh && wp_fwd && wp_bwd && H > 0 && (H % 4) == 0, "ds2_rnn_pack_whh: bad args");
   if (bf16 == 1) hipLaunchKernelGGL(rnn_pack_kernel<true>, dim3(2048), dim3(256), 0, (hipStream_t)stream, whh, wp_fwd, wp_bwd, gates, H);
   else hipLaunchKernelGGL(rnn_pack_kernel<false>, dim3(2048), dim3(256), 0, (hipStream_t)stream, whh, wp_fwd, wp_bwd, gates, H);
@@ -1802,7 +1854,7 @@ extern "C" int ds2_rnn_pack_whh(int gates, const float* whh, void* wp_fwd, void*
     hipLaunchKernelGGL(rnn_pack_split_fwd_kernel, dim3(1024), dim3(256), 0, (hipStream_t)stream, whh, (void*)hi,
                        (void*)(hi + ds2_rnn_packed_bytes(gates, H, 0, 1)), gates, H);
     DS2_LAUNCH_CHECK("rnn_pack_split_fwd_kernel");
-    if (u10_shape_ok(H)) {                                       // + the 10-unit-slice operand (rnn_fwd_u10.h) behind those
+    if (u10_avail(gates, H)) {                                   // + the 10-unit-slice operand (rnn_fwd_u10.h) behind those
       char* uh = hi + 2 * ds2_rnn_packed_bytes(gates, H, 0, 1);
       hipLaunchKernelGGL(rnn_pack_u10_kernel, dim3(1024), dim3(256), 0, (hipStream_t)stream, whh, (void*)uh, (void*)(uh + u10_plane_bytes(gates, H)), gates, H);
       DS2_LAUNCH_CHECK("rnn_pack_u10_kernel");
@@ -1850,13 +1902,13 @@ extern "C" size_t ds2_rnn_fwd_workspace_bytes(int B, int H, int bf16) {
 //   h_bf16 optional (T,B,2,H) bf16: a bf16 copy of hbuf, written by a PERSISTENT launch only (ds2_rnn_last_path() & 1 after the call)
 extern "C" int ds2_rnn_fwd_ex(ds2_rnn_ctx* ctx, int gates, float* gx, const void* wp_fwd, const float* bhh, float* hbuf, float* aux, const int* lens_dev, int T,
                               int B, int H, int bf16, void* gates_bf16, void* h_bf16, void* ws, size_t ws_bytes, void* stream) {
-  DS2_REQUIRE(gates == 3 || gates == 4, "ds2_rnn_fwd: gates must be 3 (GRU) or 4 (LSTM)");
-  DS2_REQUIRE(gx && wp_fwd && bhh && hbuf && aux && lens_dev, "ds2_rnn_fwd: null pointer");
+  DS2_REQUIRE(gates == 1 || gates == 3 || gates == 4, "ds2_rnn_fwd: gates must be 1 (tanh RNN), 3 (GRU) or 4 (LSTM)");
+  DS2_REQUIRE(gx && wp_fwd && bhh && hbuf && (aux || gates == 1) && lens_dev, "ds2_rnn_fwd: null pointer");
   DS2_REQUIRE(T > 0 && B > 0 && H > 0 && (H % 4) == 0, "ds2_rnn_fwd: need H %% 4 == 0 (H=%d)", H);
   DS2_REQUIRE(ws && ws_bytes >= ds2_rnn_fwd_workspace_bytes(B, H, bf16), "ds2_rnn_fwd: workspace too small");
   RnnArgs a{};
   a.gx = gx; a.aux = aux; a.hbuf = hbuf; a.wp = (const float*)wp_fwd; a.bhh = bhh; a.pk = (float*)ws; a.lens = lens_dev;
-  a.T = T; a.B = B; a.H = H; a.gates_bf = (__bf16*)gates_bf16; a.h_bf = (__bf16*)h_bf16;
+  a.T = T; a.B = B; a.H = H; a.gates_bf = gates == 1 ? nullptr : (__bf16*)gates_bf16; a.h_bf = (__bf16*)h_bf16;
   a.hctx = ctx; a.status = ctx ? ctx->status_dev : nullptr;
   a.prearmed = take_prearmed(ctx);
   int scratch_path = 0;
@@ -1875,8 +1927,8 @@ extern "C" int ds2_rnn_fwd_ex(ds2_rnn_ctx* ctx, int gates, float* gx, const void
         b.dbg &= ~256;
         last_path &= ~256;
         if (!(a.dbg & 256))                                         // (debug flag 256: prefer the 10-unit kernel where its shape qualifies)
-          rc = gates == 3 ? try_launch_persistent_fwd<3, true, true>(b, st) : try_launch_persistent_fwd<4, true, true>(b, st);
-        if (rc == 0 && u10_shape_ok(H)) {
+          rc = gates == 1 ? try_launch_persistent_fwd<1, true, true>(b, st) : gates == 3 ? try_launch_persistent_fwd<3, true, true>(b, st) : try_launch_persistent_fwd<4, true, true>(b, st);
+        if (rc == 0 && u10_avail(gates, H)) {
           // the 16-unit split kernel does not fit (LSTM H = 1280 at B = 32: BASELINE C4): ten-unit slices, rnn_fwd_u10.h
           b.wp = reinterpret_cast<const float*>(reinterpret_cast<const char*>(wp_fwd) + ds2_rnn_packed_bytes(gates, H, 0, 0) +
                                                 2 * ds2_rnn_packed_bytes(gates, H, 0, 1));
@@ -1885,11 +1937,11 @@ extern "C" int ds2_rnn_fwd_ex(ds2_rnn_ctx* ctx, int gates, float* gx, const void
         }
         if (rc == 1) last_path |= 32;                             // bit 5: a split kernel took the call
       }
-      if (rc == 0) { last_path &= ~32; a.dbg &= ~256; rc = gates == 3 ? try_launch_persistent_fwd<3, false>(a, st) : try_launch_persistent_fwd<4, false>(a, st); }
+      if (rc == 0) { last_path &= ~32; a.dbg &= ~256; rc = gates == 1 ? try_launch_persistent_fwd<1, false>(a, st) : gates == 3 ? try_launch_persistent_fwd<3, false>(a, st) : try_launch_persistent_fwd<4, false>(a, st); }
     } else {
       last_path &= ~(32 | 256);
-      rc = bf16 ? (gates == 3 ? try_launch_persistent_fwd<3, true>(a, st) : try_launch_persistent_fwd<4, true>(a, st))
-                : (gates == 3 ? try_launch_persistent_fwd<3, false>(a, st) : try_launch_persistent_fwd<4, false>(a, st));
+      rc = bf16 ? (gates == 1 ? try_launch_persistent_fwd<1, true>(a, st) : gates == 3 ? try_launch_persistent_fwd<3, true>(a, st) : try_launch_persistent_fwd<4, true>(a, st))
+                : (gates == 1 ? try_launch_persistent_fwd<1, false>(a, st) : gates == 3 ? try_launch_persistent_fwd<3, false>(a, st) : try_launch_persistent_fwd<4, false>(a, st));
     }
     last_path = (last_path & ~1) | (rc == 1 ? 1 : 0);
     if (rc != 0) return rc < 0 ? rc : 0;
@@ -1908,20 +1960,21 @@ extern "C" int ds2_rnn_fwd_ex(ds2_rnn_ctx* ctx, int gates, float* gx, const void
 // Returns 0 = done, 1 = see gx_bf16, < 0 error.
 extern "C" int ds2_rnn_fwd_x(ds2_rnn_ctx* ctx, int gates, float* gx, const void* gx_bf16, const void* wp_fwd, const float* bhh, float* hbuf, float* aux,
                              const int* lens_dev, int T, int B, int H, void* gates_bf16, void* h_bf16, float* hsum, void* ws, size_t ws_bytes, void* stream) {
-  DS2_REQUIRE(gates == 3 || gates == 4, "ds2_rnn_fwd_x: gates must be 3 (GRU) or 4 (LSTM)");
-  DS2_REQUIRE((gx || gx_bf16) && wp_fwd && bhh && hbuf && aux && lens_dev && gates_bf16, "ds2_rnn_fwd_x: null pointer");
+  DS2_REQUIRE(gates == 1 || gates == 3 || gates == 4, "ds2_rnn_fwd_x: gates must be 1 (tanh RNN), 3 (GRU) or 4 (LSTM)");
+  DS2_REQUIRE((gx || gx_bf16) && wp_fwd && bhh && hbuf && ((aux && gates_bf16) || gates == 1) && lens_dev, "ds2_rnn_fwd_x: null pointer");
   DS2_REQUIRE(T > 0 && B > 0 && H > 0 && (H % 4) == 0, "ds2_rnn_fwd_x: need H %% 4 == 0 (H=%d)", H);
   DS2_REQUIRE(ws && ws_bytes >= ds2_rnn_fwd_workspace_bytes(B, H, 1), "ds2_rnn_fwd_x: workspace too small");
   if (!gx && !persist_idle(ctx, false)) return 1;
   RnnArgs a{};
   a.gx = gx_bf16 ? nullptr : gx; a.gxb = (const __bf16*)gx_bf16; a.aux = aux; a.hbuf = hbuf; a.wp = (const float*)wp_fwd; a.bhh = bhh; a.pk = (float*)ws;
-  a.lens = lens_dev; a.T = T; a.B = B; a.H = H; a.gates_bf = (__bf16*)gates_bf16; a.h_bf = (__bf16*)h_bf16; a.hsum = hsum;
+  a.lens = lens_dev; a.T = T; a.B = B; a.H = H; a.gates_bf = gates == 1 ? nullptr : (__bf16*)gates_bf16; a.h_bf = (__bf16*)h_bf16; a.hsum = hsum;
   a.hctx = ctx; a.status = ctx ? ctx->status_dev : nullptr;
   a.prearmed = take_prearmed(ctx);
   a.dbg = ctx ? ctx->debug_flags : 0;
   int scratch_path = 0;
   int& last_path = ctx ? ctx->last_path : scratch_path;
-  const int rc = gates == 3 ? try_launch_persistent_fwd<3, true>(a, (hipStream_t)stream) : try_launch_persistent_fwd<4, true>(a, (hipStream_t)stream);
+  const int rc = gates == 1 ? try_launch_persistent_fwd<1, true>(a, (hipStream_t)stream)
+                 : gates == 3 ? try_launch_persistent_fwd<3, true>(a, (hipStream_t)stream) : try_launch_persistent_fwd<4, true>(a, (hipStream_t)stream);
   if (rc < 0) return rc;
   last_path = (last_path & ~(1 | 32 | 256)) | (rc == 1 ? 1 : 0);
   if (rc == 1) return 0;
@@ -1942,6 +1995,7 @@ __global__ void rnn_bias_finalize_kernel(const float* __restrict__ part, int B, 
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;        // (dir, slot, j)
   if (idx >= 2 * 4 * H) return;
   const int j = idx % H, slot = (idx / H) & 3, dir = idx / (4 * H);
+  if (G == 1 && slot != 0) return;                              // tanh cell: one slot, [d pre]; db_ih = db_hh = its sum
   // eight independent loads in flight, added in row order (one dependent load per row made this 64 x 0.45 us = 29 us per call)
   float s = 0.f;
   int b = 0;
@@ -1954,14 +2008,14 @@ __global__ void rnn_bias_finalize_kernel(const float* __restrict__ part, int B, 
   }
   for (; b < B; ++b) s += part[(long long)b * 8 * H + idx];
   const long long o = (long long)dir * G * H + j;
-  if (G == 4) { dbih[o + slot * H] = s; dbhh[o + slot * H] = s; }
+  if (G == 4 || G == 1) { dbih[o + slot * H] = s; dbhh[o + slot * H] = s; }
   else if (slot < 2) { dbih[o + slot * H] = s; dbhh[o + slot * H] = s; }
   else if (slot == 2) dbih[o + 2 * H] = s;
   else dbhh[o + 2 * H] = s;
 }
 
 extern "C" int ds2_rnn_bias_grads(int gates, const float* bias_part, int B, int H, float* dbih, float* dbhh, void* stream) {
-  DS2_REQUIRE((gates == 3 || gates == 4) && bias_part && dbih && dbhh && B > 0 && H > 0, "ds2_rnn_bias_grads: bad args");
+  DS2_REQUIRE((gates == 1 || gates == 3 || gates == 4) && bias_part && dbih && dbhh && B > 0 && H > 0, "ds2_rnn_bias_grads: bad args");
   hipLaunchKernelGGL(rnn_bias_finalize_kernel, dim3(ceil_div(8 * H, 256)), dim3(256), 0, (hipStream_t)stream, bias_part, B, H, gates, dbih, dbhh);
   DS2_LAUNCH_CHECK("rnn_bias_finalize_kernel");
   return 0;
@@ -1971,8 +2025,8 @@ extern "C" size_t ds2_rnn_bwd_workspace_bytes(int gates, int B, int H, int bf16)
   const size_t step = pk_floats(B, H, gates * H, bf16 == 1) * sizeof(float);     // two ping-pong buffers of the step kernels
   size_t pers = 4 * bwd_xbuf_bytes(gates, B, H, bf16 == 1) + 64;                  // four round-robin buffers of the persistent kernel + its census words
   if (bf16 == 2) pers = std::max(pers, 8 * bwd_xbuf_bytes(gates, B, H, 1) + 64);  // the split form: hi and lo plane per buffer
-  if (bf16 == 2 && ksplit_shape_ok(H)) pers = std::max(pers, 2 * ksplit_xbuf_bytes(B, H) + 64);   // ... of the K-split kernel: two planes of two slots
-  if (bf16 == 1 && ksplit_shape_ok(H)) pers = std::max(pers, ksplit_xbuf_bytes(B, H) + 64);   // two slots of the K-split kernel + census
+  if (bf16 == 2 && ksplit_avail(gates, H)) pers = std::max(pers, 2 * ksplit_xbuf_bytes(B, H) + 64);   // ... of the K-split kernel: two planes of two slots
+  if (bf16 == 1 && ksplit_avail(gates, H)) pers = std::max(pers, ksplit_xbuf_bytes(B, H) + 64);   // two slots of the K-split kernel + census
   return (size_t)4 * B * H * sizeof(float) + (step > pers ? step : pers);
 }
 
@@ -2030,9 +2084,9 @@ extern "C" int ds2_rnn_poison_seen(const ds2_rnn_ctx* ctx) { return (ctx && ctx-
 // (hipFuncGetAttributes), static LDS bytes, threads}.  Returns 1 if this (gates, H) shape has a K-split instance, 0 if not.  The host
 // uses it to decide whether the co-resident weight-gradient kernel (ds2_gemm_bf16_tn_group: 4 waves x 128 registers) fits beside it.
 extern "C" int ds2_rnn_bwd_ksplit_footprint(int gates, int H, int* out3) {
-  DS2_REQUIRE(out3 && (gates == 3 || gates == 4), "ds2_rnn_bwd_ksplit_footprint: bad args");
+  DS2_REQUIRE(out3 && (gates == 1 || gates == 3 || gates == 4), "ds2_rnn_bwd_ksplit_footprint: bad args");
   out3[0] = out3[1] = out3[2] = 0;
-  if (!ksplit_shape_ok(H)) return 0;
+  if (!ksplit_avail(gates, H)) return 0;                         // (no K-split kernel for the tanh cell: "not available")
   const int nt = H / 128;
   if (nt * gates * 4 > 176) return 0;
   const void* fn = nullptr;
@@ -2077,16 +2131,16 @@ extern "C" int ds2_rnn_persistent_counters(const ds2_rnn_ctx* ctx, int* out2) {
 extern "C" int ds2_rnn_bwd_ex(ds2_rnn_ctx* ctx, int gates, const float* dy, int lddy, float* gx, float* aux, const float* hbuf, const void* wp_bwd,
                               const int* lens_dev, int T, int B, int H, int bf16, void* dgx_bf16, const void* gates_bf16, void* dhn_bf16,
                               float* bias_part, void* ws, size_t ws_bytes, void* stream) {
-  DS2_REQUIRE(gates == 3 || gates == 4, "ds2_rnn_bwd: gates must be 3 (GRU) or 4 (LSTM)");
-  DS2_REQUIRE(dy && aux && hbuf && wp_bwd && lens_dev, "ds2_rnn_bwd: null pointer");
-  DS2_REQUIRE(gx || (gates_bf16 && dgx_bf16), "ds2_rnn_bwd: gx may only be NULL with both gates_bf16 and dgx_bf16 given");
+  DS2_REQUIRE(gates == 1 || gates == 3 || gates == 4, "ds2_rnn_bwd: gates must be 1 (tanh RNN), 3 (GRU) or 4 (LSTM)");
+  DS2_REQUIRE(dy && (aux || gates == 1) && hbuf && wp_bwd && lens_dev, "ds2_rnn_bwd: null pointer");
+  DS2_REQUIRE(gx || ((gates_bf16 || gates == 1) && dgx_bf16), "ds2_rnn_bwd: gx may only be NULL with both gates_bf16 (not for gates = 1) and dgx_bf16 given");
   DS2_REQUIRE(T > 0 && B > 0 && H > 0 && (H % 4) == 0, "ds2_rnn_bwd: need H %% 4 == 0 (H=%d)", H);
   DS2_REQUIRE(ws && ws_bytes >= ds2_rnn_bwd_workspace_bytes(gates, B, H, bf16), "ds2_rnn_bwd: workspace too small");
   RnnArgs a{};
   a.gx = gx; a.aux = aux; a.hbuf = const_cast<float*>(hbuf); a.wp = (const float*)wp_bwd; a.dy = dy; a.lddy = lddy;
   a.dcar = (float*)ws; a.pk = (float*)ws + (size_t)4 * B * H;
   a.dgx_bf = (__bf16*)dgx_bf16;
-  a.gates_bf = (__bf16*)const_cast<void*>(gates_bf16);
+  a.gates_bf = gates == 1 ? nullptr : (__bf16*)const_cast<void*>(gates_bf16);
   a.dhn_bf = (__bf16*)dhn_bf16; a.bsum = bias_part;
   a.lens = lens_dev; a.T = T; a.B = B; a.H = H;
   a.hctx = ctx; a.status = ctx ? ctx->status_dev : nullptr;
@@ -2098,7 +2152,7 @@ extern "C" int ds2_rnn_bwd_ex(ds2_rnn_ctx* ctx, int gates, const float* dy, int 
     a.dbg = ctx ? ctx->debug_flags : 0;
     hipStream_t st = (hipStream_t)stream;
     // bf16: the K-split kernel where the shape qualifies (2 = it does, but a starved launch's cooldown is running: step kernels)
-    int rc = bf16 == 1 ? (gates == 3 ? try_launch_ksplit_bwd<3>(a, st) : try_launch_ksplit_bwd<4>(a, st)) : 0;
+    int rc = (bf16 == 1 && gates != 1) ? (gates == 3 ? try_launch_ksplit_bwd<3>(a, st) : try_launch_ksplit_bwd<4>(a, st)) : 0;
     last_bwd_kind = rc == 1 ? 2 : 0;
     bool split = false;
     if (rc == 0 && bf16 == 2) {
@@ -2108,19 +2162,19 @@ extern "C" int ds2_rnn_bwd_ex(ds2_rnn_ctx* ctx, int gates, const float* dy, int 
         RnnArgs b = a;
         b.wp = reinterpret_cast<const float*>(reinterpret_cast<const char*>(wp_bwd) + ds2_rnn_packed_bytes(gates, H, 1, 0));
         static const char* envk = ds2_exp_getenv("DS2_RNN_KSPLIT");
-        const int rk = (envk && envk[0] == '0') ? 0 : (gates == 3 ? try_launch_ksplit_bwd<3, true>(b, st) : try_launch_ksplit_bwd<4, true>(b, st));
+        const int rk = ((envk && envk[0] == '0') || gates == 1) ? 0 : (gates == 3 ? try_launch_ksplit_bwd<3, true>(b, st) : try_launch_ksplit_bwd<4, true>(b, st));
         if (rk < 0) return rk;
         if (rk == 1) { rc = 1; split = true; last_bwd_kind = 2; }
         else {
-          rc = gates == 3 ? try_launch_persistent_bwd<3, true, true>(b, st) : try_launch_persistent_bwd<4, true, true>(b, st);
+          rc = gates == 1 ? try_launch_persistent_bwd<1, true, true>(b, st) : gates == 3 ? try_launch_persistent_bwd<3, true, true>(b, st) : try_launch_persistent_bwd<4, true, true>(b, st);
           split = rc == 1;
           if (split) last_bwd_kind = 1;
         }
       }
     }
     if (rc == 0) {
-      rc = bf16 == 1 ? (gates == 3 ? try_launch_persistent_bwd<3, true>(a, st) : try_launch_persistent_bwd<4, true>(a, st))
-                     : (gates == 3 ? try_launch_persistent_bwd<3, false>(a, st) : try_launch_persistent_bwd<4, false>(a, st));
+      rc = bf16 == 1 ? (gates == 1 ? try_launch_persistent_bwd<1, true>(a, st) : gates == 3 ? try_launch_persistent_bwd<3, true>(a, st) : try_launch_persistent_bwd<4, true>(a, st))
+                     : (gates == 1 ? try_launch_persistent_bwd<1, false>(a, st) : gates == 3 ? try_launch_persistent_bwd<3, false>(a, st) : try_launch_persistent_bwd<4, false>(a, st));
       last_bwd_kind = rc == 1 ? 1 : 0;
     }
     last_path = (last_path & ~(6 | 16 | 64)) | (rc == 1 ? 2 : 0) | (last_bwd_kind == 2 ? 4 : 0) | (split ? 64 : 0);   // bit 6: the split kernel
@@ -2133,7 +2187,8 @@ extern "C" int ds2_rnn_bwd_ex(ds2_rnn_ctx* ctx, int gates, const float* dy, int 
     if (!(env && env[0] == 'f') && !(a.dbg & ~128)) {
       a.wp = reinterpret_cast<const float*>(reinterpret_cast<const char*>(wp_bwd) + ds2_rnn_packed_bytes(gates, H, 1, 0));
       last_path |= 64;                                            // bit 6 without bit 1: split step kernels
-      return gates == 3 ? launch_steps<3, true, true>(true, a, (hipStream_t)stream) : launch_steps<4, true, true>(true, a, (hipStream_t)stream);
+      return gates == 1 ? launch_steps<1, true, true>(true, a, (hipStream_t)stream)
+                         : gates == 3 ? launch_steps<3, true, true>(true, a, (hipStream_t)stream) : launch_steps<4, true, true>(true, a, (hipStream_t)stream);
     }
   }
   return bf16 == 1 ? dispatch<true>(gates, true, a, (hipStream_t)stream) : dispatch<false>(gates, true, a, (hipStream_t)stream);
@@ -2151,10 +2206,10 @@ static int rnn_bwd_bn_impl(ds2_rnn_ctx* ctx, int gates, const float* dyn, int ld
                               float* aux, const float* hbuf, const void* wp_bwd, const int* lens_dev, int T, int B, int H, int bf16,
                               void* dgx_bf16, const void* gates_bf16, void* dhn_bf16, float* bias_part, void* ws, size_t ws_bytes,
                               void* stream) {
-  DS2_REQUIRE(gates == 3 || gates == 4, "ds2_rnn_bwd_bn: gates must be 3 (GRU) or 4 (LSTM)");
-  DS2_REQUIRE(dyn && bn_x && bn_mean && bn_var && bn_gamma && bn_s0 && bn_s1 && aux && hbuf && wp_bwd && lens_dev,
+  DS2_REQUIRE(gates == 1 || gates == 3 || gates == 4, "ds2_rnn_bwd_bn: gates must be 1 (tanh RNN), 3 (GRU) or 4 (LSTM)");
+  DS2_REQUIRE(dyn && bn_x && bn_mean && bn_var && bn_gamma && bn_s0 && bn_s1 && (aux || gates == 1) && hbuf && wp_bwd && lens_dev,
               "ds2_rnn_bwd_bn: null pointer");
-  DS2_REQUIRE(gx || (gates_bf16 && dgx_bf16), "ds2_rnn_bwd_bn: gx may only be NULL with both gates_bf16 and dgx_bf16 given");
+  DS2_REQUIRE(gx || ((gates_bf16 || gates == 1) && dgx_bf16), "ds2_rnn_bwd_bn: gx may only be NULL with both gates_bf16 (not for gates = 1) and dgx_bf16 given");
   DS2_REQUIRE(T > 0 && B > 0 && H > 0 && (H % 4) == 0, "ds2_rnn_bwd_bn: need H %% 4 == 0 (H=%d)", H);
   DS2_REQUIRE(ws && ws_bytes >= ds2_rnn_bwd_workspace_bytes(gates, B, H, bf16), "ds2_rnn_bwd_bn: workspace too small");
   hipStream_t st = (hipStream_t)stream;
@@ -2170,7 +2225,7 @@ static int rnn_bwd_bn_impl(ds2_rnn_ctx* ctx, int gates, const float* dyn, int ld
     a.prearmed = take_prearmed(ctx);
     a.dbg = ctx ? ctx->debug_flags : 0;
     // (only when the persistent backward is armed: a cool-down call is counted once, by the un-fused call below)
-    const int rc = persist_idle(ctx, true) ? (gates == 3 ? try_launch_ksplit_bwd<3>(a, st) : try_launch_ksplit_bwd<4>(a, st)) : 0;
+    const int rc = (persist_idle(ctx, true) && gates != 1) ? (gates == 3 ? try_launch_ksplit_bwd<3>(a, st) : try_launch_ksplit_bwd<4>(a, st)) : 0;
     if (rc < 0) return rc;
     if (rc == 1) {
       ctx->last_bwd_kind = 2;

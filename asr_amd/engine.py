@@ -182,7 +182,7 @@ def _bn_backward(dxn: Tensor, x: Tensor, mean, var, gamma, dgamma, dbeta, fuse: 
 
 @dataclass
 class ModelCfg:
-    rnn: str            # "gru" | "lstm"
+    rnn: str            # "gru" | "lstm" | "rnn" (Elman cell, tanh: nn.RNN)
     hidden: int
     layers: int
     classes: int
@@ -191,16 +191,16 @@ class ModelCfg:
 
     @property
     def gates(self) -> int:
-        return 3 if self.rnn == "gru" else 4
+        return {"gru": 3, "rnn": 1}.get(self.rnn, 4)
 
 
 @dataclass
 class LayerCtx:
     xin: Optional[Tensor] = None     # (M, I) raw layer input (previous y) — BN backward needs it
     xn: Optional[Tensor] = None      # (M, I) GEMM A operand (BN output, or the raw input for layer 0)
-    gx: Optional[Tensor] = None      # (M, 2GH) gates -> overwritten by dGx in backward
+    gx: Optional[Tensor] = None      # (M, 2GH) gates -> overwritten by dGx in backward (tanh cell: the x-projections, not written by the forward)
     hbuf: Optional[Tensor] = None    # (M, 2H)
-    aux: Optional[Tensor] = None     # (M, 2H)
+    aux: Optional[Tensor] = None     # (M, 2H) (None for the tanh cell: h is its whole saved state)
     mean: Optional[Tensor] = None    # BN batch stats of this layer's INPUT (layers >= 1)
     var: Optional[Tensor] = None
     wpb: Optional[Tensor] = None     # W_hh^T in fragment order for the backward recurrence
@@ -471,7 +471,7 @@ def _backward_rnn_deferred(W, Gr, cfg: ModelCfg, ctx: Ctx, dy, done, private: bo
         l, dgxT, hT, auxT, xnT, ready, hold = p
         main.wait_event(ready)
         dwhh = Gr[f"rnns.{l}.whh_cat"]                                                            # (2, GH, H)
-        rows = 2 * H if G == 3 else 4 * H
+        rows = 2 * H if G == 3 else G * H
         # both directions per launch: direction 0 pairs rows t of dGh with h[t-1], direction 1 rows t with h[t+1] (a column offset of B)
         ka = (slice(B, M), slice(0, M - B))
         kb = (slice(0, M - B), slice(B, M))
@@ -490,7 +490,7 @@ def _backward_rnn_deferred(W, Gr, cfg: ModelCfg, ctx: Ctx, dy, done, private: bo
         operands), the time shift of dW_hh is a ROW offset of B"""
         ops.rnn_bias_grads(G, bias_part, Gr[f"rnns.{l}.bih_cat"], Gr[f"rnns.{l}.bhh_cat"])           # sums over the batch rows
         dwhh = Gr[f"rnns.{l}.whh_cat"]                                                            # (2, GH, H)
-        rows = 2 * H if G == 3 else 4 * H
+        rows = 2 * H if G == 3 else G * H
         # direction 0 pairs dGh[t] with h[t-1], direction 1 dGh[t] with h[t+1]
         ra, rb = (slice(B, M), slice(0, M - B)), (slice(0, M - B), slice(B, M))
         ops.gemm_bf16_tn_pair(dgx_bf[ra[0], 0:rows], dgx_bf[ra[1], G * H:G * H + rows], h_bf[rb[0], 0:H], h_bf[rb[1], H:2 * H], dwhh[:, :rows])
@@ -509,7 +509,7 @@ def _backward_rnn_deferred(W, Gr, cfg: ModelCfg, ctx: Ctx, dy, done, private: bo
         """the products of weight_gradients_tn as ONE launch of the co-resident grouped kernel; on_side: on the side stream, not before
         `start` (an event of the compute stream) — the bucket is reported from that stream, behind the launch"""
         dwhh, dwih = Gr[f"rnns.{l}.whh_cat"], Gr[f"rnns.{l}.wih_cat"]
-        rows = 2 * H if G == 3 else 4 * H
+        rows = 2 * H if G == 3 else G * H
         probs = [(dgx_bf, xn[:, :dwih.shape[1]], dwih),
                  (dgx_bf[B:M, 0:rows], h_bf[0:M - B, 0:H], dwhh[0, :rows]),
                  (dgx_bf[0:M - B, G * H:G * H + rows], h_bf[B:M, H:2 * H], dwhh[1, :rows])]
@@ -570,7 +570,8 @@ def _backward_rnn_deferred(W, Gr, cfg: ModelCfg, ctx: Ctx, dy, done, private: bo
             ready.record(side if on_side else main)
         if on_side:
             for t in (dgx_bf, aux, hbuf, xn):                    # read on the side stream
-                t.record_stream(side)
+                if t is not None:                                # (aux: None for the tanh cell)
+                    t.record_stream(side)
         return (l, dgxT, hT, auxT, xnT, ready, (dgx_bf,))
 
     queued = None                                                # layer whose operand passes wait for the next recurrence launch
@@ -611,7 +612,7 @@ def _backward_rnn_deferred(W, Gr, cfg: ModelCfg, ctx: Ctx, dy, done, private: bo
         if queued_idle is not None:
             start_idle = torch.cuda.Event()                      # the layer above's operands are final; the recurrence launch follows
             start_idle.record(main)
-        dgx_bf = torch.empty(lc.gshape if lc.rec is not None else lc.gx.shape, dtype=torch.bfloat16, device=dev)
+        dgx_bf = torch.empty(lc.gx.shape if lc.gx is not None else lc.gshape, dtype=torch.bfloat16, device=dev)
         want_tn = lc.h_bf is not None
         dhn_bf = torch.empty(M, 2 * H, dtype=torch.bfloat16, device=dev) if (want_tn and G == 3) else None
         bias_part = torch.empty(B, 2, 4, H, dtype=torch.float32, device=dev) if want_tn else None
@@ -720,7 +721,7 @@ def backward(W: Dict[str, Tensor], Gr: Dict[str, Tensor], cfg: ModelCfg, ctx: Ct
         # bf16 mode: the step kernels write dGx in bf16 (row-major) into a side buffer that the GEMMs consume directly (needs
         # B % 8 == 0 for the 16-byte aligned time-shifted operand views below; other batch sizes keep fp32 dGx + a cast pass)
         bfd = bf and B % 8 == 0
-        gshape = lc.gshape if lc.rec is not None else lc.gx.shape
+        gshape = lc.gx.shape if lc.gx is not None else lc.gshape
         dgx_bf = torch.empty(gshape, dtype=torch.bfloat16, device=dy.device) if bfd else None
         rmode = 1 if bf else (2 if (F32_RNN == "split" and H % 32 == 0) else 0)          # (the mode lc.wpb was packed for in forward)
         ops.rnn_bwd(G, dy, lc.gx, lc.aux, lc.hbuf, lc.wpb, lens_dev, T, B, H, bf16=rmode, dgx_bf16=dgx_bf, gates_bf16=lc.rec)
@@ -778,7 +779,7 @@ def backward(W: Dict[str, Tensor], Gr: Dict[str, Tensor], cfg: ModelCfg, ctx: Ct
                 if T > 1 and bfd:
                     # bf16 MFMA path: transposed bf16 copies (dgxT: (2GH, M)), the time shift is a column offset of B elements
                     hT = ops.cast_transpose_bf16(lc.hbuf)                                             # (2H, M)
-                    rows = 2 * H if G == 3 else 4 * H
+                    rows = 2 * H if G == 3 else G * H
                     # both directions per launch: direction 0 pairs rows t of dGh with h[t-1], direction 1 rows t with h[t+1]
                     ka = (slice(B, M), slice(0, M - B))
                     kb = (slice(0, M - B), slice(B, M))
@@ -794,7 +795,7 @@ def backward(W: Dict[str, Tensor], Gr: Dict[str, Tensor], cfg: ModelCfg, ctx: Ct
                     Ip = lc.xs.shape[1] // 3
                     hs = ops.split_bf16(lc.hbuf, 2)                                                   # (M, 4H) = [hi | lo]
                     d_hi, d_lo, h_hi, h_lo = dgs[:, :C2], dgs[:, 2 * C2:], hs[:, :2 * H], hs[:, 2 * H:]
-                    rows = 2 * H if G == 3 else 4 * H
+                    rows = 2 * H if G == 3 else G * H
                     ra, rb = (slice(B, M), slice(0, M - B)), (slice(0, M - B), slice(B, M))
                     probs = []
                     for d in (0, 1):
@@ -826,7 +827,7 @@ def backward(W: Dict[str, Tensor], Gr: Dict[str, Tensor], cfg: ModelCfg, ctx: Ct
                     a1 = dgx.data_ptr() + 4 * (G * H)                   # dir 1: rows t <= T-2, column block of dir 1
                     b1 = lc.hbuf.data_ptr() + 4 * (H + B * ldh)         #        h[t+1]
                     sA, sB = (a1 - a0) // 4, (b1 - b0) // 4
-                    rows = 2 * H if G == 3 else 4 * H
+                    rows = 2 * H if G == 3 else G * H
                     ops.gemm_raw(True, False, rows, H, K, a0, ldg, sA, b0, ldh, sB, dwhh.data_ptr(), H, G * H * H, dgx.device, batch=2)
                     if G == 3:  # n-gate rows use d(hn) (aux) instead of dGx_n
                         x0 = lc.aux.data_ptr() + 4 * (B * ldh)

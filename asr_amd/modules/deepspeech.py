@@ -91,7 +91,7 @@ class DeepSpeech(nn.Module):
         self._flat: Optional[FlatParams] = None
         self._on_bucket = None          # DP hook: called as each layer's gradients become final
         self._param_names = [n for n, _ in self.named_parameters()]
-        kind = {nn.GRU: "gru", nn.LSTM: "lstm"}.get(self.rnn_type)
+        kind = {nn.GRU: "gru", nn.LSTM: "lstm", nn.RNN: "rnn"}.get(self.rnn_type)
         self._cfg = engine.ModelCfg(rnn=kind or "unsupported", hidden=rnn_hidden_size, layers=rnn_hidden_layers,
                                     classes=self.num_classes, freq=int(math.floor(self.sample_rate * self.window_size / 2) + 1))
 
@@ -175,8 +175,8 @@ class DeepSpeech(nn.Module):
         if not self.bidirectional:
             return self._forward_unidirectional(x, output_lengths)
         if self._cfg.rnn == "unsupported":
-            raise NotImplementedError("only GRU / LSTM cells have MI355X kernels (asr_deepspeech.vars.supported_rnns lists nn.RNN too: use "
-                                      "asr_deepspeech.modules.DeepSpeech for that cell)")
+            raise NotImplementedError(f"no MI355X kernels for rnn_type {self.rnn_type!r}: the cells of asr_amd.vars.supported_rnns "
+                                      "(nn.GRU, nn.LSTM, nn.RNN) are")
         if not x.is_cuda:
             raise _lib.DS2LibraryError(
                 "asr_amd.DeepSpeech.forward needs GPU input: the MI355X HIP kernels are the only implementation. "

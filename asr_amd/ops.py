@@ -1046,6 +1046,7 @@ def rnn_persistent_counters(device=None):
 def rnn_fwd(gates: int, gx: Tensor, wp_fwd: Tensor, bhh: Tensor, lens_dev: Tensor, T: int, B: int, H: int, bf16=False,
             packed_gates: bool = False, h_bf16: Optional[Tensor] = None, hsum: Optional[Tensor] = None, ws: Optional[Tensor] = None):
     """gx (T*B, 2*G*H) in/out; returns (hbuf (T*B, 2H), aux (T*B, 2H)[, gates_bf (T*B, 2H, 4) bf16]).
+    gates = 1 (tanh cell): gx stays the x-projections and h is the whole saved state — aux and gates_bf are returned as None.
     bf16: False / 0 fp32, True / 1 bf16 operands, 2 = fp32 mode with the split persistent kernel (h and W_hh as hi + lo bf16 planes, three MFMAs
     per product: fp32-grade results at the bf16 matrix rate; wp_fwd from rnn_pack(bf16=2); rnn_last_path() & 32 when it took the call).
     packed_gates: the saved-for-backward gates go to one 8-byte bf16 record per hidden unit (gx keeps the x-projections; GRU aux
@@ -1059,8 +1060,8 @@ def rnn_fwd(gates: int, gx: Tensor, wp_fwd: Tensor, bhh: Tensor, lens_dev: Tenso
         assert h_bf16.dtype == torch.bfloat16 and h_bf16.is_contiguous() and h_bf16.numel() == T * B * 2 * H
     lib = _lib.load()
     hbuf = torch.empty(T * B, 2 * H, dtype=torch.float32, device=gx.device)
-    aux = torch.empty_like(hbuf)
-    rec = torch.empty(T * B, 2 * H, 4, dtype=torch.bfloat16, device=gx.device) if packed_gates else None
+    aux = torch.empty_like(hbuf) if gates != 1 else None
+    rec = torch.empty(T * B, 2 * H, 4, dtype=torch.bfloat16, device=gx.device) if (packed_gates and gates != 1) else None
     wsb = lib.ds2_rnn_fwd_workspace_bytes(B, H, int(bf16))
     ws, armed = _take_ws(ws, wsb, gx.device)
     if gx.dtype == torch.bfloat16 or hsum is not None:
@@ -1072,7 +1073,7 @@ def rnn_fwd(gates: int, gx: Tensor, wp_fwd: Tensor, bhh: Tensor, lens_dev: Tenso
         gxf = None if gxb is not None else gx
         for _attempt in (0, 1):
             rc = _rnn_call(gx.device, armed and _attempt == 0, lambda: lib.ds2_rnn_fwd_x(
-                _ctxp(gx.device), gates, _ptr(gxf), _ptr(gxb), wp_fwd.data_ptr(), bhh.data_ptr(), hbuf.data_ptr(), aux.data_ptr(),
+                _ctxp(gx.device), gates, _ptr(gxf), _ptr(gxb), wp_fwd.data_ptr(), bhh.data_ptr(), hbuf.data_ptr(), _ptr(aux),
                 lens_dev.data_ptr(), T, B, H, _ptr(rec), _ptr(h_bf16), _ptr(hsum), ws.data_ptr(), wsb, _stream()))
             if rc != 1:
                 break
@@ -1081,7 +1082,7 @@ def rnn_fwd(gates: int, gx: Tensor, wp_fwd: Tensor, bhh: Tensor, lens_dev: Tenso
         return hbuf, aux, rec
     _chk_f32(gx)
     _lib.check(_rnn_call(gx.device, armed, lambda: lib.ds2_rnn_fwd_ex(
-        _ctxp(gx.device), gates, gx.data_ptr(), wp_fwd.data_ptr(), bhh.data_ptr(), hbuf.data_ptr(), aux.data_ptr(),
+        _ctxp(gx.device), gates, gx.data_ptr(), wp_fwd.data_ptr(), bhh.data_ptr(), hbuf.data_ptr(), _ptr(aux),
         lens_dev.data_ptr(), T, B, H, int(bf16), _ptr(rec), _ptr(h_bf16), ws.data_ptr(), wsb, _stream())), "ds2_rnn_fwd")
     return (hbuf, aux, rec) if packed_gates else (hbuf, aux)
 
@@ -1108,13 +1109,14 @@ def rnn_last_path(device=None) -> int:
     return _lib.load().ds2_rnn_last_path(_ctxp(device))
 
 
-def rnn_bwd(gates: int, dy: Tensor, gx: Optional[Tensor], aux: Tensor, hbuf: Tensor, wp_bwd: Tensor, lens_dev: Tensor, T: int, B: int, H: int,
+def rnn_bwd(gates: int, dy: Tensor, gx: Optional[Tensor], aux: Optional[Tensor], hbuf: Tensor, wp_bwd: Tensor, lens_dev: Tensor, T: int, B: int, H: int,
             bf16: bool = False, dgx_bf16: Optional[Tensor] = None, gates_bf16: Optional[Tensor] = None, dhn_bf16: Optional[Tensor] = None,
             bias_part: Optional[Tensor] = None, ws: Optional[Tensor] = None):
     """dgx_bf16: optional (T*B, 2*G*H) bf16 buffer that receives dGx (then `gx` keeps the gates).
     gates_bf16: the packed records of rnn_fwd(packed_gates=True), read instead of gx / GRU aux (gx may then be None).
     dhn_bf16 (GRU, (T*B, 2H) bf16 copy of d(hn)) and bias_part ((B, 2, 4, H) fp32 per-batch-row sums over time of the gate gradients):
-    optional outputs of a persistent launch only (rnn_last_path() & 2)."""
+    optional outputs of a persistent launch only (rnn_last_path() & 2).
+    gates = 1 (tanh cell): aux is None and no gate record exists (h comes from hbuf); gx may be None when dgx_bf16 is given."""
     _chk_f32(dy, gx, aux, hbuf, bias_part)
     if dgx_bf16 is not None:
         assert dgx_bf16.dtype == torch.bfloat16 and dgx_bf16.is_contiguous() and dgx_bf16.numel() == T * B * 2 * gates * H
@@ -1124,12 +1126,13 @@ def rnn_bwd(gates: int, dy: Tensor, gx: Optional[Tensor], aux: Tensor, hbuf: Ten
         assert dhn_bf16.dtype == torch.bfloat16 and dhn_bf16.is_contiguous() and dhn_bf16.numel() == T * B * 2 * H
     if bias_part is not None:
         assert bias_part.is_contiguous() and bias_part.numel() == B * 2 * 4 * H
-    assert gx is not None or (dgx_bf16 is not None and gates_bf16 is not None)
+    assert gx is not None or (dgx_bf16 is not None and (gates_bf16 is not None or gates == 1))
+    assert aux is not None or gates == 1
     lib = _lib.load()
     wsb = lib.ds2_rnn_bwd_workspace_bytes(gates, B, H, int(bf16))
     ws, armed = _take_ws(ws, wsb, dy.device)
     _lib.check(_rnn_call(dy.device, armed, lambda: lib.ds2_rnn_bwd_ex(
-        _ctxp(dy.device), gates, dy.data_ptr(), _row_pitch(dy), _ptr(gx), aux.data_ptr(), hbuf.data_ptr(), wp_bwd.data_ptr(),
+        _ctxp(dy.device), gates, dy.data_ptr(), _row_pitch(dy), _ptr(gx), _ptr(aux), hbuf.data_ptr(), wp_bwd.data_ptr(),
         lens_dev.data_ptr(), T, B, H, int(bf16), _ptr(dgx_bf16), _ptr(gates_bf16), _ptr(dhn_bf16), _ptr(bias_part),
         ws.data_ptr(), wsb, _stream())), "ds2_rnn_bwd")
 
@@ -1153,7 +1156,7 @@ def bn1d_bwd_sums(dY: Tensor, X: Tensor, mean: Tensor, var: Tensor, gamma: Tenso
     return s0, s1
 
 
-def rnn_bwd_bn(gates: int, dyn: Tensor, bn_x: Tensor, mean: Tensor, var: Tensor, gamma: Tensor, sums: Tensor, gx: Optional[Tensor], aux: Tensor,
+def rnn_bwd_bn(gates: int, dyn: Tensor, bn_x: Tensor, mean: Tensor, var: Tensor, gamma: Tensor, sums: Tensor, gx: Optional[Tensor], aux: Optional[Tensor],
                hbuf: Tensor, wp_bwd: Tensor, lens_dev: Tensor, T: int, B: int, H: int, bf16: bool = False, dgx_bf16: Optional[Tensor] = None,
                gates_bf16: Optional[Tensor] = None, dhn_bf16: Optional[Tensor] = None, bias_part: Optional[Tensor] = None, ws: Optional[Tensor] = None):
     """rnn_bwd for a layer whose output feeds a BatchNorm1d: `dyn` is the gradient wrt the BatchNorm's OUTPUT, `bn_x` its input, `sums` the
@@ -1169,7 +1172,7 @@ def rnn_bwd_bn(gates: int, dyn: Tensor, bn_x: Tensor, mean: Tensor, var: Tensor,
     ws, armed = _take_ws(ws, wsb, dyn.device)
     def call(scratch):
         return _rnn_call(dyn.device, armed and scratch is None, lambda: (lib.ds2_rnn_bwd_bn_xbf16 if xbf else lib.ds2_rnn_bwd_bn)(_ctxp(dyn.device), gates, dyn.data_ptr(), _row_pitch(dyn), bn_x.data_ptr(), bn_x.stride(0), mean.data_ptr(), var.data_ptr(),
-                                  gamma.data_ptr(), s0.data_ptr(), s1.data_ptr(), BN_EPS, _ptr(scratch), _ptr(gx), aux.data_ptr(),
+                                  gamma.data_ptr(), s0.data_ptr(), s1.data_ptr(), BN_EPS, _ptr(scratch), _ptr(gx), _ptr(aux),
                                   hbuf.data_ptr(), wp_bwd.data_ptr(), lens_dev.data_ptr(), T, B, H, int(bf16), _ptr(dgx_bf16), _ptr(gates_bf16),
                                   _ptr(dhn_bf16), _ptr(bias_part), ws.data_ptr(), wsb, _stream()))
     rc = call(None)                  # the fused K-split launch needs no scratch: the (T*B, H) fp32 buffer is allocated only on the fallback (rc 1)

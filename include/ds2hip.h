@@ -257,9 +257,13 @@ int ds2_conv2_wgrad_bf16(const void* a1p, const void* dy2p, const int* lens_dev,
 int ds2_conv2_wgrad_nhwc_bf16(const void* a1_nhwc, const void* dy2_nhwc, const int* lens_dev, float* dW2, int B, int D1, int T, void* ws,
                               size_t ws_bytes, void* stream);
 
-/* ---- bidirectional GRU / LSTM recurrence -------------------------------------------------------
- * pack_padded_sequence -> aten::gru / aten::lstm -> pad_packed_sequence, modules/blocks.py:87-89, h0 = 0,
- * gate order r,z,n (GRU) / i,f,g,o (LSTM); gates = 3 | 4.  See asr_amd/csrc/rnn.hip for buffer roles. */
+/* ---- bidirectional GRU / LSTM / tanh-RNN recurrence ----------------------------------------------
+ * pack_padded_sequence -> aten::gru / aten::lstm / aten::rnn_tanh -> pad_packed_sequence, modules/blocks.py:87-89, h0 = 0,
+ * gate order r,z,n (GRU) / i,f,g,o (LSTM); gates = 3 | 4 | 1 (nn.RNN, tanh: h_t = tanh(x W_ih^T + b_ih + h W_hh^T + b_hh)).
+ * gates = 1: h is the whole saved-for-backward state — aux may be NULL and is never touched, gates_bf16 is ignored (no record), the forward
+ * leaves gx as it is (the x-projections) and the backward writes dGx = d(pre-activation) into gx or dgx_bf16 (gx may be NULL when
+ * dgx_bf16 is given).  The K-split backward and the ten-unit-slice forward have no gates = 1 instance (the K-split footprint reports 0).
+ * See asr_amd/csrc/rnn.hip for buffer roles. */
 size_t ds2_rnn_packed_bytes(int gates, int H, int which /*0: forward operand, 1: backward operand*/, int bf16);
 /* re-pack W_hh = [weight_hh_l0 ; weight_hh_l0_reverse] (2,G*H,H) fp32 into MFMA-fragment order, fp32 or bf16 fragments
  * (once per optimizer step).  bf16 = 2 (here, in ds2_rnn_packed_bytes, ds2_rnn_fwd_workspace_bytes and ds2_rnn_fwd*): the fp32 mode with the
@@ -337,7 +341,8 @@ int ds2_rnn_bwd(ds2_rnn_ctx* ctx, int gates, const float* dy, int lddy, float* g
  * is given dhn_bf16 writes ONLY that bf16 copy of d(W_hn h + b_hn), not the fp32 one into aux.
  * ds2_rnn_bwd plus two optional outputs of a PERSISTENT launch (check ds2_rnn_last_path() & 2 after the call; untouched otherwise):
  * dhn_bf16 (GRU): (T,B,2,H) bf16 copy of d(W_hn h + b_hn); bias_part: (B,2,4,H) fp32 per-batch-row sums over time of
- * [d r, d z, d n, d(hn)] (GRU) / [d i, d f, d g, d o] (LSTM) - their column sums over B are the bias gradients, so no pass over dGx. */
+ * [d r, d z, d n, d(hn)] (GRU) / [d i, d f, d g, d o] (LSTM) / [d pre, -, -, -] (tanh cell: slot 0 only is written) - their column sums
+ * over B are the bias gradients, so no pass over dGx. */
 int ds2_rnn_bwd_ex(ds2_rnn_ctx* ctx, int gates, const float* dy, int lddy, float* gx, float* aux, const float* hbuf, const void* wp_bwd, const int* lens_dev,
                    int T, int B, int H, int bf16, void* dgx_bf16, const void* gates_bf16, void* dhn_bf16, float* bias_part, void* ws,
                    size_t ws_bytes, void* stream);
@@ -362,7 +367,7 @@ int ds2_rnn_bwd_bn_xbf16(ds2_rnn_ctx* ctx, int gates, const float* dyn, int lddy
                          const void* gates_bf16, void* dhn_bf16, float* bias_part, void* ws, size_t ws_bytes, void* stream);
 
 /* bias gradients of one recurrent layer from ds2_rnn_bwd_ex's bias_part (B,2,4,H): db_ih (2,G*H) [bias_ih_l0 | bias_ih_l0_reverse] and
- * db_hh (2,G*H); GRU: db_ih = [d r, d z, d n], db_hh = [d r, d z, d(hn)]; LSTM: both = [d i, d f, d g, d o]. */
+ * db_hh (2,G*H); GRU: db_ih = [d r, d z, d n], db_hh = [d r, d z, d(hn)]; LSTM: both = [d i, d f, d g, d o]; tanh cell: both = [d pre]. */
 int ds2_rnn_bias_grads(int gates, const float* bias_part, int B, int H, float* dbih, float* dbhh, void* stream);
 
 /* ---- log-softmax + CTC loss + gradient ---------------------------------------------------------
