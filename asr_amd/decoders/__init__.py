@@ -1,5 +1,5 @@
-"""Greedy CTC decoder + WER/CER (host-side mirror of asr_deepspeech/decoders/{decoder,greedy_decoder}.py).
-`decode()` runs on the GPU (csrc/decode.hip); process_string / convert_to_strings are the host utilities the
+"""Greedy and beam CTC decoders + WER/CER (host-side mirror of asr_deepspeech/decoders/{decoder,greedy_decoder,beam_decoder}.py).
+`decode()` runs on the GPU (csrc/decode.hip, csrc/ctc_beam.h); process_string / convert_to_strings are the host utilities the
 reference uses for TARGET strings.  Eval-only, not on the train step.
 The edit distance is a small pure-Python DP (the reference imports the `Levenshtein` C package)."""
 from __future__ import annotations
@@ -104,8 +104,61 @@ class GreedyDecoder(Decoder):
         return strings, offsets
 
 
-def _device():
+class BeamCTCDecoder(Decoder):
+    """beam_decoder.py: the reference's constructor and decode(), without its external `ctcdecode` dependency.  The prefix beam search
+    runs as one HIP kernel (`ds2_ctc_beam_decode_f32`, contract in include/ds2hip.h).  There is no language-model scorer: `lm_path`
+    must be None; `alpha`, `beta` and `num_processes` are accepted and unused, as in a scorer-less ctcdecode."""
+
+    def __init__(self, labels, lm_path=None, alpha=0, beta=0, cutoff_top_n=40, cutoff_prob=1.0, beam_width=100, num_processes=4,
+                 blank_index=0):
+        if lm_path is not None:
+            raise NotImplementedError("BeamCTCDecoder: language-model scoring (lm_path) is not implemented; pass lm_path=None")
+        super().__init__(labels, blank_index)
+        self.lm_path, self.alpha, self.beta, self.num_processes = lm_path, alpha, beta, num_processes
+        self.cutoff_top_n, self.cutoff_prob, self.beam_width = int(cutoff_top_n), float(cutoff_prob), int(beam_width)
+        self.last_scores = None
+
+    def _char(self, i):
+        return " " if i == self.space_index else self.int_to_char.get(i, "")
+
+    def convert_to_strings(self, out, seq_len):
+        """beam_decoder.py: out[b][k] label ids, seq_len[b][k] their lengths -> strings[b][k]."""
+        return [["".join(self._char(int(i)) for i in (utt[:int(seq_len[b][k])].tolist() if torch.is_tensor(utt) else utt[:int(seq_len[b][k])]))
+                 for k, utt in enumerate(batch)] for b, batch in enumerate(out)]
+
+    def convert_tensor(self, offsets, sizes):
+        """beam_decoder.py: offsets[b][k] cut to sizes[b][k] (an empty int tensor for an empty beam)."""
+        return [[torch.as_tensor(utt[:int(sizes[b][k])], dtype=torch.int) for k, utt in enumerate(batch)] for b, batch in enumerate(offsets)]
+
+    def decode(self, probs, sizes=None):
+        """probs (B,T,C) probabilities -> (strings[b][k], offsets[b][k]), best beam first, beam_width entries per utterance
+        (an empty string past the surviving beams).  One device->host copy; the beams' log-probabilities stay in
+        `last_scores` (B, beam_width) on the host.  Host tensors are uploaded first: there is no CPU implementation."""
+        from .. import ops
+        probs = torch.as_tensor(probs)
+        if not probs.is_cuda:
+            probs = probs.to(_device("BeamCTCDecoder"))
+        probs = probs.float()
+        if probs.stride(2) != 1:
+            probs = probs.contiguous()
+        if sizes is not None:
+            sizes = torch.as_tensor(sizes)
+        labels, offs, lens, scores = ops.ctc_beam_decode(probs, sizes, self.blank_index, self.beam_width, self.cutoff_top_n,
+                                                         self.cutoff_prob)
+        B, K, T = labels.shape
+        host = torch.cat((labels.reshape(-1), offs.reshape(-1), lens.reshape(-1), scores.view(torch.int32).reshape(-1))).cpu()
+        if ops.rnn_poison_seen(labels.device):
+            # as in GreedyDecoder.decode: a poisoned forward (a starved persistent recurrence launch) raises here
+            ops.rnn_persistent_check(labels.device)
+        n = B * K * T
+        labels_h, offs_h = host[:n].view(B, K, T), host[n:2 * n].view(B, K, T)
+        lens_h = host[2 * n:2 * n + B * K].view(B, K)
+        self.last_scores = host[2 * n + B * K:].view(torch.float32).view(B, K).clone()
+        return self.convert_to_strings(labels_h, lens_h), self.convert_tensor(offs_h, lens_h)
+
+
+def _device(who="GreedyDecoder"):
     from .._lib import DS2LibraryError
     if not torch.cuda.is_available():
-        raise DS2LibraryError("GreedyDecoder.decode needs a GPU (no CPU fallback exists)")
+        raise DS2LibraryError(f"{who}.decode needs a GPU (no CPU fallback exists)")
     return torch.device("cuda", torch.cuda.current_device())

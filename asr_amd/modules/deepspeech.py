@@ -250,6 +250,7 @@ class DeepSpeech(nn.Module):
     # -- evaluation loop (deepspeech.py:161-273) --------------------------------------------------
     def evaluate(self, loader=None, manifest=None, batch_size=None, device="auto", num_workers=32, verbose=False, half=False,
                  output_file=None, main_proc=True, **_unused):
+        from ..decoders import BeamCTCDecoder, GreedyDecoder
         device = resolve_device(device)
         with torch.no_grad():
             if loader is None:
@@ -275,7 +276,8 @@ class DeepSpeech(nn.Module):
                 out, output_sizes = self.forward(inputs, input_sizes)
                 decoded_output, _ = decoder.decode(out, output_sizes)   # (copies to the host: the device is idle behind it)
                 ops.rnn_persistent_check(inputs.device)                 # raise if a persistent recurrence of this batch starved (the logits are NaN then)
-                target_strings = decoder.convert_to_strings(split_targets)
+                # a BeamCTCDecoder's convert_to_strings takes (beams, lengths): the targets are spelt by the greedy one on the same labels
+                target_strings = (GreedyDecoder(self.labels) if isinstance(decoder, BeamCTCDecoder) else decoder).convert_to_strings(split_targets)
                 if output_file is not None:
                     output_data.append((out.detach().cpu().numpy(), output_sizes.numpy(), target_strings))
                 for i in range(len(target_strings)):

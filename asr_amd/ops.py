@@ -1242,7 +1242,9 @@ def greedy_decode(probs: Tensor, sizes: Tensor | None = None, blank: int = 0):
     B, T, C = probs.shape
     dev = probs.device
     if sizes is not None:
-        sizes = sizes.to(device=dev, dtype=torch.int32).contiguous()
+        if sizes.numel() != B:
+            raise ValueError(f"sizes has {sizes.numel()} entries for a batch of {B}")
+        sizes = sizes.to(device=dev, dtype=torch.int32).contiguous().view(-1)
     ids = torch.empty((B, T), dtype=torch.int32, device=dev)
     offs = torch.empty((B, T), dtype=torch.int32, device=dev)
     lens = torch.empty((B,), dtype=torch.int32, device=dev)
@@ -1253,6 +1255,36 @@ def greedy_decode(probs: Tensor, sizes: Tensor | None = None, blank: int = 0):
                                          sizes.data_ptr() if sizes is not None else None, blank, ids.data_ptr(), offs.data_ptr(),
                                          lens.data_ptr(), ws.data_ptr(), n, _stream()), "ds2_greedy_decode_f32")
     return ids, offs, lens
+
+
+def ctc_beam_decode(probs: Tensor, sizes: Tensor | None = None, blank: int = 0, beam_width: int = 100, cutoff_top_n: int = 40,
+                    cutoff_prob: float = 1.0):
+    """CTC prefix beam search (no language model) of probs (B,T,C) fp32 on the GPU -> (labels (B,K,T) i32, offsets (B,K,T) i32,
+    lengths (B,K) i32, scores (B,K) fp32), all on the GPU, best beam first (contract: include/ds2hip.h)."""
+    _chk_f32(probs)
+    if probs.dim() != 3 or probs.stride(2) != 1:
+        raise ValueError("ctc_beam_decode: probs must be (B,T,C) with a contiguous class dim")
+    lib = _lib.load()
+    K = int(beam_width)
+    if not 1 <= K <= lib.ds2_ctc_beam_max_width():
+        raise ValueError(f"ctc_beam_decode: beam_width {K} outside the supported 1..{lib.ds2_ctc_beam_max_width()}")
+    B, T, C = probs.shape
+    dev = probs.device
+    if sizes is not None:
+        if sizes.numel() != B:
+            raise ValueError(f"sizes has {sizes.numel()} entries for a batch of {B}")
+        sizes = sizes.to(device=dev, dtype=torch.int32).contiguous().view(-1)
+    labels = torch.empty((B, K, T), dtype=torch.int32, device=dev)
+    offs = torch.empty((B, K, T), dtype=torch.int32, device=dev)
+    lens = torch.empty((B, K), dtype=torch.int32, device=dev)
+    scores = torch.empty((B, K), dtype=torch.float32, device=dev)
+    n = lib.ds2_ctc_beam_workspace_bytes(B, T, K)
+    ws = _ws(n, dev)
+    _lib.check(lib.ds2_ctc_beam_decode_f32(probs.data_ptr(), probs.stride(0), probs.stride(1), B, T, C,
+                                           sizes.data_ptr() if sizes is not None else None, int(blank), K, int(cutoff_top_n),
+                                           float(cutoff_prob), labels.data_ptr(), offs.data_ptr(), lens.data_ptr(), scores.data_ptr(),
+                                           ws.data_ptr(), n, _stream()), "ds2_ctc_beam_decode_f32")
+    return labels, offs, lens, scores
 
 
 _BASIS_CACHE = {}

@@ -394,6 +394,31 @@ size_t ds2_greedy_decode_workspace_bytes(int B, int T);
 int ds2_greedy_decode_f32(const float* probs, long long ld_b, long long ld_t, int B, int T, int C, const int* sizes_dev, int blank,
                           int* ids, int* offs, int* out_len, void* ws, size_t ws_bytes, void* stream);
 
+/* CTC prefix beam search without a language model; replaces BeamCTCDecoder.decode, decoders/beam_decoder.py (which calls the
+ * external ctcdecode package).  One workgroup per utterance runs every frame in one launch (csrc/ctc_beam.h).
+ * Contract, in natural log (log 0 = -inf), logaddexp written (+):
+ *  - every prefix l (labels without blanks) carries pb (paths ending in blank) and pnb (ending in l's last label e);
+ *    total = pb (+) pnb; the start is the empty prefix with pb = 0, pnb = -inf;
+ *  - per frame the classes are sorted by probability, highest first, ties to the lower index; at most cutoff_top_n are kept,
+ *    and if cutoff_prob < 1 the list stops after the first class at which the running sum reaches cutoff_prob (the blank
+ *    is pruned like any class);
+ *  - for every beam l and kept class c with log-prob lp, into fresh -inf accumulators: c == blank: pb'(l) (+)= total(l) + lp;
+ *    c == e: pnb'(l) (+)= pnb(l) + lp and pnb'(l+c) (+)= pb(l) + lp; otherwise pnb'(l+c) (+)= total(l) + lp.  Contributions to
+ *    the same prefix are summed whichever beam they came from; a prefix with total -inf drops out;
+ *  - the beam_width (K) prefixes with the highest total survive; ties: shorter prefix first, then the lexicographically
+ *    smaller class-index sequence.  A prefix that was a beam keeps its offsets, a new l+c gets offsets(l) followed by t;
+ *  - after frame sizes[b]-1 the survivors, in that order, fill the K output slots; empty slots have length 0, score -inf.
+ * probs (B,T,C) fp32 probabilities with element strides ld_b, ld_t (C contiguous); sizes_dev (B) int32 or NULL (= T; 0 leaves
+ * only the empty prefix).  Outputs: labels / offsets (B,K,T) int32 (zero past each length), lens (B,K) int32, scores (B,K) fp32,
+ * best beam first.  Accuracy: fp32 on the device against the fp64 restatement tests/ctc_beam_oracle.py.
+ * Limits: 1 <= K <= ds2_ctc_beam_max_width() (256), 2 <= C <= 16384, T < 2^20, cutoff_top_n >= 1.  The workspace holds the prefix
+ * back-pointers (parent, label, frame per node, at most T*K nodes per utterance): ds2_ctc_beam_workspace_bytes = 12*B*T*K. */
+int ds2_ctc_beam_max_width(void);
+size_t ds2_ctc_beam_workspace_bytes(int B, int T, int beam_width);
+int ds2_ctc_beam_decode_f32(const float* probs, long long ld_b, long long ld_t, int B, int T, int C, const int* sizes_dev, int blank,
+                            int beam_width, int cutoff_top_n, float cutoff_prob, int* labels, int* offsets, int* lens, float* scores,
+                            void* ws, size_t ws_bytes, void* stream);
+
 /* conv1 in bf16 mode (Conv2d(1,32,(41,11),s=(2,2),p=(20,5)), deepspeech.py:61, forward + weight gradient; conv1 has no data
  * gradient).  ds2_conv1_gather_bf16 builds the two bf16 operand images from the spectrogram batch: XB (B,F,P) = the rows themselves as
  * bf16, XB[..][7 + s] = x[..][s] with zeros in front and behind (P = ds2_conv1_bf16_row_pitch(T)) for the forward — the 16 taps of an output
