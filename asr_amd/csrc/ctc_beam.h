@@ -6,6 +6,9 @@
 //   c == blank: pb'(l) += total(l) + lp;   c == e: pnb'(l) += pnb(l) + lp, pnb'(l+c) += pb(l) + lp;
 //   otherwise:  pnb'(l+c) += total(l) + lp
 // and the K prefixes with the highest total = logaddexp(pb, pnb) survive (ties: shorter first, then smaller label sequence).
+// ctc_beam_kernel<PROF, true> is the language-model arm (ds2_ctc_beam_decode_lm_f32): the LM terms of ctc_lm.h ride in pnb of
+// each extension, every beam is extended by every kept class (no staircase) and, in word mode, the survivors are re-scored and
+// re-sorted after the last frame.  LM = false takes no extra kernel argument and compiles to the kernel without that arm.
 //
 // Per frame, inside the workgroup (256 threads, all state in LDS):
 //  1. class keys (prob bits, index) of the frame's row, block bitonic sort, running-sum cutoff by wave 0, the threshold key
@@ -44,7 +47,9 @@
 #error "ctc_beam.h defines the ds2_ctc_beam_* entry points: it is compiled once, as part of decode.hip"
 #endif
 #include "common.h"
+#include "ctc_lm.h"
 #include <stdio.h>
+#include <string.h>
 
 namespace {
 
@@ -228,13 +233,92 @@ struct CandLess {
 
 // PROF: thread 0 stamps the 100 MHz wall clock after each step's closing barrier and writes, per utterance, the ticks of
 // [prune classes, generate candidates, sort candidates, select], the chain walks and their steps, and the frame count.
-template <bool PROF>
+// LM arm (LM = true): shallow fusion with the packed n-gram model of ctc_lm.h.  Per-beam LM state sits in LDS after the no-LM
+// layout (LmBeams, one per beam buffer) and the kept non-blank class list is sized for every kept class (the full grid).
+struct LmArgs {
+  const void* blob;
+  float alpha, beta;
+  int m, mode, space, nbl;   // context length (order - 1), ds2lm::MODE_*, space label (word mode), non-blank list capacity
+};
+
+constexpr int LM_CTX = ds2lm::MAX_ORDER - 1;
+
+struct LmBeams {
+  int* ctx;     // K x LM_CTX: the last m tokens, oldest first (<s>-padded)
+  float* bow;   // K x LM_CTX: log10 backoff of every suffix of ctx (ds2lm::context_backoffs)
+  int* node;    // trie node of the partial word (word mode)
+  float* lmb;   // the LM bonus added when the beam's last label was appended
+};
+
+__host__ __device__ inline size_t lm_beams_bytes(int K) { return (size_t)(2 * LM_CTX + 2) * 4 * K; }
+__host__ __device__ inline size_t lm_layout_total(const Layout& L, int nbl) {
+  return Layout::align_up(L.total, 16) + 2 * lm_beams_bytes(L.K) + 8 * (size_t)nbl;
+}
+
+__device__ inline LmBeams lm_beams_at(char* smem, const Layout& L, int which) {
+  char* p = smem + Layout::align_up(L.total, 16) + which * lm_beams_bytes(L.K);
+  LmBeams s;
+  s.ctx = (int*)p;
+  s.bow = (float*)(s.ctx + LM_CTX * L.K);
+  s.node = (int*)(s.bow + LM_CTX * L.K);
+  s.lmb = (float*)(s.node + L.K);
+  return s;
+}
+
+// the LM term of the extension l -> l+c for a beam in state (ctx, bow, node) with length len and last label `last`;
+// -inf when word mode's dictionary rules out the extension
+__device__ inline float lm_bonus(const ds2lm::LmView& v, const LmArgs& a, const int* ctx, const float* bow, int node, int len, int last,
+                                 int c) {
+  if (a.mode == ds2lm::MODE_CHAR) return a.alpha * ds2lm::cond_score(v, ctx, bow, a.m, v.label_tok[c]) + a.beta;
+  if (c != a.space) return ds2lm::trie_child(v, node, c) >= 0 ? 0.f : -INFINITY;
+  const int w = v.word_of[node];   // the root (empty partial) is no word: no leading or double space
+  if (len == 0 || last == a.space || w < 0) return -INFINITY;
+  return a.alpha * ds2lm::cond_score(v, ctx, bow, a.m, w) + a.beta;
+}
+
+// the child state of l+c from the parent's state (src) into slot j of dst
+__device__ inline void lm_child(const ds2lm::LmView& v, const LmArgs& a, const LmBeams& o, int src, int c, float bonus,
+                                const LmBeams& d, int j) {
+  int tok = -2;
+  if (a.mode == ds2lm::MODE_CHAR) tok = v.label_tok[c];
+  else if (c == a.space) tok = v.word_of[o.node[src]];
+  if (tok != -2) {   // a new token enters the context
+    for (int i = 0; i + 1 < a.m; ++i) d.ctx[j * LM_CTX + i] = o.ctx[src * LM_CTX + i + 1];
+    if (a.m > 0) d.ctx[j * LM_CTX + a.m - 1] = tok;
+    ds2lm::context_backoffs(v, d.ctx + j * LM_CTX, a.m, d.bow + j * LM_CTX);
+    d.node[j] = 0;
+  } else {
+    for (int i = 0; i < a.m; ++i) {
+      d.ctx[j * LM_CTX + i] = o.ctx[src * LM_CTX + i];
+      d.bow[j * LM_CTX + i] = o.bow[src * LM_CTX + i];
+    }
+    d.node[j] = ds2lm::trie_child(v, o.node[src], c);
+  }
+  d.lmb[j] = bonus;
+}
+
+__device__ inline void lm_copy(const LmArgs& a, const LmBeams& o, int src, const LmBeams& d, int j) {
+  for (int i = 0; i < a.m; ++i) {
+    d.ctx[j * LM_CTX + i] = o.ctx[src * LM_CTX + i];
+    d.bow[j * LM_CTX + i] = o.bow[src * LM_CTX + i];
+  }
+  d.node[j] = o.node[src];
+  d.lmb[j] = o.lmb[src];
+}
+
+__device__ inline LmArgs lm_args() { return LmArgs{}; }
+__device__ inline LmArgs lm_args(const LmArgs& a) { return a; }
+
+// LM = false takes no LmArgs (an empty pack): its kernel arguments, and its code, are those of the kernel without the LM arm
+template <bool PROF, bool LM, class... Lm>
 __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __restrict__ probs, long long ld_b, long long ld_t, int T,
                                                                int C, const int* __restrict__ sizes, int blank, int K, int top_n,
                                                                float cutoff_prob, int PC, int PK, int HT, int* __restrict__ labels,
                                                                int* __restrict__ offsets, int* __restrict__ lens, float* __restrict__ scores,
-                                                               int* __restrict__ nodes, u64* __restrict__ prof) {
+                                                               int* __restrict__ nodes, u64* __restrict__ prof, Lm... lm_arg) {
+  static_assert(sizeof...(Lm) == (LM ? 1 : 0), "the LM arm takes one LmArgs");
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  const LmArgs lm = lm_args(lm_arg...);
   const Layout L(K, PC, PK, HT);
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   Header* hd = (Header*)smem;
@@ -255,6 +339,23 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
   int* n_frame = n_label + TK;
   const int n = sizes ? min(max(sizes[b], 0), T) : T;
   const int R = min(top_n, C);
+  ds2lm::LmView lv;
+  LmBeams l0, l1;
+  float* lnb_lp = nullptr;
+  int* lnb_cls = nullptr;
+  if constexpr (LM) {
+    lv = ds2lm::lm_view(lm.blob);
+    l0 = lm_beams_at(smem, L, 0);
+    l1 = lm_beams_at(smem, L, 1);
+    lnb_lp = (float*)(smem + Layout::align_up(L.total, 16) + 2 * lm_beams_bytes(K));
+    lnb_cls = (int*)(lnb_lp + lm.nbl);
+    if (tid == 0) {
+      for (int i = 0; i < lm.m; ++i) l0.ctx[i] = lv.h->bos;
+      ds2lm::context_backoffs(lv, l0.ctx, lm.m, l0.bow);
+      l0.node[0] = 0;
+      l0.lmb[0] = 0.f;
+    }
+  }
 
   if (tid == 0) {
     const Beams& s = b0;
@@ -283,6 +384,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
     const int nb_old = hd->nb;
     if (nb_old == 0) break;
     const Beams o = cur ? b1 : b0, w = cur ? b0 : b1;
+    [[maybe_unused]] const LmBeams mo = cur ? l1 : l0, mw = cur ? l0 : l1;
     const float* row = probs + b * ld_b + t * ld_t;
 
     // 1. prune the classes
@@ -317,7 +419,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
     __syncthreads();
     const int nk = hd->nkept;
     const u64 thr = hd->thr;
-    const int lim = min(nk, K + 2);
+    const int lim = LM ? nk : min(nk, K + 2);
     for (int j = tid; j < lim; j += BEAM_THREADS)
       if ((int)(unsigned)ck[j] == blank) hd->bpos = j;
     for (int k = tid; k < nb_old; k += BEAM_THREADS) {
@@ -329,14 +431,17 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
     for (int j = tid; j < lim; j += BEAM_THREADS) {
       if (j == bpos) continue;
       const int r = j - (j > bpos ? 1 : 0);
-      if (r <= K) {
+      if constexpr (LM) {   // every kept non-blank class: r < nk - blank kept <= min(top_n, C - 1) = lm.nbl
+        lnb_cls[r] = (int)(unsigned)ck[j];
+        lnb_lp[r] = logf(key_prob(ck[j]));
+      } else if (r <= K) {
         nb_cls[r] = (int)(unsigned)ck[j];
         nb_lp[r] = logf(key_prob(ck[j]));
       }
     }
     const bool blank_kept = hd->blank_kept;
     const float lp_blank = hd->lp_blank;
-    const int n_nb = min(K + 1, nk - (blank_kept ? 1 : 0));
+    const int n_nb = LM ? nk - (blank_kept ? 1 : 0) : min(K + 1, nk - (blank_kept ? 1 : 0));
     __syncthreads();   // the class keys are dead from here: the candidate arrays overwrite them
     lap(0);
 
@@ -347,13 +452,19 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
       const float npb = blank_kept ? tot + lp_blank : -INFINITY;
       float npnb = -INFINITY;
       int ecls = -1;
-      float es = -INFINITY;
+      float es = -INFINITY, eb = -INFINITY;
       if (len > 0 && class_key(row[e], e) <= thr) {
         const float lpe = logf(sane_prob(row[e]));
         npnb = pnb + lpe;
         const int p = tab_lookup(tab, HT, o, o.ph[k], len - 1);
-        if (p >= 0) npnb = lae(npnb, (o.last[p] == e ? o.pb[p] : o.tot[p]) + lpe);
-        es = pb + lpe;
+        if constexpr (LM) {   // the parent's extension carries the bonus of l's last label
+          if (p >= 0) npnb = lae(npnb, (o.last[p] == e ? o.pb[p] : o.tot[p]) + lpe + mo.lmb[k]);
+          eb = lm_bonus(lv, lm, mo.ctx + k * LM_CTX, mo.bow + k * LM_CTX, mo.node[k], len, e, e);
+          es = pb + lpe + eb;
+        } else {
+          if (p >= 0) npnb = lae(npnb, (o.last[p] == e ? o.pb[p] : o.tot[p]) + lpe);
+          es = pb + lpe;
+        }
         if (es > -INFINITY && tab_lookup(tab, HT, o, hash_ext(o.h[k], e), len + 1) < 0) ecls = e;
       }
       keys[k] = cand_key(lae(npb, npnb), len, k);
@@ -365,10 +476,10 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
       keys[s] = ecls >= 0 ? cand_key(es, len + 1, s) : dummy_key(s);
       c_src[s] = k;
       c_cls[s] = ecls;
-      c_pb[s] = -INFINITY;
+      c_pb[s] = LM ? eb : -INFINITY;   // LM: an extension's pb slot holds its bonus (its pb is -inf)
       c_pnb[s] = es;
     }
-    if (tid < 64) {   // exclusive prefix of the row lengths min(n_nb, K/(i+1) + 1)
+    if (!LM && tid < 64) {   // exclusive prefix of the row lengths min(n_nb, K/(i+1) + 1)
       int carry = 0;
       for (int base = 0; base < nb_old; base += 64) {
         const int i = base + lane;
@@ -385,8 +496,23 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
     __syncthreads();
 
     // 3b. extensions inside the staircase
-    const int ncells = hd->ncells;
+    const int ncells = LM ? nb_old * n_nb : hd->ncells;
     const int M = 2 * nb_old + ncells, P = pow2_ceil(M);
+    if constexpr (LM) {   // the full grid: per-(beam, class) bonuses and dictionary -inf cells break the staircase's monotonicity
+      for (int g = tid; g < ncells; g += BEAM_THREADS) {
+        const int i = g / n_nb, r = g - i * n_nb, c = lnb_cls[r], s = 2 * nb_old + g;
+        const int len = o.len[i];
+        const bool rep = len > 0 && c == o.last[i];
+        const float bonus = rep ? -INFINITY : lm_bonus(lv, lm, mo.ctx + i * LM_CTX, mo.bow + i * LM_CTX, mo.node[i], len, o.last[i], c);
+        const float sc = o.tot[i] + lnb_lp[r] + bonus;
+        const bool real = !rep && sc > -INFINITY && tab_lookup(tab, HT, o, hash_ext(o.h[i], c), len + 1) < 0;
+        keys[s] = real ? cand_key(sc, len + 1, s) : dummy_key(s);
+        c_src[s] = i;
+        c_cls[s] = c;
+        c_pb[s] = bonus;
+        c_pnb[s] = sc;
+      }
+    } else
     for (int g = tid; g < ncells; g += BEAM_THREADS) {
       int lo = 0, hi = nb_old - 1;   // last row with rowstart <= g
       while (lo < hi) {
@@ -428,6 +554,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
         w.last[j] = o.last[src];
         w.h[j] = o.h[src];
         w.ph[j] = o.ph[src];
+        if constexpr (LM) lm_copy(lm, mo, src, mw, j);
       } else {
         const int nd = t * K + j;
         n_parent[nd] = o.node[src];
@@ -441,6 +568,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
         w.last[j] = cls;
         w.h[j] = hash_ext(o.h[src], cls);
         w.ph[j] = o.h[src];
+        if constexpr (LM) lm_child(lv, lm, mo, src, cls, c_pb[idx], mw, j);
       }
     }
     if (tid == 0) hd->nb = nb_new;
@@ -453,6 +581,49 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
     prof[b * 8 + 4] = (unsigned)hd->pad0;
     prof[b * 8 + 5] = (unsigned)hd->pad1;
     prof[b * 8 + 6] = n;
+  }
+
+  if constexpr (LM) {
+    if (lm.mode == ds2lm::MODE_WORD && hd->nb > 0) {   // end of utterance: score the partial word, then re-sort the survivors
+      const int nbf = hd->nb, P = pow2_ceil(nbf);
+      const Beams f = cur ? b1 : b0, w = cur ? b0 : b1;
+      const LmBeams lf = cur ? l1 : l0, lw = cur ? l0 : l1;
+      u64* keys = (u64*)(smem + L.uni);
+      int* c_src = (int*)(keys + PK);
+      int* c_cls = c_src + PK;
+      float* c_tot = (float*)(c_cls + PK);
+      for (int k = tid; k < P; k += BEAM_THREADS) {
+        if (k < nbf) {
+          float tot = f.tot[k];
+          if (f.len[k] > 0 && f.last[k] != lm.space) {
+            const int wd = lv.word_of[lf.node[k]];   // an incomplete partial word is out of vocabulary
+            tot += lm.alpha * (wd < 0 ? ds2lm::OOV : ds2lm::cond_score(lv, lf.ctx + k * LM_CTX, lf.bow + k * LM_CTX, lm.m, wd)) + lm.beta;
+          }
+          keys[k] = cand_key(tot, f.len[k], k);
+          c_src[k] = k;
+          c_cls[k] = -1;
+          c_tot[k] = tot;
+        } else {
+          keys[k] = dummy_key(k);
+        }
+      }
+      __syncthreads();
+      block_sort(keys, P, CandLess{f, c_src, c_cls, n_parent, n_label, nullptr});
+      for (int j = tid; j < nbf; j += BEAM_THREADS) {
+        const int idx = (int)(keys[j] & 0xFFF);
+        w.pb[j] = f.pb[idx];
+        w.pnb[j] = f.pnb[idx];
+        w.tot[j] = c_tot[idx];
+        w.node[j] = f.node[idx];
+        w.len[j] = f.len[idx];
+        w.last[j] = f.last[idx];
+        w.h[j] = f.h[idx];
+        w.ph[j] = f.ph[idx];
+        lm_copy(lm, lf, idx, lw, j);
+      }
+      __syncthreads();
+      cur ^= 1;
+    }
   }
 
   // results: K slots per utterance, best first; label / offset rows zero past each length
@@ -511,18 +682,18 @@ extern "C" int ds2_ctc_beam_decode_f32(const float* probs, long long ld_b, long 
   const char* pe = ds2_exp_getenv("DS2_BEAM_PROFILE");
   if (!(pe && pe[0] == '1')) {
     if (lay.total > 64 * 1024)
-      DS2_HIP(hipFuncSetAttribute((const void*)ctc_beam_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lay.total));
-    hipLaunchKernelGGL(ctc_beam_kernel<false>, dim3(B), dim3(BEAM_THREADS), lay.total, s, probs, ld_b, ld_t, T, C, sizes_dev, blank, K,
+      DS2_HIP(hipFuncSetAttribute((const void*)ctc_beam_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lay.total));
+    hipLaunchKernelGGL((ctc_beam_kernel<false, false>), dim3(B), dim3(BEAM_THREADS), lay.total, s, probs, ld_b, ld_t, T, C, sizes_dev, blank, K,
                        cutoff_top_n, cutoff_prob, PC, PK, HT, labels, offsets, lens, scores, (int*)ws, nullptr);
     DS2_LAUNCH_CHECK("ctc_beam_kernel");
     return 0;
   }
   // profiling build of the same kernel (experiments only): per-step times averaged over the utterances' frames
   if (lay.total > 64 * 1024)
-    DS2_HIP(hipFuncSetAttribute((const void*)ctc_beam_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lay.total));
+    DS2_HIP(hipFuncSetAttribute((const void*)ctc_beam_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lay.total));
   u64* prof = nullptr;
   DS2_HIP(hipMalloc(&prof, (size_t)B * 8 * sizeof(u64)));
-  hipLaunchKernelGGL(ctc_beam_kernel<true>, dim3(B), dim3(BEAM_THREADS), lay.total, s, probs, ld_b, ld_t, T, C, sizes_dev, blank, K,
+  hipLaunchKernelGGL((ctc_beam_kernel<true, false>), dim3(B), dim3(BEAM_THREADS), lay.total, s, probs, ld_b, ld_t, T, C, sizes_dev, blank, K,
                      cutoff_top_n, cutoff_prob, PC, PK, HT, labels, offsets, lens, scores, (int*)ws, prof);
   hipError_t e = hipGetLastError();
   u64* h = (u64*)calloc((size_t)B * 8, sizeof(u64));
@@ -543,5 +714,119 @@ extern "C" int ds2_ctc_beam_decode_f32(const float* probs, long long ld_b, long 
           "chain walks/frame %.1f, steps/walk %.1f\n",
           K, C, sum[6], sum[0] / fr / 100, sum[1] / fr / 100, sum[2] / fr / 100, sum[3] / fr / 100, sum[4] / fr,
           sum[4] > 0 ? sum[5] / sum[4] : 0.0);
+  return 0;
+}
+
+// ---- language-model arm (ds2_ctc_lm_*, ds2_ctc_beam_decode_lm_f32) ----
+
+extern "C" int ds2_ctc_beam_lm_max_candidates(void) { return 4096; }
+
+extern "C" size_t ds2_ctc_lm_packed_bytes(int order, int n_ngrams, int n_edges, int n_nodes, int C) {
+  if (order < 1 || order > ds2lm::MAX_ORDER || n_ngrams < 1 || n_edges < 0 || n_nodes < 1 || C < 1 || n_ngrams > (1 << 28) ||
+      n_edges > (1 << 28))
+    return 0;
+  return ds2lm::lm_bytes(pow2_ceil(2 * n_ngrams), pow2_ceil(2 * n_edges + 1), n_nodes, C);
+}
+
+extern "C" int ds2_ctc_lm_pack(int order, int n_ngrams, const int* ngram_tok, const int* ngram_n, const float* prob, const float* bow,
+                               int n_edges, const int* edge_node, const int* edge_label, const int* edge_child, int n_nodes,
+                               const int* node_word, int C, const int* label_tok, int bos, int mode, void* out, size_t out_bytes) {
+  using namespace ds2lm;
+  const size_t need = ds2_ctc_lm_packed_bytes(order, n_ngrams, n_edges, n_nodes, C);
+  DS2_REQUIRE(need > 0, "ds2_ctc_lm_pack: bad sizes (order %d, %d n-grams, %d trie edges, %d nodes, %d classes)", order, n_ngrams,
+              n_edges, n_nodes, C);
+  DS2_REQUIRE(out && out_bytes >= need, "ds2_ctc_lm_pack: output buffer of %zu bytes, %zu needed", out_bytes, need);
+  DS2_REQUIRE(ngram_tok && ngram_n && prob && bow && node_word && label_tok && (n_edges == 0 || (edge_node && edge_label && edge_child)),
+              "ds2_ctc_lm_pack: null pointer");
+  DS2_REQUIRE(mode == MODE_CHAR || mode == MODE_WORD, "ds2_ctc_lm_pack: mode %d is neither character (1) nor word (2)", mode);
+  memset(out, 0, need);
+  LmHeader* h = (LmHeader*)out;
+  h->magic = MAGIC;
+  h->order = order;
+  h->ncap = pow2_ceil(2 * n_ngrams);
+  h->tcap = pow2_ceil(2 * n_edges + 1);
+  h->nnodes = n_nodes;
+  h->C = C;
+  h->bos = bos;
+  h->mode = mode;
+  const LmView v = lm_view(out);
+  LmEntry* ng = (LmEntry*)v.ng;
+  for (int i = 0; i < n_ngrams; ++i) {
+    const int n = ngram_n[i];
+    const int* tok = ngram_tok + (size_t)i * order;
+    DS2_REQUIRE(n >= 1 && n <= order, "ds2_ctc_lm_pack: n-gram %d has order %d (model order %d)", i, n, order);
+    for (int j = 0; j < n; ++j) DS2_REQUIRE(tok[j] >= 0, "ds2_ctc_lm_pack: n-gram %d has a negative token id", i);
+    DS2_REQUIRE(!ngram_find(v, n, tok), "ds2_ctc_lm_pack: n-gram %d is listed twice", i);
+    int pos = (int)(ngram_hash(n, tok) & (u64)(h->ncap - 1));
+    while (ng[pos].n != 0) pos = (pos + 1) & (h->ncap - 1);
+    ng[pos].n = n;
+    for (int j = 0; j < n; ++j) ng[pos].tok[j] = tok[j];
+    ng[pos].prob = prob[i];
+    ng[pos].bow = bow[i];
+  }
+  TrieEntry* tr = (TrieEntry*)v.trie;
+  for (int i = 0; i < h->tcap; ++i) tr[i].node = -1;
+  for (int i = 0; i < n_edges; ++i) {
+    DS2_REQUIRE(edge_node[i] >= 0 && edge_node[i] < n_nodes && edge_child[i] > 0 && edge_child[i] < n_nodes && edge_label[i] >= 0 &&
+                    edge_label[i] < C,
+                "ds2_ctc_lm_pack: trie edge %d out of range", i);
+    DS2_REQUIRE(trie_child(v, edge_node[i], edge_label[i]) < 0, "ds2_ctc_lm_pack: trie edge %d is listed twice", i);
+    int pos = (int)(trie_hash(edge_node[i], edge_label[i]) & (u64)(h->tcap - 1));
+    while (tr[pos].node >= 0) pos = (pos + 1) & (h->tcap - 1);
+    tr[pos].node = edge_node[i];
+    tr[pos].label = edge_label[i];
+    tr[pos].child = edge_child[i];
+  }
+  memcpy((int*)v.word_of, node_word, 4 * (size_t)n_nodes);
+  memcpy((int*)v.label_tok, label_tok, 4 * (size_t)C);
+  return 0;
+}
+
+extern "C" int ds2_ctc_lm_score(const void* packed, const int* hist, int n_hist, int w, float* out) {
+  using namespace ds2lm;
+  DS2_REQUIRE(packed && out && (n_hist == 0 || hist), "ds2_ctc_lm_score: null pointer");
+  const LmView v = lm_view(packed);
+  DS2_REQUIRE(v.h->magic == MAGIC, "ds2_ctc_lm_score: not a packed language model");
+  DS2_REQUIRE(n_hist == v.h->order - 1, "ds2_ctc_lm_score: %d context tokens for an order-%d model", n_hist, v.h->order);
+  float bw[MAX_ORDER];
+  context_backoffs(v, hist, n_hist, bw);
+  *out = cond_score(v, hist, bw, n_hist, w);
+  return 0;
+}
+
+extern "C" int ds2_ctc_beam_decode_lm_f32(const float* probs, long long ld_b, long long ld_t, int B, int T, int C, const int* sizes_dev,
+                                          int blank, int beam_width, int cutoff_top_n, float cutoff_prob, const void* lm_dev,
+                                          size_t lm_bytes, int lm_order, int lm_mode, int space, float alpha, float beta, int* labels,
+                                          int* offsets, int* lens, float* scores, void* ws, size_t ws_bytes, void* stream) {
+  DS2_REQUIRE(probs && labels && offsets && lens && scores && lm_dev, "ds2_ctc_beam_decode_lm_f32: null pointer");
+  DS2_REQUIRE(beam_width >= 1 && beam_width <= BEAM_MAX_K, "ds2_ctc_beam_decode_lm_f32: beam_width %d outside the supported 1..%d",
+              beam_width, BEAM_MAX_K);
+  DS2_REQUIRE(C >= 2 && C <= BEAM_MAX_C, "ds2_ctc_beam_decode_lm_f32: %d classes outside the supported 2..%d", C, BEAM_MAX_C);
+  DS2_REQUIRE(B > 0 && T > 0 && T <= BEAM_MAX_T && blank >= 0 && blank < C,
+              "ds2_ctc_beam_decode_lm_f32: bad dims (B=%d T=%d C=%d blank=%d; T <= %d)", B, T, C, blank, BEAM_MAX_T);
+  DS2_REQUIRE(cutoff_top_n >= 1 && cutoff_prob == cutoff_prob, "ds2_ctc_beam_decode_lm_f32: cutoff_top_n must be >= 1 and cutoff_prob a number");
+  DS2_REQUIRE(ws && ws_bytes >= ds2_ctc_beam_workspace_bytes(B, T, beam_width), "ds2_ctc_beam_decode_lm_f32: workspace too small");
+  DS2_REQUIRE(lm_order >= 1 && lm_order <= ds2lm::MAX_ORDER && (lm_mode == ds2lm::MODE_CHAR || lm_mode == ds2lm::MODE_WORD) &&
+                  lm_bytes >= sizeof(ds2lm::LmHeader),
+              "ds2_ctc_beam_decode_lm_f32: bad language model (order %d, mode %d, %zu bytes)", lm_order, lm_mode, lm_bytes);
+  DS2_REQUIRE(lm_mode == ds2lm::MODE_CHAR || (space >= 0 && space < C && space != blank),
+              "ds2_ctc_beam_decode_lm_f32: word mode needs a space label other than the blank (got %d)", space);
+  DS2_REQUIRE(alpha == alpha && beta == beta && fabsf(alpha) < INFINITY && fabsf(beta) < INFINITY,
+              "ds2_ctc_beam_decode_lm_f32: alpha and beta must be finite");
+  const int K = beam_width, nbl = min(cutoff_top_n, C - 1);
+  DS2_REQUIRE((long long)K * (nbl + 2) <= ds2_ctc_beam_lm_max_candidates(),
+              "ds2_ctc_beam_decode_lm_f32: beam_width * (min(cutoff_top_n, C - 1) + 2) = %lld exceeds the %d candidate slots",
+              (long long)K * (nbl + 2), ds2_ctc_beam_lm_max_candidates());
+  const int PC = pow2_ceil(C), PK = pow2_ceil(K * (nbl + 2)), HT = 2 * pow2_ceil(K);
+  const Layout lay(K, PC, PK, HT);
+  const size_t total = lm_layout_total(lay, nbl);
+  DS2_REQUIRE(total <= 160 * 1024, "ds2_ctc_beam_decode_lm_f32: LDS layout of %zu bytes does not fit", total);
+  hipStream_t s = (hipStream_t)stream;
+  if (total > 64 * 1024)
+    DS2_HIP(hipFuncSetAttribute((const void*)ctc_beam_kernel<false, true, LmArgs>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)total));
+  const LmArgs la{lm_dev, alpha, beta, lm_order - 1, lm_mode, lm_mode == ds2lm::MODE_WORD ? space : -1, nbl};
+  hipLaunchKernelGGL((ctc_beam_kernel<false, true, LmArgs>), dim3(B), dim3(BEAM_THREADS), total, s, probs, ld_b, ld_t, T, C, sizes_dev, blank, K,
+                     cutoff_top_n, cutoff_prob, PC, PK, HT, labels, offsets, lens, scores, (int*)ws, nullptr, la);
+  DS2_LAUNCH_CHECK("ctc_beam_kernel<LM>");
   return 0;
 }

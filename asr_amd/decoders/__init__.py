@@ -106,17 +106,27 @@ class GreedyDecoder(Decoder):
 
 class BeamCTCDecoder(Decoder):
     """beam_decoder.py: the reference's constructor and decode(), without its external `ctcdecode` dependency.  The prefix beam search
-    runs as one HIP kernel (`ds2_ctc_beam_decode_f32`, contract in include/ds2hip.h).  There is no language-model scorer: `lm_path`
-    must be None; `alpha`, `beta` and `num_processes` are accepted and unused, as in a scorer-less ctcdecode."""
+    runs as one HIP kernel (`ds2_ctc_beam_decode_f32`, contract in include/ds2hip.h).  `num_processes` is accepted and unused.
+
+    With `lm_path` (an ARPA n-gram model, plain or .gz, loaded here as ctcdecode loads its scorer) the kernel fuses
+    alpha * log10 lm(token | context) + beta per scored token (`ds2_ctc_beam_decode_lm_f32`): a model whose vocabulary is single
+    characters scores every label (character mode, e.g. for JSUT's unspaced transcripts); otherwise it scores words between spaces
+    and keeps only prefixes spelling dictionary words (word mode, which needs a space label).  KenLM binary files raise
+    NotImplementedError.  With an LM, beam_width * (min(cutoff_top_n, C - 1) + 2) must stay within 4096.  ctcdecode's min_cutoff
+    heuristic and approx_ctc score are not reproduced: `last_scores` are the fused totals, and parity with ctcdecode is not pinned."""
 
     def __init__(self, labels, lm_path=None, alpha=0, beta=0, cutoff_top_n=40, cutoff_prob=1.0, beam_width=100, num_processes=4,
                  blank_index=0):
-        if lm_path is not None:
-            raise NotImplementedError("BeamCTCDecoder: language-model scoring (lm_path) is not implemented; pass lm_path=None")
         super().__init__(labels, blank_index)
         self.lm_path, self.alpha, self.beta, self.num_processes = lm_path, alpha, beta, num_processes
         self.cutoff_top_n, self.cutoff_prob, self.beam_width = int(cutoff_top_n), float(cutoff_prob), int(beam_width)
         self.last_scores = None
+        self.lm = None
+        if lm_path is not None:
+            from .lm import NgramLM
+            space = self.space_index if self.int_to_char.get(self.space_index) == " " else next(
+                (i for i, c in sorted(self.int_to_char.items()) if c == " "), None)
+            self.lm = NgramLM(lm_path, self.int_to_char, self.blank_index, space)
 
     def _char(self, i):
         return " " if i == self.space_index else self.int_to_char.get(i, "")
@@ -144,7 +154,7 @@ class BeamCTCDecoder(Decoder):
         if sizes is not None:
             sizes = torch.as_tensor(sizes)
         labels, offs, lens, scores = ops.ctc_beam_decode(probs, sizes, self.blank_index, self.beam_width, self.cutoff_top_n,
-                                                         self.cutoff_prob)
+                                                         self.cutoff_prob, self.lm, self.alpha, self.beta)
         B, K, T = labels.shape
         host = torch.cat((labels.reshape(-1), offs.reshape(-1), lens.reshape(-1), scores.view(torch.int32).reshape(-1))).cpu()
         if ops.rnn_poison_seen(labels.device):

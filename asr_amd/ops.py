@@ -1258,9 +1258,10 @@ def greedy_decode(probs: Tensor, sizes: Tensor | None = None, blank: int = 0):
 
 
 def ctc_beam_decode(probs: Tensor, sizes: Tensor | None = None, blank: int = 0, beam_width: int = 100, cutoff_top_n: int = 40,
-                    cutoff_prob: float = 1.0):
-    """CTC prefix beam search (no language model) of probs (B,T,C) fp32 on the GPU -> (labels (B,K,T) i32, offsets (B,K,T) i32,
-    lengths (B,K) i32, scores (B,K) fp32), all on the GPU, best beam first (contract: include/ds2hip.h)."""
+                    cutoff_prob: float = 1.0, lm=None, alpha: float = 0.0, beta: float = 0.0):
+    """CTC prefix beam search of probs (B,T,C) fp32 on the GPU -> (labels (B,K,T) i32, offsets (B,K,T) i32, lengths (B,K) i32,
+    scores (B,K) fp32), all on the GPU, best beam first (contract: include/ds2hip.h).  With `lm` (a decoders.lm.NgramLM bound to these
+    classes) the search fuses alpha * log10 LM scores + beta per scored token (ds2_ctc_beam_decode_lm_f32)."""
     _chk_f32(probs)
     if probs.dim() != 3 or probs.stride(2) != 1:
         raise ValueError("ctc_beam_decode: probs must be (B,T,C) with a contiguous class dim")
@@ -1270,6 +1271,13 @@ def ctc_beam_decode(probs: Tensor, sizes: Tensor | None = None, blank: int = 0, 
         raise ValueError(f"ctc_beam_decode: beam_width {K} outside the supported 1..{lib.ds2_ctc_beam_max_width()}")
     B, T, C = probs.shape
     dev = probs.device
+    if lm is not None:
+        if lm.C != C:
+            raise ValueError(f"ctc_beam_decode: the language model was bound to {lm.C} classes, probs have {C}")
+        grid, cap = K * (min(int(cutoff_top_n), C - 1) + 2), lib.ds2_ctc_beam_lm_max_candidates()
+        if grid > cap:
+            raise ValueError(f"ctc_beam_decode: with a language model beam_width * (min(cutoff_top_n, C - 1) + 2) = {grid} exceeds "
+                             f"the {cap} candidate slots")
     if sizes is not None:
         if sizes.numel() != B:
             raise ValueError(f"sizes has {sizes.numel()} entries for a batch of {B}")
@@ -1280,10 +1288,18 @@ def ctc_beam_decode(probs: Tensor, sizes: Tensor | None = None, blank: int = 0, 
     scores = torch.empty((B, K), dtype=torch.float32, device=dev)
     n = lib.ds2_ctc_beam_workspace_bytes(B, T, K)
     ws = _ws(n, dev)
-    _lib.check(lib.ds2_ctc_beam_decode_f32(probs.data_ptr(), probs.stride(0), probs.stride(1), B, T, C,
-                                           sizes.data_ptr() if sizes is not None else None, int(blank), K, int(cutoff_top_n),
-                                           float(cutoff_prob), labels.data_ptr(), offs.data_ptr(), lens.data_ptr(), scores.data_ptr(),
-                                           ws.data_ptr(), n, _stream()), "ds2_ctc_beam_decode_f32")
+    sz_ptr = sizes.data_ptr() if sizes is not None else None
+    if lm is None:
+        _lib.check(lib.ds2_ctc_beam_decode_f32(probs.data_ptr(), probs.stride(0), probs.stride(1), B, T, C, sz_ptr, int(blank), K,
+                                               int(cutoff_top_n), float(cutoff_prob), labels.data_ptr(), offs.data_ptr(), lens.data_ptr(),
+                                               scores.data_ptr(), ws.data_ptr(), n, _stream()), "ds2_ctc_beam_decode_f32")
+    else:
+        tab = lm.device_tables(dev)
+        space = lm.space if lm.space is not None else -1
+        _lib.check(lib.ds2_ctc_beam_decode_lm_f32(probs.data_ptr(), probs.stride(0), probs.stride(1), B, T, C, sz_ptr, int(blank), K,
+                                                  int(cutoff_top_n), float(cutoff_prob), tab.data_ptr(), tab.numel(), lm.order, lm.mode,
+                                                  space, float(alpha), float(beta), labels.data_ptr(), offs.data_ptr(), lens.data_ptr(),
+                                                  scores.data_ptr(), ws.data_ptr(), n, _stream()), "ds2_ctc_beam_decode_lm_f32")
     return labels, offs, lens, scores
 
 

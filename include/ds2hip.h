@@ -419,6 +419,41 @@ int ds2_ctc_beam_decode_f32(const float* probs, long long ld_b, long long ld_t, 
                             int beam_width, int cutoff_top_n, float cutoff_prob, int* labels, int* offsets, int* lens, float* scores,
                             void* ws, size_t ws_bytes, void* stream);
 
+/* The same search with shallow fusion of an n-gram language model (LM) read from an ARPA file (asr_amd/decoders/lm.py parses it;
+ * replaces ctcdecode's KenLM scorer).  Logs are natural except LM scores, which are log10 as the file stores them; alpha multiplies
+ * those log10 values.  Parity with ctcdecode is not pinned.
+ *  - vocabulary: the file's 1-grams, token id = position among them.  Character mode when every entry other than <s>, </s> and
+ *    <unk> is one Unicode character, word mode otherwise (word mode needs a space label);
+ *  - lm(w | h), h the last N-1 tokens left-padded with <s> (N the order): the listed n-gram (h, w)'s log10 prob, else backoff(h)
+ *    (0 when h is not listed) + lm(w | h[1:]); OOV = -1000 when any token of (h, w) is outside the vocabulary; </s> is never scored;
+ *  - word mode: a word is the run of labels between spaces, spelt with the decoder's characters, matched exactly.  The dictionary
+ *    is every vocabulary word other than <s>, </s>, <unk> whose characters are all non-blank, non-space labels.  A prefix survives
+ *    only in the form (word ' ')* partial with every word in the dictionary and partial a (possibly empty) prefix of a dictionary
+ *    word (no leading or double space): any other extension is -inf.  Appending the space adds alpha*lm(word | ctx) + beta to
+ *    that extension's contribution.  After the last frame every surviving non-empty beam not ending in a space gets
+ *    alpha*lm(partial | ctx) + beta (OOV when partial is no dictionary word) and the survivors are re-sorted by the order above;
+ *  - character mode: every non-blank extension l -> l+c adds alpha*lm(char(c) | ctx) + beta; no dictionary, no end term;
+ *  - everything else is the contract above: the LM terms ride in pnb of the extension, so pb / pnb / total include every bonus
+ *    so far (the bonus depends only on the prefix, so merging stays exact), and scores are the fused totals.  ctcdecode's
+ *    min_cutoff heuristic and its "approx_ctc" returned score are deliberately left out.
+ * Every beam is extended by every kept non-blank class (the no-LM staircase bound does not hold with per-class bonuses):
+ * K * (min(cutoff_top_n, C-1) + 2) <= ds2_ctc_beam_lm_max_candidates() (4096), e.g. K = 100 at C = 29.
+ * The packed LM (csrc/ctc_lm.h): ds2_ctc_lm_packed_bytes sizes it, ds2_ctc_lm_pack fills it on the host from the parsed arrays
+ * (ngram_tok n_ngrams x order, -1 padded; ngram_n their orders; prob / bow log10; the trie's edges (node, label) -> child, node 0
+ * the root; node_word the token id of the word a node spells or -1; label_tok (C) the token of every label in character mode;
+ * bos the token id of <s> or -1; mode 1 character, 2 word).  ds2_ctc_lm_score is lm(w | hist) on the host (hist: order-1 token
+ * ids, oldest first; -1 = out of vocabulary).  The decode reads the packed bytes from device memory (lm_dev, lm_bytes). */
+int ds2_ctc_beam_lm_max_candidates(void);
+size_t ds2_ctc_lm_packed_bytes(int order, int n_ngrams, int n_edges, int n_nodes, int C);
+int ds2_ctc_lm_pack(int order, int n_ngrams, const int* ngram_tok, const int* ngram_n, const float* prob, const float* bow, int n_edges,
+                    const int* edge_node, const int* edge_label, const int* edge_child, int n_nodes, const int* node_word, int C,
+                    const int* label_tok, int bos, int mode, void* out, size_t out_bytes);
+int ds2_ctc_lm_score(const void* packed, const int* hist, int n_hist, int w, float* out);
+int ds2_ctc_beam_decode_lm_f32(const float* probs, long long ld_b, long long ld_t, int B, int T, int C, const int* sizes_dev, int blank,
+                               int beam_width, int cutoff_top_n, float cutoff_prob, const void* lm_dev, size_t lm_bytes, int lm_order,
+                               int lm_mode, int space, float alpha, float beta, int* labels, int* offsets, int* lens, float* scores,
+                               void* ws, size_t ws_bytes, void* stream);
+
 /* conv1 in bf16 mode (Conv2d(1,32,(41,11),s=(2,2),p=(20,5)), deepspeech.py:61, forward + weight gradient; conv1 has no data
  * gradient).  ds2_conv1_gather_bf16 builds the two bf16 operand images from the spectrogram batch: XB (B,F,P) = the rows themselves as
  * bf16, XB[..][7 + s] = x[..][s] with zeros in front and behind (P = ds2_conv1_bf16_row_pitch(T)) for the forward — the 16 taps of an output

@@ -2,8 +2,10 @@
 B = 64 utterances of T = 501 frames (c3's output length for 1001 input frames), C = 29, beam widths 10 / 100 / 256, cutoff_top_n 40.
 The decode is timed on the forward's output (a randomly initialised c3: near-uniform frames) and on peaked random frames of the
 same shape.  With --profile each timed decode is followed by one run of the profiling build (DS2_EXPERIMENTAL=1 DS2_BEAM_PROFILE=1),
-which prints the per-frame time of each step and the tie-rule chain walks to stderr.
-Prints one JSON line.  Usage: python scripts/time_beam_decode.py [--reps N] [--profile]"""
+which prints the per-frame time of each step and the tie-rule chain walks to stderr.  With --lm PATH (an ARPA file, e.g. from
+scripts/make_synthetic_arpa.py) the LM arm is timed too, at beam widths 10 and 100 with --alpha / --beta; the 29 labels are bound with
+the last one ("|") read as the space, so that a word-level model has its space label.
+Prints one JSON line.  Usage: python scripts/time_beam_decode.py [--reps N] [--profile] [--lm PATH [--alpha A] [--beta B]]"""
 import argparse
 import json
 import os
@@ -34,6 +36,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--profile", action="store_true")
+    ap.add_argument("--lm", default=None)
+    ap.add_argument("--alpha", type=float, default=0.8)
+    ap.add_argument("--beta", type=float, default=1.0)
     args = ap.parse_args()
     import bench
     from asr_amd import DeepSpeech, ops
@@ -65,6 +70,17 @@ def main():
                 print(f"[{name}]", end=" ", file=sys.stderr, flush=True)
                 ops.ctc_beam_decode(p, sz, 0, K, 40, 1.0)
                 del os.environ["DS2_EXPERIMENTAL"], os.environ["DS2_BEAM_PROFILE"]
+    if args.lm:
+        from asr_amd.decoders.lm import NgramLM
+        chars = ["_", "'"] + list("abcdefghijklmnopqrstuvwxyz") + [" "]
+        lm = NgramLM(args.lm, dict(enumerate(chars[:C])), 0, 28 if C > 28 else None)
+        res["lm"] = dict(path=os.path.basename(args.lm), mode=lm.mode_name, order=lm.order, ngrams=lm.n_ngrams, packed_mb=round(lm.packed.nbytes / 2**20, 2),
+                         alpha=args.alpha, beta=args.beta, decode_ms={"forward": {}, "peaked": {}})
+        for name, p, sz in (("forward", probs, out_lens), ("peaked", peaked, None)):
+            for K in (10, 100):
+                res["lm"]["decode_ms"][name][K] = round(_time(lambda: ops.ctc_beam_decode(p, sz, 0, K, 40, 1.0, lm, args.alpha, args.beta),
+                                                              args.reps), 3)
+        res["lm"]["k10_within_forward"] = res["lm"]["decode_ms"]["forward"][10] <= fwd_ms
     res["greedy_ms"] = round(_time(lambda: ops.greedy_decode(probs, out_lens, 0), args.reps), 3)
     res["k100_within_forward"] = res["decode_ms"]["forward"][100] <= fwd_ms
     print(json.dumps(res))
