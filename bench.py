@@ -3,13 +3,17 @@
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run)
     python bench.py ... --dump-outputs DIR                 (+ what the last timed step computed, as DIR/<name>.npy: dump_outputs)
+    python bench.py ... --full                             (+ the legs that take runs of their own, see below)
 
 A "step" = one full train step of the hot path on one synthetic batch already resident in HBM:
 forward, CTC, backward, (RCCL gradient all-reduce,) fused AdamW, loss.item() sync.
 Workloads (--workload): c3 = BASELINE metric config (5x1024 BiGRU, 10 s / 161-bin, B=64 per GPU, C=29),
 c2 = configs[1] (5x768 BiGRU, B=32).  Weak scaling: per-GPU batch fixed.
 Prints ONE JSON line (rank 0) with `roofline` (dominant kernel, measured live with HIP events on the
-launch stream) and `cpu_baseline` (the CPU oracle timed on the host cores on a bounded sample).
+launch stream).  A plain run does only that: set-up, warm-up, the timed steps, the outputs, the line.
+--full (single GPU) adds the legs that run after the timed region: `other_workloads` and `dp_path_1rank`
+(short runs of the other configurations and of the one-rank RCCL path), `cpu_baseline` (the CPU oracle
+timed on the host cores on a bounded sample) and `loss_parity`.
 """
 from __future__ import annotations
 
@@ -632,10 +636,14 @@ def main():
     ap.add_argument("--workload", default="c3", choices=list(WORKLOADS))
     ap.add_argument("--batch", type=int, default=0, help="override per-GPU batch")
     ap.add_argument("--dtype", default="", choices=["", "f32", "bf16"], help="default: the config dtype (bf16 for c3 and c5, f32 otherwise)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the legs that take runs of their own (single GPU): the other BASELINE "
+                         "configurations, the 1-rank data-parallel path, the CPU baseline and the matched-loss runs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the matched-loss runs")
     ap.add_argument("--breakdown", action="store_true", help="print a per-section time breakdown to stderr")
     ap.add_argument("--no-other-workloads", action="store_true",
-                    help="skip the short runs of the other single-GPU BASELINE configurations (c2 f32, c4 f32) and of the 1-rank data-parallel path")
+                    help="with --full: skip the short runs of the other single-GPU BASELINE configurations (c2 f32, c4 f32) and of the 1-rank "
+                         "data-parallel path")
     ap.add_argument("--ranks-on-one-gpu", action="store_true",
                     help="TEST MODE for the N > 1 code path on a 1-GPU box: every rank uses cuda:0 and the process group is gloo (RCCL cannot put "
                          "two ranks on one device) unless DS2_DIST_BACKEND says otherwise.  The line is labelled; it is not a scaling point.")
@@ -953,7 +961,7 @@ def main():
             "valid_last_step": bool(valid),
             **({"dist": dist_info} if dist_info else {}),
         }
-        if world == 1 and not args.no_other_workloads and args.workload == "c3" and not args.dtype and not args.batch:
+        if args.full and world == 1 and not args.no_other_workloads and args.workload == "c3" and not args.dtype and not args.batch:
             # the other single-GPU configurations of BASELINE.json in the driver-written record (short, after the timed region)
             del model, tr, opt, batches, x
             torch.cuda.empty_cache()
@@ -970,7 +978,7 @@ def main():
             out["other_workloads"] = other
             out["dp_path_1rank"] = dp_path_one_rank() if time.time() - t_other < 60 else {"skipped": "time box"}
             model = tr = opt = batches = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(rnn, H, L, C, tin, B)
             if out["cpu_baseline"].get("losses"):
                 model = tr = opt = batches = None                # the parity runs build their own models from the CPU port's weights

@@ -227,6 +227,30 @@ def test_bench_two_ranks_end_to_end_on_one_gpu():
     assert out["valid_last_step"] or starved > 0
 
 
+def test_bench_plain_run_has_no_extra_legs_and_full_adds_them():
+    """`python bench.py` without --full prints the line of its own timed steps and nothing else; with --full the same line also carries the
+    CPU baseline and the matched-loss runs from the CPU port's weights (c1: small enough for the CPU leg to take seconds)."""
+    import json
+    import subprocess
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    env.pop("RANK", None)
+    env.pop("WORLD_SIZE", None)
+    extra_legs = {"other_workloads", "dp_path_1rank", "cpu_baseline", "loss_parity"}
+    lines = {}
+    for flags in ((), ("--full",)):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c1", "--steps", "2", "--warmup", "1", *flags],
+                           env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+        got = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(got) == 1, r.stdout[-3000:]
+        lines[flags] = out = json.loads(got[0])
+        assert out["steps"] == 2 and out["warmup"] == 1 and out["value"] > 0 and np.isfinite(out["loss"]) and "roofline" in out
+    assert not extra_legs & set(lines[()])
+    full = lines[("--full",)]
+    assert full["cpu_baseline"]["value"] > 0, full["cpu_baseline"]
+    assert len(full["loss_parity"]["gpu_fp32"]) == len(full["cpu_baseline"]["losses"]) and full["loss_parity"]["rel_fp32"] < 1e-3
+
+
 FORWARD_ONLY_WORKER = r'''
 import os, sys, json
 import torch
