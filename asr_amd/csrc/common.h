@@ -28,9 +28,10 @@ int ds2_set_error(const char* fmt, ...);
   } while (0)
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
-// Environment switches.  OPERATIONAL ones (DS2_RNN_PERSISTENT, DS2_RNN_SPIN_LIMIT, DS2_RNN_REARM_CALLS, DS2_RNN_XCD_LOCAL, DS2_F32_RNN) are read
-// with getenv.  TUNING / A-B switches of experiments — most of which lost (DS2_GEMM_RING, DS2_GEMM_WAVES, DS2_GEMM_TILE, DS2_GEMM_DBG, ...) —
-// are honoured only when DS2_EXPERIMENTAL=1 is set as well, so that a stray variable cannot change what the product runs.
+// Environment switches (the list: INTEGRATION.md §1).  OPERATIONAL ones (DS2_RNN_PERSISTENT, DS2_RNN_SPIN_LIMIT, DS2_RNN_REARM_CALLS,
+// DS2_RNN_XCD_LOCAL, DS2_F32_RNN) are read with getenv.  TUNING / A-B switches (DS2_RNN_KSPLIT, DS2_BEAM_PROFILE) are honoured only when
+// DS2_EXPERIMENTAL=1 is set as well, so that a stray variable cannot change what the product runs.  The dense-kernel experiments that lost
+// were measured and removed, see docs/HISTORY.md.
 #include <stdlib.h>
 static inline const char* ds2_exp_getenv(const char* name) {
   const char* on = getenv("DS2_EXPERIMENTAL");

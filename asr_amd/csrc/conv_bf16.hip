@@ -11,7 +11,7 @@
 //
 //   block = (b, R output rows, 128 time steps); per kernel row kd: stage one input row (138 pixels x 64 B, 80-B pitch)
 //   and that row's 11x2 weight fragments in LDS, then 22 R MFMAs per wave (R tiles of 32 co x 32 t).  Loads of row kd+1 are
-//   parked in registers while row kd is multiplied.  (conv2_bf16_rows_kernel; the one-row conv2_bf16_kernel is the A/B reference.)
+//   parked in registers while row kd is multiplied.  (conv2_bf16_rows_kernel; a one-row kernel was measured and removed, see docs/HISTORY.md.)
 // dgrad = the same kernel on dY (channels-last) with per-parity re-packed weights (as in conv.hip).
 #include "common.h"
 #include <stdlib.h>
@@ -42,102 +42,9 @@ constexpr int IN_IT = (IN_CHUNKS + 255) / 256;      // 3
 constexpr int W_CHUNKS = WROW / 16;                 // 1408
 constexpr int W_IT = (W_CHUNKS + 255) / 256;        // 6
 
-__device__ __forceinline__ void load_row(const CArgs& a, int b, int f, int t0, int kd, f32x4 (&ri)[IN_IT], f32x4 (&rw)[W_IT]) {
-  const bool rowok = f >= 0 && f < a.Din;
-  const char* rowp = reinterpret_cast<const char*>(a.in + (((long long)b * a.Din + (rowok ? f : 0)) * a.T) * CH);
-#pragma unroll
-  for (int u = 0; u < IN_IT; ++u) {
-    const int c = threadIdx.x + 256 * u;
-    const int pix = c >> 2, q = c & 3;
-    const int t = t0 - PT + pix;
-    const bool ok = rowok && c < IN_CHUNKS && t >= 0 && t < a.T;
-    const void* p = ok ? (const void*)(rowp + ((long long)t * CH) * 2 + q * 16) : (const void*)g_zero_cb;
-    ri[u] = *reinterpret_cast<const f32x4*>(p);
-  }
-  const char* wp = reinterpret_cast<const char*>(a.wpk) + (long long)kd * WROW;
-#pragma unroll
-  for (int u = 0; u < W_IT; ++u) {
-    const int c = threadIdx.x + 256 * u;
-    rw[u] = *reinterpret_cast<const f32x4*>(wp + (c < W_CHUNKS ? c : 0) * 16);
-  }
-}
-__device__ __forceinline__ void store_row(char* __restrict__ in_lds, char* __restrict__ w_lds, const f32x4 (&ri)[IN_IT], const f32x4 (&rw)[W_IT]) {
-#pragma unroll
-  for (int u = 0; u < IN_IT; ++u) {
-    const int c = threadIdx.x + 256 * u;
-    if (c < IN_CHUNKS) *reinterpret_cast<f32x4*>(in_lds + (c >> 2) * IPITCH + (c & 3) * 16) = ri[u];
-  }
-#pragma unroll
-  for (int u = 0; u < W_IT; ++u) {
-    const int c = threadIdx.x + 256 * u;
-    if (c < W_CHUNKS) *reinterpret_cast<f32x4*>(w_lds + c * 16) = rw[u];
-  }
-}
-
-__global__ __launch_bounds__(256) void conv2_bf16_kernel(CArgs a) {
-  __shared__ __attribute__((aligned(16))) char in_lds[NPIX * IPITCH];    // 11040
-  __shared__ __attribute__((aligned(16))) char w_lds[WROW];              // 22528
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int half = lane >> 5, l31 = lane & 31;
-  const int t0 = blockIdx.x * TT, o = blockIdx.y, b = blockIdx.z;
-  const int len = a.lens ? min(a.lens[b], a.T) : a.T;
-  const int orow = a.OS * o + a.OO;
-  const int t = t0 + wave * 32 + l31;
-  if (t0 >= len) {   // whole tile masked (MaskConv): zeros
-    if (t < a.T) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int co = (r & 3) + 8 * (r >> 2) + 4 * half;
-        a.out[(((long long)b * CH + co) * a.Dtot + orow) * a.T + t] = 0.f;
-      }
-    }
-    return;
-  }
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-
-  f32x4 ri[IN_IT], rw[W_IT];
-  load_row(a, b, a.SD * o - a.PD, t0, 0, ri, rw);
-  // this lane's fragment bases: B operand (input): pixel (wave*32 + l31 + kt), channel group (kk*16 + half*8)
-  //                              A operand (weights): [kt][kk][kgroup = half][m = l31]
-  const char* bbase = in_lds + (wave * 32 + l31) * IPITCH + half * 16;
-  const char* abase = w_lds + half * (32 * 16) + l31 * 16;
-  for (int kd = 0; kd < a.KD; ++kd) {
-    __syncthreads();
-    store_row(in_lds, w_lds, ri, rw);
-    __syncthreads();
-    if (kd + 1 < a.KD) load_row(a, b, a.SD * o + (kd + 1) - a.PD, t0, kd + 1, ri, rw);
-#pragma unroll
-    for (int kt = 0; kt < KT; ++kt) {
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        const bf16x8 af = *reinterpret_cast<const bf16x8*>(abase + (kt * 2 + kk) * (2 * 32 * 16));
-        const bf16x8 bf = *reinterpret_cast<const bf16x8*>(bbase + kt * IPITCH + kk * 32);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bf, acc, 0, 0, 0);
-      }
-    }
-  }
-  // biases first, all 16 before any store: a load inside the store loop would put an s_waitcnt vmcnt(0) — which also waits for
-  // every earlier store — in front of each store (one in-order memory counter), i.e. 16 serialised HBM write round trips
-  float bv[16];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) bv[r] = a.bias ? a.bias[(r & 3) + 8 * (r >> 2) + 4 * half] : 0.f;
-  if (t < a.T) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int co = (r & 3) + 8 * (r >> 2) + 4 * half;
-      float v = acc[r] + bv[r];
-      if (t >= len) v = 0.f;
-      a.out[(((long long)b * CH + co) * a.Dtot + orow) * a.T + t] = v;
-    }
-  }
-}
-
 // R output rows (o0 .. o0 + R - 1) per block: they read the same kernel-row weights and input rows SD apart, so the input rows live in a
 // ring of (R - 1) SD + 1 LDS slots and every staged (input row, weight row) pair feeds 22 R MFMAs per wave instead of 22 - 1/R of the
-// weight staging (22.5 KB per kernel row was 2/3 of what a block moved into LDS), of the L2 reads and of the barriers per MFMA.  Same
-// accumulation order per output as the one-row kernel: bit-identical.
+// weight staging (22.5 KB per kernel row was 2/3 of what a block moved into LDS), of the L2 reads and of the barriers per MFMA.
 template <int SD, int R>
 __global__ __launch_bounds__(256) void conv2_bf16_rows_kernel(CArgs a, int n_out, float* __restrict__ stat_part) {
   constexpr int RING = (R - 1) * SD + 1;                   // rows f0 + kd .. f0 + kd + (R - 1) SD are live at kernel row kd
@@ -376,17 +283,12 @@ extern "C" int ds2_conv2_fwd_bf16_stats(const void* a1_nhwc, const void* wf, con
   a.in = (const __bf16*)a1_nhwc; a.wpk = (const __bf16*)wf; a.bias = bias; a.out = y2; a.lens = lens_dev;
   a.B = B; a.Din = D1; a.T = T; a.Dtot = D2; a.KD = 21; a.SD = 2; a.PD = 10; a.OS = 1; a.OO = 0;
   // three output rows per block (5 input-row slots + the weight row = 77 KB of LDS, two blocks per CU): 655 -> 561 us at c3; two rows
-  // 614, four rows (one block per CU) 767.  DS2_CONV2_ROWS=1: the one-row kernel (A/B switch)
-  static const char* rows_env = ds2_exp_getenv("DS2_CONV2_ROWS");
-  DS2_REQUIRE(!stat_part || !(rows_env && rows_env[0] == '1'), "ds2_conv2_fwd_bf16_stats: the one-row kernel (DS2_CONV2_ROWS=1) has no statistics epilogue");
+  // 614, four rows (one block per CU) 767
   // blocks of a fully masked tile return early: their slots must read as zeros
   if (stat_part) DS2_HIP(hipMemsetAsync(stat_part, 0, (size_t)ds2_conv2_fwd_bf16_stat_blocks(B, D1, T) * 64 * sizeof(float), (hipStream_t)stream));
-  if (rows_env && rows_env[0] == '1') hipLaunchKernelGGL(conv2_bf16_kernel, dim3(ceil_div(T, TT), D2, B), dim3(256), 0, (hipStream_t)stream, a);
-  else {
-    a.gx = ceil_div(T, TT); a.gy = ceil_div(D2, 3); a.gz = B;
-    hipLaunchKernelGGL((conv2_bf16_rows_kernel<2, 3>), dim3(a.gx * a.gy * a.gz), dim3(256), 0, (hipStream_t)stream, a, D2, stat_part);
-  }
-  DS2_LAUNCH_CHECK("conv2_bf16_kernel fwd");
+  a.gx = ceil_div(T, TT); a.gy = ceil_div(D2, 3); a.gz = B;
+  hipLaunchKernelGGL((conv2_bf16_rows_kernel<2, 3>), dim3(a.gx * a.gy * a.gz), dim3(256), 0, (hipStream_t)stream, a, D2, stat_part);
+  DS2_LAUNCH_CHECK("conv2_bf16_rows_kernel fwd");
   return 0;
 }
 
@@ -406,14 +308,10 @@ extern "C" int ds2_conv2_dgrad_bf16(const void* dy2_nhwc, const void* wd0, const
     a.in = (const __bf16*)dy2_nhwc; a.wpk = (const __bf16*)(p == 0 ? wd0 : wd1); a.bias = nullptr; a.out = da1; a.lens = nullptr;
     a.B = B; a.Din = D2; a.T = T; a.Dtot = D1; a.KD = KDe; a.SD = 1; a.PD = KDe - 6; a.OS = 2; a.OO = p;
     // four output rows per block here (rows one apart: 4 input-row slots): 2 x 347 -> 2 x 290 us
-    static const char* rows_env = ds2_exp_getenv("DS2_CONV2_ROWS");
-    if (rows_env && rows_env[0] == '1') hipLaunchKernelGGL(conv2_bf16_kernel, dim3(ceil_div(T, TT), n_o, B), dim3(256), 0, (hipStream_t)stream, a);
-    else {
-      a.gx = ceil_div(T, TT); a.gy = ceil_div(n_o, 4); a.gz = B;
-      hipLaunchKernelGGL((conv2_bf16_rows_kernel<1, 4>), dim3(a.gx * a.gy * a.gz), dim3(256), 0, (hipStream_t)stream, a, n_o, (float*)nullptr);
-    }
+    a.gx = ceil_div(T, TT); a.gy = ceil_div(n_o, 4); a.gz = B;
+    hipLaunchKernelGGL((conv2_bf16_rows_kernel<1, 4>), dim3(a.gx * a.gy * a.gz), dim3(256), 0, (hipStream_t)stream, a, n_o, (float*)nullptr);
   }
-  DS2_LAUNCH_CHECK("conv2_bf16_kernel dgrad");
+  DS2_LAUNCH_CHECK("conv2_bf16_rows_kernel dgrad");
   return 0;
 }
 

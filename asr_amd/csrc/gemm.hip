@@ -479,10 +479,9 @@ extern "C" int ds2_gemm_f32(int transA, int transB, int M, int N, int K, const f
   const int vecB = ((ldb % 4) == 0) && (((uintptr_t)B % 16) == 0) && ((strideB % 4) == 0);
   dim3 grid(ceil_div(N, BN), ceil_div(M, BM), batch * splitk), block(256);
   hipStream_t s = (hipStream_t)stream;
-  // skinny NT (the fc logits): gemm_f32_skinny_nt_kernel, bit-identical to the tile kernel.  DS2_GEMM_SKINNY=0: the tile kernel (A/B switch)
-  static const char* skinny_env = ds2_exp_getenv("DS2_GEMM_SKINNY");
+  // skinny NT (the fc logits): gemm_f32_skinny_nt_kernel, bit-identical to the tile kernel
   if (!transA && transB && N <= 32 && M >= 1024 && K >= 128 && (K % 128) == 0 && (size_t)K * 128 <= 160 * 1024 && batch == 1 && splitk == 1 && !accumulate &&
-      vecA && vecB && !(skinny_env && skinny_env[0] == '0')) {
+      vecA && vecB) {
     static bool attr = false;
     if (!attr) {
       DS2_HIP(hipFuncSetAttribute((const void*)gemm_f32_skinny_nt_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -495,7 +494,7 @@ extern "C" int ds2_gemm_f32(int transA, int transB, int M, int N, int K, const f
   // skinny-K NN (the fc layer's input gradient): gemm_f32_skinny_k_kernel, bit-identical to the tile kernel
   // (one workgroup per CU — W fills the LDS —, 128 rows each: worth it from ~3/4 of the chip's CUs upwards; c2's 16000 rows stay on the tile kernel)
   if (!transA && !transB && K >= 1 && K <= 30 && (N % 32) == 0 && (size_t)N * 128 <= 160 * 1024 && M >= 20000 && batch == 1 && splitk == 1 && !accumulate &&
-      !bias && vecB && !(skinny_env && skinny_env[0] == '0')) {
+      !bias && vecB) {
     static bool attr = false;
     if (!attr) {
       DS2_HIP(hipFuncSetAttribute((const void*)gemm_f32_skinny_k_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -506,7 +505,7 @@ extern "C" int ds2_gemm_f32(int transA, int transB, int M, int N, int K, const f
     return 0;
   }
   // skinny-M split-K TN (the fc layer's weight gradient): gemm_f32_skinny_m_kernel writes the same slabs as the tile kernel, bit for bit
-  const bool skinny_m = transA && !transB && M <= 32 && (N % 128) == 0 && splitk > 1 && batch == 1 && kchunk >= 64 && !(skinny_env && skinny_env[0] == '0');
+  const bool skinny_m = transA && !transB && M <= 32 && (N % 128) == 0 && splitk > 1 && batch == 1 && kchunk >= 64;
   if (skinny_m) {
     hipLaunchKernelGGL(gemm_f32_skinny_m_kernel, dim3(N / 128, splitk), dim3(256), 0, s, A, lda, B, ldb, (float*)workspace, M, N, K, kchunk);
     DS2_LAUNCH_CHECK("gemm_f32_skinny_m_kernel");

@@ -34,14 +34,14 @@ constexpr int PITCH = 144;                       // bytes per LDS tile row (128 
 constexpr int TILE_BYTES = BM * PITCH;           // 18432
 
 __device__ __attribute__((aligned(16))) float g_zero16[4] = {0.f, 0.f, 0.f, 0.f};   // global address space zero page
-__device__ __attribute__((aligned(16))) float g_sink16[4];                          // where store lanes outside the matrix write (gemm_nt_ring.h)
+__device__ __attribute__((aligned(16))) float g_sink16[4];                          // where store lanes outside the matrix write (gemm_nt_w4.h)
 
 struct BArgs {
   const __bf16* A; const __bf16* B; float* C; const float* bias;
   int M, N, K, lda, ldb, ldc;
   long long sA, sB, sC;
   int splitk, kchunk, accumulate;
-  int nt_store;        // final C written with non-temporal stores (streamed out once)
+  int nt_store;        // 1: final C written with non-temporal stores (streamed out once)
   int super_rows;      // 256 x 256 NT kernels: row tiles per super-row of the XCD-aware tile walk (0: row-major)
   float* partial;
 };
@@ -176,20 +176,8 @@ __device__ __forceinline__ void glds16(const void* gsrc, char* lds_dst_wave_base
 }
 
 // WM x WN waves; each wave owns a (256/WM) x (256/WN) sub-tile.  2 x 4 (8 waves, 128 x 64 per wave) is the production shape.
-// PP (ping-pong, 2 x 4 waves only): the two wave groups (rows 0-127 / 128-255 of the tile = one wave per SIMD each) run the k-steps
-// half a step out of phase, held there by two raw barriers per k-step: while one group issues its 8 MFMAs the other reads its next
-// fragments and issues DMA, so the matrix pipe of every SIMD always has a wave in its MFMA cluster.
-// PERS (2 x 4 waves, no split-K, K a multiple of 128): PERSISTENT form for short reductions.  With K = 1024 a tile is 16 k-tiles = 29 us of
-// main loop, and a workgroup that computes ONE tile pays ~12 us around it (dispatch, pointer set-up, the first operand DMA's round trip,
-// the write-out of 256 KB): 29 % of the forward projection.  Here the grid is one workgroup per CU and each walks tiles orig, orig + grid,
-// ...: the k-tile stream simply continues across the tile boundary — the DMA of the NEXT tile's first two k-tiles goes out in the last two
-// k-steps of the current one, its first fragments are read behind the last MFMAs as always, and the epilogue (wave-private LDS patch outside
-// the operand buffers, bias fetched at the tile's start) runs while that DMA lands.  Same products, same order: bit-identical results.
-constexpr int G_PATCH = 8 * 16 * 40 * 4;          // PERS epilogue: 8 wave-private patches of 16 rows x 40 floats behind the operand buffers
-template <int WM, int WN, bool PP = false, bool PERS = false>
+template <int WM, int WN>
 __global__ __launch_bounds__(WM * WN * 64) void gemm_bf16_nt_glds_kernel(BArgs g, int ntx, int nty) {
-  static_assert(!PP || (WM == 2 && WN == 4), "ping-pong schedule is written for 2 x 4 waves");
-  static_assert(!PERS || (WM == 2 && WN == 4 && !PP), "persistent form: 2 x 4 waves, software-pipelined loop");
   constexpr int NWV = WM * WN;
   constexpr int NI = 8 / WM, NJ = 8 / WN;   // 32 x 32 MFMA tiles per wave along M / N
   constexpr int NP = 32 / NWV;              // 8-row pieces per wave per operand tile
@@ -200,24 +188,22 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_bf16_nt_glds_kernel(BArgs g
   const __bf16* B = g.B + (long long)zb * g.sB;
   // XCD-aware tile order: workgroups are dealt round-robin to the 8 XCDs, so give each XCD one contiguous run of the
   // (row-tile major) tile list: the tiles sharing an A row-tile then hit the same 4 MB L2.  (bijective for any count)
-  const int nt = ntx * nty;
-  int orig = blockIdx.x;
-  // (g.super_rows > 0: the sequence runs through super-rows of that many row tiles column by column, so that the 32 tiles an XCD holds at one
-  // time form a compact block — see gemm_nt_ring.h)
-  auto tile_origin = [&](int o, int& tm0, int& tn0) {
+  // g.super_rows > 0: the sequence runs through super-rows of that many row tiles column by column, so that the 32 tiles an XCD holds at one
+  // time form a compact block.
+  int m0, n0;
+  {
+    const int nt = ntx * nty, o = blockIdx.x;
     const int xcd = o & 7, q8 = nt >> 3, r8 = nt & 7;
     const int tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (o >> 3);
     if (g.super_rows > 0) {
       const int per = g.super_rows * ntx, sr = tile / per, rem = tile - sr * per;
       const int rows = min(g.super_rows, nty - sr * g.super_rows);
       const int tn = rem / rows;
-      tm0 = (sr * g.super_rows + rem - tn * rows) * 256; tn0 = tn * 256;
+      m0 = (sr * g.super_rows + rem - tn * rows) * 256; n0 = tn * 256;
     } else {
-      tm0 = (tile / ntx) * 256; tn0 = (tile % ntx) * 256;
+      m0 = (tile / ntx) * 256; n0 = (tile % ntx) * 256;
     }
-  };
-  int m0, n0;
-  tile_origin(orig, m0, n0);
+  }
   const int kbeg = zs * g.kchunk;
   const int kend = min(g.K, kbeg + g.kchunk);
   const int nkt = (kend - kbeg + BK - 1) / BK;
@@ -228,32 +214,12 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_bf16_nt_glds_kernel(BArgs g
 
   // staging: wave w moves pieces w, w+8, w+16, w+24 (8 rows each) of A and of B
   const int prow = lane >> 3;                       // row inside the piece
-  const __bf16* srcA[NP];
-  const __bf16* srcB[NP];
-  bool okA[NP], okB[NP];
   int segk[NP];                                     // k offset (elements) of the 16-byte segment this lane fetches
 #pragma unroll
   for (int i = 0; i < NP; ++i) {
     const int r = (wave + NWV * i) * 8 + prow;        // row inside the 256-row tile
     segk[i] = (((lane & 7) ^ ((r >> 1) & 7)) << 3);
-    okA[i] = m0 + r < g.M;
-    okB[i] = n0 + r < g.N;
-    srcA[i] = A + (long long)(m0 + r) * g.lda + segk[i];
-    srcB[i] = B + (long long)(n0 + r) * g.ldb + segk[i];
   }
-  auto stage_part = [&](int buf, int k0, int i) {     // one A piece + one B piece (2 of the wave's 8 DMA instructions)
-    char* dA = ldsg + buf * 2 * G_TILE;
-    char* dB = dA + G_TILE;
-    const bool kok = k0 + segk[i] + 8 <= kend;
-    const void* pa = (okA[i] && kok) ? (const void*)(srcA[i] + k0) : (const void*)g_zero16;
-    const void* pb = (okB[i] && kok) ? (const void*)(srcB[i] + k0) : (const void*)g_zero16;
-    glds16(pa, dA + (wave + NWV * i) * 1024);
-    glds16(pb, dB + (wave + NWV * i) * 1024);
-  };
-  auto stage = [&](int buf, int k0) {
-#pragma unroll
-    for (int i = 0; i < NP; ++i) stage_part(buf, k0, i);
-  };
 
   f32x16 acc[NI][NJ];
 #pragma unroll
@@ -271,102 +237,54 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_bf16_nt_glds_kernel(BArgs g
   const int arow = (wm * (NI * 32) + l31) * 128;
   const int brow = G_TILE + (wn * (NJ * 32) + l31) * 128;
 
-  if constexpr (PP) {
-    stage(0, kbeg);
-    // Schedule per k-step (kk):  [read fragments kk | DMA slice | waits]  BARRIER  [8 MFMAs]  BARRIER.  Group B (wm = 1) runs one
-    // barrier behind group A, so A's MFMA section always coincides with B's read section and vice versa.
-    //  * fragments of a k-step are complete (lgkmcnt 0) before its first barrier, so a buffer is dead once both groups have passed
-    //    that barrier of the tile's last k-step -> the DMA of tile kt+1 (into the other buffer) may start in k-step 0 of tile kt;
-    //  * every wave waits for its own DMA of tile kt+1 (vmcnt 0) in k-step 3 of tile kt, before its first barrier: when group A
-    //    passes the last barrier of tile kt, all eight waves have done so.
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (wm == 1) __builtin_amdgcn_s_barrier();          // phase offset of group B
-    for (int kt = 0; kt < nkt; ++kt) {
-      const bool more = kt + 1 < nkt;                   // block-uniform
-      const char* base = ldsg + (kt & 1) * 2 * G_TILE;
+  // ---- software-pipelined main loop, ONE barrier per k-tile.  The fragments of k-step kk+1 (for kk = 3: of the NEXT tile's
+  // k-step 0) are read while the MFMAs of k-step kk issue, so the matrix pipe never waits for an LDS round trip; the barrier sits in
+  // front of the last k-step, behind 8 MFMAs that are still executing, and the DMA of tile kt+2 goes out right behind it into the
+  // buffer whose last fragment read that barrier has just retired.  Two tiles of DMA are in flight at any time.
+  //   order per tile:  R(1) M(0) | R(2) M(1) | R(3) M(2) | wait own DMA + own reads, BARRIER | DMA(kt+2) R(next 0) M(3)
+  // LDS-DMA visibility: a tile is read only after every wave's vmcnt(0) AND a barrier (guide: "one barrier after the wait").
+  // Rows beyond M / N are CLAMPED to the last valid row instead of zero-filled: they only feed C rows / columns that are never stored.
+  const char* zp = reinterpret_cast<const char*>(g_zero16);
+  const char* qA[NP];
+  const char* qB[NP];
 #pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
-        bf16x8 a[NI], b[NJ];
-#pragma unroll
-        for (int i = 0; i < NI; ++i) a[i] = *reinterpret_cast<const bf16x8*>(base + arow + i * 32 * 128 + koff[kk]);
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) b[j] = *reinterpret_cast<const bf16x8*>(base + brow + j * 32 * 128 + koff[kk]);
-        if (more) {
-          if (kk == 0) { stage_part((kt + 1) & 1, kbeg + (kt + 1) * BK, 0); stage_part((kt + 1) & 1, kbeg + (kt + 1) * BK, 1); }
-          if (kk == 1) stage_part((kt + 1) & 1, kbeg + (kt + 1) * BK, 2);
-          if (kk == 2) stage_part((kt + 1) & 1, kbeg + (kt + 1) * BK, 3);
-          if (kk == 3) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int i = 0; i < NI; ++i)
-#pragma unroll
-          for (int j = 0; j < NJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
-        __builtin_amdgcn_s_setprio(0);
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-      }
+  for (int i = 0; i < NP; ++i) {
+    const int r = (wave + NWV * i) * 8 + prow;
+    qA[i] = reinterpret_cast<const char*>(A + (long long)min(m0 + r, g.M - 1) * g.lda + segk[i] + kbeg);
+    qB[i] = reinterpret_cast<const char*>(B + (long long)min(n0 + r, g.N - 1) * g.ldb + segk[i] + kbeg);
+  }
+  const int nfull = (kend - kbeg) / BK;             // tiles that lie completely inside [kbeg, kend)
+  // piece i (8 rows of A + 8 rows of B per wave) of tile kt -> buffer buf.  Tiles are staged in order, so the pointers just advance.
+  auto stage_piece = [&](int buf, int kt, int i) {
+    char* dA = ldsg + buf * 2 * G_TILE + (wave + NWV * i) * 1024;
+    if (kt < nfull) {
+      glds16(qA[i], dA);
+      glds16(qB[i], dA + G_TILE);
+      qA[i] += BK * 2;
+      qB[i] += BK * 2;
+    } else {                                        // the K tail: per-segment bounds (the pointers already stand on this tile)
+      const bool kok = kbeg + kt * BK + segk[i] + 8 <= kend;
+      glds16(kok ? qA[i] : zp, dA);
+      glds16(kok ? qB[i] : zp, dA + G_TILE);
     }
-    if (wm == 0) __builtin_amdgcn_s_barrier();          // group A catches the barrier group B is one behind on
-  } else {
-    // ---- software-pipelined main loop, ONE barrier per k-tile.  The fragments of k-step kk+1 (for kk = 3: of the NEXT tile's
-    // k-step 0) are read while the MFMAs of k-step kk issue, so the matrix pipe never waits for an LDS round trip; the barrier sits in
-    // front of the last k-step, behind 8 MFMAs that are still executing, and the DMA of tile kt+2 goes out right behind it into the
-    // buffer whose last fragment read that barrier has just retired.  Two tiles of DMA are in flight at any time.
-    //   order per tile:  R(1) M(0) | R(2) M(1) | R(3) M(2) | wait own DMA + own reads, BARRIER | DMA(kt+2) R(next 0) M(3)
-    // LDS-DMA visibility: a tile is read only after every wave's vmcnt(0) AND a barrier (guide: "one barrier after the wait").
-    const char* zp = reinterpret_cast<const char*>(g_zero16);
-    // rows beyond M / N are CLAMPED to the last valid row instead of zero-filled: they only feed C rows / columns that are never stored
-    const char* qA[NP];
-    const char* qB[NP];
-    auto retarget = [&](int tm0, int tn0) {
+  };
+  auto stage_tile = [&](int buf, int kt) {
 #pragma unroll
-      for (int i = 0; i < NP; ++i) {
-        const int r = (wave + NWV * i) * 8 + prow;
-        qA[i] = reinterpret_cast<const char*>(A + (long long)min(tm0 + r, g.M - 1) * g.lda + segk[i] + kbeg);
-        qB[i] = reinterpret_cast<const char*>(B + (long long)min(tn0 + r, g.N - 1) * g.ldb + segk[i] + kbeg);
-      }
-    };
-    retarget(m0, n0);
-    bool more_tiles = false;                            // PERS: another tile follows this one (its first k-tiles are staged from inside this one)
-    const int nfull = (g.nt_store & 2) ? 1 : (kend - kbeg) / BK;       // tiles that lie completely inside [kbeg, kend)  (bit 1: timing experiment)
-    // piece i (8 rows of A + 8 rows of B per wave) of tile kt -> buffer buf.  Tiles are staged in order, so the pointers just advance.
-    auto stage_piece = [&](int buf, int kt, int i) {
-      char* dA = ldsg + buf * 2 * G_TILE + (wave + NWV * i) * 1024;
-      if (PERS || kt < nfull) {                       // (PERS: K is a multiple of the k-tile; `kt` may run into the next tile)
-        glds16(qA[i], dA);
-        glds16(qB[i], dA + G_TILE);
-        qA[i] += BK * 2;
-        qB[i] += BK * 2;
-      } else if (!(g.nt_store & 2)) {                 // the K tail: per-segment bounds (the pointers already stand on this tile)
-        const bool kok = kbeg + kt * BK + segk[i] + 8 <= kend;
-        glds16(kok ? qA[i] : zp, dA);
-        glds16(kok ? qB[i] : zp, dA + G_TILE);
-      }
-    };
-    auto stage_tile = [&](int buf, int kt) {
+    for (int i = 0; i < NP; ++i) stage_piece(buf, kt, i);
+  };
+  // The fragment reads and their waits are inline asm, and every read is issued in the execution shadow of an MFMA (one read
+  // behind each of the first NI + NJ MFMAs of a k-step): a 32x32x16 MFMA occupies the matrix pipe for 32 cycles during which its
+  // wave is free to issue other instructions, whereas reads issued in a block in front of the MFMAs cost ~20 % of the loop when the
+  // two waves of a SIMD run in step.  Left to the compiler, every wait for an LDS read also becomes lgkmcnt(0) in FRONT of the MFMAs.
+  // Each wait names the registers it retires as in/out operands, so the MFMAs that consume them cannot be scheduled above it.
+  f32x4 fa[2][NI], fb[2][NJ];
+  const unsigned lds0 = (unsigned)(uintptr_t)(lds_void*)ldsg;
+  unsigned ra[4], rb[4];                              // byte address of this lane's fragment slot per k-step, buffer 0
 #pragma unroll
-      for (int i = 0; i < NP; ++i) stage_piece(buf, kt, i);
-    };
-    // The fragment reads and their waits are inline asm, and every read is issued in the execution shadow of an MFMA (one read
-    // behind each of the first NI + NJ MFMAs of a k-step): a 32x32x16 MFMA occupies the matrix pipe for 32 cycles during which its
-    // wave is free to issue other instructions, whereas reads issued in a block in front of the MFMAs cost ~20 % of the loop when the
-    // two waves of a SIMD run in step.  Left to the compiler, every wait for an LDS read also becomes lgkmcnt(0) in FRONT of the MFMAs.
-    // Each wait names the registers it retires as in/out operands, so the MFMAs that consume them cannot be scheduled above it.
-    f32x4 fa[2][NI], fb[2][NJ];
-    const unsigned lds0 = (unsigned)(uintptr_t)(lds_void*)ldsg;
-    unsigned ra[4], rb[4];                              // byte address of this lane's fragment slot per k-step, buffer 0
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) { ra[kk] = lds0 + arow + koff[kk]; rb[kk] = lds0 + brow + koff[kk]; }
-    static_assert(NI + NJ <= NI * NJ + 2 && NI <= 4 && NJ <= 2, "interleave below");
-    constexpr int NR = NI + NJ;                          // fragment reads per k-step
-    // read r of a k-step, in the order the next k-step consumes them: A0, B0 .. B(NJ-1), A1 .. A(NI-1)
+  for (int kk = 0; kk < 4; ++kk) { ra[kk] = lds0 + arow + koff[kk]; rb[kk] = lds0 + brow + koff[kk]; }
+  static_assert(NI + NJ <= NI * NJ + 2 && NI <= 4 && NJ <= 2, "interleave below");
+  constexpr int NR = NI + NJ;                          // fragment reads per k-step
+  // read r of a k-step, in the order the next k-step consumes them: A0, B0 .. B(NJ-1), A1 .. A(NI-1)
 #define G_ISA(r_) ((r_) == 0 || (r_) > NJ)
 #define G_IDX(r_) ((r_) == 0 ? 0 : (r_) <= NJ ? (r_) - 1 : (r_) - NJ)
 #define G_RD1(set, bufoff, kk, r_)                                                                                                    \
@@ -378,7 +296,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_bf16_nt_glds_kernel(BArgs g
       asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(fb[set][(r_) < NR && !G_ISA(r_) ? G_IDX(r_) : 0]) : "v"(rb[kk] + (bufoff)), \
                    "n"(((r_) < NR && !G_ISA(r_) ? G_IDX(r_) : 0) * 4096));                                                            \
   } while (0)
-    // every LDS read of this wave has returned (both fragment sets complete); WAITSTR may add vmcnt(0)
+  // every LDS read of this wave has returned (both fragment sets complete); WAITSTR may add vmcnt(0)
 #define G_RETIRE_ALL(WAITSTR)                                                                                                         \
   asm volatile(WAITSTR " lgkmcnt(0)"                                                                                                  \
                : "+v"(fa[0][0]), "+v"(fa[0][NI > 1 ? 1 : 0]), "+v"(fa[0][NI > 2 ? 2 : 0]), "+v"(fa[0][NI > 3 ? 3 : 0]),               \
@@ -387,10 +305,10 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_bf16_nt_glds_kernel(BArgs g
                  "+v"(fb[1][0]), "+v"(fb[1][NJ > 1 ? 1 : 0])                                                                          \
                :                                                                                                                      \
                : "memory")
-    // One k-step: the MFMAs of fragment set `cur` row by row; behind MFMA m goes read m of k-step kk_n (buffer offset off_n) into set
-    // `nxt` and — when DMA is true — piece m of tile kt+2.  Before row i a COUNTED wait retires exactly the fragments that row needs
-    // (A_i, for i = 0 also every B): of the previous step's NR reads NI-1-i may still be in flight, plus the min(i*NJ, NR) reads this
-    // step has issued so far — every fragment gets 6 to 9 MFMA times (190-290 cycles) between its issue and its first use.
+  // One k-step: the MFMAs of fragment set `cur` row by row; behind MFMA m goes read m of k-step kk_n (buffer offset off_n) into set
+  // `nxt` and — when DMA is true — piece m of tile kt+2.  Before row i a COUNTED wait retires exactly the fragments that row needs
+  // (A_i, for i = 0 also every B): of the previous step's NR reads NI-1-i may still be in flight, plus the min(i*NJ, NR) reads this
+  // step has issued so far — every fragment gets 6 to 9 MFMA times (190-290 cycles) between its issue and its first use.
 #define G_STEP(cur, nxt, off_n, kk_n, DMA)                                                                                            \
   do {                                                                                                                                \
     _Pragma("unroll") for (int m_ = 0; m_ < NI * NJ; ++m_) {                                                                          \
@@ -403,103 +321,40 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_bf16_nt_glds_kernel(BArgs g
                                                                      __builtin_bit_cast(bf16x8, fb[cur][m_ % NJ]), acc[m_ / NJ][m_ % NJ], 0, 0, 0); \
       __builtin_amdgcn_sched_barrier(0);                                                                                              \
       G_RD1(nxt, off_n, kk_n, m_);                                                                                                    \
-      if ((DMA) && m_ < NP && (kt + 2 < nkt || more_tiles)) stage_piece(kt & 1, kt + 2, m_);                                          \
+      if ((DMA) && m_ < NP && kt + 2 < nkt) stage_piece(kt & 1, kt + 2, m_);                                                          \
       __builtin_amdgcn_sched_barrier(0);                                                                                              \
     }                                                                                                                                 \
   } while (0)
-    stage_tile(0, 0);
-    if (nkt > 1) {
-      stage_tile(1, 1);
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NP) : "memory");   // tile 0 has landed; tile 1 may still be in flight
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
+  stage_tile(0, 0);
+  if (nkt > 1) {
+    stage_tile(1, 1);
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NP) : "memory");   // tile 0 has landed; tile 1 may still be in flight
+  } else {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int r = 0; r < NR; ++r) G_RD1(0, 0u, 0, r);
+  for (int kt = 0; kt < nkt; ++kt) {
+    const unsigned boff = (kt & 1) * 2 * G_TILE, noff = ((kt + 1) & 1) * 2 * G_TILE;
+    __builtin_amdgcn_sched_barrier(0);
+    G_STEP(0, 1, boff, 1, false);
+    G_STEP(1, 0, boff, 2, false);
+    G_STEP(0, 1, boff, 3, false);
+    // own DMA of tile kt+1 has landed and own reads of buffer kt&1 are complete; past the barrier that holds for every wave:
+    // tile kt+1 may be read, buffer kt&1 may be refilled (the last k-step's MFMAs still run from registers)
+    G_RETIRE_ALL("s_waitcnt vmcnt(0)");
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int r = 0; r < NR; ++r) G_RD1(0, 0u, 0, r);
-    for (;;) {                                         // PERS: one iteration per tile of this workgroup; else exactly one
-      int m0n = 0, n0n = 0;
-      f32x4 pbv[NJ];                                   // PERS: the tile's bias values, fetched here so that the epilogue waits for nothing
-      if constexpr (PERS) {
-        more_tiles = orig + (int)gridDim.x < nt;
-        if (more_tiles) tile_origin(orig + (int)gridDim.x, m0n, n0n);
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-          const int col = n0 + wn * (NJ * 32) + j * 32 + (lane & 7) * 4;
-          pbv[j] = (g.bias && col < g.N) ? *reinterpret_cast<const f32x4*>(g.bias + col) : f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-#pragma unroll
-        for (int i = 0; i < NI; ++i)
-#pragma unroll
-          for (int j = 0; j < NJ; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-      }
-      for (int kt = 0; kt < nkt; ++kt) {
-        const unsigned boff = (kt & 1) * 2 * G_TILE, noff = ((kt + 1) & 1) * 2 * G_TILE;
-        __builtin_amdgcn_sched_barrier(0);
-        G_STEP(0, 1, boff, 1, false);
-        G_STEP(1, 0, boff, 2, false);
-        G_STEP(0, 1, boff, 3, false);
-        // own DMA of tile kt+1 has landed and own reads of buffer kt&1 are complete; past the barrier that holds for every wave:
-        // tile kt+1 may be read, buffer kt&1 may be refilled (the last k-step's MFMAs still run from registers)
-        G_RETIRE_ALL("s_waitcnt vmcnt(0)");
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (PERS) {
-          if (more_tiles && kt == nkt - 2) retarget(m0n, n0n);   // from here on the DMA stages the next tile's k-tiles 0 and 1
-        }
-        G_STEP(1, 0, noff, 0, true);                   // (after the last tile: harmless reads of stale LDS, retired below)
-      }
-      if constexpr (!PERS) break;
-      if constexpr (PERS) {
-        // ---- epilogue of this tile (the next tile's operands are landing meanwhile; its k-step-0 fragments are already on their way into
-        // fragment set 0): every 32 x 32 accumulator tile through the wave-private patch in two halves of 16 rows, out as 16-byte stores
-        constexpr int EP = 40;
-        float* patch = reinterpret_cast<float*>(ldsg + G_LDS) + wave * (16 * EP);
-        const int prow8 = lane >> 3, pc4 = (lane & 7) * 4;
-        float* C = g.C;
-        const long long ldc = g.ldc;
-        const bool stream_out = (g.nt_store & 1) != 0;
-#pragma unroll
-        for (int i = 0; i < NI; ++i) {
-#pragma unroll
-          for (int j = 0; j < NJ; ++j) {
-            const int col = n0 + wn * (NJ * 32) + j * 32 + pc4;
-#pragma unroll
-            for (int hh = 0; hh < 2; ++hh) {
-#pragma unroll
-              for (int r = 0; r < 8; ++r) patch[((r & 3) + 8 * (r >> 2) + 4 * half) * EP + l31] = acc[i][j][hh * 8 + r];
-              __builtin_amdgcn_wave_barrier();
-#pragma unroll
-              for (int it = 0; it < 2; ++it) {
-                const int rl = it * 8 + prow8;
-                const int row = m0 + wm * (NI * 32) + i * 32 + hh * 16 + rl;
-                f32x4 v = *reinterpret_cast<const f32x4*>(&patch[rl * EP + pc4]);
-                if (row < g.M && col < g.N) {
-                  v += pbv[j];
-                  f32x4* pc = reinterpret_cast<f32x4*>(C + (long long)row * ldc + col);
-                  if (stream_out) __builtin_nontemporal_store(v, pc);
-                  else *pc = v;
-                }
-              }
-              __builtin_amdgcn_wave_barrier();
-            }
-          }
-        }
-        if (!more_tiles) break;
-        orig += (int)gridDim.x; m0 = m0n; n0 = n0n;
-      }
-    }
-    G_RETIRE_ALL("s_waitcnt");
-    if constexpr (PERS) return;
+    G_STEP(1, 0, noff, 0, true);                     // (after the last tile: harmless reads of stale LDS, retired below)
+  }
+  G_RETIRE_ALL("s_waitcnt");
 #undef G_RD1
 #undef G_ISA
 #undef G_IDX
 #undef G_RETIRE_ALL
 #undef G_STEP
-  }
 
   float* C;
   long long ldc;
@@ -516,8 +371,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_bf16_nt_glds_kernel(BArgs g
   // form below (the address unit spends ~16 cycles on a wave-instruction whatever the width per lane: 256 KB of C per tile take
   // ~16 B/clk with 4-byte lanes).  Patch pitch 40 floats: the two half-waves of a write (rows r, r + 4) land on disjoint bank halves.
   {
-    const bool wide = (g.N % 4) == 0 && (ldc % 4) == 0 && ((uintptr_t)C % 16) == 0 && !(g.nt_store & (32 | 64 | 128)) &&
-                      (partial || !g.bias || ((uintptr_t)g.bias % 16) == 0);
+    const bool wide = (g.N % 4) == 0 && (ldc % 4) == 0 && ((uintptr_t)C % 16) == 0 && (partial || !g.bias || ((uintptr_t)g.bias % 16) == 0);
     if constexpr (NWV == 8) if (wide) {                // (the 16-wave variant sits at its 128-register cap: with this branch compiled in it spills accumulators inside the main loop)
       constexpr int EP = 40;
       __syncthreads();                                  // every wave is done with the operand tiles: the LDS is free
@@ -528,7 +382,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_bf16_nt_glds_kernel(BArgs g
       const int l31 = el & 31, half = el >> 5;
       float* patch = reinterpret_cast<float*>(ldsg) + wave * (32 * EP);
       const int prow = el >> 3, pc4 = (el & 7) * 4;
-      const bool stream_out = !partial && (g.nt_store & 1);
+      const bool stream_out = !partial && g.nt_store;
       f32x4 bv[NJ];
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
@@ -580,10 +434,9 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_bf16_nt_glds_kernel(BArgs g
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int row = m0 + wm * (NI * 32) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-        if (row < g.M && !((g.nt_store & 32) && r != 0)) {      // (bit 5: timing experiment, 1/16 of the stores)
+        if (row < g.M) {
           float v = acc[i][j][r] + bv;
           float* p = C + (long long)row * ldc + col;
-          if (g.nt_store & 64) p = C + (long long)((blockIdx.x % 120) * 256 + (row & 255)) * ldc + (col & 255);   // timing experiment: L2-resident target
           if (!partial && g.accumulate) v += *p;
           // final C is streamed out once (788 MB for the forward Gx) -> non-temporal; split-K slabs are re-read right away -> cached
           if (partial || !g.nt_store) *p = v;
@@ -612,17 +465,24 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_bf16_nt_glds_kernel(BArgs g
 // TERMS: consecutive problems that name the same C are terms of ONE product (the fp32 mode's hi.hi + hi.lo + lo.hi on row-pitched views of
 // split operands): each term is an entry of its own, all of them write slabs of the product's slab array (slab0 = term * splitk) and the
 // entry of the first term carries the reduce over all nslab = terms * splitk slabs.
+// grouped TN launches (gemm_bf16_tn_glds_kernel<true>, gemm_tn_w4.h): blockIdx.x -> item.  Workgroup ids go round the 8 XCDs, one workgroup
+// per CU, so the 32 workgroups an XCD holds at a time are the ids 256 c + x + 8 j.  They take 32 CONSECUTIVE items = (with at most 8 column
+// tiles) a few whole tile rows of one K slice, which share their A / B panels through that XCD's L2: 12 panels for 64 panel reads at 4 column
+// tiles.  The items of a last, partial run of 256 ids are dealt to the XCDs as contiguous runs.
+__device__ __forceinline__ int tn_item_order(int nitems) {
+  const int item = blockIdx.x, full = nitems & ~255;
+  if (item < full) return (item & ~255) + ((item & 7) << 5) + ((item & 255) >> 3);
+  const int R = nitems - full, o = item - full, x = o & 7, q8 = R >> 3, r8 = R & 7;
+  return full + (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + (o >> 3);
+}
 struct TnSProb {
   const __bf16* A; const __bf16* B; float* C; float* partial;       // partial: the product's slabs [nslab][M][N] (unused when it has one slab)
   int M, N, K, lda, ldb, ldc, ntx, ntiles, kchunk, first_item;
   int slab0, nslab, to_slab;                                        // this entry's first slab; slabs to reduce (first term only, else 0); write a slab?
-  // fused reduce (gemm_tn_w4.h): the product's arrival counters, one per tile (zeroed by the launcher), and how many slabs a tile waits for —
-  // the workgroup that stores the LAST slab of a tile adds all of them in slab order and writes C; tick == NULL: the separate reduce launch
-  int* tick; int nslab_all;
 };
 struct TnSGroup {
   TnSProb p[TN_MAX_PROBLEMS];
-  int nprob, splitk, nitems, order;
+  int nprob, splitk, nitems;
   // epilogue of ONE product in the reduce launch (ds2_gemm_bf16_tn_splitk_group_ep; ep_prob < 0: none):
   //   C[r][c] = (sum of slabs)[r][c] * ep_scale[c] + ep_rowv[r] * ep_shift[c]   — the weight gradient of a projection with a folded BatchNorm
   int ep_prob;
@@ -640,17 +500,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_tn_glds_kernel(BArgs g, int ntx
   bool partial;
   if constexpr (GROUPED) {
     // the item's problem: field by field with wave-uniform compares (a dynamically indexed kernel-argument struct would go to scratch)
-    // items handed to the workgroups in XCD-sized runs of 32 consecutive (slice, tile) pairs: see gemm_tn_w4.h (same order, same reason)
-    int item = blockIdx.x;
-    if (grp.order) {
-      const int full = grp.nitems & ~255;
-      if (item < full) {
-        item = (item & ~255) + ((item & 7) << 5) + ((item & 255) >> 3);
-      } else {
-        const int R = grp.nitems - full, o = item - full, x = o & 7, q8 = R >> 3, r8 = R & 7;
-        item = full + (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + (o >> 3);
-      }
-    }
+    const int item = tn_item_order(grp.nitems);
     A = grp.p[0].A; B = grp.p[0].B; Cfinal = grp.p[0].C; Cslab = grp.p[0].partial;
     pM = grp.p[0].M; pN = grp.p[0].N; pK = grp.p[0].K; plda = grp.p[0].lda; pldb = grp.p[0].ldb; ldcf = grp.p[0].ldc; ntx = grp.p[0].ntx;
     nt = grp.p[0].ntiles; kchunk = grp.p[0].kchunk;
@@ -679,7 +529,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_tn_glds_kernel(BArgs g, int ntx
     Cslab = g.partial + ((long long)zb * g.splitk + zs) * (long long)g.M * g.N;
   }
   int tile = orig;
-  if (!(GROUPED && grp.order)) {
+  if (!GROUPED) {                                     // each XCD a contiguous run of the tiles (see the NT kernel)
     const int xcd = orig & 7, q8 = nt >> 3, r8 = nt & 7;
     tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
   }
@@ -829,7 +679,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_tn_glds_kernel(BArgs g, int ntx
   const long long ldc = partial ? (long long)pN : ldcf;
   const bool accumulate = !partial && !GROUPED && g.accumulate;
   // wide epilogue (see the NT kernel): 32 x 32 accumulator tiles through a wave-private LDS patch, 16-byte stores
-  if ((ldc % 4) == 0 && ((uintptr_t)C % 16) == 0 && !(!GROUPED && (g.nt_store & 128))) {
+  if ((ldc % 4) == 0 && ((uintptr_t)C % 16) == 0) {
     constexpr int EP = 40;
     __syncthreads();
     float* patch = reinterpret_cast<float*>(ldsg) + wave * (32 * EP);
@@ -1075,7 +925,6 @@ __global__ __launch_bounds__(256) void split_bf16_kernel(const float* __restrict
   }
 }
 
-#include "gemm_nt_ring.h"
 #include "permlane.h"
 #include "gemm_nt_w4.h"
 #include "gemm_tn_group.h"
@@ -1141,80 +990,26 @@ extern "C" int ds2_gemm_bf16_nt(int M, int N, int K, const void* A, int lda, lon
   g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
   g.sA = strideA; g.sB = strideB; g.sC = strideC;
   g.splitk = splitk; g.kchunk = kchunk; g.accumulate = accumulate; g.partial = (float*)workspace;
-  static const char* nt_env = ds2_exp_getenv("DS2_GEMM_NT");       // tuning override, default on
-  g.nt_store = nt_env ? (nt_env[0] != '0') : 1;
-  // timing experiments only (WRONG RESULTS; scripts/ab_gemm_dbg.sh): 1 = no operand DMA after the first k-tile, 16 = 1/16 of the C
-  // stores, 32 = C stores aimed at an L2-resident region
-  static const int dbg_bits = ds2_exp_getenv("DS2_GEMM_DBG") ? atoi(ds2_exp_getenv("DS2_GEMM_DBG")) << 1 : 0;
-  g.nt_store |= dbg_bits;
-  static const char* wide_env = ds2_exp_getenv("DS2_GEMM_WIDE");  // "0": lane-per-column epilogue stores (A/B switch)
-  if (wide_env && wide_env[0] == '0') g.nt_store |= 128;
-  static const int super_rows = ds2_exp_getenv("DS2_GEMM_SR") ? atoi(ds2_exp_getenv("DS2_GEMM_SR")) : 4;   // row tiles per super-row of the tile walk (0: row-major)
-  g.super_rows = batch == 1 ? super_rows : 0;
+  g.nt_store = 1;
+  g.super_rows = batch == 1 ? 4 : 0;                                 // row tiles per super-row of the tile walk (0: row-major)
   hipStream_t s = (hipStream_t)stream;
   // 256 x 256 LDS-DMA kernel whenever its tiles cover at least half the chip; the 128 x 128 kernel for everything smaller
   const long long tiles256 = (long long)ceil_div(N, 256) * ceil_div(M, 256) * batch * splitk;
-  static const char* force = ds2_exp_getenv("DS2_GEMM_TILE");      // "128" | "glds": tuning override (scripts/bench_gemm.py)
-  const bool use_glds = force ? (force[0] == 'g') : (M >= 256 && N >= 256 && tiles256 >= 128);
-  if (use_glds) {
-    DS2_ATTR_ONCE((gemm_bf16_nt_glds_kernel<2, 4>), G_LDS);
+  if (M >= 256 && N >= 256 && tiles256 >= 128) {
     const int ntx = ceil_div(N, 256), nty = ceil_div(M, 256);
-    // 8 waves (128 x 64 per wave) for every shape (a 16-wave 64 x 64 variant lost to it in round 2 once the epilogue went through LDS and is no
-    // longer built).
-    static const char* wv = ds2_exp_getenv("DS2_GEMM_WAVES");      // "pp": the ping-pong schedule of the one-tile kernel (tuning override)
-    const bool pp = wv && wv[0] == 'p';
-    if (pp) {
-      DS2_ATTR_ONCE((gemm_bf16_nt_glds_kernel<2, 4, true>), G_LDS);
-      hipLaunchKernelGGL((gemm_bf16_nt_glds_kernel<2, 4, true>), dim3(ntx * nty, 1, batch * splitk), dim3(512), G_LDS, s, g, ntx, nty);
+    const int cus = ds2_cus_current();
+    const bool wide = (N % 4) == 0 && (ldc % 4) == 0 && ((uintptr_t)C % 16) == 0 && (!bias || ((uintptr_t)bias % 16) == 0);
+    // four waves x 128 x 128, one workgroup per CU walking the tiles (gemm_nt_w4.h): wherever it applies — K a multiple of the 64-deep
+    // k-tile, more tiles than CUs, plain write-out, 32-bit lane offsets inside a tile.  Otherwise 8 waves (128 x 64 per wave), one
+    // workgroup per tile: the same products in the same order.
+    const bool w4 = ds2_is_gfx950() && batch == 1 && splitk == 1 && !accumulate && (K % 64) == 0 && K >= 128 && wide && ntx * nty > cus &&
+                    (long long)lda * 512 < (1ll << 31) && (long long)ldb * 512 < (1ll << 31);
+    if (w4) {
+      DS2_ATTR_ONCE((gemm_bf16_nt_w4_kernel<false>), W4_LDS);
+      hipLaunchKernelGGL((gemm_bf16_nt_w4_kernel<false>), dim3(cus, 1, 1), dim3(256), W4_LDS, s, g, ntx, nty);
     } else {
-      // persistent form (one workgroup per CU walking several tiles; see the kernel): short reductions with more tiles than CUs, plain write-out
-      static const char* pe = ds2_exp_getenv("DS2_GEMM_PERS");     // "0": one workgroup per tile for every shape (A/B switch)
-      const int cus = ds2_cus_current();
-      const int nkt = K / BK;
-      const bool wide = (N % 4) == 0 && (ldc % 4) == 0 && ((uintptr_t)C % 16) == 0 && (!bias || ((uintptr_t)bias % 16) == 0);
-      const bool pers = !(pe && pe[0] == '0') && batch == 1 && splitk == 1 && !accumulate && (K % BK) == 0 && nkt >= 2 && (nkt % 2) == 0 &&
-                        nkt <= 128 && wide && !(g.nt_store & ~1) && ntx * nty > cus;
-      // EXPERIMENTS of round 5 (gemm_nt_ring.h; profiles/r05_gemm_ring_ab.txt), bit-identical to the production kernel and not faster:
-      // DS2_GEMM_RING=1 the software-pipelined loop over a four-slice LDS ring with counted DMA waits, =q the ping-pong form on
-      // v_mfma_f32_16x16x32_bf16 with a register-direct epilogue.  Both are bound, like the production kernel, by what a CU can take in
-      // through its vector-memory path when part of the operand stream misses the L2 (the operand DMA alone, no MFMA: 350 us on the dX shape).
-      static const char* ring_env = ds2_exp_getenv("DS2_GEMM_RING");
-      const bool ring = ring_env && (ring_env[0] == '1' || ring_env[0] == 'q') && !(pe && pe[0] == '0') && batch == 1 && splitk == 1 && !accumulate &&
-                        (K % 32) == 0 && K >= 128 && wide && !(g.nt_store & ~1) && ntx * nty > cus;
-      // four waves x 128 x 128 (gemm_nt_w4.h): the default wherever it applies — K a multiple of the 64-deep k-tile, more tiles than CUs, plain
-      // write-out, 32-bit lane offsets inside a tile (DS2_GEMM_W4=0: the 8-wave persistent kernel instead, A/B switch)
-      static const char* w4_env = ds2_exp_getenv("DS2_GEMM_W4");
-      const bool w4 = ds2_is_gfx950() && !(w4_env && w4_env[0] == '0') && !(ring_env && ring_env[0] != 'w') && !(pe && pe[0] == '0') && batch == 1 && splitk == 1 &&
-                      !accumulate && (K % 64) == 0 && K >= 128 && wide && !(g.nt_store & ~1) && ntx * nty > cus &&
-                      (long long)lda * 512 < (1ll << 31) && (long long)ldb * 512 < (1ll << 31);
-      if (w4) {
-        static const int wdbg = ds2_exp_getenv("DS2_W4_DBG") ? atoi(ds2_exp_getenv("DS2_W4_DBG")) : 0;   // timing ablations (WRONG RESULTS; scripts/r5_w4_dbg.sh)
-#define DS2_W_V(n) { DS2_ATTR_ONCE((gemm_bf16_nt_w4_kernel<n>), W4_LDS); \
-                     hipLaunchKernelGGL((gemm_bf16_nt_w4_kernel<n>), dim3(cus, 1, 1), dim3(256), W4_LDS, s, g, ntx, nty); }
-        if (wdbg == 1) DS2_W_V(1) else if (wdbg == 2) DS2_W_V(2) else if (wdbg == 4) DS2_W_V(4) else if (wdbg == 5) DS2_W_V(5) else if (wdbg == 6) DS2_W_V(6) else DS2_W_V(0)
-#undef DS2_W_V
-      } else if (ring) {
-        DS2_ATTR_ONCE((gemm_bf16_nt_ring_kernel<false>), R_RING + G_PATCH);
-        DS2_ATTR_ONCE((gemm_bf16_nt_pp16_kernel<false>), R_RING);
-        static const int rdbg = ds2_exp_getenv("DS2_RING_DBG") ? atoi(ds2_exp_getenv("DS2_RING_DBG")) : 0;   // timing ablations of the pp16 kernel (WRONG RESULTS)
-        if (ring_env[0] == 'q' && rdbg) {
-#define DS2_Q_DBG(n) if (rdbg == n) { DS2_HIP(hipFuncSetAttribute((const void*)gemm_bf16_nt_pp16_kernel<false, n>, hipFuncAttributeMaxDynamicSharedMemorySize, R_RING)); \
-                       hipLaunchKernelGGL((gemm_bf16_nt_pp16_kernel<false, n>), dim3(cus, 1, 1), dim3(512), R_RING, s, g, ntx, nty); }
-          DS2_Q_DBG(1) DS2_Q_DBG(2) DS2_Q_DBG(3) DS2_Q_DBG(8) DS2_Q_DBG(18) DS2_Q_DBG(22) DS2_Q_DBG(26) DS2_Q_DBG(82) DS2_Q_DBG(146)
-#undef DS2_Q_DBG
-        } else if (ring_env[0] == 'q' && ring_env[1] == '5') {       // five slots: the whole LDS
-          DS2_ATTR_ONCE((gemm_bf16_nt_pp16_kernel<false, 0, 5>), 5 * R_SLICE);
-          hipLaunchKernelGGL((gemm_bf16_nt_pp16_kernel<false, 0, 5>), dim3(cus, 1, 1), dim3(512), 5 * R_SLICE, s, g, ntx, nty);
-        } else if (ring_env[0] == 'q')
-          hipLaunchKernelGGL((gemm_bf16_nt_pp16_kernel<false>), dim3(cus, 1, 1), dim3(512), R_RING, s, g, ntx, nty);
-        else
-          hipLaunchKernelGGL((gemm_bf16_nt_ring_kernel<false>), dim3(cus, 1, 1), dim3(512), R_RING + G_PATCH, s, g, ntx, nty);
-      } else if (pers) {
-        DS2_ATTR_ONCE((gemm_bf16_nt_glds_kernel<2, 4, false, true>), G_LDS + G_PATCH);
-        hipLaunchKernelGGL((gemm_bf16_nt_glds_kernel<2, 4, false, true>), dim3(cus, 1, 1), dim3(512), G_LDS + G_PATCH, s, g, ntx, nty);
-      } else {
-        hipLaunchKernelGGL((gemm_bf16_nt_glds_kernel<2, 4>), dim3(ntx * nty, 1, batch * splitk), dim3(512), G_LDS, s, g, ntx, nty);
-      }
+      DS2_ATTR_ONCE((gemm_bf16_nt_glds_kernel<2, 4>), G_LDS);
+      hipLaunchKernelGGL((gemm_bf16_nt_glds_kernel<2, 4>), dim3(ntx * nty, 1, batch * splitk), dim3(512), G_LDS, s, g, ntx, nty);
     }
     DS2_LAUNCH_CHECK("gemm_bf16_nt_glds_kernel");
   } else {
@@ -1249,8 +1044,8 @@ extern "C" int ds2_gemm_bf16_nt_obf16(int M, int N, int K, const void* A, int ld
   g.sA = g.sB = g.sC = 0;
   g.splitk = 1; g.kchunk = K; g.accumulate = 0; g.partial = nullptr;
   g.nt_store = 1; g.super_rows = 4;
-  DS2_ATTR_ONCE((gemm_bf16_nt_w4_kernel<0, true>), W4_LDS);
-  hipLaunchKernelGGL((gemm_bf16_nt_w4_kernel<0, true>), dim3(cus, 1, 1), dim3(256), W4_LDS, (hipStream_t)stream, g, ntx, nty);
+  DS2_ATTR_ONCE((gemm_bf16_nt_w4_kernel<true>), W4_LDS);
+  hipLaunchKernelGGL((gemm_bf16_nt_w4_kernel<true>), dim3(cus, 1, 1), dim3(256), W4_LDS, (hipStream_t)stream, g, ntx, nty);
   DS2_LAUNCH_CHECK("gemm_bf16_nt_w4_kernel<obf16>");
   return 0;
 }
@@ -1275,7 +1070,6 @@ extern "C" int ds2_gemm_bf16_tn(int M, int N, int K, const void* A, int lda, lon
   g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
   g.sA = strideA; g.sB = strideB; g.sC = strideC;
   g.splitk = splitk; g.kchunk = kchunk; g.accumulate = accumulate; g.partial = (float*)workspace; g.nt_store = 0; g.super_rows = 0;
-  { static const char* wide_env = ds2_exp_getenv("DS2_GEMM_WIDE"); if (wide_env && wide_env[0] == '0') g.nt_store |= 128; }
   hipStream_t s = (hipStream_t)stream;
   DS2_ATTR_ONCE((gemm_bf16_tn_glds_kernel<false>), G_LDS);
   const int ntx = ceil_div(N, 256), nty = ceil_div(M, 256);
@@ -1295,8 +1089,7 @@ extern "C" size_t ds2_gemm_bf16_tn_splitk_group_workspace_bytes(int nprob, const
   if (splitk < 1) splitk = 1;
   size_t n = 0;
   for (int i = 0; i < nprob; ++i) n += (size_t)splitk * probs[i].M * probs[i].N * sizeof(float);   // (an upper bound: one-slab products use none)
-  for (int i = 0; i < nprob; ++i) n += (size_t)ceil_div(probs[i].M, 256) * ceil_div(probs[i].N, 256) * sizeof(int);   // arrival counters of the fused reduce
-  return n + 256;
+  return n;
 }
 
 static int tn_splitk_group_impl(int nprob, const ds2_tn_problem* probs, int splitk, int ep_index, const float* ep_scale, const float* ep_rowv,
@@ -1353,7 +1146,6 @@ static int tn_splitk_group_impl(int nprob, const ds2_tn_problem* probs, int spli
     p.to_slab = nslab > 1;
     p.slab0 = term * splitk;
     p.nslab = (term == 0 && nslab > 1) ? nslab : 0;
-    p.tick = nullptr; p.nslab_all = nslab;
     if (term == 0) {
       p.partial = (float*)((char*)workspace + off);
       if (nslab > 1) { off += (size_t)nslab * q.M * q.N * sizeof(float); elems += (long long)q.M * q.N / 4; any_slab = true; }
@@ -1361,52 +1153,30 @@ static int tn_splitk_group_impl(int nprob, const ds2_tn_problem* probs, int spli
       p.partial = g.p[i - term].partial;
     }
   }
-  // arrival counters behind the slabs (256-byte aligned), one int per tile of every product that has slabs
-  const size_t tick_off = (off + 255) & ~(size_t)255;
-  size_t tick_bytes = 0;
-  for (int i = 0; i < nprob; ++i) {
-    if (g.p[i].nslab > 0) { g.p[i].tick = (int*)((char*)workspace + tick_off + tick_bytes); tick_bytes += (size_t)g.p[i].ntiles * sizeof(int); }
-    else if (g.p[i].to_slab) {                           // a further term of a product: its first term's counters
-      int t0 = i; while (t0 > 0 && probs[t0 - 1].C == probs[i].C) --t0;
-      g.p[i].tick = g.p[t0].tick;
-    }
-  }
   for (int i = nprob; i < TN_MAX_PROBLEMS; ++i) { g.p[i] = g.p[0]; g.p[i].nslab = 0; }
   g.nprob = nprob; g.splitk = splitk; g.nitems = items;
   g.ep_prob = ep_index; g.ep_scale = ep_scale; g.ep_rowv = ep_rowv; g.ep_shift = ep_shift;
   if (ep_index >= 0 && g.p[ep_index].nslab == 0) return 1;       // (single slab, or a further term of a product: nothing reduces it)
-  static const char* ord_env = ds2_exp_getenv("DS2_TN_ORDER");
-  g.order = !(ord_env && ord_env[0] == '0');
   if (any_slab) DS2_REQUIRE(workspace && workspace_bytes >= off, "ds2_gemm_bf16_tn_splitk_group: workspace too small");
   DS2_ATTR_ONCE((gemm_bf16_tn_glds_kernel<true>), G_LDS);
-  // four waves x 128 x 128 (gemm_tn_w4.h) when every k-tile of every slice is full; DS2_GEMM_W4=0: the 8-wave kernel (A/B switch)
-  static const char* w4_env = ds2_exp_getenv("DS2_GEMM_W4");
-  bool w4 = ds2_is_gfx950() && !(w4_env && w4_env[0] == '0');
+  // four waves x 128 x 128 (gemm_tn_w4.h) when every k-tile of every slice is full
+  bool w4 = ds2_is_gfx950();
   for (int i = 0; i < nprob; ++i) {
     const ds2_tn_problem& q = probs[i];
     const int kc = g.p[i].kchunk, klast = q.K - (splitk - 1) * kc;
     w4 = w4 && (q.K % 64) == 0 && kc >= 128 && klast >= 128 && (long long)q.lda * 128 < (1ll << 31) && (long long)q.ldb * 128 < (1ll << 31);
   }
-  // EXPERIMENT of round 6, measured and NOT the default (DS2_TN_FUSED_REDUCE=1 with DS2_EXPERIMENTAL=1 selects it; profiles/r06_experiments.txt):
-  // fused reduce in the four-wave kernel — the last workgroup to deliver a slab of a tile sums the tile's slabs in slab order and writes C, the
-  // same additions in the same order as splitk_reduce_group_kernel, without that launch.  Bit-identical, and SLOWER: c3 step +1.1 ms with a
-  // full device-scope fence per workgroup (768 cache write-back + invalidate operations per launch drop the operand panels the XCD's L2 holds
-  // for the workgroups that are still multiplying), +0.6 ms with release-only fences (the last arrivers' 768 KB of slab reads at a single
-  // CU's HBM rate sit on the launch's tail, and the write-backs remain) — against 4 x 53 us of reduce launches saved.
-  static const char* fr_env = ds2_exp_getenv("DS2_TN_FUSED_REDUCE");
-  const bool fused = w4 && any_slab && (fr_env && fr_env[0] == '1') && workspace_bytes >= tick_off + tick_bytes;
-  if (!fused) for (int i = 0; i < TN_MAX_PROBLEMS; ++i) g.p[i].tick = nullptr;
-  else DS2_HIP(hipMemsetAsync((char*)workspace + tick_off, 0, tick_bytes, (hipStream_t)stream));
+  // (a reduce fused into the four-wave kernel was measured and removed, see docs/HISTORY.md)
   if (w4) {
-    DS2_ATTR_ONCE((gemm_bf16_tn_w4_kernel<0>), W4_LDS);
-    hipLaunchKernelGGL(gemm_bf16_tn_w4_kernel<0>, dim3(items), dim3(256), W4_LDS, (hipStream_t)stream, g);
+    DS2_ATTR_ONCE(gemm_bf16_tn_w4_kernel, W4_LDS);
+    hipLaunchKernelGGL(gemm_bf16_tn_w4_kernel, dim3(items), dim3(256), W4_LDS, (hipStream_t)stream, g);
     DS2_LAUNCH_CHECK("gemm_bf16_tn_w4_kernel");
   } else {
     BArgs unused{};
     hipLaunchKernelGGL(gemm_bf16_tn_glds_kernel<true>, dim3(items), dim3(512), G_LDS, (hipStream_t)stream, unused, 0, 0, g);
     DS2_LAUNCH_CHECK("gemm_bf16_tn_glds_kernel<grouped>");
   }
-  if (any_slab && !fused) {
+  if (any_slab) {
     int blocks = (int)((elems + 255) / 256);
     if (blocks > 8192) blocks = 8192;
     hipLaunchKernelGGL(splitk_reduce_group_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, g, elems);

@@ -52,7 +52,7 @@ __device__ __forceinline__ void w4_dma(unsigned voff, const char* sbase, unsigne
 // j, j + 1 are packed to two dwords each; two v_permlane16_swap hand the odd 16-lane rows' block-j halves to the even rows and the even rows'
 // block-(j + 1) halves to the odd rows, so that every lane owns EIGHT consecutive columns of one block: 32 sixteen-byte stores per wave and
 // tile (64 B contiguous per row and store instruction, as in the fp32 form) instead of 64.
-template <int DBG = 0, bool OBF = false>
+template <bool OBF = false>
 __global__ __launch_bounds__(256) void gemm_bf16_nt_w4_kernel(BArgs g, int ntx, int nty) {
   extern __shared__ __attribute__((aligned(1024))) char ldsg[];
   const int nt = ntx * nty;
@@ -89,14 +89,13 @@ __global__ __launch_bounds__(256) void gemm_bf16_nt_w4_kernel(BArgs g, int ntx, 
       voffA[p] = (unsigned)(min(r, g.M - 1 - tm0) * g.lda * 2 + seg * 16);
       voffB[p] = (unsigned)(min(r, g.N - 1 - tn0) * g.ldb * 2 + seg * 16);
     }
-    sA = reinterpret_cast<const char*>(g.A + ((DBG & 2) ? 0ll : (long long)tm0 * g.lda));
-    sB = reinterpret_cast<const char*>(g.B + ((DBG & 2) ? 0ll : (long long)tn0 * g.ldb));
+    sA = reinterpret_cast<const char*>(g.A + (long long)tm0 * g.lda);
+    sB = reinterpret_cast<const char*>(g.B + (long long)tn0 * g.ldb);
   };
   retarget(m0, n0);
   const unsigned dstw = lds0 + wave * 1024;              // piece p of A -> + p * 4096, of B -> + 32768 + p * 4096; buffer -> + 65536
-  // DBG (timing experiments, WRONG RESULTS): 1 = no operand DMA in the steady state, 2 = the DMA re-reads one L2-resident 64 KB, 4 = no MFMA
-  auto dma_a = [&](unsigned boff, int p) { if (!(DBG & 1)) w4_dma(voffA[p], sA, dstw + boff + p * 4096); };
-  auto dma_b = [&](unsigned boff, int p) { if (!(DBG & 1)) w4_dma(voffB[p], sB, dstw + boff + 32768 + p * 4096); };
+  auto dma_a = [&](unsigned boff, int p) { w4_dma(voffA[p], sA, dstw + boff + p * 4096); };
+  auto dma_b = [&](unsigned boff, int p) { w4_dma(voffB[p], sB, dstw + boff + 32768 + p * 4096); };
 
   // ---- fragment reads: lane -> row (lane & 15) of a 16-row block, k-segment (lane >> 4) of the k-step
   const int frow = lane & 15, fseg = lane >> 4;
@@ -119,10 +118,10 @@ __global__ __launch_bounds__(256) void gemm_bf16_nt_w4_kernel(BArgs g, int ntx, 
   // k-step 0 (see the schedule at the top of the file)
 #define W4_KTILE(DMA, VMW, NEXT)                                                                                                      \
   do {                                                                                                                                \
-    const unsigned cA1 = (raA0 ^ 64u) + boff, cB1 = (raB0 ^ 64u) + boff, nA0 = raA0 + (boff ^ 65536u), nB0 = raB0 + (boff ^ 65536u);   \
+    const unsigned cA1 = (raA0 ^ 64u) + boff, cB1 = (raB0 ^ 64u) + boff, nA0 = raA0 + (boff ^ 65536u), nB0 = raB0 + (boff ^ 65536u);  \
     W4_SB();                                                                                                                          \
     _Pragma("unroll") for (int m_ = 0; m_ < 64; ++m_) {                                                                               \
-      if (!(DBG & 4)) acc[m_ & 7][m_ >> 3] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(W4_BC(fb[0][m_ >> 3]), W4_BC(fa[0][m_ & 7]), acc[m_ & 7][m_ >> 3], 0, 0, 0); \
+      acc[m_ & 7][m_ >> 3] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(W4_BC(fb[0][m_ >> 3]), W4_BC(fa[0][m_ & 7]), acc[m_ & 7][m_ >> 3], 0, 0, 0); \
       W4_SB();                                                                                                                        \
       if (m_ < 16 && !(m_ & 1)) W4_RD(fa[1][(m_ >> 1) & 7], cA1, ((m_ >> 1) & 7) * 2048);                                             \
       if (m_ == 19) W4_LGKM0(fa[1]);                                                                                                  \
@@ -137,10 +136,10 @@ __global__ __launch_bounds__(256) void gemm_bf16_nt_w4_kernel(BArgs g, int ntx, 
       W4_SB();                                                                                                                        \
     }                                                                                                                                 \
     _Pragma("unroll") for (int m_ = 0; m_ < 64; ++m_) {                                                                               \
-      if (!(DBG & 4)) acc[m_ & 7][m_ >> 3] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(W4_BC(fb[1][m_ >> 3]), W4_BC(fa[1][m_ & 7]), acc[m_ & 7][m_ >> 3], 0, 0, 0); \
+      acc[m_ & 7][m_ >> 3] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(W4_BC(fb[1][m_ >> 3]), W4_BC(fa[1][m_ & 7]), acc[m_ & 7][m_ >> 3], 0, 0, 0); \
       W4_SB();                                                                                                                        \
       if ((DMA) && m_ < 10 && !(m_ & 1)) dma_b(boff, 3 + (m_ >> 1));                                                                  \
-      if ((DMA) && m_ == 9 && !(DBG & 2)) { sA += 128; sB += 128; }                                                                   \
+      if ((DMA) && m_ == 9) { sA += 128; sB += 128; }                                                                                 \
       if ((NEXT) && m_ == 10) asm volatile(VMW ::: "memory");                                                                         \
       if ((NEXT) && m_ == 11) __builtin_amdgcn_s_barrier();                                                                           \
       if ((NEXT) && m_ >= 13 && m_ <= 58 && (m_ - 13) % 3 == 0) {                                                                     \

@@ -45,8 +45,8 @@ OVERLAP_WGRAD = OVERLAP_MODE == "1"
 # backward recurrence — no cast / transpose pass at all.  Needs both recurrences of the layer to have run as persistent launches (they are
 # the ones that write the bf16 copies); a layer whose recurrences did not keeps the transposing-cast passes below.  0: always those passes.
 WGRAD_TN = _tune("DS2_WGRAD_TN", "1") != "0"
-# bf16 mode: BatchNorm2d batch statistics from the conv forward epilogues; needs the rows-per-block conv2 kernel (DS2_CONV2_ROWS != 1)
-CONV_STATS = _tune("DS2_CONV_STATS", "1") != "0" and _tune("DS2_CONV2_ROWS", "") != "1"
+# bf16 mode: BatchNorm2d batch statistics from the conv forward epilogues
+CONV_STATS = _tune("DS2_CONV_STATS", "1") != "0"
 # bf16 training: the elementwise half of every BatchNorm1d backward is applied inside the K-split backward recurrence of the layer below
 # (ops.rnn_bwd_bn: one more 4-byte load per pair and step instead of a pass over (T*B, H)); 0: a separate bn1d_bwd_apply pass as before
 FUSE_BN_BWD = _tune("DS2_FUSE_BN_BWD", "1") != "0"

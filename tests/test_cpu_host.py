@@ -652,3 +652,17 @@ def test_bench_dump_outputs_writes_the_step_state_as_float_arrays(tmp_path):
         else:
             assert a["param." + n].shape == a["grad." + n].shape == (bench.DUMP_MAX_ELEMS,), n
             assert np.isin(a["grad." + n], grads[n].numpy()).all(), n
+
+
+def test_every_environment_switch_the_package_reads_is_documented():
+    """The DS2_* names asr_amd/ reads (getenv, ds2_exp_getenv, engine._tune, os.environ.get) are exactly the run-time switch list of
+    INTEGRATION.md: a new switch cannot appear, and a removed one cannot stay documented, without the other side changing too."""
+    read = set()
+    for d, _, files in os.walk(os.path.join(ROOT, "asr_amd")):
+        for f in files:
+            if f.endswith((".py", ".hip", ".h", ".cpp")):
+                src = open(os.path.join(d, f), encoding="utf-8").read()
+                read |= set(re.findall(r'(?:getenv|_tune|environ\.get)\(\s*"(DS2_[A-Z0-9_]+)"', src))
+    doc = open(os.path.join(ROOT, "INTEGRATION.md"), encoding="utf-8").read()
+    switch_list = re.search(r"^\* Run-time switches.*?(?=^\S|^\* )", doc, re.M | re.S).group(0)
+    assert read == set(re.findall(r"DS2_[A-Z0-9_]+", switch_list))
