@@ -93,3 +93,7 @@ extern "C" int ds2_greedy_decode_f32(const float* probs, long long ld_b, long lo
 // list is left as it is because bench.py's recurrence-source hash covers the Makefile.
 #define DS2_CTC_BEAM_TU
 #include "ctc_beam.h"
+
+// The batched edit distance of the WER / CER scoring (ds2_edit_distance_*) is compiled here as well, for the same reason.
+#define DS2_EDIT_DISTANCE_TU
+#include "edit_distance.h"

@@ -1,9 +1,11 @@
 """Greedy and beam CTC decoders + WER/CER (host-side mirror of asr_deepspeech/decoders/{decoder,greedy_decoder,beam_decoder}.py).
 `decode()` runs on the GPU (csrc/decode.hip, csrc/ctc_beam.h); process_string / convert_to_strings are the host utilities the
 reference uses for TARGET strings.  Eval-only, not on the train step.
-The edit distance is a small pure-Python DP (the reference imports the `Levenshtein` C package)."""
+`wer` / `cer` keep a small pure-Python DP (the reference imports the `Levenshtein` C package) as the reference API; evaluate()
+scores a whole batch with `Decoder.score_batch`, one HIP launch (csrc/edit_distance.h) on ids packed by `pack_scoring`."""
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 
@@ -17,6 +19,31 @@ def _edit_distance(a, b) -> int:
             cur.append(min(prev[j] + 1, cur[j - 1] + 1, prev[j - 1] + (ca != cb)))
         prev = cur
     return prev[-1]
+
+
+def pack_scoring(hypotheses, references):
+    """Host half of Decoder.score_batch: the B (hypothesis, reference) string pairs as 2B edit-distance problems over int32 ids, in
+    O(length).  Problem b < B is pair b's word problem, whose words are `s.split()` mapped to ids by a per-pair dict (two words share
+    an id exactly when they are equal, as in `wer`); problem B + b is its character problem, over the code points of
+    `s.replace(" ", "")` (only U+0020 is removed, as in `cer`).  Side a is the hypothesis, side b the reference.
+    Returns (seq int32, a_off int64, a_len int32, b_off int64, b_len int32, ref_words int64, ref_chars int64), numpy arrays."""
+    if len(hypotheses) != len(references):
+        raise ValueError(f"{len(hypotheses)} hypotheses for {len(references)} references")
+    B = len(hypotheses)
+    pieces, ref_w, ref_c = [None] * (4 * B), np.empty(B, np.int64), np.empty(B, np.int64)
+    for b, (h, r) in enumerate(zip(hypotheses, references)):
+        ids = {}
+        hw = [ids.setdefault(w, len(ids)) for w in h.split()]
+        rw = [ids.setdefault(w, len(ids)) for w in r.split()]
+        pieces[2 * b], pieces[2 * b + 1] = np.array(hw, np.int32), np.array(rw, np.int32)
+        hc, rc = (np.frombuffer(x.replace(" ", "").encode("utf-32-le", "surrogatepass"), np.uint32).view(np.int32) for x in (h, r))
+        pieces[2 * B + 2 * b], pieces[2 * B + 2 * b + 1] = hc, rc
+        ref_w[b], ref_c[b] = len(rw), len(rc)
+    lens = np.fromiter((len(x) for x in pieces), np.int64, count=4 * B)
+    offs = np.zeros(4 * B, np.int64)
+    np.cumsum(lens[:-1], out=offs[1:])
+    seq = np.concatenate(pieces) if B else np.zeros(0, np.int32)
+    return seq, offs[0::2].copy(), lens[0::2].astype(np.int32), offs[1::2].copy(), lens[1::2].astype(np.int32), ref_w, ref_c
 
 
 class Decoder:
@@ -41,6 +68,33 @@ class Decoder:
     def cer(self, s1, s2):
         s1, s2 = s1.replace(" ", ""), s2.replace(" ", "")
         return _edit_distance(s1, s2)
+
+    def score_batch(self, hypotheses, references):
+        """The `wer` and `cer` of B (hypothesis, reference) pairs in one HIP launch -> CPU int64 tensor (B, 4) of (word distance,
+        reference words, char distance, reference chars), every entry equal to wer(h, r), len(r.split()), cer(h, r),
+        len(r.replace(" ", "")).  One pinned host-to-device copy of the packed ids (pack_scoring), one launch
+        (ops.edit_distance), one device-to-host copy.  There is no CPU implementation: without a GPU this raises."""
+        from .. import ops
+        dev = _device("Decoder.score_batch", "")
+        seq, a_off, a_len, b_off, b_len, ref_w, ref_c = pack_scoring(hypotheses, references)
+        B, P = len(ref_w), 2 * len(ref_w)
+        out = torch.empty((B, 4), dtype=torch.int64)
+        if B == 0:
+            return out
+        max_len = int(max(a_len.max(), b_len.max()))
+        # one int32 image: a_off, b_off (int64, 8-byte aligned at the front), a_len, b_len, symbols
+        host = torch.empty(6 * P + len(seq), dtype=torch.int32, pin_memory=True)
+        h = host.numpy()
+        h[:2 * P], h[2 * P:4 * P] = a_off.view(np.int32), b_off.view(np.int32)
+        h[4 * P:5 * P], h[5 * P:6 * P], h[6 * P:] = a_len, b_len, seq
+        d = host.to(dev, non_blocking=True)
+        dist = ops.edit_distance(d[6 * P:], d[:2 * P].view(torch.int64), d[4 * P:5 * P], d[2 * P:4 * P].view(torch.int64),
+                                 d[5 * P:6 * P], max_len=max_len).cpu().long()
+        if int(dist.min()) < 0:
+            raise RuntimeError("Decoder.score_batch: the edit-distance kernel rejected a problem")
+        out[:, 0], out[:, 2] = dist[:B], dist[B:]
+        out[:, 1], out[:, 3] = torch.from_numpy(ref_w), torch.from_numpy(ref_c)
+        return out
 
     def decode(self, probs, sizes=None):
         raise NotImplementedError
@@ -167,8 +221,8 @@ class BeamCTCDecoder(Decoder):
         return self.convert_to_strings(labels_h, lens_h), self.convert_tensor(offs_h, lens_h)
 
 
-def _device(who="GreedyDecoder"):
+def _device(who="GreedyDecoder", what=".decode"):
     from .._lib import DS2LibraryError
     if not torch.cuda.is_available():
-        raise DS2LibraryError(f"{who}.decode needs a GPU (no CPU fallback exists)")
+        raise DS2LibraryError(f"{who}{what} needs a GPU (no CPU fallback exists)")
     return torch.device("cuda", torch.cuda.current_device())

@@ -250,12 +250,15 @@ class DeepSpeech(nn.Module):
     # -- evaluation loop (deepspeech.py:161-273) --------------------------------------------------
     def evaluate(self, loader=None, manifest=None, batch_size=None, device="auto", num_workers=32, verbose=False, half=False,
                  output_file=None, main_proc=True, **_unused):
-        from ..decoders import BeamCTCDecoder, GreedyDecoder
+        from ..decoders import BeamCTCDecoder, Decoder, GreedyDecoder
         device = resolve_device(device)
         with torch.no_grad():
             if loader is None:
                 loader, _ = self.get_loader(manifest=manifest, batch_size=batch_size, num_workers=num_workers)
             decoder = self.decoder
+            # WER / CER of the whole batch in one HIP launch (Decoder.score_batch, integers equal to wer / cer); a decoder that overrides
+            # either method keeps the per-utterance calls, so its own scoring is what gets counted
+            gpu_scoring = type(decoder).wer is Decoder.wer and type(decoder).cer is Decoder.cer
             self.eval()
             self.to(device)
             total_cer = total_wer = num_tokens = num_chars = 0
@@ -280,12 +283,19 @@ class DeepSpeech(nn.Module):
                 target_strings = (GreedyDecoder(self.labels) if isinstance(decoder, BeamCTCDecoder) else decoder).convert_to_strings(split_targets)
                 if output_file is not None:
                     output_data.append((out.detach().cpu().numpy(), output_sizes.numpy(), target_strings))
+                scores = None
+                if gpu_scoring:
+                    scores = decoder.score_batch([decoded_output[i][0] for i in range(len(target_strings))],
+                                                 [target_strings[i][0] for i in range(len(target_strings))]).tolist()
                 for i in range(len(target_strings)):
                     transcript, reference = decoded_output[i][0], target_strings[i][0]
-                    wer_inst, cer_inst = decoder.wer(transcript, reference), decoder.cer(transcript, reference)
+                    if scores is not None:
+                        wer_inst, n_tok, cer_inst, n_chr = scores[i]
+                    else:
+                        wer_inst, cer_inst = decoder.wer(transcript, reference), decoder.cer(transcript, reference)
+                        n_tok, n_chr = len(reference.split()), len(reference.replace(" ", ""))
                     total_wer += wer_inst
                     total_cer += cer_inst
-                    n_tok, n_chr = len(reference.split()), len(reference.replace(" ", ""))
                     num_tokens += n_tok
                     num_chars += n_chr
                     wer_pct = min(100.0 * wer_inst / max(n_tok, 1), 100.0)

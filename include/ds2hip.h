@@ -455,6 +455,20 @@ int ds2_ctc_beam_decode_lm_f32(const float* probs, long long ld_b, long long ld_
                                int lm_mode, int space, float alpha, float beta, int* labels, int* offsets, int* lens, float* scores,
                                void* ws, size_t ws_bytes, void* stream);
 
+/* Batched Levenshtein distance (unit costs: insert, delete, substitute) of P independent pairs of int32 symbol sequences, one launch;
+ * the WER / CER scoring of DeepSpeech.evaluate() (replaces Decoder.wer / Decoder.cer's per-utterance DP, decoders/decoder.py:26-58,
+ * whose reference uses the `Levenshtein` C package).  The host maps words / characters to ids (asr_amd/decoders), symbols compare
+ * as plain int32 values.  Problem p compares seq[a_off[p] .. a_off[p] + a_len[p]) with seq[b_off[p] .. b_off[p] + b_len[p]);
+ * sides may alias or overlap.  a_off / b_off (P) int64, a_len / b_len (P) int32, all device arrays; n_seq = symbols in seq.
+ * Output dist (P) int32: the exact distance (an empty side gives the other side's length), or -1 for a problem whose range leaves
+ * [0, n_seq) or whose longer side exceeds max_len while its shorter side exceeds 64.
+ * Method: blocked Myers / Hyyroe bit-vectors (csrc/edit_distance.h), one wave per problem, ceil(min/64) * max column steps.
+ * Workspace: one int8 row of the longer side per problem, ds2_edit_distance_workspace_bytes(P, max_len) with max_len >= every
+ * problem's longer side (host-known lengths: the call never synchronises); 0 bytes (ws may be NULL) when max_len <= 64. */
+size_t ds2_edit_distance_workspace_bytes(int P, long long max_len);
+int ds2_edit_distance_i32(const int* seq, long long n_seq, const long long* a_off, const int* a_len, const long long* b_off,
+                          const int* b_len, int P, long long max_len, int* dist, void* ws, size_t ws_bytes, void* stream);
+
 /* conv1 in bf16 mode (Conv2d(1,32,(41,11),s=(2,2),p=(20,5)), deepspeech.py:61, forward + weight gradient; conv1 has no data
  * gradient).  ds2_conv1_gather_bf16 builds the two bf16 operand images from the spectrogram batch: XB (B,F,P) = the rows themselves as
  * bf16, XB[..][7 + s] = x[..][s] with zeros in front and behind (P = ds2_conv1_bf16_row_pitch(T)) for the forward — the 16 taps of an output
