@@ -137,6 +137,9 @@ SIGNATURES = {
     "ds2_spectrogram_frames": (i32, [i32, i32]),
     "ds2_spectrogram_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "ds2_spectrogram_f32": (i32, [vp, i64, vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, sz, vp]),
+    "ds2_spectrogram_aug_workspace_bytes": (sz, [i32, i32, i32, i32]),
+    "ds2_spectrogram_aug_f32": (i32, [vp, i64, vp, i32, i32, i32, i32, vp, i32, i32, vp, i64, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, sz,
+                                      vp]),
     "ds2_adamw_f32": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, vp]),
     "ds2_adamw_gated_f32": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, vp, vp]),
     "ds2_scale_f32": (i32, [vp, i64, f32, vp]),

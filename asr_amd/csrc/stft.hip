@@ -15,9 +15,21 @@
 
 namespace {
 
-// ypad[b*R*hop + i] = padded waveform of utterance b (i in [0, R*hop)), zero beyond n_b + 2*half
+// noise bank of the augmented front-end: utterance b mixes noise[base_b + (s_b + j) mod L_b] scaled by gain_b (0 = no noise)
+struct AugNoise {
+  const float* noise;
+  const long long* base;
+  const int* period;
+  const int* start;
+  const float* gain;
+};
+
+// ypad[b*R*hop + i] = padded waveform of utterance b (i in [0, R*hop)), zero beyond n_b + 2*half.
+// MIX: the padded signal is that of the mixed waveform x[j] + gain_b * noise_seg[j], read at the already reflected index j.
+template <bool MIX>
 __global__ __launch_bounds__(256) void stft_pad_kernel(const float* __restrict__ audio, long long ld_audio, const int* __restrict__ n_samples,
-                                                       float* __restrict__ ypad, int Bn, long long row_len, int half, int reflect, long long total) {
+                                                       float* __restrict__ ypad, int Bn, long long row_len, int half, int reflect, long long total,
+                                                       AugNoise nz) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
     float v = 0.f;
     const long long b = i / row_len;
@@ -27,17 +39,59 @@ __global__ __launch_bounds__(256) void stft_pad_kernel(const float* __restrict__
       if (j >= -(long long)half && j < (long long)n + half && n > 0) {
         if (j < 0) j = reflect ? -j : -1;
         else if (j >= n) j = reflect ? 2LL * (n - 1) - j : -1;
-        if (j >= 0 && j < n) v = audio[b * ld_audio + j];
+        if (j >= 0 && j < n) {
+          v = audio[b * ld_audio + j];
+          if constexpr (MIX) {
+            const float g = nz.gain[b];
+            if (g != 0.f) {                            // (gain_b != 0 only for a validated noise segment, see aug_gain_kernel)
+              const int L = nz.period[b];
+              long long q = (long long)nz.start[b] + j;
+              if (q >= L) q %= L;
+              v += g * nz.noise[nz.base[b] + q];
+            }
+          }
+        }
       }
     }
     ypad[i] = v;
   }
 }
 
+// SpecAugment masks of the augmented front-end: per utterance up to kMaxMasks [lo, hi) bin ranges and [lo, hi) frame ranges
+constexpr int kMaxMasks = 8;
+struct AugMasks {
+  const int* freq;   // (B, nf, 2)
+  const int* time;   // (B, nt, 2)
+  int nf, nt;
+};
+// one utterance's ranges held in registers (unused slots are empty ranges); the loops are unrolled so the arrays never go to scratch
+struct MaskRegs {
+  int flo[kMaxMasks], fhi[kMaxMasks], tlo[kMaxMasks], thi[kMaxMasks];
+  __device__ __forceinline__ void load(const AugMasks& m, int b) {
+#pragma unroll
+    for (int i = 0; i < kMaxMasks; ++i) {
+      const bool f = i < m.nf, t = i < m.nt;
+      flo[i] = f ? m.freq[((long long)b * m.nf + i) * 2] : 0;
+      fhi[i] = f ? m.freq[((long long)b * m.nf + i) * 2 + 1] : 0;
+      tlo[i] = t ? m.time[((long long)b * m.nt + i) * 2] : 0;
+      thi[i] = t ? m.time[((long long)b * m.nt + i) * 2 + 1] : 0;
+    }
+  }
+  __device__ __forceinline__ bool hit(int k, int t) const {
+    bool z = false;
+#pragma unroll
+    for (int i = 0; i < kMaxMasks; ++i) z |= (k >= flo[i] && k < fhi[i]) || (t >= tlo[i] && t < thi[i]);
+    return z;
+  }
+};
+
 // C (B*R, 2*nb) [re, im interleaved per bin] -> out (B, nb, T) = log1p(sqrt(re^2 + im^2)) for t < frames_b else 0 ;
 // part[b][blk][2] = (sum, sum of squares) over the valid elements of this block's tile.   block = 64 frames x 32 bins.
+// MASK: elements inside a mask (t < frames_b) are stored as 0; the partial sums are those of the unmasked spectrogram.
+template <bool MASK>
 __global__ __launch_bounds__(256) void stft_post_kernel(const float* __restrict__ C, int ldc, int R, int nb, int T, int hop,
-                                                        const int* __restrict__ n_samples, float* __restrict__ out, float* __restrict__ part) {
+                                                        const int* __restrict__ n_samples, float* __restrict__ out, float* __restrict__ part,
+                                                        AugMasks mk) {
   __shared__ float tile[64][33];
   __shared__ float red[2][4];
   const int b = blockIdx.z, t0 = blockIdx.x * 64, k0 = blockIdx.y * 32;
@@ -59,11 +113,17 @@ __global__ __launch_bounds__(256) void stft_post_kernel(const float* __restrict_
     tile[tl][kl] = v;
   }
   __syncthreads();
+  MaskRegs mr;
+  if constexpr (MASK) mr.load(mk, b);
 #pragma unroll
   for (int pass = 0; pass < 8; ++pass) {
     const int kl = pass * 4 + (tid >> 6), tl = tid & 63;
     const int t = t0 + tl, k = k0 + kl;
-    if (t < T && k < nb) out[((long long)b * nb + k) * T + t] = tile[tl][kl];
+    if constexpr (MASK) {
+      if (t < T && k < nb) out[((long long)b * nb + k) * T + t] = (t < frames && mr.hit(k, t)) ? 0.f : tile[tl][kl];
+    } else {
+      if (t < T && k < nb) out[((long long)b * nb + k) * T + t] = tile[tl][kl];
+    }
   }
   s = wave_sum(s);
   s2 = wave_sum(s2);
@@ -103,14 +163,88 @@ __global__ void stft_stats_kernel(const float* __restrict__ part, int nblk, int 
 }
 
 // out[b][k][t] = (out - mean_b) * rstd_b for t < frames_b (padding stays 0: _collate_fn pads AFTER normalisation)
+// MASK: SpecAugment after normalisation — elements inside a mask are stored as 0 (the statistics are those of the unmasked spectrogram)
+template <bool MASK>
 __global__ __launch_bounds__(256) void stft_normalize_kernel(float* __restrict__ out, int nb, int T, int hop, const int* __restrict__ n_samples,
-                                                             const float* __restrict__ stats, long long total) {
+                                                             const float* __restrict__ stats, long long total, AugMasks mk) {
+  MaskRegs mr;
+  int cur = -1;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
     const int t = (int)(i % T);
     const int b = (int)(i / ((long long)nb * T));
     const int n = n_samples[b];
     const int frames = n > 0 ? min(T, 1 + n / hop) : 0;
-    if (t < frames) out[i] = (out[i] - stats[2 * b]) * stats[2 * b + 1];
+    if constexpr (MASK) {
+      if (t < frames) {
+        if (b != cur) { mr.load(mk, b); cur = b; }   // a thread's stride crosses an utterance boundary rarely
+        const int k = (int)((i / T) % nb);
+        out[i] = mr.hit(k, t) ? 0.f : (out[i] - stats[2 * b]) * stats[2 * b + 1];
+      }
+    } else {
+      if (t < frames) out[i] = (out[i] - stats[2 * b]) * stats[2 * b + 1];
+    }
+  }
+}
+
+// Noise-injection energy pass, stage 1: per (utterance b, block) fp32 partials of sum x^2 and sum noise_seg^2 over j in [0, n_b) —
+// grid (kAugEnergyBlocks, B), block-strided, fixed order (no atomics).  Utterances without a valid noise segment write zeros.
+constexpr int kAugEnergyBlocks = 32;
+__device__ __forceinline__ bool aug_segment_ok(const AugNoise& nz, long long noise_len, int b, float level) {
+  const long long base = nz.base[b];
+  const int L = nz.period[b], s = nz.start[b];
+  return level != 0.f && L > 0 && s >= 0 && s < L && base >= 0 && base + L <= noise_len;
+}
+
+__global__ __launch_bounds__(256) void aug_energy_kernel(const float* __restrict__ audio, long long ld_audio, const int* __restrict__ n_samples,
+                                                         AugNoise nz, const float* __restrict__ level, long long noise_len, float* __restrict__ part) {
+  __shared__ float red[2][4];
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const int n = n_samples[b];
+  float sx = 0.f, sn = 0.f;
+  if (n > 0 && aug_segment_ok(nz, noise_len, b, level[b])) {
+    const int L = nz.period[b];
+    const long long s = nz.start[b];
+    const float* x = audio + (long long)b * ld_audio;
+    const float* w = nz.noise + nz.base[b];
+    for (long long j = (long long)blockIdx.x * 256 + tid; j < n; j += (long long)gridDim.x * 256) {
+      long long q = s + j;
+      if (q >= L) q %= L;
+      const float a = x[j], c = w[q];
+      sx += a * a;
+      sn += c * c;
+    }
+  }
+  sx = wave_sum(sx);
+  sn = wave_sum(sn);
+  if ((tid & 63) == 0) { red[0][tid >> 6] = sx; red[1][tid >> 6] = sn; }
+  __syncthreads();
+  if (tid == 0) {
+    float* p = part + ((long long)b * gridDim.x + blockIdx.x) * 2;
+    p[0] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
+    p[1] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+  }
+}
+
+// stage 2, one 64-thread block per utterance: partials combined in fp64 ->
+// gain_b = level_b * rms(x) / rms(noise_seg) = level_b * sqrt(sum x^2 / sum noise_seg^2), 0 = unmixed (no noise, or a silent segment)
+__global__ void aug_gain_kernel(const float* __restrict__ part, int nblk, const int* __restrict__ n_samples, AugNoise nz,
+                                const float* __restrict__ level, long long noise_len, float* __restrict__ gain) {
+  const int b = blockIdx.x;
+  __shared__ double sh[2][64];
+  double sx = 0.0, sn = 0.0;
+  for (int i = threadIdx.x; i < nblk; i += 64) {
+    sx += (double)part[((long long)b * nblk + i) * 2];
+    sn += (double)part[((long long)b * nblk + i) * 2 + 1];
+  }
+  sh[0][threadIdx.x] = sx;
+  sh[1][threadIdx.x] = sn;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    sx = 0.0; sn = 0.0;
+    for (int i = 0; i < 64; ++i) { sx += sh[0][i]; sn += sh[1][i]; }
+    const float lv = level[b];
+    const bool on = n_samples[b] > 0 && aug_segment_ok(nz, noise_len, b, lv) && sn > 0.0;
+    gain[b] = on ? (float)((double)lv * sqrt(sx / sn)) : 0.f;
   }
 }
 
@@ -130,6 +264,85 @@ extern "C" size_t ds2_spectrogram_workspace_bytes(int B, int T, int n_fft, int h
   return ypad + c + part + align_up((size_t)B * 2 * sizeof(float), 256);
 }
 
+// + the noise energy partials (B, kAugEnergyBlocks, 2) and the per-utterance gains (B)
+extern "C" size_t ds2_spectrogram_aug_workspace_bytes(int B, int T, int n_fft, int hop) {
+  return ds2_spectrogram_workspace_bytes(B, T, n_fft, hop) + align_up((size_t)B * kAugEnergyBlocks * 2 * sizeof(float), 256) +
+         align_up((size_t)B * sizeof(float), 256);
+}
+
+namespace {
+
+// Both entry points.  aug == nullptr: the plain front-end (the <false> kernel instances, launched exactly as before the augmented variant
+// existed).  Otherwise: noise energy + gain (when aug->level), the mix inside the pad pass, the masks inside the last pass.
+struct AugArgs {
+  AugNoise nz;
+  const float* level;
+  long long noise_len;
+  AugMasks mk;
+};
+
+int spectrogram_impl(const float* audio, long long ld_audio, const int* n_samples_dev, int B, int T, int n_fft, int hop, const float* basis,
+                     int pad_mode, int normalize, float* out, void* ws, const AugArgs* aug, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const int R = rows_per_utt(T, n_fft, hop), nb = n_fft / 2 + 1;
+  const long long row_len = (long long)R * hop;
+  const long long ypad_n = (long long)B * row_len + n_fft;
+  char* w = (char*)ws;
+  float* ypad = (float*)w;                 w += align_up((size_t)ypad_n * sizeof(float), 256);
+  float* C = (float*)w;                    w += align_up((size_t)B * R * 2 * nb * sizeof(float), 256);
+  float* part = (float*)w;                 w += align_up((size_t)B * ceil_div(T, 64) * ceil_div(nb, 32) * 2 * sizeof(float), 256);
+  float* stats = (float*)w;                w += align_up((size_t)B * 2 * sizeof(float), 256);
+  float* epart = (float*)w;                w += align_up((size_t)B * kAugEnergyBlocks * 2 * sizeof(float), 256);
+  float* gain = (float*)w;
+  const bool mix = aug && aug->level;
+  const bool mask = aug && (aug->mk.nf > 0 || aug->mk.nt > 0);
+  AugNoise nz{};
+  if (mix) {
+    nz = aug->nz;
+    nz.gain = gain;
+    hipLaunchKernelGGL(aug_energy_kernel, dim3(kAugEnergyBlocks, B), dim3(256), 0, s, audio, ld_audio, n_samples_dev, nz, aug->level,
+                       aug->noise_len, epart);
+    DS2_LAUNCH_CHECK("aug_energy_kernel");
+    hipLaunchKernelGGL(aug_gain_kernel, dim3(B), dim3(64), 0, s, (const float*)epart, kAugEnergyBlocks, n_samples_dev, nz, aug->level,
+                       aug->noise_len, gain);
+    DS2_LAUNCH_CHECK("aug_gain_kernel");
+  }
+  const AugMasks mk = mask ? aug->mk : AugMasks{};
+  int blocks = (int)((ypad_n + 255) / 256);
+  if (blocks > 16384) blocks = 16384;
+  if (mix)
+    hipLaunchKernelGGL(stft_pad_kernel<true>, dim3(blocks), dim3(256), 0, s, audio, ld_audio, n_samples_dev, ypad, B, row_len, n_fft / 2,
+                       pad_mode, ypad_n, nz);
+  else
+    hipLaunchKernelGGL(stft_pad_kernel<false>, dim3(blocks), dim3(256), 0, s, audio, ld_audio, n_samples_dev, ypad, B, row_len, n_fft / 2,
+                       pad_mode, ypad_n, nz);
+  DS2_LAUNCH_CHECK("stft_pad_kernel");
+  // every frame of every utterance is a row of ONE operand with pitch = hop (rows overlap): C = frames x basis
+  int rc = ds2_gemm_f32(0, 0, B * R, 2 * nb, n_fft, ypad, hop, 0, basis, 2 * nb, 0, C, 2 * nb, 0, nullptr, 0, 1, 1, nullptr, 0, stream);
+  if (rc) return rc;
+  dim3 grid(ceil_div(T, 64), ceil_div(nb, 32), B);
+  if (mask && !normalize)                                  // masks go into the LAST pass: here, or the normalisation below
+    hipLaunchKernelGGL(stft_post_kernel<true>, grid, dim3(256), 0, s, (const float*)C, 2 * nb, R, nb, T, hop, n_samples_dev, out, part, mk);
+  else
+    hipLaunchKernelGGL(stft_post_kernel<false>, grid, dim3(256), 0, s, (const float*)C, 2 * nb, R, nb, T, hop, n_samples_dev, out, part, mk);
+  DS2_LAUNCH_CHECK("stft_post_kernel");
+  if (normalize) {
+    hipLaunchKernelGGL(stft_stats_kernel, dim3(B), dim3(64), 0, s, (const float*)part, (int)(grid.x * grid.y), nb, T, hop, n_samples_dev, stats);
+    DS2_LAUNCH_CHECK("stft_stats_kernel");
+    const long long total = (long long)B * nb * T;
+    int nblk = (int)((total + 255) / 256);
+    if (nblk > 16384) nblk = 16384;
+    if (mask)
+      hipLaunchKernelGGL(stft_normalize_kernel<true>, dim3(nblk), dim3(256), 0, s, out, nb, T, hop, n_samples_dev, (const float*)stats, total, mk);
+    else
+      hipLaunchKernelGGL(stft_normalize_kernel<false>, dim3(nblk), dim3(256), 0, s, out, nb, T, hop, n_samples_dev, (const float*)stats, total, mk);
+    DS2_LAUNCH_CHECK("stft_normalize_kernel");
+  }
+  return 0;
+}
+
+}  // namespace
+
 //   audio      (B, ld_audio) fp32 waveforms on the device, n_samples_dev (B) int32 valid samples per row
 //   basis      (n_fft, 2*n_bins) fp32, basis[k][2j] = w[k] cos(2 pi k j / n_fft), basis[k][2j+1] = -w[k] sin(2 pi k j / n_fft)
 //   out        (B, n_bins, T) fp32 (= (B,1,n_bins,T)); T >= max frames; frames beyond each utterance's own are 0
@@ -140,33 +353,33 @@ extern "C" int ds2_spectrogram_f32(const float* audio, long long ld_audio, const
   DS2_REQUIRE(B > 0 && T > 0 && n_fft >= 4 && (n_fft % 2) == 0 && hop > 0 && (hop % 4) == 0 && hop <= n_fft,
               "ds2_spectrogram_f32: bad dims (B=%d T=%d n_fft=%d hop=%d; hop must be a multiple of 4)", B, T, n_fft, hop);
   DS2_REQUIRE(ws_bytes >= ds2_spectrogram_workspace_bytes(B, T, n_fft, hop), "ds2_spectrogram_f32: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  const int R = rows_per_utt(T, n_fft, hop), nb = n_fft / 2 + 1;
-  const long long row_len = (long long)R * hop;
-  const long long ypad_n = (long long)B * row_len + n_fft;
-  char* w = (char*)ws;
-  float* ypad = (float*)w;                 w += align_up((size_t)ypad_n * sizeof(float), 256);
-  float* C = (float*)w;                    w += align_up((size_t)B * R * 2 * nb * sizeof(float), 256);
-  float* part = (float*)w;                 w += align_up((size_t)B * ceil_div(T, 64) * ceil_div(nb, 32) * 2 * sizeof(float), 256);
-  float* stats = (float*)w;
-  int blocks = (int)((ypad_n + 255) / 256);
-  if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(stft_pad_kernel, dim3(blocks), dim3(256), 0, s, audio, ld_audio, n_samples_dev, ypad, B, row_len, n_fft / 2, pad_mode, ypad_n);
-  DS2_LAUNCH_CHECK("stft_pad_kernel");
-  // every frame of every utterance is a row of ONE operand with pitch = hop (rows overlap): C = frames x basis
-  int rc = ds2_gemm_f32(0, 0, B * R, 2 * nb, n_fft, ypad, hop, 0, basis, 2 * nb, 0, C, 2 * nb, 0, nullptr, 0, 1, 1, nullptr, 0, stream);
-  if (rc) return rc;
-  dim3 grid(ceil_div(T, 64), ceil_div(nb, 32), B);
-  hipLaunchKernelGGL(stft_post_kernel, grid, dim3(256), 0, s, (const float*)C, 2 * nb, R, nb, T, hop, n_samples_dev, out, part);
-  DS2_LAUNCH_CHECK("stft_post_kernel");
-  if (normalize) {
-    hipLaunchKernelGGL(stft_stats_kernel, dim3(B), dim3(64), 0, s, (const float*)part, (int)(grid.x * grid.y), nb, T, hop, n_samples_dev, stats);
-    DS2_LAUNCH_CHECK("stft_stats_kernel");
-    const long long total = (long long)B * nb * T;
-    int nblk = (int)((total + 255) / 256);
-    if (nblk > 16384) nblk = 16384;
-    hipLaunchKernelGGL(stft_normalize_kernel, dim3(nblk), dim3(256), 0, s, out, nb, T, hop, n_samples_dev, (const float*)stats, total);
-    DS2_LAUNCH_CHECK("stft_normalize_kernel");
-  }
-  return 0;
+  return spectrogram_impl(audio, ld_audio, n_samples_dev, B, T, n_fft, hop, basis, pad_mode, normalize, out, ws, nullptr, stream);
+}
+
+// The augmented front-end (noise injection before the STFT, SpecAugment masks after the statistics); see include/ds2hip.h.
+//   noise        (noise_len) fp32 device noise bank; noise_base (B) int64, noise_period (B) / noise_start (B) int32, noise_level (B) fp32:
+//                utterance b mixes noise[noise_base[b] + (noise_start[b] + j) mod noise_period[b]]; level 0 = no noise.  The four arrays
+//                are NULL together (no noise at all).
+//   freq_masks   (B, n_freq_masks, 2) int32 [lo, hi) bin ranges, time_masks (B, n_time_masks, 2) int32 [lo, hi) frame ranges (NULL if 0)
+extern "C" int ds2_spectrogram_aug_f32(const float* audio, long long ld_audio, const int* n_samples_dev, int B, int T, int n_fft, int hop,
+                                       const float* basis, int pad_mode, int normalize, const float* noise, long long noise_len,
+                                       const long long* noise_base, const int* noise_period, const int* noise_start, const float* noise_level,
+                                       const int* freq_masks, int n_freq_masks, const int* time_masks, int n_time_masks, float* out, void* ws,
+                                       size_t ws_bytes, void* stream) {
+  DS2_REQUIRE(audio && n_samples_dev && basis && out && ws, "ds2_spectrogram_aug_f32: null pointer");
+  DS2_REQUIRE(B > 0 && T > 0 && n_fft >= 4 && (n_fft % 2) == 0 && hop > 0 && (hop % 4) == 0 && hop <= n_fft,
+              "ds2_spectrogram_aug_f32: bad dims (B=%d T=%d n_fft=%d hop=%d; hop must be a multiple of 4)", B, T, n_fft, hop);
+  DS2_REQUIRE(ws_bytes >= ds2_spectrogram_aug_workspace_bytes(B, T, n_fft, hop), "ds2_spectrogram_aug_f32: workspace too small");
+  const bool any_noise = noise_base || noise_period || noise_start || noise_level;
+  DS2_REQUIRE(!any_noise || (noise_base && noise_period && noise_start && noise_level && noise && noise_len > 0),
+              "ds2_spectrogram_aug_f32: the noise bank (noise, noise_len > 0) and all four per-utterance noise arrays go together");
+  DS2_REQUIRE(n_freq_masks >= 0 && n_freq_masks <= kMaxMasks && n_time_masks >= 0 && n_time_masks <= kMaxMasks,
+              "ds2_spectrogram_aug_f32: %d frequency / %d time masks per utterance (at most %d of each)", n_freq_masks, n_time_masks, kMaxMasks);
+  DS2_REQUIRE((n_freq_masks == 0 || freq_masks) && (n_time_masks == 0 || time_masks), "ds2_spectrogram_aug_f32: null mask array");
+  AugArgs a{};
+  a.nz = AugNoise{noise, noise_base, noise_period, noise_start, nullptr};
+  a.level = any_noise ? noise_level : nullptr;
+  a.noise_len = noise_len;
+  a.mk = AugMasks{freq_masks, time_masks, n_freq_masks, n_time_masks};
+  return spectrogram_impl(audio, ld_audio, n_samples_dev, B, T, n_fft, hop, basis, pad_mode, normalize, out, ws, &a, stream);
 }

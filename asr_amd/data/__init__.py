@@ -6,13 +6,16 @@ DistributedBucketingSampler, AudioDataLoader, get_loader; plus the true length-b
 pre-computed spectrograms (`.npy` / `.pt`, shape (161, T)) are loaded as-is; `.wav` files go through a
 numpy STFT restatement of data/parsers/spectrogram_parser.py:36-62 (n_fft = win = sr*window_size,
 hop = sr*window_stride, centred zero-padded frames, log1p magnitude, per-utterance mean/std).
-`GpuSpectrogramFrontEnd` does the same for a whole batch on the GPU (csrc/stft.hip).
+`GpuSpectrogramFrontEnd` does the same for a whole batch on the GPU (csrc/stft.hip), optionally with noise injection
+(`NoiseInjection`) and SpecAugment; `get_loader(..., front_end="gpu")` feeds it from workers that only read WAV files.
 Parity with librosa 0.11.0 itself is UNPINNED (librosa is not installable here); both are held to
 oracle/stft_oracle.py, which is cross-checked against torch.stft and scipy.signal.stft.
 """
 from __future__ import annotations
 
 import math
+import os
+import warnings
 
 import numpy as np
 import torch
@@ -37,16 +40,187 @@ def _stft_spectrogram(y: np.ndarray, sample_rate: int, window_size: float, windo
     return np.log1p(spect)
 
 
+def _read_wav(path):
+    """(sample_rate, mono float32 waveform) of a WAV file, scaled like soundfile (audio/functional.py:11): integer PCM / 2^(bits-1),
+    8-bit unsigned PCM centred on 128; channels averaged."""
+    from scipy.io import wavfile
+    sr, y = wavfile.read(path)
+    if y.dtype.kind == "i":
+        y = y.astype(np.float32) / float(2 ** (8 * y.dtype.itemsize - 1))
+    elif y.dtype.kind == "u":
+        y = (y.astype(np.float32) - 128.0) / 128.0
+    if y.ndim > 1:
+        y = y.mean(axis=1)
+    return sr, y.astype(np.float32, copy=False)
+
+
+def noise_levels_of(audio_conf):
+    """(lo, hi) noise level range: audio_conf.noise_levels, else (noise_min, noise_max) — the keys of the reference's config.yml, on which
+    the reference's own NoiseInjection(audio_conf.noise_levels) would fail — else the reference's default (0, 0.5)."""
+    lv = getattr(audio_conf, "noise_levels", None)
+    if lv is not None:
+        lo, hi = lv
+    elif getattr(audio_conf, "noise_min", None) is not None or getattr(audio_conf, "noise_max", None) is not None:
+        lo, hi = getattr(audio_conf, "noise_min", 0.0), getattr(audio_conf, "noise_max", 0.5)
+    else:
+        lo, hi = 0.0, 0.5
+    return float(lo), float(hi)
+
+
+def noise_start(period: int, n: int, u: float) -> int:
+    """First noise sample of an utterance of n samples: floor(u * (L - n)) when the file is at least as long, else floor(u * L) (the segment
+    then wraps around the file: this port's choice — the reference fails on noise shorter than the utterance)."""
+    return int(math.floor(u * (period - n))) if period >= n else int(math.floor(u * period))
+
+
+_AUDIO_EXTS = ("aac", "au", "flac", "m4a", "mp3", "ogg", "wav")     # librosa.util.find_files' default extensions
+
+
+class NoiseInjection:
+    """The reference's NoiseInjection (asr_deepspeech/data/noise_injection.py:9-38) as ONE noise bank: every `.wav` under `path` (recursively,
+    sorted, as librosa.util.find_files lists them) is read once with the scaling of SpectrogramDataset.parse_audio and the files are kept
+    concatenated — `samples` (fp32, host) plus `starts` / `lengths` per file; `device_samples(device)` is the same bank in one device buffer
+    (uploaded once per device) for GpuSpectrogramFrontEnd.  Other audio formats are skipped with a warning (no sox here: no decoding, no
+    resampling); files must be at `sample_rate`.
+
+    `inject_noise(data)` keeps the reference's host method and its draws from numpy's global state (file, level ~ U(noise_levels), u ~ U[0,1));
+    the mix is `data + level * seg * rms(data) / rms(seg)` with seg = noise[(s + j) mod L], s = noise_start(L, n, u); a silent segment leaves
+    the data unmixed (the reference divides by zero there)."""
+
+    def __init__(self, path=None, sample_rate=16000, noise_levels=(0, 0.5)):
+        if path is None or not os.path.exists(path):
+            print("Directory doesn't exist: {}".format(path))
+            raise IOError(f"noise directory does not exist: {path}")
+        found = []
+        for root, _dirs, files in os.walk(path):
+            for f in files:
+                if f.rsplit(".", 1)[-1].lower() in _AUDIO_EXTS and "." in f:
+                    found.append(os.path.abspath(os.path.join(root, f)))
+        found.sort()
+        skipped = [f for f in found if not f.lower().endswith(".wav")]
+        if skipped:
+            warnings.warn(f"asr_amd.data.NoiseInjection: {len(skipped)} non-WAV noise file(s) skipped (no decoder / resampler here), e.g. {skipped[0]}")
+        self.paths = [f for f in found if f.lower().endswith(".wav")]
+        if not self.paths:
+            raise ValueError(f"NoiseInjection: no .wav file under {path}")
+        self.sample_rate, self.noise_levels = int(sample_rate), tuple(float(v) for v in noise_levels)
+        waves = []
+        for f in self.paths:
+            sr, y = _read_wav(f)
+            if sr != self.sample_rate:
+                raise ValueError(f"NoiseInjection: {f} is sampled at {sr} Hz, expected {self.sample_rate} Hz (no resampling here)")
+            if len(y) == 0:
+                raise ValueError(f"NoiseInjection: {f} holds no samples")
+            waves.append(y)
+        self.lengths = np.array([len(y) for y in waves], dtype=np.int64)
+        self.starts = np.concatenate([[0], np.cumsum(self.lengths)[:-1]]).astype(np.int64)
+        self.samples = np.concatenate(waves).astype(np.float32)
+        self._device = {}
+
+    def __len__(self):
+        return len(self.paths)
+
+    def device_samples(self, device) -> torch.Tensor:
+        key = str(device)
+        if key not in self._device:
+            self._device[key] = torch.from_numpy(self.samples).to(device)
+        return self._device[key]
+
+    def segment(self, index: int, n: int, u: float) -> np.ndarray:
+        """The n noise samples file `index` contributes to an utterance of n samples for draw u."""
+        L, b = int(self.lengths[index]), int(self.starts[index])
+        return self.samples[b + (noise_start(L, n, u) + np.arange(n)) % L]
+
+    def inject_noise(self, data):
+        index = np.random.choice(len(self.paths))
+        noise_level = np.random.uniform(*self.noise_levels)
+        return self.inject_noise_sample(data, index, noise_level, np.random.rand())
+
+    def inject_noise_sample(self, data, index, noise_level, u):
+        seg = self.segment(index, len(data), u).astype(np.float64)
+        x = np.asarray(data, dtype=np.float64)
+        noise_energy = np.sqrt(seg.dot(seg) / seg.size)
+        data_energy = np.sqrt(x.dot(x) / x.size)
+        if noise_energy == 0.0:
+            return np.asarray(data)
+        return (x + noise_level * seg * data_energy / noise_energy).astype(np.asarray(data).dtype)
+
+
+def draw_augmentation(rng, n_samples, hop, n_bins, noise=None, noise_prob=0.0, spec_augment=False, freq_mask_param=27, time_mask_param=70,
+                      freq_masks=1, time_masks=1):
+    """Per-utterance augmentation parameters of one batch, drawn from `rng` (numpy Generator) on the host.  Order, per utterance in batch
+    order (after the batch is sorted by frame count):
+      with a noise bank:  coin = rng.binomial(1, noise_prob); if coin: file = rng.integers(len(bank)), level = rng.uniform(*levels),
+                          u = rng.random()
+      with spec_augment:  freq_masks x (f = min(int(rng.uniform(0, F)), n_bins), f0 = rng.integers(0, n_bins - f, endpoint=True)),
+                          then time_masks x (t = min(int(rng.uniform(0, T_param)), tau), t0 = rng.integers(0, tau - t, endpoint=True)),
+                          tau = the utterance's own frame count 1 + n // hop.
+    Returns a dict of numpy arrays: file (-1 = no noise), level, u, base, period, start, freq (B, Mf, 2), time (B, Mt, 2) [lo, hi) ranges."""
+    B = len(n_samples)
+    p = dict(file=np.full(B, -1, np.int64), level=np.zeros(B, np.float32), u=np.zeros(B), base=np.zeros(B, np.int64),
+             period=np.ones(B, np.int32), start=np.zeros(B, np.int32), freq=np.zeros((B, freq_masks if spec_augment else 0, 2), np.int32),
+             time=np.zeros((B, time_masks if spec_augment else 0, 2), np.int32))
+    for b, n in enumerate(int(v) for v in n_samples):
+        if noise is not None and rng.binomial(1, noise_prob):
+            i = int(rng.integers(len(noise)))
+            level = rng.uniform(*noise.noise_levels)
+            u = rng.random()
+            L = int(noise.lengths[i])
+            p["file"][b], p["level"][b], p["u"][b] = i, level, u
+            p["base"][b], p["period"][b], p["start"][b] = int(noise.starts[i]), L, noise_start(L, n, u)
+        if spec_augment:
+            tau = 1 + n // hop if n > 0 else 0
+            for m in range(freq_masks):
+                f = min(int(rng.uniform(0.0, freq_mask_param)), n_bins)
+                f0 = int(rng.integers(0, n_bins - f, endpoint=True))
+                p["freq"][b, m] = (f0, f0 + f)
+            for m in range(time_masks):
+                t = min(int(rng.uniform(0.0, time_mask_param)), tau)
+                t0 = int(rng.integers(0, tau - t, endpoint=True))
+                p["time"][b, m] = (t0, t0 + t)
+    return p
+
+
 class GpuSpectrogramFrontEnd:
     """Batch spectrogram front-end on the GPU (csrc/stft.hip, `ds2_spectrogram_f32`): a list of 1-D waveforms in, the
     `_collate_fn` contract out — `(inputs (B,1,161,T) on the GPU, input_percentages (B,) float32)` — i.e. what
     SpectrogramParser.parse_audio (spectrogram_parser.py:36-62) + _collate_fn (functional.py:9-32) produce per batch, with
-    the STFT, log1p, per-utterance mean/std and zero padding done in four kernels instead of per item in DataLoader workers."""
+    the STFT, log1p, per-utterance mean/std and zero padding done in four kernels instead of per item in DataLoader workers.
 
-    def __init__(self, audio_conf, normalize=False, pad_mode="constant", device=None):
+    `augment=True` (ds2_spectrogram_aug_f32) honours the augmentations audio_conf asks for:
+      * noise injection when `audio_conf.noise_dir` is set: with probability `noise_prob` an utterance is mixed with a segment of a noise
+        file before the STFT, y = x + level * seg * rms(x) / rms(seg) (NoiseInjection; levels from noise_levels or noise_min / noise_max);
+      * SpecAugment when `audio_conf.spec_augment`: `freq_masks` frequency masks of up to `freq_mask_param` bins and `time_masks` time
+        masks of up to `time_mask_param` frames of the utterance's own length, set to 0 after the normalisation (upstream deepspeech.pytorch's
+        spec_augment without time warp; time warp is not implemented).  Padding frames stay 0.
+    The draws are made on the host from the front-end's own numpy Generator, in the order documented at `draw_augmentation`; `seed=None`
+    takes the seed from numpy's global state (offset by the rank under torch.distributed; only when there is something to draw), a fixed
+    seed gives bit-identical batches.
+    With augment=False (default) the output is that of the plain front-end."""
+
+    def __init__(self, audio_conf, normalize=False, pad_mode="constant", device=None, augment=False, seed=None, freq_mask_param=27,
+                 time_mask_param=70, freq_masks=1, time_masks=1, noise=None):
         self.n_fft = int(audio_conf.sample_rate * audio_conf.window_size)
         self.hop = int(audio_conf.sample_rate * audio_conf.window_stride)
         self.window, self.normalize, self.pad_mode, self.device = audio_conf.window, normalize, pad_mode, device
+        self.augment = bool(augment)
+        self.noise, self.noise_prob, self.spec_augment = None, 0.0, False
+        if self.augment:
+            if not (0 <= int(freq_masks) <= 8 and 0 <= int(time_masks) <= 8):
+                raise ValueError(f"freq_masks={freq_masks}, time_masks={time_masks}: at most 8 masks of each kind")
+            self.freq_mask_param, self.time_mask_param = float(freq_mask_param), float(time_mask_param)
+            self.freq_masks, self.time_masks = int(freq_masks), int(time_masks)
+            self.spec_augment = bool(getattr(audio_conf, "spec_augment", False))
+            if noise is None and getattr(audio_conf, "noise_dir", None) is not None:
+                noise = NoiseInjection(audio_conf.noise_dir, audio_conf.sample_rate, noise_levels_of(audio_conf))
+            self.noise = noise
+            self.noise_prob = float(getattr(audio_conf, "noise_prob", 0.4)) if noise is not None else 0.0
+            if seed is None and (noise is not None or self.spec_augment):     # (nothing to draw: numpy's global state is left alone)
+                seed = int(np.random.randint(0, 2 ** 31 - 1))
+                if torch.distributed.is_available() and torch.distributed.is_initialized():
+                    seed += torch.distributed.get_rank()
+            self.seed = None if seed is None else int(seed)
+            self.rng = np.random.default_rng(self.seed)
 
     def __call__(self, waves):
         from .. import ops
@@ -56,8 +230,23 @@ class GpuSpectrogramFrontEnd:
         batch = torch.zeros(len(waves), max(n), dtype=torch.float32)
         for i, w in enumerate(waves):
             batch[i, :n[i]] = torch.as_tensor(w, dtype=torch.float32)
-        spect, frames = ops.spectrogram(batch.to(dev), torch.tensor(n), self.n_fft, self.hop, self.window, self.pad_mode, self.normalize)
+        if self.augment and (self.noise is not None or self.spec_augment):
+            p = self.draw(n)
+            nz = {}
+            if self.noise is not None:
+                nz = dict(noise=self.noise.device_samples(dev), noise_base=p["base"], noise_period=p["period"], noise_start=p["start"],
+                          noise_level=p["level"])
+            spect, frames = ops.spectrogram_augmented(batch.to(dev), torch.tensor(n), self.n_fft, self.hop, self.window, self.pad_mode,
+                                                      self.normalize, freq_masks=p["freq"] if self.spec_augment else None,
+                                                      time_masks=p["time"] if self.spec_augment else None, **nz)
+        else:
+            spect, frames = ops.spectrogram(batch.to(dev), torch.tensor(n), self.n_fft, self.hop, self.window, self.pad_mode, self.normalize)
         return spect, frames.float() / float(spect.size(3))
+
+    def draw(self, n_samples):
+        """The next batch's augmentation parameters (draw_augmentation with this front-end's settings and Generator)."""
+        return draw_augmentation(self.rng, n_samples, self.hop, self.n_fft // 2 + 1, self.noise, self.noise_prob, self.spec_augment,
+                                 self.freq_mask_param, self.time_mask_param, self.freq_masks, self.time_masks)
 
 
 class SpectrogramDataset(Dataset):
@@ -86,15 +275,7 @@ class SpectrogramDataset(Dataset):
         elif path.endswith(".pt"):
             spect = torch.load(path).float()
         else:
-            from scipy.io import wavfile
-            sr, y = wavfile.read(path)
-            if y.dtype.kind == "i":
-                # soundfile (audio/functional.py:11) scales integer PCM by 2^(bits-1): int16 / 32768
-                y = y.astype(np.float32) / float(2 ** (8 * y.dtype.itemsize - 1))
-            elif y.dtype.kind == "u":
-                y = (y.astype(np.float32) - 128.0) / 128.0      # 8-bit WAV is unsigned
-            if y.ndim > 1:
-                y = y.mean(axis=1)
+            sr, y = _read_wav(path)
             assert sr == self.audio_conf.sample_rate, f"expected {self.audio_conf.sample_rate} Hz audio"
             spect = torch.from_numpy(_stft_spectrogram(y, sr, self.audio_conf.window_size, self.audio_conf.window_stride,
                                                        self.audio_conf.window))
@@ -118,6 +299,86 @@ class SpectrogramDataset(Dataset):
 
     def __len__(self):
         return self.size
+
+
+class WaveformDataset(Dataset):
+    """The dataset behind `get_loader(front_end="gpu")`: the manifest and labels of SpectrogramDataset, but an item is `(waveform (n,) float32
+    CPU tensor, transcript ids)` — workers only read WAV files (same scaling as SpectrogramDataset.parse_audio) and transcripts; the
+    spectrogram is made per batch on the GPU.  Pre-computed spectrograms (`.npy` / `.pt`) cannot be augmented as waveforms and are refused.
+    `caching=True` keeps waveforms, not spectrograms, so the augmentation is drawn anew every epoch."""
+
+    def __init__(self, audio_conf, manifest_filepath, labels, caching=False):
+        import pandas as pd
+        self.df = pd.read_csv(manifest_filepath)
+        self.size = len(self.df)
+        if isinstance(labels, str):
+            labels = dict([(v, k) for k, v in pd.read_csv(labels).to_dict()["label"].items()])
+        self.labels_map = labels
+        self.audio_conf, self.caching = audio_conf, caching
+        self._cache = {}
+        for f in self.df.audio_filepath:
+            if str(f).endswith((".npy", ".pt")):
+                raise ValueError(f"front_end='gpu' reads waveforms, but the manifest lists a pre-computed spectrogram: {f} "
+                                 "(use front_end='host' for .npy / .pt spectrograms)")
+        if bool(getattr(audio_conf, "speed_volume_perturb", False)):
+            warnings.warn("asr_amd.data (front_end='gpu'): speed_volume_perturb is not implemented, ignored — its sox tempo time-stretch "
+                          "needs a resampling kernel of its own and is a separate issue; noise_dir and spec_augment are applied on the GPU")
+
+    parse_transcript = SpectrogramDataset.parse_transcript
+
+    def parse_audio(self, path):
+        sr, y = _read_wav(path)
+        if sr != self.audio_conf.sample_rate:
+            raise ValueError(f"{path}: {sr} Hz, expected {self.audio_conf.sample_rate} Hz audio")
+        return torch.from_numpy(np.ascontiguousarray(y, dtype=np.float32))
+
+    def __getitem__(self, index):
+        if self.caching and index in self._cache:
+            return self._cache[index]
+        row = self.df.iloc[index]
+        item = (self.parse_audio(row.audio_filepath), self.parse_transcript(row.text))
+        if self.caching:
+            self._cache[index] = item
+        return item
+
+    def __len__(self):
+        return self.size
+
+
+def _waveform_batch(batch):
+    return batch
+
+
+class GpuAudioDataLoader:
+    """Iterates a DataLoader of (waveform, transcript) items and turns each batch into the `_collate_fn` 4-tuple in the MAIN process:
+    `(inputs (B,1,161,T) on the GPU, targets, input_percentages, target_sizes)`.  Items are sorted like _collate_fn (frame count 1 + n // hop,
+    descending, stable), then GpuSpectrogramFrontEnd makes the spectrograms (and draws the augmentation, in that sorted order)."""
+
+    def __init__(self, dataset, batch_sampler, num_workers, front_end):
+        self.dataset, self.batch_sampler, self.front_end = dataset, batch_sampler, front_end
+        self.loader = DataLoader(dataset, num_workers=num_workers, batch_sampler=batch_sampler, collate_fn=_waveform_batch)
+
+    def __len__(self):
+        return len(self.loader)
+
+    def collate(self, batch):
+        hop = self.front_end.hop
+        frames = [1 + len(w) // hop if len(w) > 0 else 0 for w, _ in batch]
+        batch = [batch[i] for i in sorted(range(len(batch)), key=lambda i: frames[i], reverse=True)]
+        inputs, _ = self.front_end([w for w, _ in batch])
+        max_len = inputs.size(3)
+        input_percentages = torch.zeros(len(batch), dtype=torch.float32)
+        target_sizes = torch.zeros(len(batch), dtype=torch.int32)
+        targets = []
+        for i, (w, target) in enumerate(batch):
+            input_percentages[i] = min(1 + len(w) // hop, max_len) / float(max_len)
+            target_sizes[i] = len(target)
+            targets.extend(target)
+        return inputs, torch.tensor(targets, dtype=torch.int32), input_percentages, target_sizes
+
+    def __iter__(self):
+        for batch in self.loader:
+            yield self.collate(batch)
 
 
 def _durations_of(data_source, durations=None):
@@ -330,17 +591,31 @@ class AudioDataLoader(DataLoader):
         self.collate_fn = _collate_fn
 
 
-def get_loader(audio_conf, labels, manifest, batch_size, num_workers, caching=False, length_bucketing=False):
+def get_loader(audio_conf, labels, manifest, batch_size, num_workers, caching=False, length_bucketing=False, front_end="host"):
     """data/loaders/functional.py:6-24.  `length_bucketing=True` (not in the reference) sorts the manifest by its `duration` column
-    before binning (LengthBucketingSampler; the distributed variant when torch.distributed is initialised)."""
-    dataset = SpectrogramDataset(audio_conf=audio_conf, manifest_filepath=manifest, labels=labels, normalize=True,
-                                 spec_augment=getattr(audio_conf, "spec_augment", False), caching=caching)
+    before binning (LengthBucketingSampler; the distributed variant when torch.distributed is initialised).
+
+    front_end="host" (default): SpectrogramDataset + AudioDataLoader, spectrograms per item in the workers, no augmentation.
+    front_end="gpu": WaveformDataset + GpuAudioDataLoader — workers read WAV files and transcripts only; per batch, in the main process,
+    GpuSpectrogramFrontEnd(normalize=True, augment=True) makes the spectrograms on the GPU with the noise injection (audio_conf.noise_dir,
+    noise_prob, noise_levels or noise_min / noise_max) and SpecAugment (audio_conf.spec_augment) that audio_conf asks for.  Batches are the
+    same 4-tuple, `inputs` already on the GPU.  With caching=True the waveforms are cached and the augmentation is redrawn every epoch."""
+    if front_end not in ("host", "gpu"):
+        raise ValueError(f"front_end={front_end!r}: expected host or gpu")
+    if front_end == "gpu":
+        dataset = WaveformDataset(audio_conf=audio_conf, manifest_filepath=manifest, labels=labels, caching=caching)
+        fe = GpuSpectrogramFrontEnd(audio_conf, normalize=True, augment=True)
+        make = lambda sampler: GpuAudioDataLoader(dataset, sampler, num_workers, fe)      # noqa: E731
+    else:
+        dataset = SpectrogramDataset(audio_conf=audio_conf, manifest_filepath=manifest, labels=labels, normalize=True,
+                                     spec_augment=getattr(audio_conf, "spec_augment", False), caching=caching)
+        make = lambda sampler: AudioDataLoader(dataset, num_workers=num_workers, batch_sampler=sampler)   # noqa: E731
     if length_bucketing and torch.distributed.is_available() and torch.distributed.is_initialized():
         sampler = DistributedLengthBucketingSampler(dataset, batch_size=batch_size)
-        loader = AudioDataLoader(dataset, num_workers=num_workers, batch_sampler=sampler)
+        loader = make(sampler)
         sampler.shuffle(0)
         return loader, sampler
     sampler = (LengthBucketingSampler if length_bucketing else BucketingSampler)(dataset, batch_size=batch_size)
-    loader = AudioDataLoader(dataset, num_workers=num_workers, batch_sampler=sampler)
+    loader = make(sampler)
     sampler.shuffle()
     return loader, sampler

@@ -1381,6 +1381,56 @@ def spectrogram(audio: Tensor, n_samples: Tensor, n_fft: int, hop: int, window: 
     return out, torch.tensor([min(f, T) for f in fr], dtype=torch.int32)
 
 
+def spectrogram_augmented(audio: Tensor, n_samples: Tensor, n_fft: int, hop: int, window: str = "hamming", pad_mode: str = "constant",
+                          normalize: bool = False, noise: Optional[Tensor] = None, noise_base=None, noise_period=None, noise_start=None,
+                          noise_level=None, freq_masks=None, time_masks=None, frames: int = 0):
+    """`spectrogram` with noise injection before the STFT and SpecAugment masks after the statistics (ds2_spectrogram_aug_f32, contract in
+    include/ds2hip.h).  noise: 1-D fp32 GPU noise bank (or None); noise_base (B) int64, noise_period / noise_start (B) int32, noise_level
+    (B) fp32 (0 = no noise for that utterance), all four given or none; freq_masks / time_masks: (B, M, 2) int32 [lo, hi) bin / frame ranges,
+    M <= 8, or None.  Per-utterance arrays may live on the host: they are copied to audio's device.  Returns (spect, frames) as `spectrogram`."""
+    _chk_f32(audio)
+    assert audio.dim() == 2 and audio.stride(1) == 1
+    lib = _lib.load()
+    B, dev = audio.size(0), audio.device
+    n_host = [int(v) for v in n_samples.tolist()]
+    fr = [lib.ds2_spectrogram_frames(n, hop) for n in n_host]
+    T = frames or max(max(fr), 1)
+    n_dev = torch.as_tensor(n_host, dtype=torch.int32).to(dev)
+
+    def per_utt(x, dtype, shape):
+        t = torch.as_tensor(x, dtype=dtype).to(dev).contiguous()
+        assert tuple(t.shape) == shape, f"expected shape {shape}, got {tuple(t.shape)}"
+        return t
+    keep = []                                            # device copies stay alive until the call is enqueued
+    nz = (noise_base, noise_period, noise_start, noise_level)
+    if any(a is not None for a in nz):
+        assert all(a is not None for a in nz) and noise is not None, "noise_base, noise_period, noise_start, noise_level and noise go together"
+        _chk_f32(noise)
+        assert noise.dim() == 1 and noise.device == dev
+        keep = [per_utt(noise_base, torch.int64, (B,)), per_utt(noise_period, torch.int32, (B,)), per_utt(noise_start, torch.int32, (B,)),
+                per_utt(noise_level, torch.float32, (B,))]
+        nz_ptrs, noise_ptr, noise_len = [t.data_ptr() for t in keep], noise.data_ptr(), noise.numel()
+    else:
+        nz_ptrs, noise_ptr, noise_len = [None] * 4, None, 0
+    masks = []
+    for m in (freq_masks, time_masks):
+        if m is None:
+            masks.append((None, 0))
+        else:
+            mt = torch.as_tensor(m, dtype=torch.int32).to(dev).contiguous()
+            assert mt.dim() == 3 and mt.size(0) == B and mt.size(2) == 2, f"masks: expected (B, M, 2), got {tuple(mt.shape)}"
+            keep.append(mt)
+            masks.append((mt.data_ptr() if mt.size(1) else None, mt.size(1)))
+    out = torch.empty((B, 1, n_fft // 2 + 1, T), dtype=torch.float32, device=dev)
+    wsb = lib.ds2_spectrogram_aug_workspace_bytes(B, T, n_fft, hop)
+    ws = _ws(wsb, dev)
+    _lib.check(lib.ds2_spectrogram_aug_f32(audio.data_ptr(), audio.stride(0), n_dev.data_ptr(), B, T, n_fft, hop,
+                                           dft_basis(n_fft, window, dev).data_ptr(), {"constant": 0, "reflect": 1}[pad_mode],
+                                           int(bool(normalize)), noise_ptr, noise_len, *nz_ptrs, masks[0][0], masks[0][1], masks[1][0],
+                                           masks[1][1], out.data_ptr(), ws.data_ptr(), wsb, _stream()), "ds2_spectrogram_aug_f32")
+    return out, torch.tensor([min(f, T) for f in fr], dtype=torch.int32)
+
+
 # ------------------------------------------------------------------------------------------------
 # optimizer
 # ------------------------------------------------------------------------------------------------

@@ -499,6 +499,25 @@ int ds2_spectrogram_frames(int n_samples, int hop);
 size_t ds2_spectrogram_workspace_bytes(int B, int T, int n_fft, int hop);
 int ds2_spectrogram_f32(const float* audio, long long ld_audio, const int* n_samples_dev, int B, int T, int n_fft, int hop,
                         const float* basis, int pad_mode, int normalize, float* out, void* ws, size_t ws_bytes, void* stream);
+/* The augmented front-end: the same spectrogram with noise injection before the STFT and SpecAugment masks after the statistics.
+ * Per-utterance parameters are drawn on the host (asr_amd.data.GpuSpectrogramFrontEnd); the device only applies them.
+ *  Noise injection (asr_deepspeech/data/noise_injection.py:22-38): utterance b with noise_level[b] != 0 is mixed as
+ *      y[j] = x[j] + level_b * seg[j] * rms(x) / rms(seg),   seg[j] = noise[noise_base[b] + (noise_start[b] + j) mod noise_period[b]],
+ *  rms over the utterance's own n_b samples (energies: fp32 block partials combined in fp64); rms(seg) == 0 leaves the utterance unmixed.
+ *  The padding (zeros or reflect) is that of the mixed signal; no mixed copy of the waveform is written and `audio` is not modified.
+ *  noise (noise_len) fp32 = ONE bank of concatenated noise files; noise_base (B) int64, noise_period / noise_start (B) int32,
+ *  noise_level (B) fp32 (0 = off); a segment outside the bank (base + period > noise_len, start outside [0, period)) is not mixed.
+ *  The four arrays are all NULL for no noise at all.
+ *  SpecAugment (no time warp): freq_masks (B, n_freq_masks, 2) / time_masks (B, n_time_masks, 2) int32 [lo, hi) bin / frame ranges,
+ *  at most 8 of each; an element inside any range of its utterance, with t < frames_b, is written as 0 — after the per-utterance
+ *  normalisation when `normalize` (masks do not enter the statistics).  Padding frames stay exactly 0.
+ *  Level 0 and no masks give the bits of ds2_spectrogram_f32. */
+size_t ds2_spectrogram_aug_workspace_bytes(int B, int T, int n_fft, int hop);
+int ds2_spectrogram_aug_f32(const float* audio, long long ld_audio, const int* n_samples_dev, int B, int T, int n_fft, int hop,
+                            const float* basis, int pad_mode, int normalize, const float* noise, long long noise_len,
+                            const long long* noise_base, const int* noise_period, const int* noise_start, const float* noise_level,
+                            const int* freq_masks, int n_freq_masks, const int* time_masks, int n_time_masks, float* out, void* ws,
+                            size_t ws_bytes, void* stream);
 
 /* ---- optimizer ----------------------------------------------------------------------------------
  * torch.optim.AdamW.step over one flat parameter buffer, trainers/__main__.py:41-47. */
