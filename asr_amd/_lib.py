@@ -140,6 +140,10 @@ SIGNATURES = {
     "ds2_spectrogram_aug_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "ds2_spectrogram_aug_f32": (i32, [vp, i64, vp, i32, i32, i32, i32, vp, i32, i32, vp, i64, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, sz,
                                       vp]),
+    "ds2_tempo_sizes": (i32, [i32, f64, f64, f64, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+    "ds2_tempo_out_samples": (i32, [i32, f64]),
+    "ds2_tempo_workspace_bytes": (sz, [i32]),
+    "ds2_tempo_gain_f32": (i32, [vp, i64, vp, vp, vp, i32, i32, f64, f64, f64, vp, i64, vp, vp, i32, vp, sz, vp]),
     "ds2_adamw_f32": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, vp]),
     "ds2_adamw_gated_f32": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, vp, vp]),
     "ds2_scale_f32": (i32, [vp, i64, f32, vp]),

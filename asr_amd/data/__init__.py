@@ -146,6 +146,17 @@ class NoiseInjection:
         return (x + noise_level * seg * data_energy / noise_energy).astype(np.asarray(data).dtype)
 
 
+def draw_perturbation(rng, B, tempo_range=(0.85, 1.15), gain_range=(-6, 8)):
+    """Tempo factors and gains (dB) of one batch, drawn from `rng` (numpy Generator) on the host: per utterance, in the order given,
+    tempo = rng.uniform(*tempo_range) then gain = rng.uniform(*gain_range) (load_randomly_augmented_audio's ranges, audio/functional.py:94-104).
+    One block of 2 B numbers, drawn BEFORE draw_augmentation's for the same batch.  Returns (tempo (B,) float64, gain (B,) float64)."""
+    tempo, gain = np.zeros(B, np.float64), np.zeros(B, np.float64)
+    for b in range(B):
+        tempo[b] = rng.uniform(*tempo_range)
+        gain[b] = rng.uniform(*gain_range)
+    return tempo, gain
+
+
 def draw_augmentation(rng, n_samples, hop, n_bins, noise=None, noise_prob=0.0, spec_augment=False, freq_mask_param=27, time_mask_param=70,
                       freq_masks=1, time_masks=1):
     """Per-utterance augmentation parameters of one batch, drawn from `rng` (numpy Generator) on the host.  Order, per utterance in batch
@@ -193,19 +204,31 @@ class GpuSpectrogramFrontEnd:
       * SpecAugment when `audio_conf.spec_augment`: `freq_masks` frequency masks of up to `freq_mask_param` bins and `time_masks` time
         masks of up to `time_mask_param` frames of the utterance's own length, set to 0 after the normalisation (upstream deepspeech.pytorch's
         spec_augment without time warp; time warp is not implemented).  Padding frames stay 0.
+      * tempo / gain perturbation when `audio_conf.speed_volume_perturb` AND `speed_volume_perturb=True` here: every utterance is
+        time-stretched by tempo ~ U(*tempo_range) (WSOLA, pitch kept) and scaled by gain ~ U(*gain_range) dB, clipped to [-1, 1], first of
+        all (ops.tempo_gain, ds2_tempo_gain_f32) — noise and masks then follow the perturbed utterance of floor(n / tempo + 0.5) samples.
+        Modelled on sox's `tempo` / `gain` effects that the reference runs per file; parity with sox is unpinned, and its 16-bit
+        requantisation with dither is not reproduced.  Its draws (draw_perturbation) come as one block before draw_augmentation's.
     The draws are made on the host from the front-end's own numpy Generator, in the order documented at `draw_augmentation`; `seed=None`
     takes the seed from numpy's global state (offset by the rank under torch.distributed; only when there is something to draw), a fixed
     seed gives bit-identical batches.
     With augment=False (default) the output is that of the plain front-end."""
 
     def __init__(self, audio_conf, normalize=False, pad_mode="constant", device=None, augment=False, seed=None, freq_mask_param=27,
-                 time_mask_param=70, freq_masks=1, time_masks=1, noise=None):
+                 time_mask_param=70, freq_masks=1, time_masks=1, noise=None, speed_volume_perturb=False, tempo_range=(0.85, 1.15),
+                 gain_range=(-6, 8)):
+        self.sample_rate = int(audio_conf.sample_rate)
         self.n_fft = int(audio_conf.sample_rate * audio_conf.window_size)
         self.hop = int(audio_conf.sample_rate * audio_conf.window_stride)
         self.window, self.normalize, self.pad_mode, self.device = audio_conf.window, normalize, pad_mode, device
         self.augment = bool(augment)
-        self.noise, self.noise_prob, self.spec_augment = None, 0.0, False
+        self.noise, self.noise_prob, self.spec_augment, self.perturb = None, 0.0, False, False
         if self.augment:
+            self.perturb = bool(speed_volume_perturb) and bool(getattr(audio_conf, "speed_volume_perturb", False))
+            self.tempo_range = (float(tempo_range[0]), float(tempo_range[1]))
+            self.gain_range = (float(gain_range[0]), float(gain_range[1]))
+            if self.perturb and not 0.5 <= self.tempo_range[0] <= self.tempo_range[1] <= 2.0:
+                raise ValueError(f"tempo_range={tempo_range}: tempo factors lie in [0.5, 2]")
             if not (0 <= int(freq_masks) <= 8 and 0 <= int(time_masks) <= 8):
                 raise ValueError(f"freq_masks={freq_masks}, time_masks={time_masks}: at most 8 masks of each kind")
             self.freq_mask_param, self.time_mask_param = float(freq_mask_param), float(time_mask_param)
@@ -215,14 +238,16 @@ class GpuSpectrogramFrontEnd:
                 noise = NoiseInjection(audio_conf.noise_dir, audio_conf.sample_rate, noise_levels_of(audio_conf))
             self.noise = noise
             self.noise_prob = float(getattr(audio_conf, "noise_prob", 0.4)) if noise is not None else 0.0
-            if seed is None and (noise is not None or self.spec_augment):     # (nothing to draw: numpy's global state is left alone)
+            if seed is None and (noise is not None or self.spec_augment or self.perturb):     # (nothing to draw: numpy's global state is left alone)
                 seed = int(np.random.randint(0, 2 ** 31 - 1))
                 if torch.distributed.is_available() and torch.distributed.is_initialized():
                     seed += torch.distributed.get_rank()
             self.seed = None if seed is None else int(seed)
             self.rng = np.random.default_rng(self.seed)
 
-    def __call__(self, waves):
+    def __call__(self, waves, perturb=None):
+        """`perturb`: an already drawn (tempo, gain dB) pair of arrays for this batch (GpuAudioDataLoader draws before it sorts); None draws
+        here when the perturbation is on."""
         from .. import ops
         from ..device import resolve_device
         dev = torch.device(self.device) if self.device is not None else resolve_device("auto")
@@ -230,6 +255,12 @@ class GpuSpectrogramFrontEnd:
         batch = torch.zeros(len(waves), max(n), dtype=torch.float32)
         for i, w in enumerate(waves):
             batch[i, :n[i]] = torch.as_tensor(w, dtype=torch.float32)
+        if self.perturb:
+            tempo, gain = perturb if perturb is not None else self.draw_perturbation(len(waves))
+            batch, _, _ = ops.tempo_gain(batch.to(dev), n, tempo, gain, self.sample_rate)
+            n = self.perturbed_lengths(n, tempo)
+        elif perturb is not None:
+            raise ValueError("perturb= given, but this front-end does not perturb (augment, speed_volume_perturb and audio_conf.speed_volume_perturb)")
         if self.augment and (self.noise is not None or self.spec_augment):
             p = self.draw(n)
             nz = {}
@@ -242,6 +273,16 @@ class GpuSpectrogramFrontEnd:
         else:
             spect, frames = ops.spectrogram(batch.to(dev), torch.tensor(n), self.n_fft, self.hop, self.window, self.pad_mode, self.normalize)
         return spect, frames.float() / float(spect.size(3))
+
+    def draw_perturbation(self, B):
+        """The next batch's (tempo, gain dB) arrays (draw_perturbation with this front-end's ranges and Generator)."""
+        return draw_perturbation(self.rng, B, self.tempo_range, self.gain_range)
+
+    @staticmethod
+    def perturbed_lengths(n_samples, tempo):
+        """floor(n / tempo + 0.5) per utterance: the lengths ops.tempo_gain produces (a host computation)."""
+        from .. import ops
+        return [ops.tempo_out_samples(n, f) for n, f in zip(n_samples, tempo)]
 
     def draw(self, n_samples):
         """The next batch's augmentation parameters (draw_augmentation with this front-end's settings and Generator)."""
@@ -307,7 +348,7 @@ class WaveformDataset(Dataset):
     spectrogram is made per batch on the GPU.  Pre-computed spectrograms (`.npy` / `.pt`) cannot be augmented as waveforms and are refused.
     `caching=True` keeps waveforms, not spectrograms, so the augmentation is drawn anew every epoch."""
 
-    def __init__(self, audio_conf, manifest_filepath, labels, caching=False):
+    def __init__(self, audio_conf, manifest_filepath, labels, caching=False, perturb=False):
         import pandas as pd
         self.df = pd.read_csv(manifest_filepath)
         self.size = len(self.df)
@@ -320,7 +361,7 @@ class WaveformDataset(Dataset):
             if str(f).endswith((".npy", ".pt")):
                 raise ValueError(f"front_end='gpu' reads waveforms, but the manifest lists a pre-computed spectrogram: {f} "
                                  "(use front_end='host' for .npy / .pt spectrograms)")
-        if bool(getattr(audio_conf, "speed_volume_perturb", False)):
+        if bool(getattr(audio_conf, "speed_volume_perturb", False)) and not perturb:     # perturb=True: the loader's front-end applies it
             warnings.warn("asr_amd.data (front_end='gpu'): speed_volume_perturb is not implemented, ignored — its sox tempo time-stretch "
                           "needs a resampling kernel of its own and is a separate issue; noise_dir and spec_augment are applied on the GPU")
 
@@ -352,7 +393,8 @@ def _waveform_batch(batch):
 class GpuAudioDataLoader:
     """Iterates a DataLoader of (waveform, transcript) items and turns each batch into the `_collate_fn` 4-tuple in the MAIN process:
     `(inputs (B,1,161,T) on the GPU, targets, input_percentages, target_sizes)`.  Items are sorted like _collate_fn (frame count 1 + n // hop,
-    descending, stable), then GpuSpectrogramFrontEnd makes the spectrograms (and draws the augmentation, in that sorted order)."""
+    descending, stable), then GpuSpectrogramFrontEnd makes the spectrograms (and draws the augmentation, in that sorted order).  With a
+    perturbing front-end the tempo / gain draws come first, in arrival order, and n is the perturbed length floor(n / tempo + 0.5)."""
 
     def __init__(self, dataset, batch_sampler, num_workers, front_end):
         self.dataset, self.batch_sampler, self.front_end = dataset, batch_sampler, front_end
@@ -363,15 +405,22 @@ class GpuAudioDataLoader:
 
     def collate(self, batch):
         hop = self.front_end.hop
-        frames = [1 + len(w) // hop if len(w) > 0 else 0 for w, _ in batch]
-        batch = [batch[i] for i in sorted(range(len(batch)), key=lambda i: frames[i], reverse=True)]
-        inputs, _ = self.front_end([w for w, _ in batch])
+        lengths, perturb = [len(w) for w, _ in batch], None
+        if self.front_end.perturb:                       # drawn in arrival order; the batch is then sorted by its PERTURBED lengths
+            tempo, gain = self.front_end.draw_perturbation(len(batch))
+            lengths = self.front_end.perturbed_lengths(lengths, tempo)
+        frames = [1 + n // hop if n > 0 else 0 for n in lengths]
+        order = sorted(range(len(batch)), key=lambda i: frames[i], reverse=True)
+        batch, lengths = [batch[i] for i in order], [lengths[i] for i in order]
+        if self.front_end.perturb:
+            perturb = (tempo[order], gain[order])
+        inputs, _ = self.front_end([w for w, _ in batch], perturb=perturb)
         max_len = inputs.size(3)
         input_percentages = torch.zeros(len(batch), dtype=torch.float32)
         target_sizes = torch.zeros(len(batch), dtype=torch.int32)
         targets = []
         for i, (w, target) in enumerate(batch):
-            input_percentages[i] = min(1 + len(w) // hop, max_len) / float(max_len)
+            input_percentages[i] = min(1 + lengths[i] // hop, max_len) / float(max_len)
             target_sizes[i] = len(target)
             targets.extend(target)
         return inputs, torch.tensor(targets, dtype=torch.int32), input_percentages, target_sizes
@@ -591,7 +640,8 @@ class AudioDataLoader(DataLoader):
         self.collate_fn = _collate_fn
 
 
-def get_loader(audio_conf, labels, manifest, batch_size, num_workers, caching=False, length_bucketing=False, front_end="host"):
+def get_loader(audio_conf, labels, manifest, batch_size, num_workers, caching=False, length_bucketing=False, front_end="host",
+               perturb=False):
     """data/loaders/functional.py:6-24.  `length_bucketing=True` (not in the reference) sorts the manifest by its `duration` column
     before binning (LengthBucketingSampler; the distributed variant when torch.distributed is initialised).
 
@@ -599,12 +649,17 @@ def get_loader(audio_conf, labels, manifest, batch_size, num_workers, caching=Fa
     front_end="gpu": WaveformDataset + GpuAudioDataLoader — workers read WAV files and transcripts only; per batch, in the main process,
     GpuSpectrogramFrontEnd(normalize=True, augment=True) makes the spectrograms on the GPU with the noise injection (audio_conf.noise_dir,
     noise_prob, noise_levels or noise_min / noise_max) and SpecAugment (audio_conf.spec_augment) that audio_conf asks for.  Batches are the
-    same 4-tuple, `inputs` already on the GPU.  With caching=True the waveforms are cached and the augmentation is redrawn every epoch."""
+    same 4-tuple, `inputs` already on the GPU.  With caching=True the waveforms are cached and the augmentation is redrawn every epoch.
+    `perturb=True` (front_end="gpu" only) also applies audio_conf.speed_volume_perturb there: tempo ~ U(0.85, 1.15) and gain ~ U(-6, 8) dB per
+    utterance, first of all, the batch sorted by its perturbed lengths (ops.tempo_gain; modelled on sox's effects, parity with sox unpinned).
+    With the default perturb=False the switch is ignored with a warning, as on the host path."""
     if front_end not in ("host", "gpu"):
         raise ValueError(f"front_end={front_end!r}: expected host or gpu")
+    if perturb and front_end != "gpu":
+        raise ValueError("perturb=True needs front_end='gpu' (the host front-end has no tempo / gain perturbation)")
     if front_end == "gpu":
-        dataset = WaveformDataset(audio_conf=audio_conf, manifest_filepath=manifest, labels=labels, caching=caching)
-        fe = GpuSpectrogramFrontEnd(audio_conf, normalize=True, augment=True)
+        dataset = WaveformDataset(audio_conf=audio_conf, manifest_filepath=manifest, labels=labels, caching=caching, perturb=perturb)
+        fe = GpuSpectrogramFrontEnd(audio_conf, normalize=True, augment=True, speed_volume_perturb=perturb)
         make = lambda sampler: GpuAudioDataLoader(dataset, sampler, num_workers, fe)      # noqa: E731
     else:
         dataset = SpectrogramDataset(audio_conf=audio_conf, manifest_filepath=manifest, labels=labels, normalize=True,

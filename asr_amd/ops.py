@@ -1431,6 +1431,60 @@ def spectrogram_augmented(audio: Tensor, n_samples: Tensor, n_fft: int, hop: int
     return out, torch.tensor([min(f, T) for f in fr], dtype=torch.int32)
 
 
+TEMPO_SEGMENT_MS, TEMPO_SEARCH_MS, TEMPO_OVERLAP_MS = 82.0, 14.68, 12.0
+
+
+def tempo_sizes(sample_rate: int, segment_ms: float = TEMPO_SEGMENT_MS, search_ms: float = TEMPO_SEARCH_MS,
+                overlap_ms: float = TEMPO_OVERLAP_MS) -> Tuple[int, int, int]:
+    """(S, R, O): segment, search and overlap lengths in samples (ds2_tempo_sizes; a host function, no GPU needed)."""
+    S, R, O = C.c_int(), C.c_int(), C.c_int()
+    _lib.check(_lib.load().ds2_tempo_sizes(int(sample_rate), float(segment_ms), float(search_ms), float(overlap_ms), C.byref(S), C.byref(R),
+                                           C.byref(O)), "ds2_tempo_sizes")
+    return S.value, R.value, O.value
+
+
+def tempo_out_samples(n: int, tempo: float) -> int:
+    """floor(n / tempo + 0.5): the length of a tempo-perturbed utterance (ds2_tempo_out_samples; a host function, no GPU needed)."""
+    n_out = _lib.load().ds2_tempo_out_samples(int(n), float(tempo))
+    if n_out < 0:
+        raise _lib.DS2LibraryError(f"tempo_out_samples: n = {n} (0 .. 2^29), tempo = {tempo} (0.5 .. 2) outside the contract")
+    return n_out
+
+
+def tempo_gain(audio: Tensor, n_samples, tempo, gain, sample_rate: int, segment_ms: float = TEMPO_SEGMENT_MS,
+               search_ms: float = TEMPO_SEARCH_MS, overlap_ms: float = TEMPO_OVERLAP_MS):
+    """Tempo (WSOLA time-stretch, pitch kept) and gain perturbation of a waveform batch (ds2_tempo_gain_f32, contract in include/ds2hip.h;
+    modelled on sox's `tempo` / `gain` effects, parity with sox itself unpinned; sox's 16-bit requantisation with dither is not reproduced).
+    audio (B, L) fp32 GPU rows (garbage allowed beyond n_samples); n_samples (B) ints, tempo (B) factors in [0.5, 2], gain (B) in dB —
+    host values; the kernel is given G = float32(10 ** (gain / 20)).
+    Returns (out (B, max n_out) fp32 GPU, exact zeros beyond each n_out; n_out (B) int32 GPU; offsets (B, Kmax) int32 GPU: the search
+    result d_k of every segment, 0 beyond an utterance's own segments).  The host-side lengths are `tempo_out_samples(n, tempo)`."""
+    import numpy as np
+    _chk_f32(audio)
+    assert audio.dim() == 2 and audio.stride(1) == 1
+    lib = _lib.load()
+    B, dev = audio.size(0), audio.device
+    n_host = np.ascontiguousarray([int(v) for v in (n_samples.tolist() if isinstance(n_samples, Tensor) else n_samples)], dtype=np.int32)
+    f_host = np.ascontiguousarray(tempo.tolist() if isinstance(tempo, Tensor) else tempo, dtype=np.float64)
+    g_db = np.ascontiguousarray(gain.tolist() if isinstance(gain, Tensor) else gain, dtype=np.float64)
+    assert n_host.shape == f_host.shape == g_db.shape == (B,), f"n_samples, tempo and gain: one value per utterance ({B})"
+    assert B == 0 or int(n_host.max()) <= audio.size(1), "n_samples exceeds the batch's row length"
+    g_host = np.ascontiguousarray(np.float32(10.0 ** (g_db / 20.0)))
+    S, _, O = tempo_sizes(sample_rate, segment_ms, search_ms, overlap_ms)
+    n_out = [tempo_out_samples(n, f) for n, f in zip(n_host.tolist(), f_host.tolist())]
+    ld_out = max(max(n_out), 1)
+    ld_off = max(-(-max(n_out) // (S - O)), 1)
+    out = torch.empty((B, ld_out), dtype=torch.float32, device=dev)
+    n_out_dev = torch.empty(B, dtype=torch.int32, device=dev)
+    offsets = torch.empty((B, ld_off), dtype=torch.int32, device=dev)
+    wsb = lib.ds2_tempo_workspace_bytes(B)
+    ws = _ws(wsb, dev)
+    _lib.check(lib.ds2_tempo_gain_f32(audio.data_ptr(), audio.stride(0), n_host.ctypes.data, f_host.ctypes.data, g_host.ctypes.data, B,
+                                      int(sample_rate), float(segment_ms), float(search_ms), float(overlap_ms), out.data_ptr(), ld_out,
+                                      n_out_dev.data_ptr(), offsets.data_ptr(), ld_off, ws.data_ptr(), wsb, _stream()), "ds2_tempo_gain_f32")
+    return out, n_out_dev, offsets
+
+
 # ------------------------------------------------------------------------------------------------
 # optimizer
 # ------------------------------------------------------------------------------------------------

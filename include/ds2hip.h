@@ -519,6 +519,37 @@ int ds2_spectrogram_aug_f32(const float* audio, long long ld_audio, const int* n
                             const int* freq_masks, int n_freq_masks, const int* time_masks, int n_time_masks, float* out, void* ws,
                             size_t ws_bytes, void* stream);
 
+/* ---- tempo / gain perturbation (audio_conf.speed_volume_perturb) ----------------------------------------------
+ * load_randomly_augmented_audio, audio/functional.py:94-104, runs `sox ... tempo f gain g` per utterance, before noise injection
+ * (spectrogram_parser.py:36-44).  sox is not part of the reference tree: PARITY WITH SOX IS UNPINNED.  The contract below is modelled
+ * on what its `tempo` effect is published to do (WSOLA, waveform-similarity overlap-add) and is what tests/tempo_oracle.py restates.
+ * Per utterance: x[0..n) fp32 (reads outside [0, n) give 0), tempo factor f (fp64, 0.5 <= f <= 2), linear gain G (fp32, >= 0).
+ *  Sizes, each int(sample_rate * ms / 1000 + 0.5): segment S (82 ms), search R (14.68 ms), overlap O (12 ms); hop H = S - O
+ *  (16 kHz: 1312, 235, 192, 1120).  S > 2 O, R >= 1, O >= 1, R + O <= 2048.  ds2_tempo_sizes returns them (non-zero: outside the contract).
+ *  n_out = floor(n / f + 0.5) in fp64 (ds2_tempo_out_samples, a host function; -1 for n outside [0, 2^29] or f outside [0.5, 2]);
+ *  K = ceil(n_out / H) segments.  Nominal input position of segment k: p_k = floor(k * f * H + 0.5), IEEE fp64, every operation
+ *  rounded on its own — the device evaluates exactly this expression.
+ *  Search signal: s[i] = clamp(rint(x[i] * 32768), -32768, 32767), an integer (round half to even): the 16-bit sample sox is handed.
+ *  q_0 = 0.  For k >= 1, with the tail t[i] = s[q_{k-1} + H + i], i in [0, O) — what would naturally follow segment k-1 — d_k in [0, R)
+ *  minimises SSD(d) = sum_i (s[p_k + d + i] - t[i])^2 in exact integer arithmetic, the lowest d on ties; q_k = p_k + d_k.
+ *  Output of segment k at y[k H ...], cut to n_out: O samples a + w_i (b - a), a = x[q_{k-1} + H + i], b = x[q_k + i],
+ *  w_i = (i + 0.5) / O in fp32 (k = 0: x[i]; b == a gives a itself), then H - O samples x[q_k + O + j].
+ *  Last, y = min(max(G y, -1), 1).  f = 1, G = 1 returns x bit for bit (|x| <= 1).  sox's requantisation to 16 bits with dither is
+ *  noise by design and is not reproduced.
+ * ds2_tempo_gain_f32: audio (B, ld_audio) fp32 device rows; n_samples (B) int32, tempo (B) fp64 and gain (B) fp32 (linear) are HOST
+ * arrays (the host sizes everything from them; nothing is copied back).  out (B, ld_out) fp32 device: y in [0, n_out_b), exact zeros
+ * in [n_out_b, ld_out), so the batch can go straight into ds2_spectrogram_f32 / ds2_spectrogram_aug_f32 with n_out_dev (B) int32 device,
+ * which is written too.  offsets_out (B, ld_offsets) int32 device: d_k for k < K_b (d_0 = 0), 0 for K_b <= k < ld_offsets;
+ * ld_offsets >= every K_b.  workspace: ds2_tempo_workspace_bytes(B) device bytes.  Arguments outside the contract return non-zero
+ * and launch nothing.  Two kernels (csrc/tempo.hip): the chain of searches, one workgroup per utterance, and the synthesis over
+ * (utterance, segment); no atomics, reruns are bit-identical. */
+int ds2_tempo_sizes(int sample_rate, double segment_ms, double search_ms, double overlap_ms, int* S, int* R, int* O);
+int ds2_tempo_out_samples(int n, double f);
+size_t ds2_tempo_workspace_bytes(int B);
+int ds2_tempo_gain_f32(const float* audio, long long ld_audio, const int* n_samples, const double* tempo, const float* gain, int B,
+                       int sample_rate, double segment_ms, double search_ms, double overlap_ms, float* out, long long ld_out,
+                       int* n_out_dev, int* offsets_out, int ld_offsets, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- optimizer ----------------------------------------------------------------------------------
  * torch.optim.AdamW.step over one flat parameter buffer, trainers/__main__.py:41-47. */
 int ds2_adamw_f32(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps,
