@@ -383,3 +383,96 @@ extern "C" int ds2_spectrogram_aug_f32(const float* audio, long long ld_audio, c
   a.mk = AugMasks{freq_masks, time_masks, n_freq_masks, n_time_masks};
   return spectrogram_impl(audio, ld_audio, n_samples_dev, B, T, n_fft, hop, basis, pad_mode, normalize, out, ws, &a, stream);
 }
+
+// ---- packed waveform feed: unpack -----------------------------------------------------------------------------------------------
+// A ragged batch of waveforms -> the zero-padded (B, n_max) fp32 batch the kernels above (and tempo.hip's) read: the device half of the
+// pipelined waveform feed (asr_amd.data, get_loader(front_end="gpu", prefetch=N)).  The host sends ONE packed buffer per batch — raw
+// 16-bit PCM when every file is 16-bit mono, fp32 otherwise — and this pass does what the host did with B slice copies into a
+// pageable torch.zeros(B, n_max): scale (int16 * 2^-15, exact: the bits of `astype(float32) / 32768`), permute rows, zero the padding.
+//
+// Mapping: one thread per 8 output samples of one row.  Every utterance starts at a multiple of 8 elements of a 16-byte-aligned
+// buffer, so the 8 source samples are one 128-bit load (int16) or two (fp32); the row pitch of `out` is arbitrary (the front-end's
+// batches have ld = n_max), so the two 128-bit stores are only 4-byte aligned, which global memory allows.  One pass, no LDS, no
+// atomics: reruns are bit-identical.  The kernels above are untouched.
+namespace {
+
+typedef short i16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x4_u __attribute__((ext_vector_type(4), aligned(4)));      // a 128-bit store at any 4-byte boundary
+
+constexpr int kUnpackThreads = 256;
+constexpr int kChunk = 8;
+constexpr int kTagI16 = 0, kTagF32 = 1;                 // the dtype tag of the C ABI
+
+// A row whose description is outside the contract is written as zeros: nothing is ever read outside [0, packed_elems).  The host
+// wrapper rejects such descriptions before the launch (ops.wave_unpack); this is the second line.
+template <bool I16>
+__global__ __launch_bounds__(kUnpackThreads) void wave_unpack_kernel(const void* __restrict__ packed, long long packed_elems,
+                                                                     const int* __restrict__ offsets, const int* __restrict__ lengths,
+                                                                     const int* __restrict__ src_index, int B, int n_max,
+                                                                     float* __restrict__ out, long long ld_out) {
+  const int b = blockIdx.y;
+  const int j0 = (blockIdx.x * kUnpackThreads + threadIdx.x) * kChunk;
+  if (j0 >= n_max) return;
+  const int src = src_index[b];
+  int off = 0, len = 0;
+  if (src >= 0 && src < B) {
+    off = offsets[src], len = lengths[src];
+    const long long end = (long long)off + (((long long)len + kChunk - 1) & ~(long long)(kChunk - 1));
+    if (off < 0 || (off & (kChunk - 1)) || len < 0 || end > packed_elems) len = 0;
+    len = min(len, n_max);
+  }
+  float v[kChunk];
+#pragma unroll
+  for (int i = 0; i < kChunk; ++i) v[i] = 0.0f;
+  if (j0 < len) {                                      // the whole chunk lies inside the buffer (gaps up to the next multiple of 8 exist)
+    if constexpr (I16) {
+      const i16x8 s = *reinterpret_cast<const i16x8*>(static_cast<const short*>(packed) + off + j0);
+#pragma unroll
+      for (int i = 0; i < kChunk; ++i) v[i] = (j0 + i < len) ? (float)s[i] * 0x1p-15f : 0.0f;
+    } else {
+      const f32x4* p = reinterpret_cast<const f32x4*>(static_cast<const float*>(packed) + off + j0);
+      const f32x4 lo = p[0], hi = p[1];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        v[i] = (j0 + i < len) ? lo[i] : 0.0f;
+        v[4 + i] = (j0 + 4 + i < len) ? hi[i] : 0.0f;
+      }
+    }
+  }
+  float* y = out + (long long)b * ld_out + j0;
+  if (j0 + kChunk <= n_max) {
+    f32x4_u a, c;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) a[i] = v[i], c[i] = v[4 + i];
+    *reinterpret_cast<f32x4_u*>(y) = a;
+    *reinterpret_cast<f32x4_u*>(y + 4) = c;
+  } else {
+#pragma unroll
+    for (int i = 0; i < kChunk; ++i)
+      if (j0 + i < n_max) y[i] = v[i];
+  }
+}
+
+}  // namespace
+
+extern "C" int ds2_wave_unpack_f32(const void* packed, long long packed_elems, int dtype, const int* offsets_dev, const int* lengths_dev,
+                                   const int* src_index_dev, int B, int n_max, float* out, long long ld_out, void* stream) {
+  DS2_REQUIRE(offsets_dev && lengths_dev && src_index_dev && out, "ds2_wave_unpack_f32: null pointer");
+  DS2_REQUIRE(dtype == kTagI16 || dtype == kTagF32, "ds2_wave_unpack_f32: dtype tag %d (0 = int16, 1 = fp32)", dtype);
+  DS2_REQUIRE(B > 0 && B <= 65535 && n_max >= 0 && n_max <= (1 << 30) && ld_out >= n_max, "ds2_wave_unpack_f32: bad dims (B=%d n_max=%d ld_out=%lld)", B, n_max, ld_out);
+  DS2_REQUIRE(packed_elems >= 0 && packed_elems <= 0x7fffffffLL && packed_elems % kChunk == 0,
+              "ds2_wave_unpack_f32: packed_elems = %lld: a multiple of 8 in [0, 2^31)", packed_elems);
+  DS2_REQUIRE(packed || packed_elems == 0, "ds2_wave_unpack_f32: null packed buffer of %lld elements", packed_elems);
+  DS2_REQUIRE(((uintptr_t)packed & 15) == 0 && ((uintptr_t)out & 3) == 0, "ds2_wave_unpack_f32: packed must be 16-byte aligned, out 4-byte aligned");
+  if (n_max == 0) return 0;
+  const dim3 grid((unsigned)ceil_div(ceil_div(n_max, kChunk), kUnpackThreads), (unsigned)B);
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == kTagI16)
+    hipLaunchKernelGGL(wave_unpack_kernel<true>, grid, dim3(kUnpackThreads), 0, s, packed, packed_elems, offsets_dev, lengths_dev, src_index_dev,
+                       B, n_max, out, ld_out);
+  else
+    hipLaunchKernelGGL(wave_unpack_kernel<false>, grid, dim3(kUnpackThreads), 0, s, packed, packed_elems, offsets_dev, lengths_dev, src_index_dev,
+                       B, n_max, out, ld_out);
+  DS2_LAUNCH_CHECK("wave_unpack_kernel");
+  return 0;
+}

@@ -40,18 +40,34 @@ def _stft_spectrogram(y: np.ndarray, sample_rate: int, window_size: float, windo
     return np.log1p(spect)
 
 
-def _read_wav(path):
-    """(sample_rate, mono float32 waveform) of a WAV file, scaled like soundfile (audio/functional.py:11): integer PCM / 2^(bits-1),
-    8-bit unsigned PCM centred on 128; channels averaged."""
-    from scipy.io import wavfile
-    sr, y = wavfile.read(path)
+def _mono_float32(y):
+    """wavfile.read's samples -> mono float32, scaled like soundfile (audio/functional.py:11): integer PCM / 2^(bits-1), 8-bit unsigned PCM
+    centred on 128; channels averaged."""
     if y.dtype.kind == "i":
         y = y.astype(np.float32) / float(2 ** (8 * y.dtype.itemsize - 1))
     elif y.dtype.kind == "u":
         y = (y.astype(np.float32) - 128.0) / 128.0
     if y.ndim > 1:
         y = y.mean(axis=1)
-    return sr, y.astype(np.float32, copy=False)
+    return y.astype(np.float32, copy=False)
+
+
+def _read_wav(path):
+    """(sample_rate, mono float32 waveform) of a WAV file, scaled like soundfile (audio/functional.py:11): integer PCM / 2^(bits-1),
+    8-bit unsigned PCM centred on 128; channels averaged."""
+    from scipy.io import wavfile
+    sr, y = wavfile.read(path)
+    return sr, _mono_float32(y)
+
+
+def _read_wav_raw(path):
+    """(sample_rate, samples) for the packed feed: the int16 samples themselves when the file is 16-bit mono PCM (the GPU scales them by
+    2^-15, which is exact), else `_read_wav`'s float32 waveform (8 / 24 / 32-bit, float and multi-channel files)."""
+    from scipy.io import wavfile
+    sr, y = wavfile.read(path)
+    if y.dtype == np.int16 and y.ndim == 1:
+        return sr, y
+    return sr, _mono_float32(y)
 
 
 def noise_levels_of(audio_conf):
@@ -245,19 +261,29 @@ class GpuSpectrogramFrontEnd:
             self.seed = None if seed is None else int(seed)
             self.rng = np.random.default_rng(self.seed)
 
+    def _dev(self):
+        from ..device import resolve_device
+        return torch.device(self.device) if self.device is not None else resolve_device("auto")
+
     def __call__(self, waves, perturb=None):
         """`perturb`: an already drawn (tempo, gain dB) pair of arrays for this batch (GpuAudioDataLoader draws before it sorts); None draws
         here when the perturbation is on."""
-        from .. import ops
-        from ..device import resolve_device
-        dev = torch.device(self.device) if self.device is not None else resolve_device("auto")
         n = [int(len(w)) for w in waves]
         batch = torch.zeros(len(waves), max(n), dtype=torch.float32)
         for i, w in enumerate(waves):
             batch[i, :n[i]] = torch.as_tensor(w, dtype=torch.float32)
+        return self.from_device_batch(batch.to(self._dev()), n, perturb=perturb)
+
+    def from_device_batch(self, batch, n, perturb=None):
+        """The same front-end on a batch that is on the device already: `batch` (B, >= max(n)) fp32, zeros beyond each utterance's
+        n[b] samples (what ops.wave_unpack makes), `n` (B) host integers; `perturb` as in `__call__`.  Every draw is made here, in
+        `__call__`'s order."""
+        from .. import ops
+        dev = batch.device
+        n = [int(v) for v in n]
         if self.perturb:
-            tempo, gain = perturb if perturb is not None else self.draw_perturbation(len(waves))
-            batch, _, _ = ops.tempo_gain(batch.to(dev), n, tempo, gain, self.sample_rate)
+            tempo, gain = perturb if perturb is not None else self.draw_perturbation(len(n))
+            batch, _, _ = ops.tempo_gain(batch, n, tempo, gain, self.sample_rate)
             n = self.perturbed_lengths(n, tempo)
         elif perturb is not None:
             raise ValueError("perturb= given, but this front-end does not perturb (augment, speed_volume_perturb and audio_conf.speed_volume_perturb)")
@@ -267,11 +293,11 @@ class GpuSpectrogramFrontEnd:
             if self.noise is not None:
                 nz = dict(noise=self.noise.device_samples(dev), noise_base=p["base"], noise_period=p["period"], noise_start=p["start"],
                           noise_level=p["level"])
-            spect, frames = ops.spectrogram_augmented(batch.to(dev), torch.tensor(n), self.n_fft, self.hop, self.window, self.pad_mode,
+            spect, frames = ops.spectrogram_augmented(batch, torch.tensor(n), self.n_fft, self.hop, self.window, self.pad_mode,
                                                       self.normalize, freq_masks=p["freq"] if self.spec_augment else None,
                                                       time_masks=p["time"] if self.spec_augment else None, **nz)
         else:
-            spect, frames = ops.spectrogram(batch.to(dev), torch.tensor(n), self.n_fft, self.hop, self.window, self.pad_mode, self.normalize)
+            spect, frames = ops.spectrogram(batch, torch.tensor(n), self.n_fft, self.hop, self.window, self.pad_mode, self.normalize)
         return spect, frames.float() / float(spect.size(3))
 
     def draw_perturbation(self, B):
@@ -356,7 +382,7 @@ class WaveformDataset(Dataset):
             labels = dict([(v, k) for k, v in pd.read_csv(labels).to_dict()["label"].items()])
         self.labels_map = labels
         self.audio_conf, self.caching = audio_conf, caching
-        self._cache = {}
+        self._cache, self._raw_cache = {}, {}
         for f in self.df.audio_filepath:
             if str(f).endswith((".npy", ".pt")):
                 raise ValueError(f"front_end='gpu' reads waveforms, but the manifest lists a pre-computed spectrogram: {f} "
@@ -385,49 +411,275 @@ class WaveformDataset(Dataset):
     def __len__(self):
         return self.size
 
+    def parse_audio_raw(self, path):
+        """`parse_audio` for the packed feed: a numpy array, int16 for a 16-bit mono file (its raw samples), float32 otherwise."""
+        sr, y = _read_wav_raw(path)
+        if sr != self.audio_conf.sample_rate:
+            raise ValueError(f"{path}: {sr} Hz, expected {self.audio_conf.sample_rate} Hz audio")
+        return np.ascontiguousarray(y)
+
+    def get_raw(self, index):
+        """Item `index` as `(parse_audio_raw's array, transcript ids)`; `caching=True` keeps these arrays (a cache of their own)."""
+        if self.caching and index in self._raw_cache:
+            return self._raw_cache[index]
+        row = self.df.iloc[index]
+        item = (self.parse_audio_raw(row.audio_filepath), self.parse_transcript(row.text))
+        if self.caching:
+            self._raw_cache[index] = item
+        return item
+
+    def raw_items(self):
+        """A Dataset over the same manifest whose items are `get_raw`'s: what the workers of the packed feed read."""
+        return _RawWaveforms(self)
+
+
+class _RawWaveforms(Dataset):
+    def __init__(self, dataset):
+        self.dataset = dataset
+
+    def __getitem__(self, index):
+        return self.dataset.get_raw(index)
+
+    def __len__(self):
+        return len(self.dataset)
+
 
 def _waveform_batch(batch):
     return batch
+
+
+WAVE_ALIGN = 8                     # every utterance of a packed batch starts at a multiple of 8 elements: 128-bit loads on the device
+WAVE_MAX_ELEMS = 2 ** 31 - 1       # offsets are int64 on the host and int32 on the device
+
+
+def packed_layout(lengths, limit=WAVE_MAX_ELEMS):
+    """(offsets (B,) int64, total) of a packed batch: utterance b occupies [offsets[b], offsets[b] + lengths[b]), every offset a multiple
+    of WAVE_ALIGN elements, total = the 8-aligned end of the last one.  ValueError when the total does not fit the device's int32."""
+    lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    if (lengths < 0).any():
+        raise ValueError(f"packed_layout: negative length in {lengths.tolist()}")
+    padded = (lengths + WAVE_ALIGN - 1) // WAVE_ALIGN * WAVE_ALIGN
+    ends = np.cumsum(padded)
+    total = int(ends[-1]) if len(ends) else 0
+    if total > limit:
+        raise ValueError(f"a packed batch of {total} elements does not fit int32 device offsets (at most {limit}): use a smaller batch")
+    return (ends - padded).astype(np.int64), total
+
+
+def pack_waveforms(batch):
+    """Worker-side collate_fn of the packed feed (a pure host function): a list of `(samples, transcript)` items, samples a 1-D int16 or
+    float32 array, -> `(buffer, offsets, lengths, transcripts)`: ONE ragged 1-D tensor per batch, laid out by `packed_layout` (gaps are
+    zero), int16 when EVERY item is int16 (raw 16-bit mono PCM), else float32 with the int16 items scaled like `_read_wav` does
+    (/ 32768) — so both buffers unpack to the bits of the per-item float32 path; offsets, lengths: (B,) int64 numpy arrays."""
+    waves = [np.asarray(w) for w, _ in batch]
+    for w in waves:
+        if w.ndim != 1 or w.dtype not in (np.int16, np.float32):
+            raise ValueError(f"pack_waveforms: expected 1-D int16 or float32 samples, got {w.dtype} with shape {w.shape}")
+    dtype = np.int16 if all(w.dtype == np.int16 for w in waves) else np.float32
+    lengths = np.array([len(w) for w in waves], dtype=np.int64)
+    offsets, total = packed_layout(lengths)
+    buf = np.zeros(total, dtype=dtype)
+    for w, o in zip(waves, offsets.tolist()):
+        buf[o:o + len(w)] = w if w.dtype == dtype else w.astype(np.float32) / 32768.0
+    return torch.from_numpy(buf), offsets, lengths, [t for _, t in batch]
+
+
+class _FeedEnd:
+    """Last item of a feeder's queue: the epoch is over (exc None) or the feeder / a worker failed (exc is raised in the consumer)."""
+
+    def __init__(self, exc=None):
+        self.exc = exc
+
+
+def _feed_batches(batches, device, depth, put, stop):
+    torch.cuda.set_device(device)
+    stream = torch.cuda.Stream(device)
+    ring = [None] * (depth + 1)                         # [pinned uint8 buffer, event of the last copy out of it]
+    k = 0
+    while not stop.is_set():
+        try:
+            buf, offsets, lengths, transcripts = next(batches)
+        except StopIteration:
+            return
+        nbytes = buf.numel() * buf.element_size()
+        slot = ring[k % len(ring)]
+        if slot is not None:
+            slot[1].synchronize()
+        if slot is None or slot[0].numel() < nbytes:
+            slot = ring[k % len(ring)] = [torch.empty(max(nbytes, 16), dtype=torch.uint8, pin_memory=True), None]
+        host = slot[0][:nbytes].view(buf.dtype)
+        host.copy_(buf)
+        copied = torch.cuda.Event()
+        with torch.cuda.stream(stream):
+            dev = torch.empty(buf.numel(), dtype=buf.dtype, device=device)
+            dev.copy_(host, non_blocking=True)
+            copied.record(stream)
+        slot[1] = copied
+        if not put((dev, copied, offsets, lengths, transcripts)):
+            return
+        del buf, dev
+        k += 1
+
+
+def _feed(batches, device, depth, out, stop):
+    """Body of the feeder thread: packed host batches -> a ring of depth + 1 pinned buffers (grown on demand, a slot reused only after
+    its copy event) -> asynchronous copies on a copy stream of its own -> `out`, a queue of (device buffer, copy event, offsets, lengths,
+    transcripts).  No random draw and no kernel here: only host copies and host-to-device copies."""
+    import queue
+    import traceback
+
+    def put(item):
+        while not stop.is_set():
+            try:
+                out.put(item, timeout=0.1)
+                return True
+            except queue.Full:
+                pass
+        return False
+    try:
+        _feed_batches(batches, device, depth, put, stop)
+        put(_FeedEnd())
+    except BaseException as e:                          # noqa: BLE001 — a worker's or this thread's failure is the consumer's to raise
+        # the frames below hold pinned and device buffers, events and the DataLoader iterator: an exception that outlives this thread must
+        # not keep them alive (garbage with GPU resources that a later fork hands to worker processes, which must never free it)
+        traceback.clear_frames(e.__traceback__)
+        put(_FeedEnd(e))
+    finally:
+        batches = None                                  # the DataLoader iterator goes here: its workers are shut down
+
+
+class _WaveformFeeder:
+    """One background thread per iterator of a prefetching GpuAudioDataLoader (`_feed`), and the consumer's end of its queue."""
+
+    def __init__(self, batches, device, depth):
+        import queue
+        import threading
+        self.queue, self.stop = queue.Queue(maxsize=depth), threading.Event()
+        self.thread = threading.Thread(target=_feed, args=(batches, device, depth, self.queue, self.stop), name="asr_amd-waveform-feeder",
+                                       daemon=True)
+        self.thread.start()
+
+    def get(self):
+        """The next queued batch, None at the end of the epoch; raises what the feeder or a worker raised, or RuntimeError when the thread
+        is gone without a word."""
+        import queue
+        while True:
+            try:
+                item = self.queue.get(timeout=0.2)
+            except queue.Empty:
+                if not self.thread.is_alive() and self.queue.empty():
+                    raise RuntimeError("asr_amd.data: the waveform feeder thread ended without finishing the epoch")
+                continue
+            if isinstance(item, _FeedEnd):
+                exc, item = item.exc, None
+                if exc is not None:
+                    try:
+                        raise exc
+                    finally:
+                        exc = None                      # (no cycle exception -> traceback -> this frame -> exception)
+                return None
+            return item
+
+    def close(self):
+        import queue
+        self.stop.set()
+        while self.thread.is_alive():
+            try:
+                self.queue.get_nowait()
+            except queue.Empty:
+                pass
+            self.thread.join(0.05)
 
 
 class GpuAudioDataLoader:
     """Iterates a DataLoader of (waveform, transcript) items and turns each batch into the `_collate_fn` 4-tuple in the MAIN process:
     `(inputs (B,1,161,T) on the GPU, targets, input_percentages, target_sizes)`.  Items are sorted like _collate_fn (frame count 1 + n // hop,
     descending, stable), then GpuSpectrogramFrontEnd makes the spectrograms (and draws the augmentation, in that sorted order).  With a
-    perturbing front-end the tempo / gain draws come first, in arrival order, and n is the perturbed length floor(n / tempo + 0.5)."""
+    perturbing front-end the tempo / gain draws come first, in arrival order, and n is the perturbed length floor(n / tempo + 0.5).
 
-    def __init__(self, dataset, batch_sampler, num_workers, front_end):
-        self.dataset, self.batch_sampler, self.front_end = dataset, batch_sampler, front_end
-        self.loader = DataLoader(dataset, num_workers=num_workers, batch_sampler=batch_sampler, collate_fn=_waveform_batch)
+    `prefetch=N >= 1` is the pipelined feed, batch for batch bit-identical to `prefetch=0`: the workers pack every batch into ONE ragged
+    buffer (`pack_waveforms`: raw int16 PCM when every file is 16-bit mono), a feeder thread per iterator copies it through a ring of
+    N + 1 pinned buffers to the device on a copy stream of its own, up to N batches ahead, and the consumer — `next()`, on the caller's
+    current stream — makes ALL the draws, waits for the copy event, unpacks (ops.wave_unpack: scale, sort, zero padding) and runs the same
+    front-end kernels, in order between the train steps; only host work and the host-to-device copy overlap a step."""
+
+    def __init__(self, dataset, batch_sampler, num_workers, front_end, prefetch=0):
+        self.dataset, self.batch_sampler, self.front_end, self.prefetch = dataset, batch_sampler, front_end, int(prefetch)
+        if self.prefetch:
+            self.loader = DataLoader(dataset.raw_items(), num_workers=num_workers, batch_sampler=batch_sampler, collate_fn=pack_waveforms)
+        else:
+            self.loader = DataLoader(dataset, num_workers=num_workers, batch_sampler=batch_sampler, collate_fn=_waveform_batch)
 
     def __len__(self):
         return len(self.loader)
 
-    def collate(self, batch):
+    def _sort(self, lengths):
+        """The draws that precede the front-end's and the batch order: (order, lengths in that order — perturbed ones with a perturbing
+        front-end —, perturb)."""
         hop = self.front_end.hop
-        lengths, perturb = [len(w) for w, _ in batch], None
+        perturb = None
         if self.front_end.perturb:                       # drawn in arrival order; the batch is then sorted by its PERTURBED lengths
-            tempo, gain = self.front_end.draw_perturbation(len(batch))
+            tempo, gain = self.front_end.draw_perturbation(len(lengths))
             lengths = self.front_end.perturbed_lengths(lengths, tempo)
         frames = [1 + n // hop if n > 0 else 0 for n in lengths]
-        order = sorted(range(len(batch)), key=lambda i: frames[i], reverse=True)
-        batch, lengths = [batch[i] for i in order], [lengths[i] for i in order]
+        order = sorted(range(len(lengths)), key=lambda i: frames[i], reverse=True)
         if self.front_end.perturb:
             perturb = (tempo[order], gain[order])
-        inputs, _ = self.front_end([w for w, _ in batch], perturb=perturb)
-        max_len = inputs.size(3)
-        input_percentages = torch.zeros(len(batch), dtype=torch.float32)
-        target_sizes = torch.zeros(len(batch), dtype=torch.int32)
+        return order, [lengths[i] for i in order], perturb
+
+    def _batch(self, inputs, lengths, transcripts):
+        hop, max_len = self.front_end.hop, inputs.size(3)
+        input_percentages = torch.zeros(len(lengths), dtype=torch.float32)
+        target_sizes = torch.zeros(len(lengths), dtype=torch.int32)
         targets = []
-        for i, (w, target) in enumerate(batch):
+        for i, target in enumerate(transcripts):
             input_percentages[i] = min(1 + lengths[i] // hop, max_len) / float(max_len)
             target_sizes[i] = len(target)
             targets.extend(target)
         return inputs, torch.tensor(targets, dtype=torch.int32), input_percentages, target_sizes
 
+    def collate(self, batch):
+        order, lengths, perturb = self._sort([len(w) for w, _ in batch])
+        batch = [batch[i] for i in order]
+        inputs, _ = self.front_end([w for w, _ in batch], perturb=perturb)
+        return self._batch(inputs, lengths, [t for _, t in batch])
+
+    def collate_packed(self, packed, offsets, lengths, transcripts):
+        """`collate` for a packed batch whose buffer is on the device: the same draws in the same order, the sort as the unpack
+        kernel's row index."""
+        from .. import ops
+        raw = [int(v) for v in lengths]
+        order, lengths, perturb = self._sort(raw)
+        n_in = [raw[i] for i in order]
+        waves = ops.wave_unpack(packed, offsets, raw, order, max(n_in))
+        inputs, _ = self.front_end.from_device_batch(waves, n_in, perturb=perturb)
+        return self._batch(inputs, lengths, [transcripts[i] for i in order])
+
     def __iter__(self):
-        for batch in self.loader:
-            yield self.collate(batch)
+        if not self.prefetch:
+            for batch in self.loader:
+                yield self.collate(batch)
+            return
+        dev = self.front_end._dev()
+        if dev.type != "cuda":
+            raise RuntimeError(f"prefetch={self.prefetch} needs the GPU front-end's device, got {dev}")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())          # the feeder thread sets it: threads do not inherit it
+        feeder = _WaveformFeeder(iter(self.loader), dev, self.prefetch)       # (the workers start here, in the caller's thread)
+        try:
+            while True:
+                item = feeder.get()
+                if item is None:
+                    return
+                packed, copied, offsets, lengths, transcripts = item
+                stream = torch.cuda.current_stream(dev)
+                stream.wait_event(copied)
+                out = self.collate_packed(packed, offsets, lengths, transcripts)
+                packed.record_stream(stream)             # allocated on the copy stream, read by the unpack kernel on this one
+                del item, packed
+                yield out
+        finally:
+            feeder.close()
 
 
 def _durations_of(data_source, durations=None):
@@ -641,7 +893,7 @@ class AudioDataLoader(DataLoader):
 
 
 def get_loader(audio_conf, labels, manifest, batch_size, num_workers, caching=False, length_bucketing=False, front_end="host",
-               perturb=False):
+               perturb=False, prefetch=0):
     """data/loaders/functional.py:6-24.  `length_bucketing=True` (not in the reference) sorts the manifest by its `duration` column
     before binning (LengthBucketingSampler; the distributed variant when torch.distributed is initialised).
 
@@ -652,15 +904,26 @@ def get_loader(audio_conf, labels, manifest, batch_size, num_workers, caching=Fa
     same 4-tuple, `inputs` already on the GPU.  With caching=True the waveforms are cached and the augmentation is redrawn every epoch.
     `perturb=True` (front_end="gpu" only) also applies audio_conf.speed_volume_perturb there: tempo ~ U(0.85, 1.15) and gain ~ U(-6, 8) dB per
     utterance, first of all, the batch sorted by its perturbed lengths (ops.tempo_gain; modelled on sox's effects, parity with sox unpinned).
-    With the default perturb=False the switch is ignored with a warning, as on the host path."""
+    With the default perturb=False the switch is ignored with a warning, as on the host path.
+    `prefetch=N` (front_end="gpu" only; an integer >= 0, default 0 = the synchronous loader): the pipelined feed.  The workers return
+    one packed buffer per batch (raw int16 for 16-bit mono files, float32 otherwise), a feeder thread stages it in pinned memory and
+    copies it to the GPU on a copy stream up to N batches ahead of the consumer, and `next()` unpacks it on the GPU (ops.wave_unpack)
+    and runs the same front-end kernels on the caller's stream.  Every batch is bit-identical to the `prefetch=0` batch for the same
+    seeds; the sampler's draws from numpy's global state are made up to N batches early, so code that draws from that state inside the
+    loop sees them interleaved differently.  Leaving the loop early stops the thread and the workers; a worker's error is raised by
+    `next()`."""
     if front_end not in ("host", "gpu"):
         raise ValueError(f"front_end={front_end!r}: expected host or gpu")
     if perturb and front_end != "gpu":
         raise ValueError("perturb=True needs front_end='gpu' (the host front-end has no tempo / gain perturbation)")
+    if isinstance(prefetch, bool) or not isinstance(prefetch, (int, np.integer)) or prefetch < 0:
+        raise ValueError(f"prefetch={prefetch!r}: expected an integer >= 0 (batches staged ahead of the consumer)")
+    if prefetch and front_end != "gpu":
+        raise ValueError("prefetch needs front_end='gpu' (the host front-end's batches are made in the workers already)")
     if front_end == "gpu":
         dataset = WaveformDataset(audio_conf=audio_conf, manifest_filepath=manifest, labels=labels, caching=caching, perturb=perturb)
         fe = GpuSpectrogramFrontEnd(audio_conf, normalize=True, augment=True, speed_volume_perturb=perturb)
-        make = lambda sampler: GpuAudioDataLoader(dataset, sampler, num_workers, fe)      # noqa: E731
+        make = lambda sampler: GpuAudioDataLoader(dataset, sampler, num_workers, fe, prefetch=int(prefetch))      # noqa: E731
     else:
         dataset = SpectrogramDataset(audio_conf=audio_conf, manifest_filepath=manifest, labels=labels, normalize=True,
                                      spec_augment=getattr(audio_conf, "spec_augment", False), caching=caching)

@@ -1485,6 +1485,51 @@ def tempo_gain(audio: Tensor, n_samples, tempo, gain, sample_rate: int, segment_
     return out, n_out_dev, offsets
 
 
+WAVE_ALIGN = 8                     # every utterance of a packed waveform buffer starts at a multiple of this many ELEMENTS
+WAVE_MAX_ELEMS = 2 ** 31 - 1       # device offsets are int32
+
+
+def wave_unpack(packed: Tensor, offsets, lengths, src_index=None, n_max: Optional[int] = None) -> Tensor:
+    """A packed ragged waveform buffer -> the zero-padded (B, n_max) fp32 batch of the front-end (ds2_wave_unpack_f32, contract in
+    include/ds2hip.h).  packed: 1-D int16 (raw PCM, scaled by 2^-15: exact) or fp32 GPU tensor, a multiple of 8 elements long; offsets,
+    lengths, src_index: (B) HOST integers — utterance u is packed[offsets[u] : offsets[u] + lengths[u]], row b of the result is utterance
+    src_index[b] (default: b); n_max defaults to max(lengths).  The description is checked here, on the host (ValueError: an offset that
+    is negative or not a multiple of 8, a length below 0 or above n_max, an utterance whose 8-aligned end passes the buffer, an index outside
+    [0, B)), then uploaded from pinned memory with one asynchronous copy: the call does not block the host."""
+    import numpy as np
+    if packed.dtype not in (torch.int16, torch.float32) or not packed.is_cuda or packed.dim() != 1 or not packed.is_contiguous():
+        raise ValueError("wave_unpack: packed must be a contiguous 1-D int16 or fp32 GPU tensor")
+    off = np.asarray(offsets.tolist() if isinstance(offsets, Tensor) else offsets, dtype=np.int64).reshape(-1)
+    ln = np.asarray(lengths.tolist() if isinstance(lengths, Tensor) else lengths, dtype=np.int64).reshape(-1)
+    B, total = int(ln.size), int(packed.numel())
+    src = np.arange(B, dtype=np.int64) if src_index is None else np.asarray(
+        src_index.tolist() if isinstance(src_index, Tensor) else src_index, dtype=np.int64).reshape(-1)
+    if B == 0 or off.size != B or src.size != B:
+        raise ValueError(f"wave_unpack: offsets ({off.size}), lengths ({B}) and src_index ({src.size}): one value per utterance, at least one")
+    if n_max is None:
+        n_max = int(ln.max())
+    n_max = int(n_max)
+    if total % WAVE_ALIGN or total > WAVE_MAX_ELEMS:
+        raise ValueError(f"wave_unpack: packed holds {total} elements: a multiple of {WAVE_ALIGN}, at most 2^31 - 1")
+    if (off < 0).any() or (off % WAVE_ALIGN).any():
+        raise ValueError(f"wave_unpack: every offset is a non-negative multiple of {WAVE_ALIGN} elements, got {off.tolist()}")
+    if (ln < 0).any() or (ln > n_max).any():
+        raise ValueError(f"wave_unpack: lengths lie in [0, n_max = {n_max}], got {ln.tolist()}")
+    if (off + (ln + WAVE_ALIGN - 1) // WAVE_ALIGN * WAVE_ALIGN > total).any():
+        raise ValueError(f"wave_unpack: an utterance (rounded up to {WAVE_ALIGN} elements) ends beyond the {total} packed elements")
+    if (src < 0).any() or (src >= B).any():
+        raise ValueError(f"wave_unpack: src_index outside [0, {B})")
+    dev = packed.device
+    if n_max == 0:
+        return torch.zeros((B, 0), dtype=torch.float32, device=dev)
+    meta = torch.from_numpy(np.stack([off, ln, src]).astype(np.int32)).pin_memory().to(dev, non_blocking=True)
+    out = torch.empty((B, n_max), dtype=torch.float32, device=dev)
+    _lib.check(_lib.load().ds2_wave_unpack_f32(packed.data_ptr() if total else None, total, 0 if packed.dtype == torch.int16 else 1,
+                                               meta[0].data_ptr(), meta[1].data_ptr(), meta[2].data_ptr(), B, n_max, out.data_ptr(),
+                                               out.stride(0), _stream()), "ds2_wave_unpack_f32")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 # optimizer
 # ------------------------------------------------------------------------------------------------

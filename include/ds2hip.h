@@ -550,6 +550,27 @@ int ds2_tempo_gain_f32(const float* audio, long long ld_audio, const int* n_samp
                        int sample_rate, double segment_ms, double search_ms, double overlap_ms, float* out, long long ld_out,
                        int* n_out_dev, int* offsets_out, int ld_offsets, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- packed waveform feed (asr_amd.data, get_loader(front_end="gpu", prefetch=N)) ------------------------------
+ * The host side of the waveform loader (data/loaders/functional.py:6-24 + the per-item parse_audio, spectrogram_parser.py:36-44) sends
+ * ONE ragged buffer per batch; this pass makes the zero-padded (B, n_max) fp32 batch that ds2_tempo_gain_f32 / ds2_spectrogram_f32 /
+ * ds2_spectrogram_aug_f32 read, in place of B host slice copies into a pageable fp32 tensor.
+ *  packed (packed_elems) device elements of the type `dtype` tags: 0 = int16 (raw 16-bit PCM), 1 = fp32; 16-byte aligned;
+ *  packed_elems a multiple of 8, below 2^31 (0 allowed, packed may then be NULL).
+ *  Utterance u occupies [offsets[u], offsets[u] + lengths[u]); ALIGNMENT RULE: every offset is a multiple of 8 ELEMENTS and
+ *  offsets[u] + round_up(lengths[u], 8) <= packed_elems, so the elements up to the next multiple of 8 exist (their values are not used).
+ *  lengths[u] == 0 is allowed (the row is all zeros).  offsets_dev, lengths_dev, src_index_dev: (B) int32 DEVICE arrays.
+ *  out (B, ld_out) fp32 device, ld_out >= n_max, any 4-byte-aligned pitch: row b is utterance u = src_index[b] (any index in [0, B),
+ *  repeats allowed): out[b][j] = x_u[j] for j < lengths[u], exact 0 for lengths[u] <= j < n_max; columns n_max .. ld_out are not
+ *  written.  int16 samples are scaled by 2^-15, which is exact: the bits of numpy's `astype(float32) / 32768`; fp32 is copied.
+ *  Rejected (non-zero, nothing launched): null pointers, another dtype tag, B outside [1, 65535], n_max outside [0, 2^30],
+ *  ld_out < n_max, packed_elems negative / not a multiple of 8 / >= 2^31, a misaligned packed or out.  n_max == 0 launches nothing.
+ *  The per-utterance arrays live on the device, so the CALLER checks them (asr_amd.ops.wave_unpack does, on the host values it uploads);
+ *  the kernel re-checks each row it is given — src_index in range, offset >= 0 and a multiple of 8, length in [0, n_max], the rounded-up
+ *  end inside packed_elems — and writes a row that fails as zeros: nothing outside the two buffers is read or written.
+ *  One kernel (wave_unpack_kernel, csrc/stft.hip), one pass: a 128-bit load per 8 int16 samples (two per 8 fp32), two 128-bit stores; no atomics. */
+int ds2_wave_unpack_f32(const void* packed, long long packed_elems, int dtype, const int* offsets_dev, const int* lengths_dev,
+                        const int* src_index_dev, int B, int n_max, float* out, long long ld_out, void* stream);
+
 /* ---- optimizer ----------------------------------------------------------------------------------
  * torch.optim.AdamW.step over one flat parameter buffer, trainers/__main__.py:41-47. */
 int ds2_adamw_f32(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps,
