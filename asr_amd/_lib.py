@@ -100,6 +100,7 @@ SIGNATURES = {
     "ds2_conv2_wgrad_nhwc_bf16": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, sz, vp]),
     "ds2_rnn_packed_bytes": (sz, [i32, i32, i32, i32]),
     "ds2_rnn_pack_whh": (i32, [i32, vp, vp, vp, i32, i32, vp]),
+    "ds2_weight_prep_bf16": (i32, [vp, i32, vp]),
     "ds2_rnn_fwd_workspace_bytes": (sz, [i32, i32, i32]),
     "ds2_rnn_fwd_ex": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
     "ds2_rnn_fwd": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, sz, vp]),
@@ -111,6 +112,7 @@ SIGNATURES = {
     "ds2_rnn_bwd": (i32, [vp, i32, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
     "ds2_ctc_workspace_bytes": (sz, [i32, i32, i32]),
     "ds2_ctc_loss_f32": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, i32, f32, vp, sz, vp]),
+    "ds2_ctc_loss_ex_f32": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, i32, f32, i32, vp, sz, vp]),
     "ds2_ctc_batch_mean_f32": (i32, [vp, i32, vp, vp]),
     "ds2_add_i64": (i32, [vp, i32, i64, vp]),
     "ds2_softmax_rows_f32": (i32, [vp, i32, vp, i32, i32, i32, vp]),
@@ -156,6 +158,12 @@ SIGNATURES = {
 class TnProblem(C.Structure):
     """`ds2_tn_problem` of include/ds2hip.h (one product of ds2_gemm_bf16_tn_group)."""
     _fields_ = [("A", vp), ("B", vp), ("C", vp), ("M", i32), ("N", i32), ("K", i32), ("lda", i32), ("ldb", i32), ("ldc", i32)]
+
+
+class PrepLayer(C.Structure):
+    """`ds2_prep_layer` of include/ds2hip.h (one layer of ds2_weight_prep_bf16)."""
+    _fields_ = [("whh", vp), ("wp_fwd", vp), ("wp_bwd", vp), ("wih", vp), ("wih_t", vp), ("wih_r", vp),
+                ("gates", i32), ("H", i32), ("R", i32), ("Cc", i32), ("ld_wih", i32), ("ld_t", i32), ("ld_r", i32), ("reserved", i32)]
 
 
 class DS2LibraryError(RuntimeError):

@@ -8,9 +8,10 @@
 //          grad[t,b,c] = scale * (softmax(logits)[t,b,c] - occupancy[t,b,c]) for t < T_b, else 0
 //          (= d(sum_b nll_b)/d logits * scale; rows of an infeasible utterance get 0)
 //
-// Kernels: (1) one wavefront per (t,b) row: max/sum shuffles -> lse.  (2) one workgroup per
-// (utterance, direction): the 2U+1 lattice row lives in LDS, one barrier per frame, emission
-// gathers prefetched 4 frames ahead.  (3) occupancy + gradient, deterministic (no float atomics):
+// Kernels: (1) one wavefront per (t,b) row: max/sum shuffles -> lse.  (2) the lattices: 2U+1 <= 128 for the
+// whole batch: one WAVEFRONT per (utterance, direction), the row in registers (ctc_lattice_wave_kernel);
+// longer targets: one workgroup per (utterance, direction), the row in LDS, one barrier per frame, emission
+// gathers prefetched 4 frames ahead (ctc_lattice_kernel).  (3) occupancy + gradient, deterministic (no float atomics):
 // repeated labels are summed by the thread owning the first occurrence walking a next-same chain.
 #include "common.h"
 #include <math.h>
@@ -23,8 +24,8 @@ constexpr float NEG_INF = -INFINITY;
 // the sum lies in [1, 3], so the only extra error over libm's expf / logf is the fp32 scaling of the argument (|x| 2^-24 in the
 // exponent: < 5e-6 relative, and only on terms that are themselves < e^-80 of the sum).  The lattice is ONE dependent lse3 per frame per
 // lane: with libm's range-reduced expf / logf (~25 instructions each) a frame cost 0.56 us, with these 0.45 us (c3: 278 -> 227 us per step;
-// the rest is the LDS round trip + barrier + the dependent exp2 / log2 chain).  A one-wave-per-lattice form (K states per lane, DPP wave
-// shifts instead of LDS + barrier, bit-identical) was built and is SLOWER: K dependent chains per lane per frame.
+// the rest is the LDS round trip + barrier + the dependent exp2 / log2 chain).  A first one-wave-per-lattice form (K states per lane) lost
+// to it; the one below (ctc_lattice_wave_kernel: two states per lane, branch-free lse, vector-load ring) takes 0.19 us per frame.
 __device__ __forceinline__ float fast_exp_(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
 __device__ __forceinline__ float fast_log_(float x) { return __builtin_amdgcn_logf(x) * 0.69314718055994530942f; }
 __device__ __forceinline__ float lse2(float a, float b) {
@@ -171,6 +172,141 @@ __global__ __launch_bounds__(1024) void ctc_lattice_kernel(const float* __restri
   }
 }
 
+// The same lattice for S <= 128 as ONE wavefront per (utterance, direction): lane l owns the adjacent states 2l (blank) and 2l + 1
+// (label l), the row stays in registers, and the only cross-lane traffic per frame is a one-lane wave shift (DPP, no LDS, no barrier):
+// forward in t the odd state of lane l - 1 (s - 1 of the even state, s - 2 of the odd one; the odd state's s - 1 is its own lane's even
+// state), backward in t both states of lane l + 1.  The two lse3 chains of a lane are independent within a frame and overlap.  Emissions
+// are loaded WPF frames ahead from clamped frame indices into a register ring; the ab stores hang off the chain.  Every value is
+// computed by the expressions of ctc_lattice_kernel in the same operand order (a0, a1, a2), so ab / nll are the same bits: an even
+// state's a2 is always NEG_INF there, whose term is exp2(-inf) = +0 added last — leaving it out changes nothing.  States >= S are held
+// at NEG_INF (backward in t, state S - 1 reads state S).
+constexpr int WPF = 8;
+typedef float f32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
+template <int CTRL>
+__device__ __forceinline__ float wave_shift1(float v) {      // CTRL 0x138: lane l <- lane l - 1 ; 0x130: lane l <- lane l + 1 ; the end lane gets NEG_INF
+  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(NEG_INF), __float_as_int(v), CTRL, 0xf, 0xf, false));
+}
+// lse3 / lse3(a, b, NEG_INF) as selects instead of an early return: the same value (the discarded arm may be NaN), and a frame's two
+// chains stay in one basic block where they interleave
+__device__ __forceinline__ float lse3_sel(float a, float b, float c) {
+  const float m = fmaxf(a, fmaxf(b, c));
+  const float r = m + fast_log_(fast_exp_(a - m) + fast_exp_(b - m) + fast_exp_(c - m));
+  return (m == NEG_INF) ? NEG_INF : r;
+}
+__device__ __forceinline__ float lse2_sel(float a, float b) {
+  const float m = fmaxf(a, fmaxf(b, NEG_INF));
+  const float r = m + fast_log_(fast_exp_(a - m) + fast_exp_(b - m));
+  return (m == NEG_INF) ? NEG_INF : r;
+}
+
+template <int DIRN>
+__device__ __forceinline__ void ctc_lattice_wave_body(const float* __restrict__ logits, int ld, int T, int Bn, const int* __restrict__ lab,
+                                                      int b, int Tb, int U, const float* __restrict__ lse, float* __restrict__ out, int Smax,
+                                                      float* __restrict__ nll) {
+  const int S = 2 * U + 1;
+  const int l = threadIdx.x;
+  const bool actE = 2 * l < S, actO = 2 * l + 1 < S;
+  const int step = DIRN == 0 ? 1 : -1;
+  const int tfirst = DIRN == 0 ? 0 : Tb - 1;
+  int cls = 0;
+  bool skip = false;
+  if (actO) {
+    cls = lab[l];
+    if (DIRN == 0) skip = (l >= 1) && (cls != lab[l - 1]);
+    else skip = (l + 1 < U) && (cls != lab[l + 1]);
+  }
+  const long long lg_stride = (long long)step * Bn * ld;
+  const int ls_stride = step * Bn, out_stride = step * Smax;
+  // the frame's three loads (this lane's label logit, the blank's logit, the row's lse) are all VECTOR loads — the last two through a
+  // lane offset the compiler cannot see is zero: scalar loads return out of order, so waiting for the oldest of a ring of them waits for
+  // all, and the ring would hide one frame of latency instead of WPF
+  int vz;
+  asm volatile("v_mov_b32 %0, 0" : "=v"(vz));
+  const float* lgb = logits + ((long long)tfirst * Bn + b) * ld + vz;         // frame tfirst: the blank's logit; + cls: this lane's label
+  const float* lsp = lse + (long long)tfirst * Bn + b + vz;
+  float* op = out + (long long)tfirst * Smax + (actE ? 2 * l : 0);
+  const int last = Tb - 1;
+  auto fetch = [&](int i, float& lgE, float& lgO, float& ls) {                 // frame index clamped: always a valid address
+    const int ii = i < last ? i : last;
+    ls = lsp[(long long)ii * ls_stride];
+    lgE = lgb[(long long)ii * lg_stride];
+    lgO = lgb[(long long)ii * lg_stride + cls];
+  };
+  float E = NEG_INF, O = NEG_INF;
+  // the lane's two states leave as ONE 8-byte store (rows of `ab` are only 4-byte aligned: Smax is odd), so that a store instruction
+  // covers a contiguous run of the row; written one state per instruction — every other dword — the lattice's 26 MB of half-filled
+  // 32-byte sectors were still draining when ctc_grad_kernel read them back (54 -> 183 us)
+  auto store_pair = [&]() {
+    if (actO) *reinterpret_cast<f32x2_a4*>(op) = f32x2_a4{E, O};
+    else if (actE) op[0] = E;
+  };
+  // init row
+  {
+    float lgE, lgO, ls;
+    fetch(0, lgE, lgO, ls);
+    const float eE = lgE - ls, eO = lgO - ls;
+    if (DIRN == 0) { if (l == 0) { E = eE; if (actO) O = eO; } }
+    else { if (2 * l == S - 1) E = eE; if (actO && 2 * l + 1 == S - 2) O = eO; }
+    store_pair();
+  }
+  // one frame: a state >= S gets the emission NEG_INF, which holds it at NEG_INF without a select on the chain
+  auto frame = [&](float lgE, float lgO, float ls) {
+    const float lpE = actE ? lgE - ls : NEG_INF, lpO = actO ? lgO - ls : NEG_INF;
+    op += out_stride;
+    float mE, mO;
+    if (DIRN == 0) {
+      const float Om = wave_shift1<0x138>(O);                                   // state 2l - 1
+      mE = lse2_sel(E, Om);
+      mO = lse3_sel(O, E, skip ? Om : NEG_INF);
+    } else {
+      const float Ep = wave_shift1<0x130>(E), Op = wave_shift1<0x130>(O);       // states 2l + 2, 2l + 3
+      mE = lse2_sel(E, O);
+      mO = lse3_sel(O, Ep, skip ? Op : NEG_INF);
+    }
+    E = (mE == NEG_INF) ? NEG_INF : mE + lpE;
+    O = (mO == NEG_INF) ? NEG_INF : mO + lpO;
+    store_pair();
+  };
+  float rE[WPF], rO[WPF], rL[WPF];
+#pragma unroll
+  for (int k = 0; k < WPF; ++k) fetch(1 + k, rE[k], rO[k], rL[k]);
+  int i0 = 1;
+  for (; i0 + WPF <= Tb; i0 += WPF) {                                           // whole groups: slot k holds frame i0 + k, refilled with i0 + k + WPF
+#pragma unroll
+    for (int k = 0; k < WPF; ++k) {
+      const float lgE = rE[k], lgO = rO[k], ls = rL[k];
+      fetch(i0 + k + WPF, rE[k], rO[k], rL[k]);
+      frame(lgE, lgO, ls);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < WPF - 1; ++k)                                             // the last Tb - i0 < WPF frames are in the ring already
+    if (i0 + k < Tb) frame(rE[k], rO[k], rL[k]);
+  if (DIRN == 0) {
+    const float l1 = __shfl(E, U, 64);                                          // state S - 1 = 2U
+    const float l2 = __shfl(O, U >= 1 ? U - 1 : 0, 64);                         // state S - 2
+    if (l == 0) nll[b] = -lse2(l1, (S >= 2) ? l2 : NEG_INF);
+  }
+}
+
+// blockIdx.x = utterance, blockIdx.y = direction; 64 threads.  Needs 2 * tgt_lens[b] + 1 <= 128 for every b (the launcher checks Smax).
+__global__ __launch_bounds__(64) void ctc_lattice_wave_kernel(const float* __restrict__ logits, int ld, int T, int Bn, int C,
+                                                              const int* __restrict__ targets, const int* __restrict__ tgt_off,
+                                                              const int* __restrict__ in_lens, const int* __restrict__ tgt_lens,
+                                                              const float* __restrict__ lse, float* __restrict__ ab, int Smax,
+                                                              float* __restrict__ nll) {
+  const int b = blockIdx.x, dirn = blockIdx.y;
+  const int Tb = min(in_lens[b], T), U = tgt_lens[b];
+  float* out = ab + (((long long)dirn * Bn + b) * T) * Smax;
+  if (Tb <= 0) {
+    if (dirn == 0 && threadIdx.x == 0) nll[b] = (U == 0) ? 0.f : INFINITY;
+    return;
+  }
+  const int* lab = targets + tgt_off[b];
+  if (dirn == 0) ctc_lattice_wave_body<0>(logits, ld, T, Bn, lab, b, Tb, U, lse, out, Smax, nll);
+  else ctc_lattice_wave_body<1>(logits, ld, T, Bn, lab, b, Tb, U, lse, out, Smax, nll);
+}
+
 // grid = (ceil(T / TCH), B); block = 128 threads; dynamic LDS: q[C] + val[S] + nxt[U] (ints) + lab[U]
 constexpr int TCH = 8;
 __global__ __launch_bounds__(128) void ctc_grad_kernel(const float* __restrict__ logits, int ld, float* __restrict__ grad, int ldg, int T,
@@ -302,11 +438,14 @@ extern "C" size_t ds2_ctc_workspace_bytes(int T, int B, int max_target_len) {
 }
 
 // targets: flat labels (device int32), tgt_off[b] = start of utterance b in `targets` (device int32).
-extern "C" int ds2_ctc_loss_f32(const float* logits, int ld, int T, int B, int C, const int* targets_dev, const int* tgt_off_dev,
-                                const int* in_lens_dev, const int* tgt_lens_dev, int max_target_len, float* nll_dev,
-                                float* grad, int ldg, float grad_scale, void* ws, size_t ws_bytes, void* stream) {
+// lattice: 0 = the launcher chooses (one wave per lattice when 2 * max_target_len + 1 <= 128, else one workgroup per lattice),
+//          1 = always one workgroup per lattice (ctc_lattice_kernel; the two produce the same bits: tests/test_gpu_ctc_wave.py)
+extern "C" int ds2_ctc_loss_ex_f32(const float* logits, int ld, int T, int B, int C, const int* targets_dev, const int* tgt_off_dev,
+                                   const int* in_lens_dev, const int* tgt_lens_dev, int max_target_len, float* nll_dev, float* grad, int ldg,
+                                   float grad_scale, int lattice, void* ws, size_t ws_bytes, void* stream) {
   DS2_REQUIRE(logits && targets_dev && tgt_off_dev && in_lens_dev && tgt_lens_dev && nll_dev, "ds2_ctc_loss_f32: null pointer");
   DS2_REQUIRE(T > 0 && B > 0 && C > 0 && max_target_len >= 0, "ds2_ctc_loss_f32: bad dims");
+  DS2_REQUIRE(lattice == 0 || lattice == 1, "ds2_ctc_loss_ex_f32: lattice must be 0 or 1");
   DS2_REQUIRE(ws && ws_bytes >= ds2_ctc_workspace_bytes(T, B, max_target_len), "ds2_ctc_loss_f32: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   const int Smax = 2 * max_target_len + 1;
@@ -314,13 +453,19 @@ extern "C" int ds2_ctc_loss_f32(const float* logits, int ld, int T, int B, int C
   float* ab = (float*)((char*)ws + align_up((size_t)T * B * sizeof(float), 256));
   hipLaunchKernelGGL(ctc_lse_kernel, dim3(ceil_div(T * B, 4)), dim3(256), 0, s, logits, ld, T, B, C, in_lens_dev, lse);
   DS2_LAUNCH_CHECK("ctc_lse_kernel");
-  int threads = ceil_div(Smax, 64) * 64;
-  if (threads > 1024) threads = 1024;
-  const size_t lds = (size_t)2 * Smax * sizeof(float);
-  DS2_REQUIRE(lds <= 64 * 1024, "ds2_ctc_loss_f32: target too long for LDS lattice rows (Smax=%d)", Smax);
-  hipLaunchKernelGGL(ctc_lattice_kernel, dim3(B, 2), dim3(threads), lds, s, logits, ld, T, B, C, targets_dev, tgt_off_dev,
-                     in_lens_dev, tgt_lens_dev, (const float*)lse, ab, Smax, nll_dev);
-  DS2_LAUNCH_CHECK("ctc_lattice_kernel");
+  if (lattice == 0 && Smax <= 128) {
+    hipLaunchKernelGGL(ctc_lattice_wave_kernel, dim3(B, 2), dim3(64), 0, s, logits, ld, T, B, C, targets_dev, tgt_off_dev, in_lens_dev,
+                       tgt_lens_dev, (const float*)lse, ab, Smax, nll_dev);
+    DS2_LAUNCH_CHECK("ctc_lattice_wave_kernel");
+  } else {
+    int threads = ceil_div(Smax, 64) * 64;
+    if (threads > 1024) threads = 1024;
+    const size_t lds = (size_t)2 * Smax * sizeof(float);
+    DS2_REQUIRE(lds <= 64 * 1024, "ds2_ctc_loss_f32: target too long for LDS lattice rows (Smax=%d)", Smax);
+    hipLaunchKernelGGL(ctc_lattice_kernel, dim3(B, 2), dim3(threads), lds, s, logits, ld, T, B, C, targets_dev, tgt_off_dev,
+                       in_lens_dev, tgt_lens_dev, (const float*)lse, ab, Smax, nll_dev);
+    DS2_LAUNCH_CHECK("ctc_lattice_kernel");
+  }
   if (grad) {
     const size_t lds2 = ((size_t)C + Smax) * sizeof(float) + 3 * ((size_t)Smax / 2 + 1) * sizeof(int);
     DS2_REQUIRE(lds2 <= 64 * 1024, "ds2_ctc_loss_f32: C/S too large for LDS (C=%d Smax=%d)", C, Smax);
@@ -330,4 +475,11 @@ extern "C" int ds2_ctc_loss_f32(const float* logits, int ld, int T, int B, int C
     DS2_LAUNCH_CHECK("ctc_grad_kernel");
   }
   return 0;
+}
+
+extern "C" int ds2_ctc_loss_f32(const float* logits, int ld, int T, int B, int C, const int* targets_dev, const int* tgt_off_dev,
+                                const int* in_lens_dev, const int* tgt_lens_dev, int max_target_len, float* nll_dev,
+                                float* grad, int ldg, float grad_scale, void* ws, size_t ws_bytes, void* stream) {
+  return ds2_ctc_loss_ex_f32(logits, ld, T, B, C, targets_dev, tgt_off_dev, in_lens_dev, tgt_lens_dev, max_target_len, nll_dev, grad, ldg,
+                             grad_scale, 0, ws, ws_bytes, stream);
 }

@@ -152,3 +152,225 @@ extern "C" int ds2_sum3_f32(const float* a, const float* b, const float* c, floa
   DS2_LAUNCH_CHECK("sum3_kernel");
   return 0;
 }
+
+// ---- weight-operand preparation of a whole recurrent stack in ONE launch (bf16 mode, once per optimizer step) -------------------------
+// Per layer: the packed bf16 W_hh fragments of both recurrences (the layout of ds2_rnn_pack_whh, bf16 = 1) and the bf16 copies of W_ih
+// (the layout of ds2_cast_bf16_both / ds2_cast_transpose_bf16), byte for byte what those per-layer entry points write.  A table in the
+// kernel arguments maps a workgroup to its job; every job works on 64 x 64 fp32 tiles staged in LDS, read with 16-byte loads, written with
+// 16-byte stores.  One tile of W_hh yields its forward AND its backward fragments (the per-layer kernel reads W_hh once for each, the
+// backward half with 64-byte runs of scalar loads).
+namespace {
+
+typedef __bf16 pbf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 pbf16x4 __attribute__((ext_vector_type(4)));
+
+enum { PREP_PACK_TILE = 0, PREP_PACK_VEC = 1, PREP_CAST_T = 2 };
+constexpr int PREP_MAX_JOBS = 32;
+struct PrepJob {
+  const float* src;
+  void* d0;            // pack: forward fragments ; cast: transposed copy
+  void* d1;            // pack: backward fragments ; cast: row-major copy or NULL
+  int kind, first;     // first workgroup of this job
+  int G, H;            // pack
+  int R, Cc, lds, ldt, ldr, vec, gx;   // cast: src (R, Cc) pitch lds ; dT pitch ldt ; dR pitch ldr ; float4-readable ; tiles along Cc
+};
+struct PrepTable {
+  int njobs;
+  PrepJob job[PREP_MAX_JOBS];
+};
+
+constexpr int PT = 68;   // tile pitch of the pack jobs (16-byte aligned rows); the cast jobs keep cast_transpose_bf16_kernel's 65
+
+__device__ __forceinline__ pbf16x8 to_bf16x8(const float* v) {
+  pbf16x8 o;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) o[e] = (__bf16)v[e];
+  return o;
+}
+
+// H % 16 == 0: a 64-row tile of the (G*H, H) matrix of one direction never cuts a 16-unit slice, and its row chunks of 32 are the backward
+// operand's chunks.  Everything outside the matrix is staged as zero, as rnn_pack_kernel pads.
+__device__ __forceinline__ void prep_pack_tile(const PrepJob& jb, int lb, float* tile) {
+  const int G = jb.G, H = jb.H, GH = G * H;
+  const int rt = (GH + 63) >> 6, ct = (H + 63) >> 6;
+  const int dir = lb / (rt * ct), rem = lb % (rt * ct);
+  const int r0 = (rem / ct) * 64, c0 = (rem % ct) * 64;
+  const int nsl = H >> 4, nch = (H + 31) >> 5, nchb = (GH + 31) >> 5;
+  const float* src = jb.src + (long long)dir * GH * H;
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int pass = 0; pass < 4; ++pass) {
+    const int rl = pass * 16 + (tid >> 4), cl = (tid & 15) * 4;
+    const int r = r0 + rl, c = c0 + cl;
+    f32x4 q = {0.f, 0.f, 0.f, 0.f};
+    if (r < GH && c < H) q = *reinterpret_cast<const f32x4*>(src + (long long)r * H + c);      // (H % 4 == 0: c < H is c + 4 <= H)
+    *reinterpret_cast<f32x4*>(tile + rl * PT + cl) = q;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int p = 0; p < 2; ++p) {                                  // forward fragments: [dir][slice][gate][32-k chunk][lane] = 8 consecutive k of row (g, j)
+    const int v = p * 256 + tid, lane = v & 63, cc = (v >> 6) & 1, i = v >> 7;
+    const int row = r0 + 16 * i, c = (c0 >> 5) + cc;
+    if (row < GH && c < nch) {
+      const int g = row / H, slice = (row % H) >> 4;
+      const float* t = tile + (16 * i + (lane & 15)) * PT + cc * 32 + (lane >> 4) * 8;
+      float x[8];
+      *reinterpret_cast<f32x4*>(x) = *reinterpret_cast<const f32x4*>(t);
+      *reinterpret_cast<f32x4*>(x + 4) = *reinterpret_cast<const f32x4*>(t + 4);
+      reinterpret_cast<pbf16x8*>(jb.d0)[((((long long)dir * nsl + slice) * G + g) * nch + c) * 64 + lane] = to_bf16x8(x);
+    }
+  }
+#pragma unroll
+  for (int p = 0; p < 2; ++p) {                                  // backward fragments: [dir][slice][32-row chunk][lane] = 8 consecutive rows of column j
+    const int v = p * 256 + tid, lane = v & 63, sj = (v >> 6) & 3, ci = v >> 8;
+    const int cb = (r0 >> 5) + ci, slice = (c0 >> 4) + sj;
+    if (cb < nchb && slice < nsl) {
+      const float* t = tile + (ci * 32 + (lane >> 4) * 8) * PT + sj * 16 + (lane & 15);
+      float x[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) x[e] = t[e * PT];
+      reinterpret_cast<pbf16x8*>(jb.d1)[(((long long)dir * nsl + slice) * nchb + cb) * 64 + lane] = to_bf16x8(x);
+    }
+  }
+}
+
+// any H % 4 == 0: rnn_pack_kernel<true>'s own indexing, one 16-byte fragment per thread
+__device__ __forceinline__ void prep_pack_vec(const PrepJob& jb, int lb) {
+  const int G = jb.G, H = jb.H;
+  const int nsl = (H + 15) >> 4, nch = (H + 31) >> 5, nchb = (G * H + 31) >> 5;
+  const long long nf = (long long)2 * nsl * G * nch * 64, nb = (long long)2 * nsl * nchb * 64;
+  const long long i = (long long)lb * 256 + threadIdx.x;
+  if (i >= nf + nb) return;
+  const bool fwd = i < nf;
+  const long long ii = fwd ? i : i - nf;
+  const int lane = (int)(ii & 63);
+  long long r = ii >> 6;
+  float v[8];
+  if (fwd) {
+    const int c = r % nch; r /= nch;
+    const int g = r % G; r /= G;
+    const int slice = r % nsl, dir = r / nsl;
+    const int j = slice * 16 + (lane & 15), k0 = c * 32 + (lane >> 4) * 8;
+    const float* src = jb.src + ((long long)dir * G * H + g * H + j) * H + k0;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = (j < H && k0 + e < H) ? src[e] : 0.f;
+  } else {
+    const int c = r % nchb; r /= nchb;
+    const int slice = r % nsl, dir = r / nsl;
+    const int j = slice * 16 + (lane & 15), k0 = c * 32 + (lane >> 4) * 8;
+    const float* src = jb.src + ((long long)dir * G * H + k0) * H + j;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = (j < H && k0 + e < G * H) ? src[(long long)e * H] : 0.f;
+  }
+  reinterpret_cast<pbf16x8*>(fwd ? jb.d0 : jb.d1)[ii] = to_bf16x8(v);
+}
+
+// cast_transpose_bf16_kernel (gemm_bf16.hip) without the column sums: dT[c][r] = bf16(src[r][c]), optionally dR[r][c] = bf16(src[r][c])
+__device__ __forceinline__ void prep_cast_t(const PrepJob& jb, int lb, float* tile) {
+  const int R = jb.R, Cc = jb.Cc, ldt = jb.ldt, ldr = jb.ldr;
+  __bf16* dstT = (__bf16*)jb.d0;
+  __bf16* dstR = (__bf16*)jb.d1;
+  const int r0 = (lb / jb.gx) * 64, c0 = (lb % jb.gx) * 64;
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int pass = 0; pass < 4; ++pass) {
+    const int rl = pass * 16 + (tid >> 4), cl = (tid & 15) * 4;
+    const int r = r0 + rl, c = c0 + cl;
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
+    if (r < R) {
+      const float* sp = jb.src + (long long)r * jb.lds + c;
+      if (jb.vec && c + 4 <= Cc) {
+        const f32x4 q = *reinterpret_cast<const f32x4*>(sp);
+        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = (c + j < Cc) ? sp[j] : 0.f;
+      }
+      if (dstR && c < ldr) *reinterpret_cast<pbf16x4*>(dstR + (long long)r * ldr + c) = pbf16x4{(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) tile[rl * 65 + cl + j] = v[j];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int pass = 0; pass < 2; ++pass) {
+    const int cl = pass * 32 + (tid >> 3), rl = (tid & 7) * 8;
+    const int c = c0 + cl, r = r0 + rl;
+    if (c < Cc && r < ldt) {                      // rows >= R were staged as zeros; ldt % 8 == 0 keeps the 8-run inside the pitch
+      float x[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) x[j] = tile[(rl + j) * 65 + cl];
+      *reinterpret_cast<pbf16x8*>(dstT + (long long)c * ldt + r) = to_bf16x8(x);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void weight_prep_kernel(const PrepTable tab) {
+  __shared__ __attribute__((aligned(16))) float tile[64 * PT];
+  const int bid = blockIdx.x;
+  int j = 0;
+  while (j + 1 < tab.njobs && bid >= tab.job[j + 1].first) ++j;      // (uniform: a few scalar loads)
+  const PrepJob& jb = tab.job[j];
+  const int lb = bid - jb.first;
+  if (jb.kind == PREP_PACK_TILE) prep_pack_tile(jb, lb, tile);
+  else if (jb.kind == PREP_PACK_VEC) prep_pack_vec(jb, lb);
+  else prep_cast_t(jb, lb, tile);
+}
+
+}  // namespace
+
+// layers[i]: whh (2, gates*H, H) fp32 contiguous -> wp_fwd / wp_bwd (ds2_rnn_packed_bytes(gates, H, 0 | 1, 1) bytes), skipped when whh is
+// NULL; wih (R, Cc) fp32, row pitch ld_wih -> wih_t (Cc, ld_t) bf16 = wih^T (ld_t % 8 == 0, ld_t >= R) and, when wih_r is not NULL,
+// wih_r (R, ld_r) bf16 (ld_r % 8 == 0, Cc <= ld_r <= the next multiple of 64); pads zero; skipped when wih is NULL.
+extern "C" int ds2_weight_prep_bf16(const ds2_prep_layer* layers, int n, void* stream) {
+  DS2_REQUIRE(layers && n > 0, "ds2_weight_prep_bf16: bad args");
+  PrepTable tab;
+  tab.njobs = 0;
+  long long blocks = 0;
+  auto flush = [&]() -> int {
+    if (tab.njobs == 0) return 0;
+    hipLaunchKernelGGL(weight_prep_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, tab);
+    DS2_LAUNCH_CHECK("weight_prep_kernel");
+    tab.njobs = 0;
+    blocks = 0;
+    return 0;
+  };
+  for (int i = 0; i < n; ++i) {
+    const ds2_prep_layer& L = layers[i];
+    if (tab.njobs + 2 > PREP_MAX_JOBS && flush()) return 1;                       // (more than 16 layers: a second launch)
+    if (L.whh) {
+      DS2_REQUIRE(L.gates == 1 || L.gates == 3 || L.gates == 4, "ds2_weight_prep_bf16: gates must be 1, 3 or 4");
+      DS2_REQUIRE(L.wp_fwd && L.wp_bwd && L.H > 0 && (L.H % 4) == 0 && ((uintptr_t)L.whh % 16) == 0 && ((uintptr_t)L.wp_fwd % 16) == 0 &&
+                      ((uintptr_t)L.wp_bwd % 16) == 0,
+                  "ds2_weight_prep_bf16: bad W_hh arguments (layer %d)", i);
+      PrepJob& jb = tab.job[tab.njobs++];
+      jb = PrepJob{};
+      jb.src = L.whh; jb.d0 = L.wp_fwd; jb.d1 = L.wp_bwd; jb.G = L.gates; jb.H = L.H; jb.first = (int)blocks;
+      if ((L.H % 16) == 0) {
+        jb.kind = PREP_PACK_TILE;
+        blocks += 2LL * ceil_div(L.gates * L.H, 64) * ceil_div(L.H, 64);
+      } else {
+        jb.kind = PREP_PACK_VEC;
+        const long long nsl = ceil_div(L.H, 16);
+        const long long nv = 2 * nsl * L.gates * ceil_div(L.H, 32) * 64 + 2 * nsl * ceil_div(L.gates * L.H, 32) * 64;
+        blocks += (nv + 255) / 256;
+      }
+    }
+    if (L.wih) {
+      DS2_REQUIRE(L.wih_t && L.R > 0 && L.Cc > 0 && L.ld_wih >= L.Cc && L.ld_t >= L.R && (L.ld_t % 8) == 0 && ((uintptr_t)L.wih_t % 16) == 0,
+                  "ds2_weight_prep_bf16: bad W_ih arguments (layer %d)", i);
+      DS2_REQUIRE(!L.wih_r || (L.ld_r >= L.Cc && L.ld_r <= ceil_div(L.Cc, 64) * 64 && (L.ld_r % 8) == 0 && ((uintptr_t)L.wih_r % 16) == 0),
+                  "ds2_weight_prep_bf16: bad row-major pitch (layer %d, ld_r=%d)", i, L.ld_r);
+      PrepJob& jb = tab.job[tab.njobs++];
+      jb = PrepJob{};
+      jb.kind = PREP_CAST_T;
+      jb.src = L.wih; jb.d0 = L.wih_t; jb.d1 = L.wih_r; jb.first = (int)blocks;
+      jb.R = L.R; jb.Cc = L.Cc; jb.lds = L.ld_wih; jb.ldt = L.ld_t; jb.ldr = L.wih_r ? L.ld_r : 0;
+      jb.vec = ((L.ld_wih % 4) == 0) && (((uintptr_t)L.wih % 16) == 0);
+      jb.gx = ceil_div(L.wih_r ? (L.Cc > L.ld_r ? L.Cc : L.ld_r) : L.Cc, 64);
+      blocks += (long long)jb.gx * ceil_div(L.ld_t, 64);
+    }
+    DS2_REQUIRE(blocks < (1LL << 31), "ds2_weight_prep_bf16: too many tiles");
+  }
+  return flush();
+}

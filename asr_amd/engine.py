@@ -332,9 +332,18 @@ def forward(W: Dict[str, Tensor], cfg: ModelCfg, x: Tensor, lens_dev: Tensor, tr
 
     # ---- recurrent stack ------------------------------------------------------------------------
     mean = var = delta = None
+    bf = cfg.precision == "bf16"
+    prep = None
+    if bf and save:
+        # bf16 training: every layer's weight operands (packed W_hh fragments of both recurrences, W_ih^T for dX, and the row-major bf16 W_ih
+        # of the layers that do not fold their BatchNorm into it) in ONE launch, from the weights as they are NOW (after the optimizer step,
+        # load_state_dict or a skipped step alike: nothing is carried from step to step)
+        may_fold = (BN_FOLD and training and B % 8 == 0 and H % 8 == 0 and OVERLAP_MODE == "2" and T > 1
+                    and (BN_FOLD_IDLE or not _wgrad_idle_schedule(x.device, B, H)))
+        prep = ops.weight_prep_bf16([(G, W[f"rnns.{l}.whh_cat"], W[f"rnns.{l}.wih_cat"],
+                                      xn0.shape[1] if l == 0 else (None if may_fold else ops._pad8(H))) for l in range(L)])
     for l in range(L):
         lc = LayerCtx()
-        bf = cfg.precision == "bf16"
         rmode = 1 if bf else (2 if (F32_RNN == "split" and H % 32 == 0) else 0)
         ws_f = ops.rnn_ws("fwd", G, B, H, rmode, x.device) if WS_PREARM else None
         folded = l > 0 and xin.dtype == torch.bfloat16       # BN_FOLD: the layer in front left the centred bf16 operand (+ mean, var, delta)
@@ -343,7 +352,8 @@ def forward(W: Dict[str, Tensor], cfg: ModelCfg, x: Tensor, lens_dev: Tensor, tr
             xn = xin
             w_bf, bias_eff, colscale, colshift = ops.wih_fold(W[f"rnns.{l}.wih_cat"], W[f"rnns.{l}.bih_cat"], var, W[bp + "weight"], W[bp + "bias"], delta,
                                                               ld=xn.shape[1])
-            lc.wihT = ops.cast_transpose_bf16(W[f"rnns.{l}.wih_cat"])          # (un-scaled: dX is the gradient wrt BN's OUTPUT, as before)
+            # (un-scaled: dX is the gradient wrt BN's OUTPUT, as before)
+            lc.wihT = prep[l][2] if prep is not None else ops.cast_transpose_bf16(W[f"rnns.{l}.wih_cat"])
             lc.mean, lc.var, lc.fold = delta, var, (colscale, colshift)        # (the mean OF xin)
             gx = ops.gemm_bf16_nt(xn, w_bf, bias=bias_eff)
             del w_bf
@@ -361,7 +371,10 @@ def forward(W: Dict[str, Tensor], cfg: ModelCfg, x: Tensor, lens_dev: Tensor, tr
         elif cfg.precision == "bf16":
             if save:
                 # training: ONE read of W_ih gives the row-major bf16 operand of this projection and the transposed one of dX (kept for backward)
-                w_bf, lc.wihT = ops.cast_bf16_both(W[f"rnns.{l}.wih_cat"], ld_r=xn.shape[1])
+                if prep is not None and prep[l][3] is not None and prep[l][3].shape[1] == xn.shape[1]:
+                    lc.wihT, w_bf = prep[l][2], prep[l][3]
+                else:
+                    w_bf, lc.wihT = ops.cast_bf16_both(W[f"rnns.{l}.wih_cat"], ld_r=xn.shape[1])
             else:
                 w_bf = ops.cast_bf16(W[f"rnns.{l}.wih_cat"], ld=xn.shape[1])
             gx = None
@@ -380,7 +393,9 @@ def forward(W: Dict[str, Tensor], cfg: ModelCfg, x: Tensor, lens_dev: Tensor, tr
                 xn = None                                        # backward takes dW_ih from the split copy (6 bytes per element instead of 4 + 6)
         else:
             gx = ops.gemm(xn, W[f"rnns.{l}.wih_cat"], transB=True, bias=W[f"rnns.{l}.bih_cat"])  # (M, 2GH)
-        wpf, wpb = ops.rnn_pack(G, W[f"rnns.{l}.whh_cat"], bf16=rmode)
+        wpf, wpb = prep[l][:2] if prep is not None else ops.rnn_pack(G, W[f"rnns.{l}.whh_cat"], bf16=rmode)
+        if prep is not None:
+            prep[l] = None                                       # (the forward operands die with their layer, as before)
         # bf16 training (B % 8 == 0, the condition of the bf16 dGx path in backward): the saved gates are ONE packed bf16 record per
         # hidden unit; the fp32 x-projection buffer is then dead after the recurrence
         pack = bf and save and B % 8 == 0

@@ -970,6 +970,36 @@ def rnn_pack(gates: int, whh: Tensor, bf16=False):
     return wpf, wpb
 
 
+def weight_prep_bf16(layers):
+    """The bf16 weight operands of a recurrent stack in ONE launch.  layers: a list of (gates, whh (2, G*H, H) or None, wih (R, C) or None,
+    ld_r or None); returns a list of (wp_fwd, wp_bwd, wihT (C, pad8(R)) bf16, wih_r (R, ld_r) bf16 or None), entries None where the input
+    was: the bytes rnn_pack(bf16=True), cast_transpose_bf16 and cast_bf16_both write for each layer on its own."""
+    lib = _lib.load()
+    tab = (_lib.PrepLayer * len(layers))()
+    out = []
+    for e, (gates, whh, wih, ld_r) in zip(tab, layers):
+        wpf = wpb = wt = wr = None
+        if whh is not None:
+            _chk_f32(whh)
+            assert whh.is_contiguous() and whh.dim() == 3
+            dev, H = whh.device, whh.size(2)
+            wpf = torch.empty(lib.ds2_rnn_packed_bytes(gates, H, 0, 1), dtype=torch.uint8, device=dev)
+            wpb = torch.empty(lib.ds2_rnn_packed_bytes(gates, H, 1, 1), dtype=torch.uint8, device=dev)
+            e.whh, e.wp_fwd, e.wp_bwd, e.gates, e.H = whh.data_ptr(), wpf.data_ptr(), wpb.data_ptr(), gates, H
+        if wih is not None:
+            _chk_f32(wih)
+            R, Cc = wih.shape
+            wt = torch.empty(Cc, _pad8(R), dtype=torch.bfloat16, device=wih.device)
+            e.wih, e.wih_t, e.R, e.Cc, e.ld_wih, e.ld_t = wih.data_ptr(), wt.data_ptr(), R, Cc, _row_pitch(wih), wt.size(1)
+            if ld_r is not None:
+                assert ld_r >= Cc and ld_r % 8 == 0
+                wr = torch.empty(R, ld_r, dtype=torch.bfloat16, device=wih.device)
+                e.wih_r, e.ld_r = wr.data_ptr(), ld_r
+        out.append((wpf, wpb, wt, wr))
+    _lib.check(lib.ds2_weight_prep_bf16(tab, len(layers), _stream()), "ds2_weight_prep_bf16")
+    return out
+
+
 def rnn_ws(kind: str, gates: int, B: int, H: int, bf16, device) -> Tensor:
     """The workspace of ONE rnn_fwd ("fwd") / rnn_bwd / rnn_bwd_bn ("bwd") call, filled with 0xff bytes NOW, in stream order: pass it as `ws=` to
     the call.  A persistent launch needs its exchange buffers armed with that pattern; armed here — ahead of the GEMM in front of the recurrence —
@@ -1193,8 +1223,10 @@ def rnn_bias_grads(gates: int, bias_part: Tensor, dbih: Tensor, dbhh: Tensor):
 # CTC
 # ------------------------------------------------------------------------------------------------
 def ctc_loss(logits: Tensor, targets_dev: Tensor, tgt_off_dev: Tensor, in_lens_dev: Tensor, tgt_lens_dev: Tensor, max_tgt: int,
-             grad_scale: float, want_grad: bool = True):
-    """logits (T,B,C) (last dim contiguous, uniform row pitch).  Returns (nll (B,), grad (T,B,C) or None)."""
+             grad_scale: float, want_grad: bool = True, lattice: int = 0, return_ab: bool = False):
+    """logits (T,B,C) (last dim contiguous, uniform row pitch).  Returns (nll (B,), grad (T,B,C) or None).
+    lattice: 0 = the library chooses the lattice kernel, 1 = one workgroup per lattice whatever the target length (the two write the same
+    bits).  return_ab: also a copy of the alpha / beta lattices (2, B, T, 2 * max_tgt + 1), zero outside an utterance's (T_b, S_b)."""
     _chk_f32(logits)
     lib = _lib.load()
     T, B, Cc = logits.shape
@@ -1204,9 +1236,15 @@ def ctc_loss(logits: Tensor, targets_dev: Tensor, tgt_off_dev: Tensor, in_lens_d
     grad = torch.empty(T, B, Cc, dtype=torch.float32, device=logits.device) if want_grad else None
     wsb = lib.ds2_ctc_workspace_bytes(T, B, max_tgt)
     ws = _ws(wsb, logits.device)
-    _lib.check(lib.ds2_ctc_loss_f32(logits.data_ptr(), ld, T, B, Cc, targets_dev.data_ptr(), tgt_off_dev.data_ptr(),
-                                    in_lens_dev.data_ptr(), tgt_lens_dev.data_ptr(), int(max_tgt), nll.data_ptr(), _ptr(grad), Cc,
-                                    float(grad_scale), ws.data_ptr(), wsb, _stream()), "ds2_ctc_loss_f32")
+    if return_ab:
+        ws.zero_()
+    _lib.check(lib.ds2_ctc_loss_ex_f32(logits.data_ptr(), ld, T, B, Cc, targets_dev.data_ptr(), tgt_off_dev.data_ptr(),
+                                       in_lens_dev.data_ptr(), tgt_lens_dev.data_ptr(), int(max_tgt), nll.data_ptr(), _ptr(grad), Cc,
+                                       float(grad_scale), int(lattice), ws.data_ptr(), wsb, _stream()), "ds2_ctc_loss_ex_f32")
+    if return_ab:
+        Smax = 2 * int(max_tgt) + 1
+        off = (T * B * 4 + 255) // 256 * 256
+        return nll, grad, ws[off:off + 2 * B * T * Smax * 4].view(torch.float32).view(2, B, T, Smax).clone()
     return nll, grad
 
 

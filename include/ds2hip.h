@@ -273,6 +273,17 @@ size_t ds2_rnn_packed_bytes(int gates, int H, int which /*0: forward operand, 1:
  * is then [fp32 fragments | hi fragments | lo fragments (| the ten-unit-slice hi / lo operand of csrc/rnn_fwd_u10.h when H % 160 == 0, H <= 1280)]
  * and the fp32 kernels remain the fallback (shape does not fit, cooldown). */
 int ds2_rnn_pack_whh(int gates, const float* whh, void* wp_fwd, void* wp_bwd, int H, int bf16, void* stream);
+/* The bf16 weight operands of a whole recurrent stack in ONE launch (bf16 mode, once per optimizer step): per layer the packed W_hh
+ * fragments of ds2_rnn_pack_whh with bf16 = 1 and the bf16 copies of W_ih that ds2_cast_bf16_both / ds2_cast_transpose_bf16 write, byte
+ * for byte, into the caller's buffers.  whh NULL: no W_hh work for that layer; wih NULL: no W_ih work; wih_r NULL: only the transposed
+ * copy.  whh (2, gates*H, H) contiguous, H % 4 == 0; wih (R, Cc) with row pitch ld_wih; wih_t (Cc, ld_t), ld_t % 8 == 0, ld_t >= R;
+ * wih_r (R, ld_r), ld_r % 8 == 0, Cc <= ld_r <= the next multiple of 64; pad columns are zero-filled; all buffers 16-byte aligned. */
+typedef struct ds2_prep_layer {
+  const float* whh; void* wp_fwd; void* wp_bwd;
+  const float* wih; void* wih_t; void* wih_r;
+  int gates, H, R, Cc, ld_wih, ld_t, ld_r, reserved;
+} ds2_prep_layer;
+int ds2_weight_prep_bf16(const ds2_prep_layer* layers, int n, void* stream);
 /* Status of the persistent recurrences (a layer's whole recurrence in ONE launch whose workgroups exchange h_t / dGh_t through memory;
  * it needs every workgroup resident at once).  out8 = {starved, slice | workgroup, tile | XCD, direction | kind, step, wave, pending
  * chunk mask, L2-local exchange}: starved != 0 (1 forward, 2 backward, 3 the launch never became resident) means a wave gave up
@@ -378,6 +389,11 @@ size_t ds2_ctc_workspace_bytes(int T, int B, int max_target_len);
 int ds2_ctc_loss_f32(const float* logits, int ld, int T, int B, int C, const int* targets_dev, const int* tgt_off_dev,
                      const int* in_lens_dev, const int* tgt_lens_dev, int max_target_len, float* nll_dev, float* grad, int ldg,
                      float grad_scale, void* ws, size_t ws_bytes, void* stream);
+/* The same with the lattice kernel named: lattice = 0 lets the library choose (one wavefront per lattice when 2 * max_target_len + 1 <= 128,
+ * one workgroup per lattice otherwise), 1 = always one workgroup per lattice.  The two forms write the same bits. */
+int ds2_ctc_loss_ex_f32(const float* logits, int ld, int T, int B, int C, const int* targets_dev, const int* tgt_off_dev,
+                        const int* in_lens_dev, const int* tgt_lens_dev, int max_target_len, float* nll_dev, float* grad, int ldg,
+                        float grad_scale, int lattice, void* ws, size_t ws_bytes, void* stream);
 
 /* out[0] = sum_b nll[b] / B on the device, fixed summation order: `loss = criterion(...) / inputs.size(0)`,
  * trainers/deepspeech_trainer.py:110-112 */
