@@ -483,3 +483,8 @@ extern "C" int ds2_ctc_loss_f32(const float* logits, int ld, int T, int B, int C
   return ds2_ctc_loss_ex_f32(logits, ld, T, B, C, targets_dev, tgt_off_dev, in_lens_dev, tgt_lens_dev, max_target_len, nll_dev, grad, ldg,
                              grad_scale, 0, ws, ws_bytes, stream);
 }
+
+// CTC forced alignment (ds2_ctc_align_*): the same lattice over (max, +) with back-pointers and a backtrace.  It lives in its own file
+// and is compiled in this translation unit, next to the lattice helpers it shares (wave_shift1, WPF, NEG_INF).
+#define DS2_CTC_ALIGN_TU
+#include "ctc_align.h"

@@ -2,7 +2,9 @@
 `decode()` runs on the GPU (csrc/decode.hip, csrc/ctc_beam.h); process_string / convert_to_strings are the host utilities the
 reference uses for TARGET strings.  Eval-only, not on the train step.
 `wer` / `cer` keep a small pure-Python DP (the reference imports the `Levenshtein` C package) as the reference API; evaluate()
-scores a whole batch with `Decoder.score_batch`, one HIP launch (csrc/edit_distance.h) on ids packed by `pack_scoring`."""
+scores a whole batch with `Decoder.score_batch`, one HIP launch (csrc/edit_distance.h) on ids packed by `pack_scoring`.
+`CTCAligner.align` places a KNOWN transcript in time (csrc/ctc_align.h); its record assembly is the pure host function
+`assemble_alignments`."""
 from __future__ import annotations
 
 import numpy as np
@@ -219,6 +221,120 @@ class BeamCTCDecoder(Decoder):
         lens_h = host[2 * n:2 * n + B * K].view(B, K)
         self.last_scores = host[2 * n + B * K:].view(torch.float32).view(B, K).clone()
         return self.convert_to_strings(labels_h, lens_h), self.convert_tensor(offs_h, lens_h)
+
+
+def encode_transcripts(transcripts, labels):
+    """Transcripts (strings, or sequences of label ids) -> one list of ids each.  Strings are mapped through `labels` ({char: id} or a
+    sequence of characters); a character that is not a label raises ValueError naming it."""
+    char_to_int = labels if isinstance(labels, dict) else {c: i for i, c in enumerate(labels)}
+    out = []
+    for n, tr in enumerate(transcripts):
+        if isinstance(tr, str):
+            ids = []
+            for ch in tr:
+                if ch not in char_to_int:
+                    raise ValueError(f"transcript {n}: character {ch!r} is not in the labels")
+                ids.append(int(char_to_int[ch]))
+        else:
+            ids = [int(i) for i in (tr.tolist() if hasattr(tr, "tolist") else tr)]
+        out.append(ids)
+    return out
+
+
+def group_words(tokens):
+    """tokens [(char, start, end, logp, ...)] -> words [(word, start, end, logp)]: a word is the run of tokens between space tokens
+    (leading, trailing and doubled spaces make no word), from its first token's start to its last token's end, logp summed in fp64."""
+    words, run = [], []
+    for tok in list(tokens) + [(" ",)]:
+        if tok[0] == " ":
+            if run:
+                words.append(("".join(t[0] for t in run), run[0][1], run[-1][2], float(sum(np.float64(t[3]) for t in run))))
+            run = []
+        else:
+            run.append(tok)
+    return words
+
+
+def assemble_alignments(score, states, tok_start, tok_end, tok_logp, targets, sizes, int_to_char, space_index):
+    """Pure host half of CTCAligner.align: the kernel's raw arrays (score (B), states (B,T), tok_* flat over all targets, in target
+    order) + the targets (a list of id lists) and valid frame counts -> one record per utterance: {"score": float, "states": int tensor
+    (T_b), "tokens": [(char, start, end, logp)], "words": [(word, start, end, logp)]}.  An infeasible utterance (score -inf) has empty
+    states / tokens / words."""
+    score, states = np.asarray(score, np.float32), np.asarray(states, np.int32)
+    tok_start, tok_end, tok_logp = np.asarray(tok_start), np.asarray(tok_end), np.asarray(tok_logp, np.float32)
+    records, off = [], 0
+    for b, ids in enumerate(targets):
+        U = len(ids)
+        sc = float(score[b])
+        if sc == float("-inf"):
+            records.append({"score": sc, "states": torch.zeros(0, dtype=torch.int32), "tokens": [], "words": []})
+        else:
+            Tb = max(min(int(sizes[b]), states.shape[1]), 0)
+            tokens = [(" " if i == space_index else int_to_char.get(i, ""), int(tok_start[off + u]), int(tok_end[off + u]),
+                       float(tok_logp[off + u])) for u, i in enumerate(ids)]
+            records.append({"score": sc, "states": torch.from_numpy(states[b, :Tb].copy()), "tokens": tokens, "words": group_words(tokens)})
+        off += U
+    return records
+
+
+def add_seconds(records, frame_seconds):
+    """Every token and word tuple of the records gains (start_s, end_s) = (start, end) * frame_seconds."""
+    for r in records:
+        for key in ("tokens", "words"):
+            r[key] = [t + (t[1] * frame_seconds, t[2] * frame_seconds) for t in r[key]]
+    return records
+
+
+class CTCAligner(Decoder):
+    """CTC forced alignment: WHEN a known transcript was spoken.  `align` runs the Viterbi lattice, its backtrace and the token spans as
+    one HIP launch (`ds2_ctc_align_f32`, contract in include/ds2hip.h; restated by tests/ctc_align_oracle.py); the host packs the targets
+    and assembles the records.  The reference has no aligner and parity with any external one is not pinned."""
+
+    def __init__(self, labels, blank_index=0):
+        if blank_index != 0:
+            raise ValueError("CTCAligner: the alignment kernel takes class 0 as the blank (blank_index must be 0)")
+        super().__init__(labels, blank_index)
+        if self.int_to_char.get(self.space_index) != " ":
+            self.space_index = next((i for i, c in sorted(self.int_to_char.items()) if c == " "), -1)
+
+    def align(self, probs, sizes, transcripts, is_log=False, variant=0):
+        """probs (B,T,C) as decode() takes them (probabilities, or log-probabilities with is_log=True), sizes (B) valid frames or None,
+        transcripts: B strings (mapped through the labels) or id sequences.  One pinned upload of the packed targets, one launch, one
+        device-to-host copy.  Returns one record per utterance (assemble_alignments).  Host tensors are uploaded first: there is no CPU
+        implementation."""
+        from .. import ops
+        probs = torch.as_tensor(probs)
+        B, T = int(probs.shape[0]), int(probs.shape[1])
+        if len(transcripts) != B:
+            raise ValueError(f"{len(transcripts)} transcripts for a batch of {B}")
+        targets = encode_transcripts(transcripts, self.labels)
+        sizes_h = [T] * B if sizes is None else [int(v) for v in torch.as_tensor(sizes).reshape(-1).tolist()]
+        if len(sizes_h) != B:
+            raise ValueError(f"sizes has {len(sizes_h)} entries for a batch of {B}")
+        if not probs.is_cuda:
+            probs = probs.to(_device("CTCAligner", ".align"))
+        probs = probs.float()
+        if probs.stride(2) != 1:
+            probs = probs.contiguous()
+        dev = probs.device
+        lens = [len(t) for t in targets]
+        n_tok, max_u = sum(lens), max(lens, default=0)
+        # one int32 image: tgt_off, tgt_lens, in_lens, labels
+        host = torch.empty(3 * B + n_tok, dtype=torch.int32, pin_memory=True)
+        h = host.numpy()
+        h[:B] = np.cumsum([0] + lens[:-1]) if B else []
+        h[B:2 * B], h[2 * B:3 * B] = lens, np.clip(sizes_h, -1, T)
+        h[3 * B:] = [i for t in targets for i in t]
+        d = host.to(dev, non_blocking=True)
+        score, states, ts, te, lp = ops.ctc_forced_align(probs, d[3 * B:], d[:B], d[2 * B:3 * B], d[B:2 * B], max_u, is_log, variant)
+        out = torch.cat((score.view(torch.int32), states.reshape(-1), ts, te, lp.view(torch.int32))).cpu()
+        if ops.rnn_poison_seen(dev):
+            # as in GreedyDecoder.decode: a poisoned forward (a starved persistent recurrence launch) raises here
+            ops.rnn_persistent_check(dev)
+        o = out.numpy()
+        n = B + B * T
+        return assemble_alignments(o[:B].view(np.float32), o[B:n].reshape(B, T), o[n:n + n_tok], o[n + n_tok:n + 2 * n_tok],
+                                   o[n + 2 * n_tok:].view(np.float32), targets, sizes_h, self.int_to_char, self.space_index)
 
 
 def _device(who="GreedyDecoder", what=".decode"):

@@ -248,6 +248,19 @@ class DeepSpeech(nn.Module):
                 seq_len = (seq_len + 2 * m.padding[1] - m.dilation[1] * (m.kernel_size[1] - 1) - 1) / m.stride[1] + 1
         return seq_len.int()
 
+    # -- forced alignment (no counterpart in the reference) --------------------------------------
+    def align(self, inputs, input_sizes, transcripts):
+        """When each transcript was spoken: the eval-mode forward, then CTCAligner on its output.  inputs (B,1,F,T) and input_sizes
+        (B) as forward() takes them, transcripts B strings (or label-id sequences).  Returns CTCAligner.align's records with every
+        token and word tuple extended by (start_s, end_s): output frame t covers input frame 2t (the conv stack's time stride,
+        get_seq_lens), so seconds = frame * 2 * audio_conf.window_stride.  The model is left in eval mode."""
+        from ..decoders import CTCAligner, add_seconds
+        self.eval()
+        with torch.no_grad():
+            out, output_sizes = self.forward(inputs, input_sizes)
+            records = CTCAligner(self.labels).align(out, output_sizes, transcripts)
+        return add_seconds(records, 2.0 * float(self.audio_conf.window_stride))
+
     # -- evaluation loop (deepspeech.py:161-273) --------------------------------------------------
     def evaluate(self, loader=None, manifest=None, batch_size=None, device="auto", num_workers=32, verbose=False, half=False,
                  output_file=None, main_proc=True, **_unused):

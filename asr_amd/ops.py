@@ -1332,6 +1332,40 @@ def edit_distance(seq: Tensor, a_off, a_len, b_off, b_len, max_len: int | None =
     return dist
 
 
+def ctc_forced_align(x: Tensor, targets: Tensor, tgt_off: Tensor, in_lens: Tensor | None, tgt_lens: Tensor, max_u: int, is_log: bool,
+                     variant: int = 0):
+    """CTC forced alignment of x (B,T,C) fp32 on the GPU (any batch / frame strides, classes contiguous: the model's (T,B,C)-backed eval
+    output needs no copy) against known targets -> (score (B) f32, states (B,T) i32, tok_start, tok_end (sum U) i32, tok_logp (sum U)
+    f32), all on the GPU (contract: include/ds2hip.h, ds2_ctc_align_f32).  targets (flat), tgt_off, tgt_lens, in_lens (or None = T
+    frames each) are int32 device tensors; max_u >= every target length (host-known: nothing is copied back to size anything).
+    is_log: x holds log-probabilities (else probabilities).  variant: 0 = the library chooses, 1 = one wavefront per utterance
+    (2 * max_u + 1 <= 128), 2 = one workgroup per utterance.  One launch on the current stream."""
+    _chk_f32(x)
+    if x.dim() != 3 or x.stride(2) != 1:
+        raise ValueError("ctc_forced_align: x must be (B,T,C) with a contiguous class dim")
+    B, T, Cc = x.shape
+    dev = x.device
+    for name, t in (("targets", targets), ("tgt_off", tgt_off), ("tgt_lens", tgt_lens), ("in_lens", in_lens)):
+        if t is not None and (t.dtype != torch.int32 or t.device != dev or not t.is_contiguous()):
+            raise ValueError(f"ctc_forced_align: {name} must be a contiguous int32 tensor on {dev}")
+    if tgt_off.numel() != B or tgt_lens.numel() != B or (in_lens is not None and in_lens.numel() != B):
+        raise ValueError(f"ctc_forced_align: offsets / lengths do not match the batch of {B}")
+    n_tok = targets.numel()
+    score = torch.empty(B, dtype=torch.float32, device=dev)
+    states = torch.empty((B, T), dtype=torch.int32, device=dev)
+    tok_start = torch.empty(n_tok, dtype=torch.int32, device=dev)
+    tok_end = torch.empty(n_tok, dtype=torch.int32, device=dev)
+    tok_logp = torch.empty(n_tok, dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    wsb = lib.ds2_ctc_align_workspace_bytes(B, T, int(max_u))
+    ws = _ws(max(wsb, 1), dev)
+    _lib.check(lib.ds2_ctc_align_f32(x.data_ptr(), x.stride(0), x.stride(1), B, T, Cc, 1 if is_log else 0, _ptr(targets) if n_tok else None,
+                                     tgt_off.data_ptr(), _ptr(in_lens), tgt_lens.data_ptr(), int(max_u), int(variant), score.data_ptr(),
+                                     states.data_ptr(), _ptr(tok_start) if n_tok else None, _ptr(tok_end) if n_tok else None,
+                                     _ptr(tok_logp) if n_tok else None, ws.data_ptr(), wsb, _stream()), "ds2_ctc_align_f32")
+    return score, states, tok_start, tok_end, tok_logp
+
+
 def ctc_beam_decode(probs: Tensor, sizes: Tensor | None = None, blank: int = 0, beam_width: int = 100, cutoff_top_n: int = 40,
                     cutoff_prob: float = 1.0, lm=None, alpha: float = 0.0, beta: float = 0.0):
     """CTC prefix beam search of probs (B,T,C) fp32 on the GPU -> (labels (B,K,T) i32, offsets (B,K,T) i32, lengths (B,K) i32,

@@ -399,6 +399,41 @@ int ds2_ctc_loss_ex_f32(const float* logits, int ld, int T, int B, int C, const 
  * trainers/deepspeech_trainer.py:110-112 */
 int ds2_ctc_batch_mean_f32(const float* nll_dev, int B, float* out_dev, void* stream);
 
+/* CTC forced alignment: WHEN a known transcript was spoken.  The lattice of the loss over (max, +) instead of log-sum-exp, with
+ * back-pointers, the backtrace and the token spans in one launch (csrc/ctc_align.h).  The reference has no aligner: this text is the
+ * contract, restated in NumPy by tests/ctc_align_oracle.py.
+ * Inputs: x (B,T,C) fp32 with element strides ld_b, ld_t and C contiguous, as in the greedy decode (the model's (T,B,C)-backed eval
+ *  output and a contiguous (B,T,C) tensor both work without a copy).  is_log = 1: the emission is e = x (log-probabilities);
+ *  is_log = 0: e = log(x) (probabilities, log 0 = -inf), taken on the hardware log2 where the emission is loaded, not on the dependent
+ *  chain.  Blank is class 0.  targets / tgt_off / tgt_lens as in the loss call (flat int32 labels, tgt_off[b] the start of utterance b);
+ *  in_lens_dev (B) int32 valid frames T_b (clamped to T), or NULL = T frames for every utterance.  A target outside [1, C) makes its
+ *  utterance infeasible; nothing is read out of bounds.  NaN input is unspecified.
+ * States and recurrence: a target l[0..U) has S = 2U+1 states, state 2u blank, state 2u+1 the label l[u].
+ *  v[0][0] = e[0][blank], v[0][1] = e[0][l[0]], every other state -inf; for t >= 1
+ *    v[t][s] = max(v[t-1][s], v[t-1][s-1], v[t-1][s-2] if s is odd, s >= 3 and l[s>>1] != l[(s>>1)-1]) + e[t][class(s)]
+ *  in fp32: the max first, then ONE add, nothing else touches the values.  Back-pointer ties: the smallest move wins (stay beats
+ *  step beats skip).  The end state is S-1 or S-2, whichever is larger, a tie going to S-1; U = 0 has the single state 0.  Taken
+ *  together: among all optimal alignments, the one whose state sequence read from the last frame backwards is lexicographically
+ *  greatest.  With is_log = 1 every output is therefore pinned bit for bit by a float32 restatement.
+ * Outputs: score (B) the path's value; states (B,T) int32 the state per frame, -1 for t >= T_b; for every target token, in the flat
+ *  target order, tok_start / tok_end (end exclusive) the frames whose state is that token's, and tok_logp the fp32 sum of its emissions
+ *  in ascending t (the first emission, then one add per further frame).
+ * Edge cases: an infeasible utterance (optimum -inf, T_b below U plus the number of adjacent repeats, a bad label, T_b <= 0 with
+ *  U > 0, or tgt_lens[b] outside [0, max_target_len]) gets score -inf, states -1, token spans (-1, -1), tok_logp -inf; T_b <= 0 with
+ *  U = 0 gets score 0.  Nonzero return on bad arguments or when the workspace is too small (before any launch).
+ * Variants: 1 = one wavefront per utterance, the row in registers, two states per lane (only when 2*max_target_len+1 <= 128: nonzero
+ *  return otherwise); 2 = one workgroup per utterance, any target length that fits the LDS rows (beyond 1024 state pairs every thread
+ *  loops over its pairs); 0 = the library chooses (1 when it is valid).  All variants write the same bits.
+ * Workspace: the back-pointers, 2 bits per (frame, state), packed 8 frames of a state pair to a dword:
+ *  ds2_ctc_align_workspace_bytes = 4 * B * ceil(T/8) * (max_target_len+1), from host-known sizes only; tok_* hold sum(tgt_lens)
+ *  entries (they may be NULL when max_target_len == 0). */
+size_t ds2_ctc_align_workspace_bytes(int B, int T, int max_target_len);
+int ds2_ctc_align_f32(const float* x, long long ld_b, long long ld_t, int B, int T, int C, int is_log,
+                      const int* targets_dev, const int* tgt_off_dev, const int* in_lens_dev, const int* tgt_lens_dev,
+                      int max_target_len, int variant,
+                      float* score, int* states, int* tok_start, int* tok_end, float* tok_logp,
+                      void* ws, size_t ws_bytes, void* stream);
+
 /* softmax over the last dim (eval-mode InferenceBatchSoftmax, modules/blocks.py:59-64) */
 int ds2_softmax_rows_f32(const float* x, int ldx, float* y, int ldy, int rows, int C, void* stream);
 
