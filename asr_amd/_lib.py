@@ -149,6 +149,9 @@ SIGNATURES = {
     "ds2_tempo_workspace_bytes": (sz, [i32]),
     "ds2_tempo_gain_f32": (i32, [vp, i64, vp, vp, vp, i32, i32, f64, f64, f64, vp, i64, vp, vp, i32, vp, sz, vp]),
     "ds2_wave_unpack_f32": (i32, [vp, i64, i32, vp, vp, vp, i32, i32, vp, i64, vp]),
+    "ds2_resample_out_samples": (i64, [i64, i32, i32]),
+    "ds2_resample_tile_samples": (i32, []),
+    "ds2_wave_resample_f32": (i32, [vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, vp, i64, vp]),
     "ds2_adamw_f32": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, vp]),
     "ds2_adamw_gated_f32": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, vp, vp]),
     "ds2_scale_f32": (i32, [vp, i64, f32, vp]),

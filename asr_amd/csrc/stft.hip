@@ -476,3 +476,7 @@ extern "C" int ds2_wave_unpack_f32(const void* packed, long long packed_elems, i
   DS2_LAUNCH_CHECK("wave_unpack_kernel");
   return 0;
 }
+
+// ---- packed waveform feed: unpack with a sample-rate conversion in it (ds2_wave_resample_f32) --------------------------------------
+#define DS2_STFT_UNPACK_DEFS 1
+#include "resample.h"

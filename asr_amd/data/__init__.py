@@ -70,6 +70,31 @@ def _read_wav_raw(path):
     return sr, _mono_float32(y)
 
 
+def resample_waveform(y, fs, ft):
+    """Host sample-rate conversion, fs -> ft Hz: the sum of the ds2_wave_resample_f32 contract (include/ds2hip.h) — the same fp32 table
+    (ops.resample_taps), y[m] = sum_j tab[p][j] x[i0 - J + 1 + j] with i0 = (m M) div L, p = (m M) mod L, x = 0 outside the utterance —
+    in vectorised numpy fp64, rounded to fp32 once; ceil(n L / M) samples.  fs == ft returns the input's float32 samples bit for bit.
+    ValueError for an unsupported rate pair (ops.resample_ratio).  Used where there is no GPU batch: the noise bank and the host front-end."""
+    from .. import ops
+    y = np.ascontiguousarray(y, dtype=np.float32)
+    if y.ndim != 1:
+        raise ValueError(f"resample_waveform: expected a 1-D waveform, got shape {y.shape}")
+    L, M, J = ops.resample_ratio(fs, ft)
+    if L == 1 and M == 1:
+        return y
+    tab = ops.resample_taps(fs, ft).astype(np.float64)
+    n, P = len(y), 2 * J
+    n_out = -(-n * L // M)
+    x = np.concatenate([np.zeros(P, np.float64), y.astype(np.float64), np.zeros(P + 1, np.float64)])      # x[i] is at i + P
+    out = np.empty(n_out, dtype=np.float32)
+    j = np.arange(P, dtype=np.int64)[None, :]
+    for lo in range(0, n_out, 16384):
+        t = np.arange(lo, min(lo + 16384, n_out), dtype=np.int64) * M
+        i0, p = t // L, t % L                           # i0 - J + 1 >= -J + 1 and i0 + J <= n - 1 + J: inside the padding
+        out[lo:lo + len(t)] = (tab[p] * x[(i0 - J + 1 + P)[:, None] + j]).sum(axis=1)
+    return out
+
+
 def noise_levels_of(audio_conf):
     """(lo, hi) noise level range: audio_conf.noise_levels, else (noise_min, noise_max) — the keys of the reference's config.yml, on which
     the reference's own NoiseInjection(audio_conf.noise_levels) would fail — else the reference's default (0, 0.5)."""
@@ -97,13 +122,14 @@ class NoiseInjection:
     sorted, as librosa.util.find_files lists them) is read once with the scaling of SpectrogramDataset.parse_audio and the files are kept
     concatenated — `samples` (fp32, host) plus `starts` / `lengths` per file; `device_samples(device)` is the same bank in one device buffer
     (uploaded once per device) for GpuSpectrogramFrontEnd.  Other audio formats are skipped with a warning (no sox here: no decoding, no
-    resampling); files must be at `sample_rate`.
+    resampling); files must be at `sample_rate`, unless `resample=True`: an off-rate file is then converted once, here, on the host
+    (`resample_waveform`), so the bank, `starts` and `lengths` are at `sample_rate` and nothing downstream changes.
 
     `inject_noise(data)` keeps the reference's host method and its draws from numpy's global state (file, level ~ U(noise_levels), u ~ U[0,1));
     the mix is `data + level * seg * rms(data) / rms(seg)` with seg = noise[(s + j) mod L], s = noise_start(L, n, u); a silent segment leaves
     the data unmixed (the reference divides by zero there)."""
 
-    def __init__(self, path=None, sample_rate=16000, noise_levels=(0, 0.5)):
+    def __init__(self, path=None, sample_rate=16000, noise_levels=(0, 0.5), resample=False):
         if path is None or not os.path.exists(path):
             print("Directory doesn't exist: {}".format(path))
             raise IOError(f"noise directory does not exist: {path}")
@@ -124,7 +150,9 @@ class NoiseInjection:
         for f in self.paths:
             sr, y = _read_wav(f)
             if sr != self.sample_rate:
-                raise ValueError(f"NoiseInjection: {f} is sampled at {sr} Hz, expected {self.sample_rate} Hz (no resampling here)")
+                if not resample:
+                    raise ValueError(f"NoiseInjection: {f} is sampled at {sr} Hz, expected {self.sample_rate} Hz (no resampling here)")
+                y = resample_waveform(y, sr, self.sample_rate)   # once per off-rate file: the bank is at the target rate
             if len(y) == 0:
                 raise ValueError(f"NoiseInjection: {f} holds no samples")
             waves.append(y)
@@ -228,11 +256,12 @@ class GpuSpectrogramFrontEnd:
     The draws are made on the host from the front-end's own numpy Generator, in the order documented at `draw_augmentation`; `seed=None`
     takes the seed from numpy's global state (offset by the rank under torch.distributed; only when there is something to draw), a fixed
     seed gives bit-identical batches.
-    With augment=False (default) the output is that of the plain front-end."""
+    With augment=False (default) the output is that of the plain front-end.  `resample=True` lets the noise bank it builds from
+    audio_conf.noise_dir hold off-rate files (NoiseInjection(resample=True)); the front-end itself always works at audio_conf.sample_rate."""
 
     def __init__(self, audio_conf, normalize=False, pad_mode="constant", device=None, augment=False, seed=None, freq_mask_param=27,
                  time_mask_param=70, freq_masks=1, time_masks=1, noise=None, speed_volume_perturb=False, tempo_range=(0.85, 1.15),
-                 gain_range=(-6, 8)):
+                 gain_range=(-6, 8), resample=False):
         self.sample_rate = int(audio_conf.sample_rate)
         self.n_fft = int(audio_conf.sample_rate * audio_conf.window_size)
         self.hop = int(audio_conf.sample_rate * audio_conf.window_stride)
@@ -251,7 +280,7 @@ class GpuSpectrogramFrontEnd:
             self.freq_masks, self.time_masks = int(freq_masks), int(time_masks)
             self.spec_augment = bool(getattr(audio_conf, "spec_augment", False))
             if noise is None and getattr(audio_conf, "noise_dir", None) is not None:
-                noise = NoiseInjection(audio_conf.noise_dir, audio_conf.sample_rate, noise_levels_of(audio_conf))
+                noise = NoiseInjection(audio_conf.noise_dir, audio_conf.sample_rate, noise_levels_of(audio_conf), resample=resample)
             self.noise = noise
             self.noise_prob = float(getattr(audio_conf, "noise_prob", 0.4)) if noise is not None else 0.0
             if seed is None and (noise is not None or self.spec_augment or self.perturb):     # (nothing to draw: numpy's global state is left alone)
@@ -317,7 +346,7 @@ class GpuSpectrogramFrontEnd:
 
 
 class SpectrogramDataset(Dataset):
-    def __init__(self, audio_conf, manifest_filepath, labels, normalize=False, spec_augment=False, caching=False):
+    def __init__(self, audio_conf, manifest_filepath, labels, normalize=False, spec_augment=False, caching=False, resample=False):
         import pandas as pd
         self.df = pd.read_csv(manifest_filepath)
         self.size = len(self.df)
@@ -325,6 +354,7 @@ class SpectrogramDataset(Dataset):
             labels = dict([(v, k) for k, v in pd.read_csv(labels).to_dict()["label"].items()])
         self.labels_map = labels
         self.audio_conf, self.normalize, self.caching = audio_conf, normalize, caching
+        self.resample = bool(resample)                   # an off-rate WAV file is converted on the host (resample_waveform)
         self._cache = {}
         # spectrogram_parser.py:29-44 / :64-80: noise injection, tempo/gain perturbation and SpecAugment are host-side augmentations of
         # the reference's parser that this loader does not implement — say so instead of training silently without them
@@ -343,6 +373,8 @@ class SpectrogramDataset(Dataset):
             spect = torch.load(path).float()
         else:
             sr, y = _read_wav(path)
+            if self.resample and sr != self.audio_conf.sample_rate:
+                sr, y = int(self.audio_conf.sample_rate), resample_waveform(y, sr, self.audio_conf.sample_rate)
             assert sr == self.audio_conf.sample_rate, f"expected {self.audio_conf.sample_rate} Hz audio"
             spect = torch.from_numpy(_stft_spectrogram(y, sr, self.audio_conf.window_size, self.audio_conf.window_stride,
                                                        self.audio_conf.window))
@@ -372,16 +404,19 @@ class WaveformDataset(Dataset):
     """The dataset behind `get_loader(front_end="gpu")`: the manifest and labels of SpectrogramDataset, but an item is `(waveform (n,) float32
     CPU tensor, transcript ids)` — workers only read WAV files (same scaling as SpectrogramDataset.parse_audio) and transcripts; the
     spectrogram is made per batch on the GPU.  Pre-computed spectrograms (`.npy` / `.pt`) cannot be augmented as waveforms and are refused.
-    `caching=True` keeps waveforms, not spectrograms, so the augmentation is drawn anew every epoch."""
+    `caching=True` keeps waveforms, not spectrograms, so the augmentation is drawn anew every epoch.
+    `resample=True` accepts WAV files at any supported rate (ops.resample_ratio): the rate in the FILE HEADER counts, the manifest's `fq`
+    column is not trusted.  Raw items then carry it — `get_raw` returns `(samples, rate, ids)` and the loader converts the batch on the
+    GPU (ops.wave_resample) — while `__getitem__` returns the waveform converted on the host (`resample_waveform`)."""
 
-    def __init__(self, audio_conf, manifest_filepath, labels, caching=False, perturb=False):
+    def __init__(self, audio_conf, manifest_filepath, labels, caching=False, perturb=False, resample=False):
         import pandas as pd
         self.df = pd.read_csv(manifest_filepath)
         self.size = len(self.df)
         if isinstance(labels, str):
             labels = dict([(v, k) for k, v in pd.read_csv(labels).to_dict()["label"].items()])
         self.labels_map = labels
-        self.audio_conf, self.caching = audio_conf, caching
+        self.audio_conf, self.caching, self.resample = audio_conf, caching, bool(resample)
         self._cache, self._raw_cache = {}, {}
         for f in self.df.audio_filepath:
             if str(f).endswith((".npy", ".pt")):
@@ -396,7 +431,9 @@ class WaveformDataset(Dataset):
     def parse_audio(self, path):
         sr, y = _read_wav(path)
         if sr != self.audio_conf.sample_rate:
-            raise ValueError(f"{path}: {sr} Hz, expected {self.audio_conf.sample_rate} Hz audio")
+            if not self.resample:
+                raise ValueError(f"{path}: {sr} Hz, expected {self.audio_conf.sample_rate} Hz audio")
+            y = resample_waveform(y, sr, self.audio_conf.sample_rate)
         return torch.from_numpy(np.ascontiguousarray(y, dtype=np.float32))
 
     def __getitem__(self, index):
@@ -412,18 +449,25 @@ class WaveformDataset(Dataset):
         return self.size
 
     def parse_audio_raw(self, path):
-        """`parse_audio` for the packed feed: a numpy array, int16 for a 16-bit mono file (its raw samples), float32 otherwise."""
+        """`parse_audio` for the packed feed: a numpy array, int16 for a 16-bit mono file (its raw samples), float32 otherwise; with
+        resample=True `(array, rate of the file header)`, the samples untouched."""
         sr, y = _read_wav_raw(path)
+        if self.resample:
+            from .. import ops
+            ops.resample_ratio(sr, self.audio_conf.sample_rate)        # ValueError for a pair the resampler does not support
+            return np.ascontiguousarray(y), int(sr)
         if sr != self.audio_conf.sample_rate:
             raise ValueError(f"{path}: {sr} Hz, expected {self.audio_conf.sample_rate} Hz audio")
         return np.ascontiguousarray(y)
 
     def get_raw(self, index):
-        """Item `index` as `(parse_audio_raw's array, transcript ids)`; `caching=True` keeps these arrays (a cache of their own)."""
+        """Item `index` as `(parse_audio_raw's array, transcript ids)`, with resample=True `(samples, rate, transcript ids)`; `caching=True`
+        keeps these arrays (a cache of their own)."""
         if self.caching and index in self._raw_cache:
             return self._raw_cache[index]
         row = self.df.iloc[index]
-        item = (self.parse_audio_raw(row.audio_filepath), self.parse_transcript(row.text))
+        audio = self.parse_audio_raw(row.audio_filepath)
+        item = (*audio, self.parse_transcript(row.text)) if self.resample else (audio, self.parse_transcript(row.text))
         if self.caching:
             self._raw_cache[index] = item
         return item
@@ -470,7 +514,13 @@ def pack_waveforms(batch):
     """Worker-side collate_fn of the packed feed (a pure host function): a list of `(samples, transcript)` items, samples a 1-D int16 or
     float32 array, -> `(buffer, offsets, lengths, transcripts)`: ONE ragged 1-D tensor per batch, laid out by `packed_layout` (gaps are
     zero), int16 when EVERY item is int16 (raw 16-bit mono PCM), else float32 with the int16 items scaled like `_read_wav` does
-    (/ 32768) — so both buffers unpack to the bits of the per-item float32 path; offsets, lengths: (B,) int64 numpy arrays."""
+    (/ 32768) — so both buffers unpack to the bits of the per-item float32 path; offsets, lengths: (B,) int64 numpy arrays.
+    Items that carry their sample rate, `(samples, rate, transcript)` (WaveformDataset(resample=True)), give a fifth field: rates, (B,)
+    int64.  All items of a batch have the same form."""
+    if len({len(item) for item in batch}) > 1:
+        raise ValueError("pack_waveforms: items with and without a sample rate in one batch")
+    rates = np.array([item[1] for item in batch], dtype=np.int64) if batch and len(batch[0]) == 3 else None
+    batch = [(item[0], item[-1]) for item in batch]
     waves = [np.asarray(w) for w, _ in batch]
     for w in waves:
         if w.ndim != 1 or w.dtype not in (np.int16, np.float32):
@@ -481,7 +531,8 @@ def pack_waveforms(batch):
     buf = np.zeros(total, dtype=dtype)
     for w, o in zip(waves, offsets.tolist()):
         buf[o:o + len(w)] = w if w.dtype == dtype else w.astype(np.float32) / 32768.0
-    return torch.from_numpy(buf), offsets, lengths, [t for _, t in batch]
+    packed = (torch.from_numpy(buf), offsets, lengths, [t for _, t in batch])
+    return packed if rates is None else packed + (rates,)
 
 
 class _FeedEnd:
@@ -498,7 +549,7 @@ def _feed_batches(batches, device, depth, put, stop):
     k = 0
     while not stop.is_set():
         try:
-            buf, offsets, lengths, transcripts = next(batches)
+            buf, *fields = next(batches)                # (offsets, lengths, transcripts[, rates])
         except StopIteration:
             return
         nbytes = buf.numel() * buf.element_size()
@@ -515,7 +566,7 @@ def _feed_batches(batches, device, depth, put, stop):
             dev.copy_(host, non_blocking=True)
             copied.record(stream)
         slot[1] = copied
-        if not put((dev, copied, offsets, lengths, transcripts)):
+        if not put((dev, copied, *fields)):
             return
         del buf, dev
         k += 1
@@ -524,7 +575,7 @@ def _feed_batches(batches, device, depth, put, stop):
 def _feed(batches, device, depth, out, stop):
     """Body of the feeder thread: packed host batches -> a ring of depth + 1 pinned buffers (grown on demand, a slot reused only after
     its copy event) -> asynchronous copies on a copy stream of its own -> `out`, a queue of (device buffer, copy event, offsets, lengths,
-    transcripts).  No random draw and no kernel here: only host copies and host-to-device copies."""
+    transcripts[, rates]).  No random draw and no kernel here: only host copies and host-to-device copies."""
     import queue
     import traceback
 
@@ -601,11 +652,17 @@ class GpuAudioDataLoader:
     buffer (`pack_waveforms`: raw int16 PCM when every file is 16-bit mono), a feeder thread per iterator copies it through a ring of
     N + 1 pinned buffers to the device on a copy stream of its own, up to N batches ahead, and the consumer — `next()`, on the caller's
     current stream — makes ALL the draws, waits for the copy event, unpacks (ops.wave_unpack: scale, sort, zero padding) and runs the same
-    front-end kernels, in order between the train steps; only host work and the host-to-device copy overlap a step."""
+    front-end kernels, in order between the train steps; only host work and the host-to-device copy overlap a step.
+
+    A dataset with `resample=True` hands over files at their own rates.  The lengths at the front-end's rate, ceil(n L / M), are computed
+    on the host first — tempo draws, the sort and input_percentages all use them — and the batch is converted where it is unpacked
+    (ops.wave_resample in place of ops.wave_unpack; a batch whose files are all at the target rate still takes ops.wave_unpack, so it is
+    bit-identical to the resample=False batch).  `prefetch=0` then packs on the host too (`pack_waveforms`) and takes the same route."""
 
     def __init__(self, dataset, batch_sampler, num_workers, front_end, prefetch=0):
         self.dataset, self.batch_sampler, self.front_end, self.prefetch = dataset, batch_sampler, front_end, int(prefetch)
-        if self.prefetch:
+        self.resample = bool(getattr(dataset, "resample", False))
+        if self.prefetch or self.resample:
             self.loader = DataLoader(dataset.raw_items(), num_workers=num_workers, batch_sampler=batch_sampler, collate_fn=pack_waveforms)
         else:
             self.loader = DataLoader(dataset, num_workers=num_workers, batch_sampler=batch_sampler, collate_fn=_waveform_batch)
@@ -644,18 +701,29 @@ class GpuAudioDataLoader:
         inputs, _ = self.front_end([w for w, _ in batch], perturb=perturb)
         return self._batch(inputs, lengths, [t for _, t in batch])
 
-    def collate_packed(self, packed, offsets, lengths, transcripts):
+    def collate_packed(self, packed, offsets, lengths, transcripts, rates=None):
         """`collate` for a packed batch whose buffer is on the device: the same draws in the same order, the sort as the unpack
-        kernel's row index."""
+        kernel's row index.  `rates`: the files' sample rates when the dataset resamples (None: all at the front-end's rate)."""
         from .. import ops
         raw = [int(v) for v in lengths]
-        order, lengths, perturb = self._sort(raw)
-        n_in = [raw[i] for i in order]
-        waves = ops.wave_unpack(packed, offsets, raw, order, max(n_in))
+        target = self.front_end.sample_rate
+        convert = rates is not None and any(int(r) != target for r in rates)
+        at_target = [ops.resample_out_samples(n, r, target) for n, r in zip(raw, rates)] if convert else raw
+        order, lengths, perturb = self._sort(at_target)
+        n_in = [at_target[i] for i in order]
+        if convert:
+            waves, _ = ops.wave_resample(packed, offsets, raw, [int(r) for r in rates], order, target, max(n_in), n_out=at_target)
+        else:
+            waves = ops.wave_unpack(packed, offsets, raw, order, max(n_in))
         inputs, _ = self.front_end.from_device_batch(waves, n_in, perturb=perturb)
         return self._batch(inputs, lengths, [transcripts[i] for i in order])
 
     def __iter__(self):
+        if not self.prefetch and self.resample:          # synchronous, but packed on the host and converted by the same kernel
+            dev = self.front_end._dev()
+            for buf, *fields in self.loader:
+                yield self.collate_packed(buf.to(dev), *fields)
+            return
         if not self.prefetch:
             for batch in self.loader:
                 yield self.collate(batch)
@@ -671,10 +739,10 @@ class GpuAudioDataLoader:
                 item = feeder.get()
                 if item is None:
                     return
-                packed, copied, offsets, lengths, transcripts = item
+                packed, copied, *fields = item
                 stream = torch.cuda.current_stream(dev)
                 stream.wait_event(copied)
-                out = self.collate_packed(packed, offsets, lengths, transcripts)
+                out = self.collate_packed(packed, *fields)
                 packed.record_stream(stream)             # allocated on the copy stream, read by the unpack kernel on this one
                 del item, packed
                 yield out
@@ -893,7 +961,7 @@ class AudioDataLoader(DataLoader):
 
 
 def get_loader(audio_conf, labels, manifest, batch_size, num_workers, caching=False, length_bucketing=False, front_end="host",
-               perturb=False, prefetch=0):
+               perturb=False, prefetch=0, resample=False):
     """data/loaders/functional.py:6-24.  `length_bucketing=True` (not in the reference) sorts the manifest by its `duration` column
     before binning (LengthBucketingSampler; the distributed variant when torch.distributed is initialised).
 
@@ -911,7 +979,13 @@ def get_loader(audio_conf, labels, manifest, batch_size, num_workers, caching=Fa
     and runs the same front-end kernels on the caller's stream.  Every batch is bit-identical to the `prefetch=0` batch for the same
     seeds; the sampler's draws from numpy's global state are made up to N batches early, so code that draws from that state inside the
     loop sees them interleaved differently.  Leaving the loop early stops the thread and the workers; a worker's error is raised by
-    `next()`."""
+    `next()`.
+    `resample=True` (default False: a file at another rate is an error) accepts WAV files at any supported rate — the rate of the file
+    header, a ratio to audio_conf.sample_rate in [1/8, 8] with a small enough polyphase table (ops.resample_ratio; 48, 44.1, 22.05 and
+    8 kHz against 16 kHz are) — and converts each to audio_conf.sample_rate by Kaiser-windowed sinc interpolation: with front_end="gpu"
+    per batch on the GPU, fused into the unpack pass (ops.wave_resample), ahead of the unchanged tempo, noise, STFT and SpecAugment
+    kernels, for `prefetch=0` too; the noise bank converts its off-rate files once; with front_end="host" per item in the workers
+    (`resample_waveform`).  Parity with sox / ffmpeg is unpinned."""
     if front_end not in ("host", "gpu"):
         raise ValueError(f"front_end={front_end!r}: expected host or gpu")
     if perturb and front_end != "gpu":
@@ -921,12 +995,13 @@ def get_loader(audio_conf, labels, manifest, batch_size, num_workers, caching=Fa
     if prefetch and front_end != "gpu":
         raise ValueError("prefetch needs front_end='gpu' (the host front-end's batches are made in the workers already)")
     if front_end == "gpu":
-        dataset = WaveformDataset(audio_conf=audio_conf, manifest_filepath=manifest, labels=labels, caching=caching, perturb=perturb)
-        fe = GpuSpectrogramFrontEnd(audio_conf, normalize=True, augment=True, speed_volume_perturb=perturb)
+        dataset = WaveformDataset(audio_conf=audio_conf, manifest_filepath=manifest, labels=labels, caching=caching, perturb=perturb,
+                                  resample=bool(resample))
+        fe = GpuSpectrogramFrontEnd(audio_conf, normalize=True, augment=True, speed_volume_perturb=perturb, resample=bool(resample))
         make = lambda sampler: GpuAudioDataLoader(dataset, sampler, num_workers, fe, prefetch=int(prefetch))      # noqa: E731
     else:
         dataset = SpectrogramDataset(audio_conf=audio_conf, manifest_filepath=manifest, labels=labels, normalize=True,
-                                     spec_augment=getattr(audio_conf, "spec_augment", False), caching=caching)
+                                     spec_augment=getattr(audio_conf, "spec_augment", False), caching=caching, resample=bool(resample))
         make = lambda sampler: AudioDataLoader(dataset, num_workers=num_workers, batch_sampler=sampler)   # noqa: E731
     if length_bucketing and torch.distributed.is_available() and torch.distributed.is_initialized():
         sampler = DistributedLengthBucketingSampler(dataset, batch_size=batch_size)

@@ -1602,6 +1602,144 @@ def wave_unpack(packed: Tensor, offsets, lengths, src_index=None, n_max: Optiona
     return out
 
 
+RESAMPLE_ZEROS, RESAMPLE_ROLLOFF, RESAMPLE_BETA = 32, 0.945, 9.0
+RESAMPLE_MAX_RATIO = 8             # fs / ft and ft / fs
+RESAMPLE_MAX_TAPS = 2 ** 18        # L * P of one rate pair (1 MiB of fp32)
+RESAMPLE_MAX_TABLE = 2 ** 22       # the concatenated tables of one call (the C ABI's limit)
+
+_TAPS_CACHE = {}
+_TAPS_DEVICE_CACHE = {}
+
+
+def resample_ratio(fs: int, ft: int, zeros: int = RESAMPLE_ZEROS, rolloff: float = RESAMPLE_ROLLOFF) -> Tuple[int, int, int]:
+    """(L, M, J) of a rate pair: L = ft / gcd, M = fs / gcd, J = ceil(zeros / (rolloff * min(1, L / M))) taps per side.  ValueError for a
+    pair outside what the resampler supports: a ratio outside [1/8, 8] or a table of more than RESAMPLE_MAX_TAPS taps."""
+    import math
+    if isinstance(fs, bool) or isinstance(ft, bool) or int(fs) != fs or int(ft) != ft or fs < 1 or ft < 1:
+        raise ValueError(f"resample: sample rates are positive integers, got {fs!r} -> {ft!r}")
+    fs, ft = int(fs), int(ft)
+    g = math.gcd(fs, ft)
+    L, M = ft // g, fs // g
+    if M > RESAMPLE_MAX_RATIO * L or L > RESAMPLE_MAX_RATIO * M:
+        raise ValueError(f"resample: {fs} Hz -> {ft} Hz is outside the supported ratios [1/{RESAMPLE_MAX_RATIO}, {RESAMPLE_MAX_RATIO}]")
+    if L == 1 and M == 1:
+        return 1, 1, 0
+    J = int(math.ceil(zeros / (rolloff * min(1.0, L / M))))
+    if L * 2 * J > RESAMPLE_MAX_TAPS:
+        raise ValueError(f"resample: {fs} Hz -> {ft} Hz needs a table of {L} x {2 * J} taps, more than the {RESAMPLE_MAX_TAPS} supported "
+                         "(rates with a large common divisor, such as 48000, 44100, 22050 or 8000 Hz against 16000 Hz, are)")
+    return L, M, J
+
+
+def resample_taps(fs: int, ft: int, zeros: int = RESAMPLE_ZEROS, rolloff: float = RESAMPLE_ROLLOFF, beta: float = RESAMPLE_BETA):
+    """The (L, P = 2 J) fp32 polyphase table of the contract in include/ds2hip.h (a host numpy array, cached per argument tuple):
+    tab[p][j] = fp32(s sinc(s tau) w(tau)), tau = p / L + J - 1 - j, s = rolloff min(1, L / M), w the Kaiser window of half-width
+    zeros / s — computed in fp64, rounded once.  fs == ft has no table: ValueError."""
+    import numpy as np
+    key = (int(fs), int(ft), int(zeros), float(rolloff), float(beta))
+    if key not in _TAPS_CACHE:
+        L, M, J = resample_ratio(fs, ft, zeros, rolloff)
+        if L == 1 and M == 1:
+            raise ValueError("resample_taps: equal rates are copied, there is no table")
+        s = rolloff * min(1.0, L / M)
+        tau = np.arange(L, dtype=np.float64)[:, None] / L + (J - 1 - np.arange(2 * J, dtype=np.float64))[None, :]
+        r = tau * s / zeros
+        w = np.where(np.abs(r) <= 1.0, np.i0(beta * np.sqrt(np.maximum(1.0 - r * r, 0.0))) / np.i0(beta), 0.0)
+        tab = np.ascontiguousarray((s * np.sinc(s * tau) * w).astype(np.float32))
+        tab.setflags(write=False)
+        _TAPS_CACHE[key] = tab
+    return _TAPS_CACHE[key]
+
+
+def resample_out_samples(n: int, fs: int, ft: int) -> int:
+    """ceil(n L / M): the length of an n-sample utterance at fs after conversion to ft (ds2_resample_out_samples; a host function)."""
+    import math
+    g = math.gcd(int(fs), int(ft))
+    n_out = _lib.load().ds2_resample_out_samples(int(n), int(ft) // g, int(fs) // g)
+    if n_out < 0:
+        raise _lib.DS2LibraryError(f"resample_out_samples: n = {n} (0 .. 2^31), {fs} Hz -> {ft} Hz outside the contract")
+    return int(n_out)
+
+
+def _resample_tables(pairs, device):
+    """(table buffer, {pair: base}) on `device` covering the rate pairs of one call.  ONE buffer per device holds the tables of every
+    pair seen so far, in order of first use (so it is bounded by RESAMPLE_MAX_TABLE taps = 16 MiB however the rates mix in the batches);
+    a new pair makes a longer buffer, the old one stays alive for the launches that hold it.  No pair: (None, {})."""
+    import numpy as np
+    key = str(device)
+    buf, bases = _TAPS_DEVICE_CACHE.get(key, (None, {}))
+    new = [p for p in pairs if p not in bases]
+    if new:
+        order = list(bases) + new
+        tabs = [resample_taps(fs, ft) for fs, ft in order]
+        starts = np.concatenate([[0], np.cumsum([t.size for t in tabs])]).astype(np.int64)
+        if int(starts[-1]) > RESAMPLE_MAX_TABLE:
+            raise ValueError(f"wave_resample: the tables of the {len(order)} rate pairs seen on {key} hold {int(starts[-1])} taps, "
+                             f"at most {RESAMPLE_MAX_TABLE}")
+        buf = torch.from_numpy(np.concatenate([t.reshape(-1) for t in tabs])).to(device)
+        bases = {p: int(b) for p, b in zip(order, starts[:-1])}
+        _TAPS_DEVICE_CACHE[key] = (buf, bases)
+    return buf, bases
+
+
+def wave_resample(packed: Tensor, offsets, lengths, rates, src_index=None, target_rate: int = 16000, n_out_max: Optional[int] = None,
+                  n_out=None):
+    """`wave_unpack` with a sample-rate conversion in it (ds2_wave_resample_f32, contract in include/ds2hip.h): utterance u, `lengths[u]`
+    samples at `rates[u]` Hz, becomes ceil(n L / M) samples at `target_rate` by Kaiser-windowed sinc interpolation; an utterance already
+    at the target rate is copied bit for bit.  packed, offsets, lengths, src_index as in `wave_unpack`; rates: (B) HOST integers.
+    The description is checked here, on the host (ValueError, wave_unpack's cases plus an unsupported rate pair), the tables are built
+    once per rate pair and device, everything is sized on the host and uploaded from pinned memory with one asynchronous copy: nothing is
+    copied back.  `n_out`: the resampled lengths when the caller has them already (resample_out_samples per utterance; the loader has).
+    Returns (batch (B, n_out_max) fp32 GPU in src_index order, n_out: a list of B ints in UTTERANCE order)."""
+    import numpy as np
+    if packed.dtype not in (torch.int16, torch.float32) or not packed.is_cuda or packed.dim() != 1 or not packed.is_contiguous():
+        raise ValueError("wave_resample: packed must be a contiguous 1-D int16 or fp32 GPU tensor")
+    off = np.asarray(offsets.tolist() if isinstance(offsets, Tensor) else offsets, dtype=np.int64).reshape(-1)
+    ln = np.asarray(lengths.tolist() if isinstance(lengths, Tensor) else lengths, dtype=np.int64).reshape(-1)
+    fs = [int(v) for v in (rates.tolist() if isinstance(rates, (Tensor, np.ndarray)) else rates)]
+    B, total = int(ln.size), int(packed.numel())
+    src = np.arange(B, dtype=np.int64) if src_index is None else np.asarray(
+        src_index.tolist() if isinstance(src_index, Tensor) else src_index, dtype=np.int64).reshape(-1)
+    if B == 0 or off.size != B or src.size != B or len(fs) != B:
+        raise ValueError(f"wave_resample: offsets ({off.size}), lengths ({B}), rates ({len(fs)}) and src_index ({src.size}): one value per "
+                         "utterance, at least one")
+    if total % WAVE_ALIGN or total > WAVE_MAX_ELEMS:
+        raise ValueError(f"wave_resample: packed holds {total} elements: a multiple of {WAVE_ALIGN}, at most 2^31 - 1")
+    if (off < 0).any() or (off % WAVE_ALIGN).any():
+        raise ValueError(f"wave_resample: every offset is a non-negative multiple of {WAVE_ALIGN} elements, got {off.tolist()}")
+    if (ln < 0).any():
+        raise ValueError(f"wave_resample: negative length in {ln.tolist()}")
+    if (off + (ln + WAVE_ALIGN - 1) // WAVE_ALIGN * WAVE_ALIGN > total).any():
+        raise ValueError(f"wave_resample: an utterance (rounded up to {WAVE_ALIGN} elements) ends beyond the {total} packed elements")
+    if (src < 0).any() or (src >= B).any():
+        raise ValueError(f"wave_resample: src_index outside [0, {B})")
+    target_rate = int(target_rate)
+    lmj = {r: resample_ratio(r, target_rate) for r in sorted(set(fs))}
+    if n_out is None:
+        n_out = [resample_out_samples(n, r, target_rate) for n, r in zip(ln.tolist(), fs)]
+    n_out = [int(v) for v in n_out]
+    if len(n_out) != B or any(v != -(-n * lmj[r][0] // lmj[r][1]) for v, n, r in zip(n_out, ln.tolist(), fs)):
+        raise ValueError("wave_resample: n_out must be ceil(n L / M) per utterance")
+    if n_out_max is None:
+        n_out_max = max(n_out)
+    n_out_max = int(n_out_max)
+    if max(n_out) > n_out_max or n_out_max > 2 ** 30:
+        raise ValueError(f"wave_resample: resampled lengths lie in [0, n_out_max = {n_out_max}] and n_out_max <= 2^30, got {n_out}")
+    dev = packed.device
+    if n_out_max == 0:
+        return torch.zeros((B, 0), dtype=torch.float32, device=dev), n_out
+    tab, bases = _resample_tables(tuple((r, target_rate) for r in lmj if lmj[r][:2] != (1, 1)), dev)
+    rows = [off, ln, src, [lmj[r][0] for r in fs], [lmj[r][1] for r in fs], [lmj[r][2] for r in fs],
+            [bases.get((r, target_rate), 0) for r in fs]]
+    meta = torch.from_numpy(np.stack([np.asarray(r, dtype=np.int64) for r in rows]).astype(np.int32)).pin_memory().to(dev, non_blocking=True)
+    out = torch.empty((B, n_out_max), dtype=torch.float32, device=dev)
+    _lib.check(_lib.load().ds2_wave_resample_f32(packed.data_ptr() if total else None, total, 0 if packed.dtype == torch.int16 else 1,
+                                                 *[meta[i].data_ptr() for i in range(7)], tab.data_ptr() if tab is not None else None,
+                                                 tab.numel() if tab is not None else 0, B, n_out_max, out.data_ptr(), out.stride(0),
+                                                 _stream()), "ds2_wave_resample_f32")
+    return out, n_out
+
+
 # ------------------------------------------------------------------------------------------------
 # optimizer
 # ------------------------------------------------------------------------------------------------

@@ -622,6 +622,39 @@ int ds2_tempo_gain_f32(const float* audio, long long ld_audio, const int* n_samp
 int ds2_wave_unpack_f32(const void* packed, long long packed_elems, int dtype, const int* offsets_dev, const int* lengths_dev,
                         const int* src_index_dev, int B, int n_max, float* out, long long ld_out, void* stream);
 
+/* ---- sample-rate conversion in the packed waveform feed (get_loader(front_end="gpu", resample=True)) -----------
+ * The reference converts its corpus outside the loader: audio/wav_converter.py runs `ffmpeg -ar 16000` over every file and audio_with_sox
+ * (audio/functional.py) `sox -r` per noise segment.  Neither tool is part of the reference tree: PARITY WITH SOX AND FFMPEG IS UNPINNED.
+ * The contract below — band-limited sinc interpolation with a Kaiser window — is what tests/resample_oracle.py restates.
+ * Per utterance: source rate fs, target rate ft, g = gcd(fs, ft), L = ft / g, M = fs / g; x[0..n), reads outside [0, n) give 0.
+ *  n_out = ceil(n L / M) in 64-bit integers (ds2_resample_out_samples, a host function; -1 for n outside [0, 2^31] or L, M < 1).
+ *  Output sample m sits at input time m M / L: i0 = (m M) div L, phase p = (m M) mod L, exact integers, and
+ *      y[m] = sum_{j in [0, P)} tab[p][j] * x[i0 - J + 1 + j],   P = 2 J.
+ *  The table is the CALLER's (asr_amd.ops.resample_taps builds it in fp64 and rounds to fp32, as dft_basis does for the STFT):
+ *      tab[p][j] = fp32( s sinc(s tau) w(tau) ),  tau = p / L + J - 1 - j,  sinc(t) = sin(pi t) / (pi t),
+ *      s = rolloff min(1, L / M),  J = ceil(zeros / s),  w(tau) = I0(beta sqrt(1 - (tau s / zeros)^2)) / I0(beta) for |tau| <= zeros / s, else 0;
+ *  defaults zeros = 32, rolloff = 0.945, beta = 9.0 (P = 204, 188, 94, 68 for 48, 44.1, 22.05 and 8 kHz -> 16 kHz).
+ *  The device accumulates in fp32, j ascending, one fused multiply-add per tap; no atomics, reruns are bit-identical.
+ *  An utterance with L = M = 1 is copied bit for bit (its J and tab_base are not used).
+ * ds2_wave_resample_f32 is the ds2_wave_unpack_f32 contract with more arguments.  Unchanged: packed / packed_elems / dtype (int16 scaled
+ *  by 2^-15), the 8-element ALIGNMENT RULE, offsets_dev, lengths_dev (SOURCE samples), src_index_dev.  New: L_dev, M_dev, J_dev,
+ *  tab_base_dev, (B) int32 DEVICE arrays indexed by utterance like offsets; tab (tab_elems) fp32 device, the concatenated tables:
+ *  utterance u reads tab[tab_base[u] + p * 2 J[u] + j]; out (B, ld_out) fp32 device, ld_out >= n_out_max: row b holds the resampled
+ *  utterance u = src_index[b] in [0, n_out_u) and exact zeros in [n_out_u, n_out_max); columns n_out_max .. ld_out are not written.
+ *  Rejected (non-zero, nothing launched): everything ds2_wave_unpack_f32 rejects (n_out_max in place of n_max: outside [0, 2^30]), a null
+ *  per-utterance array, tab_elems outside [0, 2^22], a null tab with tab_elems > 0, a tab that is not 4-byte aligned.
+ *  The per-utterance arrays live on the device, so the CALLER checks them (asr_amd.ops.wave_resample does, on the host values it uploads);
+ *  the kernel re-checks each row it is given — the ds2_wave_unpack_f32 row checks, 1 <= L, M <= 2^16 with M <= 8 L and L <= 8 M, and unless
+ *  L = M = 1: 1 <= J <= 512, tab_base >= 0, tab_base + L * 2 J <= tab_elems; n_out in [0, n_out_max] — and writes a row that fails as
+ *  zeros: nothing outside the three buffers is read or written.
+ *  One kernel (wave_resample_kernel, csrc/resample.h): one workgroup per (row, tile of ds2_resample_tile_samples() outputs), the
+ *  tile's input window staged once in LDS. */
+long long ds2_resample_out_samples(long long n, int L, int M);
+int ds2_resample_tile_samples(void);
+int ds2_wave_resample_f32(const void* packed, long long packed_elems, int dtype, const int* offsets_dev, const int* lengths_dev,
+                          const int* src_index_dev, const int* L_dev, const int* M_dev, const int* J_dev, const int* tab_base_dev,
+                          const float* tab, long long tab_elems, int B, int n_out_max, float* out, long long ld_out, void* stream);
+
 /* ---- optimizer ----------------------------------------------------------------------------------
  * torch.optim.AdamW.step over one flat parameter buffer, trainers/__main__.py:41-47. */
 int ds2_adamw_f32(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps,
