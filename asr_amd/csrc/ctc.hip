@@ -488,3 +488,5 @@ extern "C" int ds2_ctc_loss_f32(const float* logits, int ld, int T, int B, int C
 // and is compiled in this translation unit, next to the lattice helpers it shares (wave_shift1, WPF, NEG_INF).
 #define DS2_CTC_ALIGN_TU
 #include "ctc_align.h"
+// ... and its tiled form for long recordings (ds2_ctc_align_tiled_*), which shares the cell, the emission and the back-pointer layout
+#include "ctc_align_tiled.h"

@@ -301,7 +301,8 @@ class CTCAligner(Decoder):
         """probs (B,T,C) as decode() takes them (probabilities, or log-probabilities with is_log=True), sizes (B) valid frames or None,
         transcripts: B strings (mapped through the labels) or id sequences.  One pinned upload of the packed targets, one launch, one
         device-to-host copy.  Returns one record per utterance (assemble_alignments).  Host tensors are uploaded first: there is no CPU
-        implementation."""
+        implementation.  variant 0 - 2 as ops.ctc_forced_align takes them (one launch, targets up to about 3 275 labels); variant 3
+        is ops.ctc_forced_align_tiled with the default tiles: the same records for a recording and a transcript of any length."""
         from .. import ops
         probs = torch.as_tensor(probs)
         B, T = int(probs.shape[0]), int(probs.shape[1])
@@ -326,7 +327,10 @@ class CTCAligner(Decoder):
         h[B:2 * B], h[2 * B:3 * B] = lens, np.clip(sizes_h, -1, T)
         h[3 * B:] = [i for t in targets for i in t]
         d = host.to(dev, non_blocking=True)
-        score, states, ts, te, lp = ops.ctc_forced_align(probs, d[3 * B:], d[:B], d[2 * B:3 * B], d[B:2 * B], max_u, is_log, variant)
+        if variant == 3:                                 # the tiled lattice (ds2_ctc_align_tiled_f32, default tiles): any T, any target length
+            score, states, ts, te, lp = ops.ctc_forced_align_tiled(probs, d[3 * B:], d[:B], d[2 * B:3 * B], d[B:2 * B], max_u, is_log)
+        else:
+            score, states, ts, te, lp = ops.ctc_forced_align(probs, d[3 * B:], d[:B], d[2 * B:3 * B], d[B:2 * B], max_u, is_log, variant)
         out = torch.cat((score.view(torch.int32), states.reshape(-1), ts, te, lp.view(torch.int32))).cpu()
         if ops.rnn_poison_seen(dev):
             # as in GreedyDecoder.decode: a poisoned forward (a starved persistent recurrence launch) raises here

@@ -47,3 +47,29 @@ def check_loss(loss, loss_value):
     if loss_value < 0:
         return False, "WARNING: received a negative loss"
     return True, ""
+
+
+def long_windows(n_frames, window, overlap):
+    """Cut a recording of n_frames input (spectrogram) frames into overlapping windows for DeepSpeech.posteriors_long (no counterpart in
+    the reference).  window and overlap are in input frames, both even, window > 2 * overlap; hop = window - 2 * overlap, window i
+    starts at i * hop, and the last window is the first one with start + window >= n_frames.  Returns one tuple
+    (start, length, out_start, keep_from, keep_to) per window: length = min(window, n_frames - start) input frames; the window's own
+    output has (length - 1) // 2 + 1 frames (get_seq_lens), its local output frame l being global output frame start // 2 + l; the
+    local frames [keep_from, keep_to) are kept (overlap // 2 frames dropped at every inner edge) and land at out_start.  The kept ranges
+    partition [0, (n_frames - 1) // 2 + 1) in order."""
+    n_frames, window, overlap = int(n_frames), int(window), int(overlap)
+    if n_frames <= 0:
+        raise ValueError(f"long_windows: n_frames must be positive, got {n_frames}")
+    if window <= 0 or overlap < 0 or window % 2 or overlap % 2 or window <= 2 * overlap:
+        raise ValueError(f"long_windows: window and overlap must be even with window > 2 * overlap >= 0, got {window} and {overlap}")
+    hop = window - 2 * overlap
+    out, start = [], 0
+    while True:
+        length = min(window, n_frames - start)
+        last = start + window >= n_frames
+        keep_from = 0 if start == 0 else overlap // 2
+        keep_to = (length - 1) // 2 + 1 if last else hop // 2 + overlap // 2
+        out.append((start, length, start // 2 + keep_from, keep_from, keep_to))
+        if last:
+            return out
+        start += hop

@@ -262,6 +262,51 @@ class DeepSpeech(nn.Module):
             records = CTCAligner(self.labels).align(out, output_sizes, transcripts)
         return add_seconds(records, 2.0 * float(self.audio_conf.window_stride))
 
+    def posteriors_long(self, spect, window=2000, overlap=200, batch_size=32):
+        """Posteriors of ONE recording of any length: spect (F,T) or (1,1,F,T), on the host or the device -> (T_out, C) fp32
+        probabilities on the device, T_out = (T - 1) // 2 + 1.  The recording is cut into overlapping windows
+        (functional.long_windows; window and overlap in input frames), the windows are stacked batch_size at a time, in order and
+        zero-padded (the short last window sits last in its batch), run through the eval-mode forward() with their lengths, and each
+        window's kept frames are copied into the result: no new model arithmetic, and no recurrence over more than window // 2 steps.
+        The starvation check of evaluate() runs once after the last batch.  NOT CLAIMED: what a window edge costs in accuracy is
+        unmeasured; the frames next to an inner edge were computed with `overlap` input frames of context on that side, and the overlap
+        is the caller's knob.  The defaults (20 s windows, 2 s overlap at a 10 ms stride) keep the model near its training lengths.
+        The model is left in eval mode."""
+        from ..functional import long_windows
+        spect = torch.as_tensor(spect)
+        if spect.dim() == 4 and spect.size(0) == 1 and spect.size(1) == 1:
+            spect = spect[0, 0]
+        if spect.dim() != 2:
+            raise ValueError(f"posteriors_long: spect must be (F,T) or (1,1,F,T), got {tuple(spect.shape)}")
+        if int(batch_size) < 1:
+            raise ValueError("posteriors_long: batch_size must be positive")
+        wins = long_windows(spect.size(1), window, overlap)
+        self.eval()
+        dev = spect.device if spect.is_cuda else next(self.parameters()).device
+        probs = None
+        with torch.no_grad():
+            for i in range(0, len(wins), int(batch_size)):
+                chunk = wins[i:i + int(batch_size)]
+                x = torch.zeros((len(chunk), 1, spect.size(0), max(w[1] for w in chunk)), dtype=torch.float32, device=dev)
+                for n, (start, length, _, _, _) in enumerate(chunk):
+                    x[n, 0, :, :length] = spect[:, start:start + length]
+                out, _ = self.forward(x, torch.tensor([w[1] for w in chunk], dtype=torch.int32))
+                if probs is None:
+                    probs = torch.empty(((spect.size(1) - 1) // 2 + 1, out.size(2)), dtype=torch.float32, device=out.device)
+                for n, (_, _, out_start, keep_from, keep_to) in enumerate(chunk):
+                    probs[out_start:out_start + keep_to - keep_from] = out[n, keep_from:keep_to]
+            ops.rnn_persistent_check(probs.device)          # raise if a persistent recurrence of any batch starved (its rows are NaN then)
+        return probs
+
+    def align_long(self, spect, transcript, window=2000, overlap=200, batch_size=32):
+        """When a transcript was spoken in ONE recording of any length: posteriors_long (see there for the windows and for what is not
+        claimed about their edges), then the tiled lattice (CTCAligner.align(..., variant=3)), which has no limit on the frames or on
+        the transcript's length beyond device memory.  Returns one record as align() does, seconds = frame * 2 * window_stride."""
+        from ..decoders import CTCAligner, add_seconds
+        probs = self.posteriors_long(spect, window, overlap, batch_size)
+        records = CTCAligner(self.labels).align(probs[None], None, [transcript], variant=3)
+        return add_seconds(records, 2.0 * float(self.audio_conf.window_stride))[0]
+
     # -- evaluation loop (deepspeech.py:161-273) --------------------------------------------------
     def evaluate(self, loader=None, manifest=None, batch_size=None, device="auto", num_workers=32, verbose=False, half=False,
                  output_file=None, main_proc=True, **_unused):

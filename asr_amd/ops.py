@@ -1366,6 +1366,39 @@ def ctc_forced_align(x: Tensor, targets: Tensor, tgt_off: Tensor, in_lens: Tenso
     return score, states, tok_start, tok_end, tok_logp
 
 
+def ctc_forced_align_tiled(x: Tensor, targets: Tensor, tgt_off: Tensor, in_lens: Tensor | None, tgt_lens: Tensor, max_u: int, is_log: bool,
+                           tile_frames: int = 0, tile_pairs: int = 0):
+    """ctc_forced_align for long recordings: the same tensors in, the same five results out and the same bits, with the lattice tiled
+    over (frames x state pairs) and spread over the GPU, one launch per anti-diagonal of tiles (contract: include/ds2hip.h,
+    ds2_ctc_align_tiled_f32).  No limit on T or max_u beyond the workspace (back-pointers: B * ceil(T/8) * (max_u+1) dwords).
+    tile_frames / tile_pairs: 0 = the library's default, else a positive multiple of 8 / of 64 up to 1024 (DS2LibraryError otherwise)."""
+    _chk_f32(x)
+    if x.dim() != 3 or x.stride(2) != 1:
+        raise ValueError("ctc_forced_align_tiled: x must be (B,T,C) with a contiguous class dim")
+    B, T, Cc = x.shape
+    dev = x.device
+    for name, t in (("targets", targets), ("tgt_off", tgt_off), ("tgt_lens", tgt_lens), ("in_lens", in_lens)):
+        if t is not None and (t.dtype != torch.int32 or t.device != dev or not t.is_contiguous()):
+            raise ValueError(f"ctc_forced_align_tiled: {name} must be a contiguous int32 tensor on {dev}")
+    if tgt_off.numel() != B or tgt_lens.numel() != B or (in_lens is not None and in_lens.numel() != B):
+        raise ValueError(f"ctc_forced_align_tiled: offsets / lengths do not match the batch of {B}")
+    lib = _lib.load()
+    wsb = lib.ds2_ctc_align_tiled_workspace_bytes(B, T, int(max_u), int(tile_frames), int(tile_pairs))
+    n_tok = targets.numel()
+    score = torch.empty(B, dtype=torch.float32, device=dev)
+    states = torch.empty((B, T), dtype=torch.int32, device=dev)
+    tok_start = torch.empty(n_tok, dtype=torch.int32, device=dev)
+    tok_end = torch.empty(n_tok, dtype=torch.int32, device=dev)
+    tok_logp = torch.empty(n_tok, dtype=torch.float32, device=dev)
+    ws = _ws(wsb, dev)                                   # (an illegal tile shape sizes nothing: the entry refuses it below)
+    _lib.check(lib.ds2_ctc_align_tiled_f32(x.data_ptr(), x.stride(0), x.stride(1), B, T, Cc, 1 if is_log else 0,
+                                           _ptr(targets) if n_tok else None, tgt_off.data_ptr(), _ptr(in_lens), tgt_lens.data_ptr(),
+                                           int(max_u), int(tile_frames), int(tile_pairs), score.data_ptr(), states.data_ptr(),
+                                           _ptr(tok_start) if n_tok else None, _ptr(tok_end) if n_tok else None,
+                                           _ptr(tok_logp) if n_tok else None, ws.data_ptr(), wsb, _stream()), "ds2_ctc_align_tiled_f32")
+    return score, states, tok_start, tok_end, tok_logp
+
+
 def ctc_beam_decode(probs: Tensor, sizes: Tensor | None = None, blank: int = 0, beam_width: int = 100, cutoff_top_n: int = 40,
                     cutoff_prob: float = 1.0, lm=None, alpha: float = 0.0, beta: float = 0.0):
     """CTC prefix beam search of probs (B,T,C) fp32 on the GPU -> (labels (B,K,T) i32, offsets (B,K,T) i32, lengths (B,K) i32,

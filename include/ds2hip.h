@@ -434,6 +434,31 @@ int ds2_ctc_align_f32(const float* x, long long ld_b, long long ld_t, int B, int
                       float* score, int* states, int* tok_start, int* tok_end, float* tok_logp,
                       void* ws, size_t ws_bytes, void* stream);
 
+/* CTC forced alignment of LONG recordings: the lattice of ds2_ctc_align_f32 cut into tiles of tile_pairs adjacent state pairs x
+ * tile_frames frames, each worked by one workgroup (csrc/ctc_align_tiled.h).  Tile (k, f) depends only on tiles (k-1, f) and (k, f-1),
+ * so the tiles of one anti-diagonal k + f = d are independent: one launch per anti-diagonal, and the kernel boundary is the only
+ * synchronisation between workgroups; one further launch per call walks the back-pointers through a moving window of state pairs
+ * and writes the spans.  There is no limit on max_target_len or T beyond the workspace (an hour of speech against 50 000 labels is
+ * about 4.5 GB of back-pointers; all addressing is 64-bit).
+ * Contract: every input, output, edge case and tie rule is that of ds2_ctc_align_f32 above, word for word: the same recurrence in fp32
+ *  (the max first, then one add), stay beats step beats skip, the end state S-1 on a tie, the same infeasible outputs, is_log 0 / 1
+ *  with the same emission.  It writes the same bits as the variants of ds2_ctc_align_f32, for either kind of input, under every
+ *  tile shape.  Tiles that no legal path can touch (every state above 2t + 1, or too low to reach the end by T_b - 1) are skipped.
+ * tile_frames = 0 / tile_pairs = 0 choose the library's defaults (64 frames x 64 pairs, the fastest shape measured); otherwise tile_frames must be a positive
+ *  multiple of 8 (a back-pointer dword, 8 transitions of a pair, has one writer) and tile_pairs a positive multiple of 64 up to 1024
+ *  (one pair per thread; 64 = one wavefront per tile, the neighbour by DPP instead of LDS).  Nonzero return on anything else, on bad
+ *  arguments or when the workspace is too small (before any launch).
+ * Workspace, from host-known sizes only, with Wp = max_target_len+1 and K = ceil(Wp / tile_pairs): the back-pointers in the layout of
+ *  ds2_ctc_align_f32 (B * ceil(T/8) * Wp dwords), the boundary columns (B * K * T floats: the odd state of every tile's top pair per
+ *  frame), the row carries (B * K * tile_pairs * 2 floats: both states of every pair at a frame-block seam) and the end values
+ *  (2 B floats); ds2_ctc_align_tiled_workspace_bytes is 4 x their sum, or 0 for an illegal shape. */
+size_t ds2_ctc_align_tiled_workspace_bytes(int B, int T, int max_target_len, int tile_frames, int tile_pairs);
+int ds2_ctc_align_tiled_f32(const float* x, long long ld_b, long long ld_t, int B, int T, int C, int is_log,
+                            const int* targets_dev, const int* tgt_off_dev, const int* in_lens_dev, const int* tgt_lens_dev,
+                            int max_target_len, int tile_frames, int tile_pairs,
+                            float* score, int* states, int* tok_start, int* tok_end, float* tok_logp,
+                            void* ws, size_t ws_bytes, void* stream);
+
 /* softmax over the last dim (eval-mode InferenceBatchSoftmax, modules/blocks.py:59-64) */
 int ds2_softmax_rows_f32(const float* x, int ldx, float* y, int ldy, int rows, int C, void* stream);
 
