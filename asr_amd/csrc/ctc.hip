@@ -490,3 +490,5 @@ extern "C" int ds2_ctc_loss_f32(const float* logits, int ld, int T, int B, int C
 #include "ctc_align.h"
 // ... and its tiled form for long recordings (ds2_ctc_align_tiled_*), which shares the cell, the emission and the back-pointer layout
 #include "ctc_align_tiled.h"
+// ... and the wildcard / free-ends entries (ds2_ctc_align_star_*), which instantiate both with STAR = true behind a pre-pass
+#include "ctc_align_star.h"

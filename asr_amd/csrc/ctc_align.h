@@ -13,6 +13,9 @@
 // accumulates eight frames in a register and stores once, and a store instruction of a wave covers a contiguous run.
 // The backtrace (wave 0) stages whole group rows in LDS by bulk copies whose addresses do not depend on the state, then walks them; the
 // per-frame states leave 64 frames at a time.  Token spans and log-probabilities are a parallel pass over the written states.
+// STAR (ds2_ctc_align_star_f32, entries in ctc_align_star.h): the label value C is the wildcard, whose emission is the row g that a
+// pre-pass wrote (a select on the load address and on the loaded value, both off the dependent chain), and per-utterance flags open
+// the start states 2, 3 and the end states S - 3, S - 4.  STAR = false compiles to the plain kernels: no select, no flag, no g.
 #pragma once
 #ifndef DS2_CTC_ALIGN_TU
 #error "ctc_align.h is a part of ctc.hip"
@@ -33,7 +36,22 @@ struct AlignArgs {
   float* tok_logp;
   unsigned* bp;          // [B][NG][Wp]
   int Wp, NG, stage_words;
+  const float* g;        // STAR only: [B][T] the wildcard's emission per frame (a log value), and the per-utterance flags (or null)
+  const int* flags;
 };
+
+constexpr int ALIGN_FREE_START = 1, ALIGN_FREE_END = 2;
+
+template <bool STAR>
+__device__ __forceinline__ int align_flags(const AlignArgs& a, int b) {
+  return (STAR && a.flags) ? a.flags[b] : 0;
+}
+
+// a label outside [1, C), or outside [1, C] where C is the wildcard
+template <bool STAR>
+__device__ __forceinline__ bool align_bad_label(int c, int C) {
+  return (c < 1) || (STAR ? c > C : c >= C);
+}
 
 // e = x (log-probabilities) or log(x) on the hardware log2 (fast_log_'s two operations, kept out of any fused multiply-add so that
 // every path rounds the emission the same way)
@@ -45,6 +63,13 @@ __device__ __forceinline__ float align_emit(float x) {
     const float l2 = __builtin_amdgcn_logf(x);
     return l2 * 0.69314718055994530942f;
   }
+}
+
+// the emission of an odd state from its loaded value: the wildcard's row is stored as a log value
+template <int IS_LOG, bool STAR>
+__device__ __forceinline__ float align_emit_odd(float x, bool star) {
+  const float e = align_emit<IS_LOG>(x);
+  return (STAR && star) ? x : e;
 }
 
 // One frame of one pair.  E, O: the pair's states in the previous frame, Om: the odd state of the pair below (NEG_INF for pair 0).
@@ -76,25 +101,37 @@ __device__ __forceinline__ void align_write_infeasible(const AlignArgs& a, int b
 // The forward pass with one pair per thread (j = threadIdx.x): WAVE takes the neighbour by DPP, otherwise through `rowO` (2 rows of
 // blockDim.x + 1 floats, entry 0 of each the NEG_INF below pair 0).  Emissions come WPF frames ahead from clamped frame indices through
 // vector loads (see ctc_lattice_wave_body).  Leaves the last frame's states in E, O.
-template <int IS_LOG, bool WAVE>
+template <int IS_LOG, bool WAVE, bool STAR>
 __device__ __forceinline__ void align_forward_pairs(const AlignArgs& a, int b, int Tb, int U, const int* __restrict__ lab, float* rowO,
                                                     float& E, float& O) {
   const int j = threadIdx.x;
   const bool actE = j <= U, actO = j < U;
   int cls = 0;
-  bool skip = false;
+  bool skip = false, star = false;
   if (actO) {
     cls = lab[j];
     skip = (j >= 1) && (cls != lab[j - 1]);
+    if (STAR) {
+      star = cls == a.C;
+      cls = star ? 0 : cls;
+    }
   }
   int vz;
   asm volatile("v_mov_b32 %0, 0" : "=v"(vz));
   const float* xb = a.x + (long long)b * a.ld_b + vz;
+  // the odd state's emission: x[t][cls], or g[t] for the wildcard (one base and one stride per thread, chosen once)
+  const float* ob = xb + cls;
+  long long ld_o = a.ld_t;
+  if (STAR && star) {
+    ob = a.g + (long long)b * a.T + vz;
+    ld_o = 1;
+  }
   const int last = Tb - 1;
   auto fetch = [&](int i, float& xE, float& xO) {
     const int ii = i < last ? i : last;
     xE = xb[(long long)ii * a.ld_t];
-    xO = xb[(long long)ii * a.ld_t + cls];
+    if constexpr (STAR) xO = ob[(long long)ii * ld_o];
+    else xO = xb[(long long)ii * a.ld_t + cls];
   };
   const bool stores = j < a.Wp;
   unsigned* bpp = a.bp + (long long)b * a.NG * a.Wp + (stores ? j : 0);
@@ -105,9 +142,10 @@ __device__ __forceinline__ void align_forward_pairs(const AlignArgs& a, int b, i
   {
     float xE, xO;
     fetch(0, xE, xO);
-    if (j == 0) {
-      E = align_emit<IS_LOG>(xE);
-      if (actO) O = align_emit<IS_LOG>(xO);
+    const bool first = j == 0 || (STAR && j == 1 && (align_flags<STAR>(a, b) & ALIGN_FREE_START));   // pair 1: the states 2 and 3
+    if (first) {
+      if (!STAR || actE) E = align_emit<IS_LOG>(xE);             // (pair 0 always has its even state)
+      if (actO) O = align_emit_odd<IS_LOG, STAR>(xO, star);
     }
     if (!WAVE) {
       if (j == 0) prev[0] = cur[0] = NEG_INF;
@@ -118,7 +156,7 @@ __device__ __forceinline__ void align_forward_pairs(const AlignArgs& a, int b, i
   unsigned acc = 0;
   // a pair beyond the target gets the emission NEG_INF, which holds it at NEG_INF without a select on the chain
   auto frame = [&](float xE, float xO, int k) {
-    const float eE = actE ? align_emit<IS_LOG>(xE) : NEG_INF, eO = actO ? align_emit<IS_LOG>(xO) : NEG_INF;
+    const float eE = actE ? align_emit<IS_LOG>(xE) : NEG_INF, eO = actO ? align_emit_odd<IS_LOG, STAR>(xO, star) : NEG_INF;
     const float Om = WAVE ? wave_shift1<0x138>(O) : prev[j];
     acc |= align_cell(E, O, Om, skip, eE, eO) << (4 * k);
     if (!WAVE) {
@@ -150,8 +188,8 @@ __device__ __forceinline__ void align_forward_pairs(const AlignArgs& a, int b, i
 }
 
 // More pairs than threads: rows of both states in LDS (E[2][Wp], O[2][Wp + 1], acc[Wp]), every thread loops over its pairs.
-// Leaves the last frame's two end states in fin[0] (state 2U) and fin[1] (state 2U - 1).
-template <int IS_LOG>
+// Leaves the last frame's end states in fin[0] (state 2U) and fin[1] (state 2U - 1); STAR: also fin[2] (2U - 2) and fin[3] (2U - 3).
+template <int IS_LOG, bool STAR>
 __device__ __forceinline__ void align_forward_loop(const AlignArgs& a, int b, int Tb, int U, const int* __restrict__ lab, float* smem,
                                                    float* fin) {
   const int Wp = a.Wp;
@@ -162,12 +200,18 @@ __device__ __forceinline__ void align_forward_loop(const AlignArgs& a, int b, in
   unsigned* accs = reinterpret_cast<unsigned*>(cO + Wp + 1);
   const float* xb = a.x + (long long)b * a.ld_b;
   unsigned* bpp = a.bp + (long long)b * a.NG * Wp;
+  const float* gb = STAR ? a.g + (long long)b * a.T : nullptr;
+  const bool fstart = (align_flags<STAR>(a, b) & ALIGN_FREE_START) != 0;
   for (int j = threadIdx.x; j < Wp; j += blockDim.x) {
     float E = NEG_INF, O = NEG_INF;
     if (j == 0) {
       E = align_emit<IS_LOG>(xb[0]);
-      if (U >= 1) O = align_emit<IS_LOG>(xb[lab[0]]);
+      if (U >= 1) O = (STAR && lab[0] == a.C) ? gb[0] : align_emit<IS_LOG>(xb[lab[0]]);
       pO[0] = cO[0] = NEG_INF;
+    }
+    if (STAR && fstart && j == 1 && U >= 1) {                    // the states 2 and 3
+      E = align_emit<IS_LOG>(xb[0]);
+      if (U >= 2) O = lab[1] == a.C ? gb[0] : align_emit<IS_LOG>(xb[lab[1]]);
     }
     pE[j] = E;
     pO[j + 1] = O;
@@ -182,8 +226,10 @@ __device__ __forceinline__ void align_forward_loop(const AlignArgs& a, int b, in
       const bool actO = j < U;
       const int cls = actO ? lab[j] : 0;
       const bool skip = actO && (j >= 1) && (cls != lab[j - 1]);
+      const bool star = STAR && cls == a.C;
       float E = pE[j], O = pO[j + 1];
-      const float eE = align_emit<IS_LOG>(xt[0]), eO = actO ? align_emit<IS_LOG>(xt[cls]) : NEG_INF;
+      const float eE = align_emit<IS_LOG>(xt[0]);
+      const float eO = actO ? align_emit_odd<IS_LOG, STAR>(star ? gb[i] : xt[cls], star) : NEG_INF;
       const unsigned nib = align_cell(E, O, pO[j], skip, eE, eO);
       cE[j] = E;
       cO[j + 1] = O;
@@ -198,6 +244,70 @@ __device__ __forceinline__ void align_forward_loop(const AlignArgs& a, int b, in
   if (threadIdx.x == 0) {
     fin[0] = pE[U];
     fin[1] = U >= 1 ? pO[U] : NEG_INF;
+    if (STAR) {
+      fin[2] = U >= 1 ? pE[U - 1] : NEG_INF;
+      fin[3] = U >= 2 ? pO[U - 1] : NEG_INF;
+    }
+  }
+}
+
+// The end of the path from the last frame's values l1 .. l4 of the states S - 1 .. S - 4 (NEG_INF where a state does not exist): the
+// largest of the allowed ones, a tie going to the larger state.
+template <bool STAR>
+__device__ __forceinline__ void align_pick_end(int U, int flags, float l1, float l2, float l3, float l4, float& sc, int& end) {
+  sc = l2 > l1 ? l2 : l1;
+  end = l2 > l1 ? 2 * U - 1 : 2 * U;
+  if (STAR && (flags & ALIGN_FREE_END)) {
+    if (l3 > sc) { sc = l3; end = 2 * U - 2; }
+    if (l4 > sc) { sc = l4; end = 2 * U - 3; }
+  }
+}
+
+// Token spans and log-probabilities of the written states (all threads of the workgroup; the states are visible to them).
+template <int IS_LOG, bool STAR>
+__device__ __forceinline__ void align_spans(const AlignArgs& a, int b, int Tb, int U, const int* __restrict__ lab, const int* st) {
+  const int tid = threadIdx.x;
+  const int off = a.tgt_off[b];
+  if (STAR) {                                                   // a first or last token that the path leaves out has no frame to write it
+    if (tid == 0 && U >= 1) {
+      a.tok_start[off] = a.tok_end[off] = -1;
+      a.tok_start[off + U - 1] = a.tok_end[off + U - 1] = -1;
+    }
+    __syncthreads();
+  }
+  // token spans: frame t opens its token when the frame before is in another state, and closes it when the frame after is
+  for (int t = tid; t < Tb; t += blockDim.x) {
+    const int s = st[t];
+    if (s & 1) {
+      if (t == 0 || st[t - 1] != s) a.tok_start[off + (s >> 1)] = t;
+      if (t == Tb - 1 || st[t + 1] != s) a.tok_end[off + (s >> 1)] = t + 1;
+    }
+  }
+  __syncthreads();
+  const float* xb = a.x + (long long)b * a.ld_b;
+  for (int u = tid; u < U; u += blockDim.x) {
+    int t0 = a.tok_start[off + u], t1 = a.tok_end[off + u];
+    const int c = lab[u];
+    if (STAR) {
+      if (t0 < 0) {                                             // a skipped optional token
+        a.tok_logp[off + u] = 0.f;
+        continue;
+      }
+      if (c == a.C) {
+        const float* gb = a.g + (long long)b * a.T;
+        t0 = t0 < Tb ? t0 : Tb - 1;
+        t1 = t1 < Tb ? t1 : Tb;
+        float sum = gb[t0];
+        for (int t = t0 + 1; t < t1; ++t) sum += gb[t];
+        a.tok_logp[off + u] = sum;
+        continue;
+      }
+    }
+    t0 = t0 < 0 ? 0 : (t0 < Tb ? t0 : Tb - 1);                 // (a valid walk visits every token; no stray index either way)
+    t1 = t1 < Tb ? t1 : Tb;
+    float sum = align_emit<IS_LOG>(xb[(long long)t0 * a.ld_t + c]);
+    for (int t = t0 + 1; t < t1; ++t) sum += align_emit<IS_LOG>(xb[(long long)t * a.ld_t + c]);
+    a.tok_logp[off + u] = sum;
   }
 }
 
@@ -229,9 +339,9 @@ __device__ __forceinline__ void align_backtrace(const AlignArgs& a, int b, int T
 }
 
 // MODE 0: one wavefront, 1: one workgroup with a pair per thread, 2: one workgroup looping over pairs
-template <int IS_LOG, int MODE>
+template <int IS_LOG, int MODE, bool STAR>
 __device__ __forceinline__ void align_body(const AlignArgs& a, float* smem) {
-  __shared__ float fin[2];
+  __shared__ float fin[STAR ? 4 : 2];
   const int b = blockIdx.x, tid = threadIdx.x;
   const int Tb = a.in_lens ? min(a.in_lens[b], a.T) : a.T;
   const int U = a.tgt_lens[b];
@@ -243,7 +353,7 @@ __device__ __forceinline__ void align_body(const AlignArgs& a, float* smem) {
   int bad = 0;
   for (int u = tid; u < U; u += blockDim.x) {
     const int c = lab[u];
-    bad |= (c < 1) || (c >= a.C);
+    bad |= align_bad_label<STAR>(c, a.C);
   }
   bad = __syncthreads_or(bad);
   if (Tb <= 0 || bad) {
@@ -251,17 +361,23 @@ __device__ __forceinline__ void align_body(const AlignArgs& a, float* smem) {
     return;
   }
   if (MODE == 2) {
-    align_forward_loop<IS_LOG>(a, b, Tb, U, lab, smem, fin);
+    align_forward_loop<IS_LOG, STAR>(a, b, Tb, U, lab, smem, fin);
   } else {
     float E, O;
-    align_forward_pairs<IS_LOG, MODE == 0>(a, b, Tb, U, lab, smem, E, O);
+    align_forward_pairs<IS_LOG, MODE == 0, STAR>(a, b, Tb, U, lab, smem, E, O);
     if (tid == U) fin[0] = E;                                  // state S - 1 = 2U
     if (U >= 1 && tid == U - 1) fin[1] = O;                    // state S - 2
+    if (STAR) {
+      if (U >= 1 && tid == U - 1) fin[2] = E;                  // state S - 3
+      if (U >= 2 && tid == U - 2) fin[3] = O;                  // state S - 4
+    }
   }
   __syncthreads();                                             // also: the back-pointer stores have completed before wave 0 reads them
   const float l1 = fin[0], l2 = U >= 1 ? fin[1] : NEG_INF;
-  const float sc = l2 > l1 ? l2 : l1;
-  const int end = l2 > l1 ? 2 * U - 1 : 2 * U;
+  const float l3 = (STAR && U >= 1) ? fin[STAR ? 2 : 0] : NEG_INF, l4 = (STAR && U >= 2) ? fin[STAR ? 3 : 0] : NEG_INF;
+  float sc;
+  int end;
+  align_pick_end<STAR>(U, align_flags<STAR>(a, b), l1, l2, l3, l4, sc, end);
   if (sc == NEG_INF) {
     align_write_infeasible(a, b, U, NEG_INF);
     return;
@@ -271,38 +387,53 @@ __device__ __forceinline__ void align_body(const AlignArgs& a, float* smem) {
   if (tid == 0) a.score[b] = sc;
   if (tid < 64) align_backtrace(a, b, Tb, end, reinterpret_cast<unsigned*>(smem));
   __syncthreads();
-  // token spans: frame t opens its token when the frame before is in another state, and closes it when the frame after is
-  const int off = a.tgt_off[b];
-  for (int t = tid; t < Tb; t += blockDim.x) {
-    const int s = st[t];
-    if (s & 1) {
-      if (t == 0 || st[t - 1] != s) a.tok_start[off + (s >> 1)] = t;
-      if (t == Tb - 1 || st[t + 1] != s) a.tok_end[off + (s >> 1)] = t + 1;
-    }
-  }
-  __syncthreads();
-  const float* xb = a.x + (long long)b * a.ld_b;
-  for (int u = tid; u < U; u += blockDim.x) {
-    int t0 = a.tok_start[off + u], t1 = a.tok_end[off + u];
-    const int c = lab[u];
-    t0 = t0 < 0 ? 0 : (t0 < Tb ? t0 : Tb - 1);                 // (a valid walk visits every token; no stray index either way)
-    t1 = t1 < Tb ? t1 : Tb;
-    float sum = align_emit<IS_LOG>(xb[(long long)t0 * a.ld_t + c]);
-    for (int t = t0 + 1; t < t1; ++t) sum += align_emit<IS_LOG>(xb[(long long)t * a.ld_t + c]);
-    a.tok_logp[off + u] = sum;
-  }
+  align_spans<IS_LOG, STAR>(a, b, Tb, U, lab, st);
 }
 
-template <int IS_LOG>
+template <int IS_LOG, bool STAR>
 __global__ __launch_bounds__(64) void ctc_align_wave_kernel(AlignArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  align_body<IS_LOG, 0>(a, smem);
+  align_body<IS_LOG, 0, STAR>(a, smem);
 }
 
-template <int IS_LOG, int MODE>
+template <int IS_LOG, int MODE, bool STAR>
 __global__ __launch_bounds__(1024) void ctc_align_block_kernel(AlignArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  align_body<IS_LOG, MODE>(a, smem);
+  align_body<IS_LOG, MODE, STAR>(a, smem);
+}
+
+// The launch that both entries share (`who` names the entry in an error).  a.bp, a.g and a.flags are set by the caller.
+template <bool STAR>
+int align_launch(const char* who, AlignArgs& a, int B, int is_log, int variant, int max_target_len, void* stream) {
+  const int Smax = 2 * max_target_len + 1;
+  a.maxU = max_target_len;
+  a.Wp = max_target_len + 1;
+  a.NG = ceil_div(a.T, 8);
+  a.stage_words = a.Wp > ALIGN_STAGE_WORDS ? a.Wp : ALIGN_STAGE_WORDS;
+  const size_t stage_bytes = (size_t)a.stage_words * sizeof(unsigned);
+  hipStream_t s = (hipStream_t)stream;
+  if (variant == 1 || (variant == 0 && Smax <= 128)) {
+    if (is_log) hipLaunchKernelGGL((ctc_align_wave_kernel<1, STAR>), dim3(B), dim3(64), stage_bytes, s, a);
+    else hipLaunchKernelGGL((ctc_align_wave_kernel<0, STAR>), dim3(B), dim3(64), stage_bytes, s, a);
+    DS2_LAUNCH_CHECK("ctc_align_wave_kernel");
+    return 0;
+  }
+  int threads = ceil_div(a.Wp, 64) * 64;
+  if (threads > 1024) threads = 1024;
+  if (a.Wp <= threads) {
+    size_t lds = (size_t)2 * (threads + 1) * sizeof(float);
+    if (lds < stage_bytes) lds = stage_bytes;
+    if (is_log) hipLaunchKernelGGL((ctc_align_block_kernel<1, 1, STAR>), dim3(B), dim3(threads), lds, s, a);
+    else hipLaunchKernelGGL((ctc_align_block_kernel<0, 1, STAR>), dim3(B), dim3(threads), lds, s, a);
+  } else {
+    size_t lds = ((size_t)5 * a.Wp + 2) * sizeof(float);
+    if (lds < stage_bytes) lds = stage_bytes;
+    DS2_REQUIRE(lds <= 64 * 1024, "%s: target too long for LDS lattice rows (max_target_len=%d)", who, max_target_len);
+    if (is_log) hipLaunchKernelGGL((ctc_align_block_kernel<1, 2, STAR>), dim3(B), dim3(threads), lds, s, a);
+    else hipLaunchKernelGGL((ctc_align_block_kernel<0, 2, STAR>), dim3(B), dim3(threads), lds, s, a);
+  }
+  DS2_LAUNCH_CHECK("ctc_align_block_kernel");
+  return 0;
 }
 
 }  // namespace
@@ -328,34 +459,8 @@ extern "C" int ds2_ctc_align_f32(const float* x, long long ld_b, long long ld_t,
   AlignArgs a;
   a.x = x; a.ld_b = ld_b; a.ld_t = ld_t; a.T = T; a.C = C;
   a.targets = targets_dev; a.tgt_off = tgt_off_dev; a.in_lens = in_lens_dev; a.tgt_lens = tgt_lens_dev;
-  a.maxU = max_target_len;
   a.score = score; a.states = states; a.tok_start = tok_start; a.tok_end = tok_end; a.tok_logp = tok_logp;
   a.bp = (unsigned*)ws;
-  a.Wp = max_target_len + 1;
-  a.NG = ceil_div(T, 8);
-  a.stage_words = a.Wp > ALIGN_STAGE_WORDS ? a.Wp : ALIGN_STAGE_WORDS;
-  const size_t stage_bytes = (size_t)a.stage_words * sizeof(unsigned);
-  hipStream_t s = (hipStream_t)stream;
-  if (variant == 1 || (variant == 0 && Smax <= 128)) {
-    if (is_log) hipLaunchKernelGGL(ctc_align_wave_kernel<1>, dim3(B), dim3(64), stage_bytes, s, a);
-    else hipLaunchKernelGGL(ctc_align_wave_kernel<0>, dim3(B), dim3(64), stage_bytes, s, a);
-    DS2_LAUNCH_CHECK("ctc_align_wave_kernel");
-    return 0;
-  }
-  int threads = ceil_div(a.Wp, 64) * 64;
-  if (threads > 1024) threads = 1024;
-  if (a.Wp <= threads) {
-    size_t lds = (size_t)2 * (threads + 1) * sizeof(float);
-    if (lds < stage_bytes) lds = stage_bytes;
-    if (is_log) hipLaunchKernelGGL((ctc_align_block_kernel<1, 1>), dim3(B), dim3(threads), lds, s, a);
-    else hipLaunchKernelGGL((ctc_align_block_kernel<0, 1>), dim3(B), dim3(threads), lds, s, a);
-  } else {
-    size_t lds = ((size_t)5 * a.Wp + 2) * sizeof(float);
-    if (lds < stage_bytes) lds = stage_bytes;
-    DS2_REQUIRE(lds <= 64 * 1024, "ds2_ctc_align_f32: target too long for LDS lattice rows (max_target_len=%d)", max_target_len);
-    if (is_log) hipLaunchKernelGGL((ctc_align_block_kernel<1, 2>), dim3(B), dim3(threads), lds, s, a);
-    else hipLaunchKernelGGL((ctc_align_block_kernel<0, 2>), dim3(B), dim3(threads), lds, s, a);
-  }
-  DS2_LAUNCH_CHECK("ctc_align_block_kernel");
-  return 0;
+  a.g = nullptr; a.flags = nullptr;
+  return align_launch<false>("ds2_ctc_align_f32", a, B, is_log, variant, max_target_len, stream);
 }

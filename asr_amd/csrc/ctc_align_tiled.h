@@ -18,6 +18,9 @@
 // on an optimal path depends on them).  The values of states S - 1 and S - 2 at frame T_b - 1 are captured by the tile that passes them.
 // The backtrace is one further launch, one workgroup per utterance: a group row no longer fits LDS, but the state falls by at most 2
 // per frame, so it stages, for TILED_BT_GROUPS groups at a time, the window of 8 * groups + 1 pairs below the current one.
+// STAR (ds2_ctc_align_star_tiled_f32, entry in ctc_align_star.h): the wildcard label and the optional ends of ctc_align.h.  An utterance
+// that may start in the states 2 and 3 reaches every state up to 2t + 3, and one that may end in S - 3 and S - 4 needs only state S - 4
+// by frame T_b - 1: the two skip tests move by one pair, per utterance, and four end values are captured (fin has 4 floats each).
 #pragma once
 #ifndef DS2_CTC_ALIGN_TU
 #error "ctc_align_tiled.h is a part of ctc.hip"
@@ -36,7 +39,7 @@ struct AlignTiledArgs {
   AlignArgs a;           // a.bp [B][NG][Wp] as in ctc_align.h (stage_words unused)
   float* col;            // [B][K][T]   odd state of tile k's top pair per frame
   float* carry;          // [B][K * P][2]  E, O of every pair at the last frame of the frame block before
-  float* fin;            // [B][2]      states S - 1 and S - 2 at frame T_b - 1
+  float* fin;            // [B][2]      states S - 1 and S - 2 at frame T_b - 1 (STAR: [B][4], down to S - 4)
   int B, K, TF;
   int k_lo, d;           // this launch: block = tile * B + b, tiles k = k_lo + tile, fb = d - k
 };
@@ -50,7 +53,7 @@ __device__ __forceinline__ float wave_shift_up_old(float v, float old) {
   return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(v), 0x138, 0xf, 0xf, false));
 }
 
-template <int IS_LOG, bool WAVE>
+template <int IS_LOG, bool WAVE, bool STAR>
 __device__ __forceinline__ void align_tile_body(const AlignTiledArgs& ta, float* rowO) {
   const AlignArgs& a = ta.a;
   const int b = blockIdx.x % ta.B, k = ta.k_lo + blockIdx.x / ta.B, fb = ta.d - k;
@@ -62,22 +65,32 @@ __device__ __forceinline__ void align_tile_body(const AlignTiledArgs& ta, float*
   const long long t0 = (long long)fb * ta.TF;                           // the frame that the carry holds
   if (j0 > U || (fb > 0 && t0 >= Tb - 1)) return;                       // outside the utterance (block 0 always sets up frame 0)
   const int tl = (int)(t0 + ta.TF < Tb - 1 ? t0 + ta.TF : Tb - 1);      // the tile's last frame
-  if (j0 > tl) return;                                                 // every state 2 j0 .. lies above 2 tl + 1
+  const int fl = align_flags<STAR>(a, b);
+  const int free_s = (fl & ALIGN_FREE_START) ? 1 : 0, free_e = (fl & ALIGN_FREE_END) ? 1 : 0;
+  if (j0 > tl + free_s) return;                                        // every state 2 j0 .. lies above 2 tl + 1 (free start: 2 tl + 3)
   const int jtop = j0 + P - 1;
-  if (jtop < U && 2 * (long long)jtop + 1 + 2 * ((long long)Tb - 1 - t0) < 2 * (long long)U - 1) return;   // cannot reach S - 2
+  if (jtop < U && 2 * (long long)jtop + 1 + 2 * ((long long)Tb - 1 - t0) < 2 * (long long)U - 1 - 2 * free_e) return;   // cannot reach S - 2 (free end: S - 4)
   const int j = j0 + p;
   const bool actE = j <= U, actO = j < U;
   const int* __restrict__ lab = a.targets + a.tgt_off[b];
   int cls = 0;
-  bool skip = false;
+  bool skip = false, star = false;
   if (actO) {
     cls = lab[j];
     skip = (j >= 1) && (cls != lab[j - 1]);
+    star = STAR && cls == a.C;
     cls = (cls < 1 || cls >= a.C) ? 0 : cls;                           // a bad label: the utterance is infeasible, nothing is read out of bounds
   }
   int vz;
   asm volatile("v_mov_b32 %0, 0" : "=v"(vz));
   const float* xb = a.x + (long long)b * a.ld_b + vz;
+  // the odd state's emission: x[t][cls], or g[t] for the wildcard (one base and one stride per thread, chosen once)
+  const float* ob = xb + cls;
+  long long ld_o = a.ld_t;
+  if (STAR && star) {
+    ob = a.g + (long long)b * a.T + vz;
+    ld_o = 1;
+  }
   const bool below = k > 0;                                            // (uniform) there is a tile below: every thread loads its column
                                                                        // entry from the one address, thread / lane 0 is the one that uses it
   const float* colr = ta.col + ((long long)b * ta.K + (k > 0 ? k - 1 : 0)) * a.T;
@@ -86,7 +99,8 @@ __device__ __forceinline__ void align_tile_body(const AlignTiledArgs& ta, float*
   auto fetch = [&](int i, float& xE, float& xO, float& xB) {
     const int ii = i < tl ? i : tl;
     xE = xb[(long long)ii * a.ld_t];
-    xO = xb[(long long)ii * a.ld_t + cls];
+    if constexpr (STAR) xO = ob[(long long)ii * ld_o];
+    else xO = xb[(long long)ii * a.ld_t + cls];
     xB = below ? colr[ii] : NEG_INF;
   };
   const bool stores = j < a.Wp;
@@ -94,9 +108,9 @@ __device__ __forceinline__ void align_tile_body(const AlignTiledArgs& ta, float*
   float2* cr = reinterpret_cast<float2*>(ta.carry) + (long long)b * ta.K * P + j;
   float E = NEG_INF, O = NEG_INF;
   if (fb == 0) {
-    if (j == 0) {
-      E = align_emit<IS_LOG>(xb[0]);
-      if (actO) O = align_emit<IS_LOG>(xb[cls]);
+    if (j == 0 || (STAR && free_s && j == 1)) {                          // pair 1: the states 2 and 3
+      if (!STAR || actE) E = align_emit<IS_LOG>(xb[0]);                  // (pair 0 always has its even state)
+      if (actO) O = align_emit_odd<IS_LOG, STAR>(STAR ? ob[0] : xb[cls], star);
     }
     if (top) colw[0] = O;
   } else {
@@ -115,7 +129,7 @@ __device__ __forceinline__ void align_tile_body(const AlignTiledArgs& ta, float*
   unsigned acc = 0;
   float oc[8];                                                         // the group's odd states: the top pair's go to the column, 8 at a time
   auto frame = [&](float xE, float xO, float xB, int kk) {
-    const float eE = actE ? align_emit<IS_LOG>(xE) : NEG_INF, eO = actO ? align_emit<IS_LOG>(xO) : NEG_INF;
+    const float eE = actE ? align_emit<IS_LOG>(xE) : NEG_INF, eO = actO ? align_emit_odd<IS_LOG, STAR>(xO, star) : NEG_INF;
     const float Om = WAVE ? wave_shift_up_old(O, bprev) : prev[p];
     acc |= align_cell(E, O, Om, skip, eE, eO) << (4 * kk);
     oc[kk] = O;
@@ -168,22 +182,27 @@ __device__ __forceinline__ void align_tile_body(const AlignTiledArgs& ta, float*
     }
   }
   if (tl == Tb - 1) {
-    if (j == U) ta.fin[2 * b] = E;
-    if (j == U - 1) ta.fin[2 * b + 1] = O;
+    constexpr int NF = STAR ? 4 : 2;
+    if (j == U) ta.fin[NF * b] = E;
+    if (j == U - 1) ta.fin[NF * b + 1] = O;
+    if (STAR) {
+      if (j == U - 1) ta.fin[NF * b + 2] = E;
+      if (j == U - 2) ta.fin[NF * b + 3] = O;
+    }
   } else {
     *cr = make_float2(E, O);
   }
 }
 
-template <int IS_LOG>
+template <int IS_LOG, bool STAR>
 __global__ __launch_bounds__(64) void ctc_align_tile_wave_kernel(AlignTiledArgs ta) {
-  align_tile_body<IS_LOG, true>(ta, nullptr);
+  align_tile_body<IS_LOG, true, STAR>(ta, nullptr);
 }
 
-template <int IS_LOG>
+template <int IS_LOG, bool STAR>
 __global__ __launch_bounds__(1024) void ctc_align_tile_block_kernel(AlignTiledArgs ta) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  align_tile_body<IS_LOG, false>(ta, smem);
+  align_tile_body<IS_LOG, false, STAR>(ta, smem);
 }
 
 // The walk from (Tb - 1, end) to frame 0 through a moving window: for the groups [gbase, gtop] the whole workgroup stages the pairs
@@ -243,7 +262,7 @@ __device__ __forceinline__ void align_tiled_backtrace(const AlignArgs& a, int b,
 
 // One workgroup per utterance: the feasibility checks of align_body, the end state from the captured values, the walk, and the span
 // pass of ctc_align.h (the same expressions on the same values).
-template <int IS_LOG>
+template <int IS_LOG, bool STAR>
 __global__ __launch_bounds__(TILED_BT_THREADS) void ctc_align_tiled_backtrace_kernel(AlignTiledArgs ta) {
   __shared__ unsigned stage[TILED_BT_GROUPS * TILED_BT_PAIRS];
   __shared__ int sh_s;
@@ -259,16 +278,19 @@ __global__ __launch_bounds__(TILED_BT_THREADS) void ctc_align_tiled_backtrace_ke
   int bad = 0;
   for (int u = tid; u < U; u += blockDim.x) {
     const int c = lab[u];
-    bad |= (c < 1) || (c >= a.C);
+    bad |= align_bad_label<STAR>(c, a.C);
   }
   bad = __syncthreads_or(bad);
   if (Tb <= 0 || bad) {
     align_write_infeasible(a, b, U, (U == 0 && !bad) ? 0.f : NEG_INF);
     return;
   }
-  const float l1 = ta.fin[2 * b], l2 = U >= 1 ? ta.fin[2 * b + 1] : NEG_INF;
-  const float sc = l2 > l1 ? l2 : l1;
-  const int end = l2 > l1 ? 2 * U - 1 : 2 * U;
+  constexpr int NF = STAR ? 4 : 2;
+  const float l1 = ta.fin[NF * b], l2 = U >= 1 ? ta.fin[NF * b + 1] : NEG_INF;
+  const float l3 = (STAR && U >= 1) ? ta.fin[NF * b + (STAR ? 2 : 0)] : NEG_INF, l4 = (STAR && U >= 2) ? ta.fin[NF * b + (STAR ? 3 : 0)] : NEG_INF;
+  float sc;
+  int end;
+  align_pick_end<STAR>(U, align_flags<STAR>(a, b), l1, l2, l3, l4, sc, end);
   if (sc == NEG_INF) {
     align_write_infeasible(a, b, U, NEG_INF);
     return;
@@ -278,26 +300,7 @@ __global__ __launch_bounds__(TILED_BT_THREADS) void ctc_align_tiled_backtrace_ke
   if (tid == 0) a.score[b] = sc;
   align_tiled_backtrace(a, b, Tb, end, stage, &sh_s);
   __syncthreads();
-  // token spans: frame t opens its token when the frame before is in another state, and closes it when the frame after is
-  const int off = a.tgt_off[b];
-  for (int t = tid; t < Tb; t += blockDim.x) {
-    const int s = st[t];
-    if (s & 1) {
-      if (t == 0 || st[t - 1] != s) a.tok_start[off + (s >> 1)] = t;
-      if (t == Tb - 1 || st[t + 1] != s) a.tok_end[off + (s >> 1)] = t + 1;
-    }
-  }
-  __syncthreads();
-  const float* xb = a.x + (long long)b * a.ld_b;
-  for (int u = tid; u < U; u += blockDim.x) {
-    int t0 = a.tok_start[off + u], t1 = a.tok_end[off + u];
-    const int c = lab[u];
-    t0 = t0 < 0 ? 0 : (t0 < Tb ? t0 : Tb - 1);                 // (a valid walk visits every token; no stray index either way)
-    t1 = t1 < Tb ? t1 : Tb;
-    float sum = align_emit<IS_LOG>(xb[(long long)t0 * a.ld_t + c]);
-    for (int t = t0 + 1; t < t1; ++t) sum += align_emit<IS_LOG>(xb[(long long)t * a.ld_t + c]);
-    a.tok_logp[off + u] = sum;
-  }
+  align_spans<IS_LOG, STAR>(a, b, Tb, U, lab, st);
 }
 
 // 0 / 0 -> the defaults; false when the shape is not a legal one
@@ -312,7 +315,7 @@ struct AlignTiledLayout {
   int K, F, NG, Wp;
 };
 
-inline AlignTiledLayout align_tiled_layout(int B, int T, int max_target_len, int tile_frames, int tile_pairs) {
+inline AlignTiledLayout align_tiled_layout(int B, int T, int max_target_len, int tile_frames, int tile_pairs, bool star = false) {
   AlignTiledLayout L;
   L.Wp = max_target_len + 1;
   L.NG = ceil_div(T, 8);
@@ -321,8 +324,53 @@ inline AlignTiledLayout align_tiled_layout(int B, int T, int max_target_len, int
   L.bp_words = (size_t)B * (size_t)L.NG * (size_t)L.Wp;
   L.col_words = (size_t)B * (size_t)L.K * (size_t)T;
   L.carry_words = (size_t)B * (size_t)L.K * (size_t)tile_pairs * 2;
-  L.fin_words = (size_t)B * 2;
+  L.fin_words = (size_t)B * (star ? 4 : 2);
   return L;
+}
+
+// The launches that both entries share (`who` names the entry in an error): the fill, one launch per anti-diagonal, the backtrace.
+// `ws` holds carry, fin, col and the back-pointers in this order (STAR: the caller keeps g behind them); a.g and a.flags are the caller's.
+template <bool STAR>
+int align_tiled_launch(const char* who, const AlignArgs& a0, int B, int is_log, int max_target_len, int tile_frames, int tile_pairs,
+                       float* ws, void* stream) {
+  const AlignTiledLayout L = align_tiled_layout(B, a0.T, max_target_len, tile_frames, tile_pairs, STAR);
+  AlignTiledArgs ta;
+  ta.a = a0;
+  AlignArgs& a = ta.a;
+  a.maxU = max_target_len;
+  ta.carry = ws;                                       // (read and written as float2: an even number of words from the aligned base)
+  ta.fin = ta.carry + L.carry_words;
+  ta.col = ta.fin + L.fin_words;
+  a.bp = (unsigned*)(ta.col + L.col_words);
+  a.Wp = L.Wp; a.NG = L.NG; a.stage_words = 0;
+  ta.B = B; ta.K = L.K; ta.TF = tile_frames;
+  DS2_REQUIRE((long long)B * (L.K < L.F ? L.K : L.F) <= 0x7fffffffLL, "%s: too many tiles on one anti-diagonal", who);
+  hipStream_t s = (hipStream_t)stream;
+  {
+    const long long n = (long long)(L.col_words + L.carry_words + L.fin_words);
+    const long long blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(ctc_align_tiled_fill_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, s, ta.carry, n);
+    DS2_LAUNCH_CHECK("ctc_align_tiled_fill_kernel");
+  }
+  const size_t lds = (size_t)2 * (tile_pairs + 1) * sizeof(float);
+  for (int d = 0; d < L.K + L.F - 1; ++d) {
+    ta.d = d;
+    ta.k_lo = d - L.F + 1 > 0 ? d - L.F + 1 : 0;
+    const int k_hi = d < L.K - 1 ? d : L.K - 1;
+    const dim3 grid((unsigned)(k_hi - ta.k_lo + 1) * (unsigned)B);
+    if (tile_pairs == 64) {
+      if (is_log) hipLaunchKernelGGL((ctc_align_tile_wave_kernel<1, STAR>), grid, dim3(64), 0, s, ta);
+      else hipLaunchKernelGGL((ctc_align_tile_wave_kernel<0, STAR>), grid, dim3(64), 0, s, ta);
+    } else {
+      if (is_log) hipLaunchKernelGGL((ctc_align_tile_block_kernel<1, STAR>), grid, dim3(tile_pairs), lds, s, ta);
+      else hipLaunchKernelGGL((ctc_align_tile_block_kernel<0, STAR>), grid, dim3(tile_pairs), lds, s, ta);
+    }
+    DS2_LAUNCH_CHECK("ctc_align_tile_kernel");
+  }
+  if (is_log) hipLaunchKernelGGL((ctc_align_tiled_backtrace_kernel<1, STAR>), dim3(B), dim3(TILED_BT_THREADS), 0, s, ta);
+  else hipLaunchKernelGGL((ctc_align_tiled_backtrace_kernel<0, STAR>), dim3(B), dim3(TILED_BT_THREADS), 0, s, ta);
+  DS2_LAUNCH_CHECK("ctc_align_tiled_backtrace_kernel");
+  return 0;
 }
 
 }  // namespace
@@ -348,44 +396,10 @@ extern "C" int ds2_ctc_align_tiled_f32(const float* x, long long ld_b, long long
               "(or 0 for the default), got %d x %d", tile_frames, tile_pairs);
   DS2_REQUIRE(ws && ws_bytes >= ds2_ctc_align_tiled_workspace_bytes(B, T, max_target_len, tile_frames, tile_pairs),
               "ds2_ctc_align_tiled_f32: workspace too small");
-  const AlignTiledLayout L = align_tiled_layout(B, T, max_target_len, tile_frames, tile_pairs);
-  AlignTiledArgs ta;
-  AlignArgs& a = ta.a;
+  AlignArgs a;
   a.x = x; a.ld_b = ld_b; a.ld_t = ld_t; a.T = T; a.C = C;
   a.targets = targets_dev; a.tgt_off = tgt_off_dev; a.in_lens = in_lens_dev; a.tgt_lens = tgt_lens_dev;
-  a.maxU = max_target_len;
   a.score = score; a.states = states; a.tok_start = tok_start; a.tok_end = tok_end; a.tok_logp = tok_logp;
-  ta.carry = (float*)ws;                               // (read and written as float2: an even number of words from the aligned base)
-  ta.fin = ta.carry + L.carry_words;
-  ta.col = ta.fin + L.fin_words;
-  a.bp = (unsigned*)(ta.col + L.col_words);
-  a.Wp = L.Wp; a.NG = L.NG; a.stage_words = 0;
-  ta.B = B; ta.K = L.K; ta.TF = tile_frames;
-  DS2_REQUIRE((long long)B * (L.K < L.F ? L.K : L.F) <= 0x7fffffffLL, "ds2_ctc_align_tiled_f32: too many tiles on one anti-diagonal");
-  hipStream_t s = (hipStream_t)stream;
-  {
-    const long long n = (long long)(L.col_words + L.carry_words + L.fin_words);
-    const long long blocks = (n + 255) / 256;
-    hipLaunchKernelGGL(ctc_align_tiled_fill_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, s, ta.carry, n);
-    DS2_LAUNCH_CHECK("ctc_align_tiled_fill_kernel");
-  }
-  const size_t lds = (size_t)2 * (tile_pairs + 1) * sizeof(float);
-  for (int d = 0; d < L.K + L.F - 1; ++d) {
-    ta.d = d;
-    ta.k_lo = d - L.F + 1 > 0 ? d - L.F + 1 : 0;
-    const int k_hi = d < L.K - 1 ? d : L.K - 1;
-    const dim3 grid((unsigned)(k_hi - ta.k_lo + 1) * (unsigned)B);
-    if (tile_pairs == 64) {
-      if (is_log) hipLaunchKernelGGL(ctc_align_tile_wave_kernel<1>, grid, dim3(64), 0, s, ta);
-      else hipLaunchKernelGGL(ctc_align_tile_wave_kernel<0>, grid, dim3(64), 0, s, ta);
-    } else {
-      if (is_log) hipLaunchKernelGGL(ctc_align_tile_block_kernel<1>, grid, dim3(tile_pairs), lds, s, ta);
-      else hipLaunchKernelGGL(ctc_align_tile_block_kernel<0>, grid, dim3(tile_pairs), lds, s, ta);
-    }
-    DS2_LAUNCH_CHECK("ctc_align_tile_kernel");
-  }
-  if (is_log) hipLaunchKernelGGL(ctc_align_tiled_backtrace_kernel<1>, dim3(B), dim3(TILED_BT_THREADS), 0, s, ta);
-  else hipLaunchKernelGGL(ctc_align_tiled_backtrace_kernel<0>, dim3(B), dim3(TILED_BT_THREADS), 0, s, ta);
-  DS2_LAUNCH_CHECK("ctc_align_tiled_backtrace_kernel");
-  return 0;
+  a.g = nullptr; a.flags = nullptr;
+  return align_tiled_launch<false>("ds2_ctc_align_tiled_f32", a, B, is_log, max_target_len, tile_frames, tile_pairs, (float*)ws, stream);
 }

@@ -7,6 +7,8 @@ scores a whole batch with `Decoder.score_batch`, one HIP launch (csrc/edit_dista
 `assemble_alignments`."""
 from __future__ import annotations
 
+import math
+
 import numpy as np
 import torch
 
@@ -223,30 +225,48 @@ class BeamCTCDecoder(Decoder):
         return self.convert_to_strings(labels_h, lens_h), self.convert_tensor(offs_h, lens_h)
 
 
-def encode_transcripts(transcripts, labels):
+def encode_transcripts(transcripts, labels, star=None, unknown="error"):
     """Transcripts (strings, or sequences of label ids) -> one list of ids each.  Strings are mapped through `labels` ({char: id} or a
-    sequence of characters); a character that is not a label raises ValueError naming it."""
+    sequence of characters); a character that is not a label raises ValueError naming it.
+    Wildcards (CTCAligner.align's star / unknown): the id len(labels), one past the last class, is the wildcard.  `star`, a single
+    character that is not a label, maps to it; with unknown="star" so does every character that is not a label.  With either option
+    runs of adjacent wildcards collapse to one (in id sequences too, where the id len(labels) is the wildcard)."""
     char_to_int = labels if isinstance(labels, dict) else {c: i for i, c in enumerate(labels)}
+    if unknown not in ("error", "star"):
+        raise ValueError(f"unknown must be 'error' or 'star', got {unknown!r}")
+    if star is not None:
+        if not isinstance(star, str) or len(star) != 1:
+            raise ValueError(f"star must be a single character, got {star!r}")
+        if star in char_to_int:
+            raise ValueError(f"star {star!r} is a label: choose a character outside the label set")
+    star_id = len(char_to_int)
+    wild = star is not None or unknown == "star"
     out = []
     for n, tr in enumerate(transcripts):
         if isinstance(tr, str):
             ids = []
             for ch in tr:
-                if ch not in char_to_int:
+                if ch in char_to_int:
+                    ids.append(int(char_to_int[ch]))
+                elif ch == star or unknown == "star":
+                    ids.append(star_id)
+                else:
                     raise ValueError(f"transcript {n}: character {ch!r} is not in the labels")
-                ids.append(int(char_to_int[ch]))
         else:
             ids = [int(i) for i in (tr.tolist() if hasattr(tr, "tolist") else tr)]
+        if wild:
+            ids = [i for k, i in enumerate(ids) if not (i == star_id and k > 0 and ids[k - 1] == star_id)]
         out.append(ids)
     return out
 
 
-def group_words(tokens):
+def group_words(tokens, star=None):
     """tokens [(char, start, end, logp, ...)] -> words [(word, start, end, logp)]: a word is the run of tokens between space tokens
-    (leading, trailing and doubled spaces make no word), from its first token's start to its last token's end, logp summed in fp64."""
+    (leading, trailing and doubled spaces make no word), from its first token's start to its last token's end, logp summed in fp64.
+    `star`: the character of wildcard tokens, which end a word like a space and make none."""
     words, run = [], []
     for tok in list(tokens) + [(" ",)]:
-        if tok[0] == " ":
+        if tok[0] == " " or (star is not None and tok[0] == star):
             if run:
                 words.append(("".join(t[0] for t in run), run[0][1], run[-1][2], float(sum(np.float64(t[3]) for t in run))))
             run = []
@@ -255,11 +275,15 @@ def group_words(tokens):
     return words
 
 
-def assemble_alignments(score, states, tok_start, tok_end, tok_logp, targets, sizes, int_to_char, space_index):
+def assemble_alignments(score, states, tok_start, tok_end, tok_logp, targets, sizes, int_to_char, space_index, star_id=None,
+                        star_char="*"):
     """Pure host half of CTCAligner.align: the kernel's raw arrays (score (B), states (B,T), tok_* flat over all targets, in target
     order) + the targets (a list of id lists) and valid frame counts -> one record per utterance: {"score": float, "states": int tensor
     (T_b), "tokens": [(char, start, end, logp)], "words": [(word, start, end, logp)]}.  An infeasible utterance (score -inf) has empty
-    states / tokens / words."""
+    states / tokens / words.
+    star_id (None: no wildcards, the records above): the target id of the wildcard.  A token whose span is (-1, -1) (an optional first
+    or last token that the path left out) does not appear; a wildcard that took frames appears in "tokens" as (star_char, start, end,
+    logp), ends a word and makes none, and every record gains "unaligned": the (start, end) spans of its wildcards."""
     score, states = np.asarray(score, np.float32), np.asarray(states, np.int32)
     tok_start, tok_end, tok_logp = np.asarray(tok_start), np.asarray(tok_end), np.asarray(tok_logp, np.float32)
     records, off = [], 0
@@ -268,20 +292,39 @@ def assemble_alignments(score, states, tok_start, tok_end, tok_logp, targets, si
         sc = float(score[b])
         if sc == float("-inf"):
             records.append({"score": sc, "states": torch.zeros(0, dtype=torch.int32), "tokens": [], "words": []})
-        else:
+            if star_id is not None:
+                records[-1]["unaligned"] = []
+        elif star_id is None:
             Tb = max(min(int(sizes[b]), states.shape[1]), 0)
             tokens = [(" " if i == space_index else int_to_char.get(i, ""), int(tok_start[off + u]), int(tok_end[off + u]),
                        float(tok_logp[off + u])) for u, i in enumerate(ids)]
             records.append({"score": sc, "states": torch.from_numpy(states[b, :Tb].copy()), "tokens": tokens, "words": group_words(tokens)})
+        else:
+            Tb = max(min(int(sizes[b]), states.shape[1]), 0)
+            tokens, breaks, unaligned = [], [], []              # breaks: the tokens with every wildcard as a space, for the words
+            for u, i in enumerate(ids):
+                s, e, lp = int(tok_start[off + u]), int(tok_end[off + u]), float(tok_logp[off + u])
+                if s < 0:
+                    continue
+                ch = star_char if i == star_id else (" " if i == space_index else int_to_char.get(i, ""))
+                tokens.append((ch, s, e, lp))
+                breaks.append((" ", s, e, lp) if i == star_id else tokens[-1])
+                if i == star_id:
+                    unaligned.append((s, e))
+            records.append({"score": sc, "states": torch.from_numpy(states[b, :Tb].copy()), "tokens": tokens, "words": group_words(breaks),
+                            "unaligned": unaligned})
         off += U
     return records
 
 
 def add_seconds(records, frame_seconds):
-    """Every token and word tuple of the records gains (start_s, end_s) = (start, end) * frame_seconds."""
+    """Every token and word tuple of the records gains (start_s, end_s) = (start, end) * frame_seconds, and so does every (start, end)
+    span of "unaligned" where a record has that key."""
     for r in records:
         for key in ("tokens", "words"):
             r[key] = [t + (t[1] * frame_seconds, t[2] * frame_seconds) for t in r[key]]
+        if "unaligned" in r:
+            r["unaligned"] = [t + (t[0] * frame_seconds, t[1] * frame_seconds) for t in r["unaligned"]]
     return records
 
 
@@ -297,18 +340,45 @@ class CTCAligner(Decoder):
         if self.int_to_char.get(self.space_index) != " ":
             self.space_index = next((i for i, c in sorted(self.int_to_char.items()) if c == " "), -1)
 
-    def align(self, probs, sizes, transcripts, is_log=False, variant=0):
+    def align(self, probs, sizes, transcripts, is_log=False, variant=0, star=None, star_penalty=math.log(0.5), unknown="error",
+              free_start=False, free_end=False):
         """probs (B,T,C) as decode() takes them (probabilities, or log-probabilities with is_log=True), sizes (B) valid frames or None,
         transcripts: B strings (mapped through the labels) or id sequences.  One pinned upload of the packed targets, one launch, one
         device-to-host copy.  Returns one record per utterance (assemble_alignments).  Host tensors are uploaded first: there is no CPU
         implementation.  variant 0 - 2 as ops.ctc_forced_align takes them (one launch, targets up to about 3 275 labels); variant 3
-        is ops.ctc_forced_align_tiled with the default tiles: the same records for a recording and a transcript of any length."""
+        is ops.ctc_forced_align_tiled with the default tiles: the same records for a recording and a transcript of any length.
+        Imperfect transcripts (contract: include/ds2hip.h, ds2_ctc_align_star_f32); with the four options at their defaults nothing
+        below applies, the call takes the plain entries and star_penalty is unused:
+          star="*"        that character (any single one that is not a label) in a transcript is a WILDCARD: a token that takes at
+                          least one frame and matches anything, each of its frames scoring the frame's best class + star_penalty;
+          unknown="star"  a character that is not a label becomes a wildcard instead of raising (in id sequences the id len(labels) is
+                          the wildcard); runs of adjacent wildcards collapse to one;
+          free_start / free_end  put a wildcard at the front / back (unless one is there) and make that token optional: audio before
+                          the first or after the last word goes to it, and with none it is left out.
+        star_penalty (<= 0, natural log): log(0.5) gives a frame to the transcript's token while that token has at least half the
+        probability of the frame's best class.  That default is a starting point, NOT a measured one: what value serves real
+        recordings has not been measured.  Records then hold the wildcards that took frames as (star or "*", start, end, logp) tokens,
+        no word for them, and "unaligned": their (start, end) spans.  Variant 3 is ops.ctc_forced_align_star_tiled."""
         from .. import ops
         probs = torch.as_tensor(probs)
         B, T = int(probs.shape[0]), int(probs.shape[1])
         if len(transcripts) != B:
             raise ValueError(f"{len(transcripts)} transcripts for a batch of {B}")
-        targets = encode_transcripts(transcripts, self.labels)
+        wild = star is not None or unknown != "error" or bool(free_start) or bool(free_end)
+        targets = encode_transcripts(transcripts, self.labels, star, unknown)
+        star_id = len(self.labels)
+        flags = None
+        if wild:
+            if int(probs.shape[2]) != star_id:
+                raise ValueError(f"probs has {int(probs.shape[2])} classes for {star_id} labels: the wildcard is the id one past the last class")
+            sp = float(star_penalty)
+            if not (sp <= 0.0 and math.isfinite(sp)):
+                raise ValueError(f"star_penalty must be finite and <= 0, got {star_penalty}")
+            if free_start:
+                targets = [t if t[:1] == [star_id] else [star_id] + t for t in targets]
+            if free_end:
+                targets = [t if t[-1:] == [star_id] else t + [star_id] for t in targets]
+            flags = [(1 if free_start else 0) | (2 if free_end else 0)] * B
         sizes_h = [T] * B if sizes is None else [int(v) for v in torch.as_tensor(sizes).reshape(-1).tolist()]
         if len(sizes_h) != B:
             raise ValueError(f"sizes has {len(sizes_h)} entries for a batch of {B}")
@@ -320,14 +390,24 @@ class CTCAligner(Decoder):
         dev = probs.device
         lens = [len(t) for t in targets]
         n_tok, max_u = sum(lens), max(lens, default=0)
-        # one int32 image: tgt_off, tgt_lens, in_lens, labels
-        host = torch.empty(3 * B + n_tok, dtype=torch.int32, pin_memory=True)
+        # one int32 image: tgt_off, tgt_lens, in_lens, labels (, flags)
+        host = torch.empty(3 * B + n_tok + (B if wild else 0), dtype=torch.int32, pin_memory=True)
         h = host.numpy()
         h[:B] = np.cumsum([0] + lens[:-1]) if B else []
         h[B:2 * B], h[2 * B:3 * B] = lens, np.clip(sizes_h, -1, T)
-        h[3 * B:] = [i for t in targets for i in t]
+        h[3 * B:3 * B + n_tok] = [i for t in targets for i in t]
+        if wild:
+            h[3 * B + n_tok:] = flags
         d = host.to(dev, non_blocking=True)
-        if variant == 3:                                 # the tiled lattice (ds2_ctc_align_tiled_f32, default tiles): any T, any target length
+        if wild:                                         # the wildcard entries (ds2_ctc_align_star_*): a pre-pass and the same lattice
+            if variant not in (0, 1, 2, 3):
+                raise ValueError(f"variant must be 0, 1, 2 or 3, got {variant}")
+            args = (probs, d[3 * B:3 * B + n_tok], d[:B], d[2 * B:3 * B], d[B:2 * B], max_u, is_log)
+            if variant == 3:
+                score, states, ts, te, lp = ops.ctc_forced_align_star_tiled(*args, star_penalty=sp, flags=d[3 * B + n_tok:])
+            else:
+                score, states, ts, te, lp = ops.ctc_forced_align_star(*args, variant, star_penalty=sp, flags=d[3 * B + n_tok:])
+        elif variant == 3:                                 # the tiled lattice (ds2_ctc_align_tiled_f32, default tiles): any T, any target length
             score, states, ts, te, lp = ops.ctc_forced_align_tiled(probs, d[3 * B:], d[:B], d[2 * B:3 * B], d[B:2 * B], max_u, is_log)
         else:
             score, states, ts, te, lp = ops.ctc_forced_align(probs, d[3 * B:], d[:B], d[2 * B:3 * B], d[B:2 * B], max_u, is_log, variant)
@@ -338,7 +418,8 @@ class CTCAligner(Decoder):
         o = out.numpy()
         n = B + B * T
         return assemble_alignments(o[:B].view(np.float32), o[B:n].reshape(B, T), o[n:n + n_tok], o[n + n_tok:n + 2 * n_tok],
-                                   o[n + 2 * n_tok:].view(np.float32), targets, sizes_h, self.int_to_char, self.space_index)
+                                   o[n + 2 * n_tok:].view(np.float32), targets, sizes_h, self.int_to_char, self.space_index,
+                                   star_id if wild else None, star or "*")
 
 
 def _device(who="GreedyDecoder", what=".decode"):

@@ -250,16 +250,20 @@ class DeepSpeech(nn.Module):
         return seq_len.int()
 
     # -- forced alignment (no counterpart in the reference) --------------------------------------
-    def align(self, inputs, input_sizes, transcripts):
+    def align(self, inputs, input_sizes, transcripts, star=None, star_penalty=math.log(0.5), unknown="error", free_start=False,
+              free_end=False):
         """When each transcript was spoken: the eval-mode forward, then CTCAligner on its output.  inputs (B,1,F,T) and input_sizes
         (B) as forward() takes them, transcripts B strings (or label-id sequences).  Returns CTCAligner.align's records with every
         token and word tuple extended by (start_s, end_s): output frame t covers input frame 2t (the conv stack's time stride,
-        get_seq_lens), so seconds = frame * 2 * audio_conf.window_stride.  The model is left in eval mode."""
+        get_seq_lens), so seconds = frame * 2 * audio_conf.window_stride.  The model is left in eval mode.
+        star / star_penalty / unknown / free_start / free_end: CTCAligner.align's options for imperfect transcripts (a wildcard token,
+        optional ends; see there, also for what the default penalty is not); the "unaligned" spans gain seconds too."""
         from ..decoders import CTCAligner, add_seconds
         self.eval()
         with torch.no_grad():
             out, output_sizes = self.forward(inputs, input_sizes)
-            records = CTCAligner(self.labels).align(out, output_sizes, transcripts)
+            records = CTCAligner(self.labels).align(out, output_sizes, transcripts, star=star, star_penalty=star_penalty, unknown=unknown,
+                                                    free_start=free_start, free_end=free_end)
         return add_seconds(records, 2.0 * float(self.audio_conf.window_stride))
 
     def posteriors_long(self, spect, window=2000, overlap=200, batch_size=32):
@@ -298,13 +302,16 @@ class DeepSpeech(nn.Module):
             ops.rnn_persistent_check(probs.device)          # raise if a persistent recurrence of any batch starved (its rows are NaN then)
         return probs
 
-    def align_long(self, spect, transcript, window=2000, overlap=200, batch_size=32):
+    def align_long(self, spect, transcript, window=2000, overlap=200, batch_size=32, star=None, star_penalty=math.log(0.5),
+                   unknown="error", free_start=False, free_end=False):
         """When a transcript was spoken in ONE recording of any length: posteriors_long (see there for the windows and for what is not
         claimed about their edges), then the tiled lattice (CTCAligner.align(..., variant=3)), which has no limit on the frames or on
-        the transcript's length beyond device memory.  Returns one record as align() does, seconds = frame * 2 * window_stride."""
+        the transcript's length beyond device memory.  Returns one record as align() does, seconds = frame * 2 * window_stride.
+        star / star_penalty / unknown / free_start / free_end as in align()."""
         from ..decoders import CTCAligner, add_seconds
         probs = self.posteriors_long(spect, window, overlap, batch_size)
-        records = CTCAligner(self.labels).align(probs[None], None, [transcript], variant=3)
+        records = CTCAligner(self.labels).align(probs[None], None, [transcript], variant=3, star=star, star_penalty=star_penalty,
+                                                unknown=unknown, free_start=free_start, free_end=free_end)
         return add_seconds(records, 2.0 * float(self.audio_conf.window_stride))[0]
 
     # -- evaluation loop (deepspeech.py:161-273) --------------------------------------------------

@@ -7,6 +7,7 @@ Nothing in this module has a CPU path: tensors must live on the GPU.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import threading
 from typing import Optional, Tuple
 
@@ -1396,6 +1397,96 @@ def ctc_forced_align_tiled(x: Tensor, targets: Tensor, tgt_off: Tensor, in_lens:
                                            int(max_u), int(tile_frames), int(tile_pairs), score.data_ptr(), states.data_ptr(),
                                            _ptr(tok_start) if n_tok else None, _ptr(tok_end) if n_tok else None,
                                            _ptr(tok_logp) if n_tok else None, ws.data_ptr(), wsb, _stream()), "ds2_ctc_align_tiled_f32")
+    return score, states, tok_start, tok_end, tok_logp
+
+
+def _chk_star_args(who, x, targets, tgt_off, in_lens, tgt_lens, flags, star_penalty):
+    if x.dim() != 3 or x.stride(2) != 1:
+        raise ValueError(f"{who}: x must be (B,T,C) with a contiguous class dim")
+    B, dev = x.shape[0], x.device
+    for name, t in (("targets", targets), ("tgt_off", tgt_off), ("tgt_lens", tgt_lens), ("in_lens", in_lens), ("flags", flags)):
+        if t is not None and (t.dtype != torch.int32 or t.device != dev or not t.is_contiguous()):
+            raise ValueError(f"{who}: {name} must be a contiguous int32 tensor on {dev}")
+    if tgt_off.numel() != B or tgt_lens.numel() != B or (in_lens is not None and in_lens.numel() != B) or \
+            (flags is not None and flags.numel() != B):
+        raise ValueError(f"{who}: offsets / lengths / flags do not match the batch of {B}")
+    p = float(star_penalty)
+    if not (p <= 0.0 and math.isfinite(p)):
+        raise ValueError(f"{who}: star_penalty must be finite and <= 0, got {star_penalty}")
+    _chk_f32(x)
+    return p
+
+
+def ctc_star_row(x: Tensor, in_lens: Tensor | None, is_log: bool, star_penalty: float):
+    """The wildcard's emission of ctc_forced_align_star alone: g (B,T) f32 with g[b,t] = max_c e[b,t,c] + star_penalty for t < T_b and
+    -inf beyond (the library leaves those frames unwritten).  One launch that reads x once (ds2_ctc_align_star_row_f32)."""
+    if x.dim() != 3 or x.stride(2) != 1:
+        raise ValueError("ctc_star_row: x must be (B,T,C) with a contiguous class dim")
+    if in_lens is not None and (in_lens.dtype != torch.int32 or in_lens.device != x.device or not in_lens.is_contiguous()
+                                or in_lens.numel() != x.shape[0]):
+        raise ValueError(f"ctc_star_row: in_lens must be a contiguous int32 tensor of {x.shape[0]} entries on {x.device}")
+    p = float(star_penalty)
+    if not (p <= 0.0 and math.isfinite(p)):
+        raise ValueError(f"ctc_star_row: star_penalty must be finite and <= 0, got {star_penalty}")
+    _chk_f32(x)
+    B, T, Cc = x.shape
+    g = torch.full((B, T), float("-inf"), dtype=torch.float32, device=x.device)
+    lib = _lib.load()
+    _lib.check(lib.ds2_ctc_align_star_row_f32(x.data_ptr(), x.stride(0), x.stride(1), B, T, Cc, 1 if is_log else 0, _ptr(in_lens), p,
+                                              g.data_ptr(), _stream()), "ds2_ctc_align_star_row_f32")
+    return g
+
+
+def ctc_forced_align_star(x: Tensor, targets: Tensor, tgt_off: Tensor, in_lens: Tensor | None, tgt_lens: Tensor, max_u: int, is_log: bool,
+                          variant: int = 0, star_penalty: float = math.log(0.5), flags: Tensor | None = None):
+    """ctc_forced_align for imperfect transcripts (contract: include/ds2hip.h, ds2_ctc_align_star_f32): the label value C = x.shape[2]
+    in `targets` is a wildcard that emits max_c e[t][c] + star_penalty (star_penalty <= 0, finite), and flags (B) int32 or None opens,
+    per utterance, the start in the second token's states (bit 0) and the end in the last but one token's (bit 1).  The same five
+    results; a skipped first / last token has the span (-1, -1) and tok_logp 0.  Two launches (the wildcard row, the lattice) on the
+    current stream.  With flags None and no wildcard label: the bits of ctc_forced_align."""
+    p = _chk_star_args("ctc_forced_align_star", x, targets, tgt_off, in_lens, tgt_lens, flags, star_penalty)
+    B, T, Cc = x.shape
+    dev = x.device
+    n_tok = targets.numel()
+    score = torch.empty(B, dtype=torch.float32, device=dev)
+    states = torch.empty((B, T), dtype=torch.int32, device=dev)
+    tok_start = torch.empty(n_tok, dtype=torch.int32, device=dev)
+    tok_end = torch.empty(n_tok, dtype=torch.int32, device=dev)
+    tok_logp = torch.empty(n_tok, dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    wsb = lib.ds2_ctc_align_star_workspace_bytes(B, T, int(max_u))
+    ws = _ws(max(wsb, 1), dev)
+    _lib.check(lib.ds2_ctc_align_star_f32(x.data_ptr(), x.stride(0), x.stride(1), B, T, Cc, 1 if is_log else 0,
+                                          _ptr(targets) if n_tok else None, tgt_off.data_ptr(), _ptr(in_lens), tgt_lens.data_ptr(),
+                                          int(max_u), int(variant), p, _ptr(flags), score.data_ptr(), states.data_ptr(),
+                                          _ptr(tok_start) if n_tok else None, _ptr(tok_end) if n_tok else None,
+                                          _ptr(tok_logp) if n_tok else None, ws.data_ptr(), wsb, _stream()), "ds2_ctc_align_star_f32")
+    return score, states, tok_start, tok_end, tok_logp
+
+
+def ctc_forced_align_star_tiled(x: Tensor, targets: Tensor, tgt_off: Tensor, in_lens: Tensor | None, tgt_lens: Tensor, max_u: int,
+                                is_log: bool, tile_frames: int = 0, tile_pairs: int = 0, star_penalty: float = math.log(0.5),
+                                flags: Tensor | None = None):
+    """ctc_forced_align_star for long recordings: the same tensors in, the same five results out and the same bits, on the tiled lattice
+    of ctc_forced_align_tiled (contract: include/ds2hip.h, ds2_ctc_align_star_tiled_f32).  tile_frames / tile_pairs as there."""
+    p = _chk_star_args("ctc_forced_align_star_tiled", x, targets, tgt_off, in_lens, tgt_lens, flags, star_penalty)
+    B, T, Cc = x.shape
+    dev = x.device
+    lib = _lib.load()
+    wsb = lib.ds2_ctc_align_star_tiled_workspace_bytes(B, T, int(max_u), int(tile_frames), int(tile_pairs))
+    n_tok = targets.numel()
+    score = torch.empty(B, dtype=torch.float32, device=dev)
+    states = torch.empty((B, T), dtype=torch.int32, device=dev)
+    tok_start = torch.empty(n_tok, dtype=torch.int32, device=dev)
+    tok_end = torch.empty(n_tok, dtype=torch.int32, device=dev)
+    tok_logp = torch.empty(n_tok, dtype=torch.float32, device=dev)
+    ws = _ws(wsb, dev)                                   # (an illegal tile shape sizes nothing: the entry refuses it below)
+    _lib.check(lib.ds2_ctc_align_star_tiled_f32(x.data_ptr(), x.stride(0), x.stride(1), B, T, Cc, 1 if is_log else 0,
+                                                _ptr(targets) if n_tok else None, tgt_off.data_ptr(), _ptr(in_lens), tgt_lens.data_ptr(),
+                                                int(max_u), int(tile_frames), int(tile_pairs), p, _ptr(flags), score.data_ptr(),
+                                                states.data_ptr(), _ptr(tok_start) if n_tok else None, _ptr(tok_end) if n_tok else None,
+                                                _ptr(tok_logp) if n_tok else None, ws.data_ptr(), wsb, _stream()),
+               "ds2_ctc_align_star_tiled_f32")
     return score, states, tok_start, tok_end, tok_logp
 
 

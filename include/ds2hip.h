@@ -459,6 +459,53 @@ int ds2_ctc_align_tiled_f32(const float* x, long long ld_b, long long ld_t, int 
                             float* score, int* states, int* tok_start, int* tok_end, float* tok_logp,
                             void* ws, size_t ws_bytes, void* stream);
 
+/* CTC forced alignment of IMPERFECT transcripts: a wildcard ("star") token and optional first / last tokens on top of
+ * ds2_ctc_align_f32 (csrc/ctc_align_star.h; the lattice kernels of ctc_align.h / ctc_align_tiled.h instantiated with the two additions).
+ * The reference has no aligner: this text is the contract, restated in NumPy by tests/ctc_align_star_oracle.py.  Everything that is not
+ * named here (inputs, strides, is_log, recurrence, tie rule, back-pointer layout, outputs, infeasible outputs, variants 0 / 1 / 2) is
+ * ds2_ctc_align_f32's, word for word.
+ * Wildcard emission, per valid frame, with e the emission of that contract:
+ *    g[t] = (max over all classes c in [0, C), blank included, of e[t][c]) + star_penalty
+ *  the max first, then ONE fp32 add.  With is_log = 0 the max is taken on x and the emission expression (the hardware log2, then the
+ *  ln 2 multiply) is applied to that maximum.  g is stored as a log value in the workspace by a pre-pass that reads x once; the lattice
+ *  loads it as it is.  An all -inf row gives -inf.  NaN is unspecified.  star_penalty is fp32, <= 0 and finite: anything else is a
+ *  nonzero return before any launch.
+ * Wildcard as a label: in targets the value C (one past the last class) is the wildcard, legal only through these entries (the plain
+ *  entries keep calling it a bad label).  It is an ordinary odd state that emits g[t]: it takes at least one frame, it may repeat,
+ *  blank states sit on both sides, and the skip rule compares label VALUES as before (C differs from every class; two adjacent C
+ *  behave like a repeated label).  A target outside [1, C] makes its utterance infeasible.
+ * Optional first and last token: flags_dev (B) int32 per utterance, NULL = all 0.
+ *  bit 0: the path may also START in state 2 or 3:  v[0][s] = e[0][class(s)] for s < min(S, 4) instead of s < 2;
+ *  bit 1: the path may also END in state S-3 or S-4: the end is the largest v[T_b-1][s] over the allowed end states that exist
+ *         (S-1, S-2, S-3, S-4, those >= 0), a tie going to the larger state.
+ *  The global statement stays true: among all optimal legal paths, the one whose state sequence, read from the last frame backwards,
+ *  is lexicographically greatest.  A token whose state no frame takes (a skipped first or last token) gets tok_start = tok_end = -1
+ *  and tok_logp = 0; a wildcard token's tok_logp is the fp32 sum of its g[t] in ascending t.  Everything infeasible keeps the outputs
+ *  of ds2_ctc_align_f32.  With is_log = 1 every output is pinned bit for bit by a float32 restatement; with flags NULL and no
+ *  wildcard label the outputs are the bits of ds2_ctc_align_f32.
+ * ds2_ctc_align_star_row_f32 is the pre-pass alone: g (B,T) contiguous, frames t >= T_b are not written.
+ * Workspace: that of ds2_ctc_align_f32, then g:  ds2_ctc_align_star_workspace_bytes = ds2_ctc_align_workspace_bytes + 4 * B * T. */
+int ds2_ctc_align_star_row_f32(const float* x, long long ld_b, long long ld_t, int B, int T, int C, int is_log,
+                               const int* in_lens_dev, float star_penalty, float* g, void* stream);
+size_t ds2_ctc_align_star_workspace_bytes(int B, int T, int max_target_len);
+int ds2_ctc_align_star_f32(const float* x, long long ld_b, long long ld_t, int B, int T, int C, int is_log,
+                           const int* targets_dev, const int* tgt_off_dev, const int* in_lens_dev, const int* tgt_lens_dev,
+                           int max_target_len, int variant, float star_penalty, const int* flags_dev,
+                           float* score, int* states, int* tok_start, int* tok_end, float* tok_logp,
+                           void* ws, size_t ws_bytes, void* stream);
+
+/* The tiled form of ds2_ctc_align_star_f32 for long recordings: ds2_ctc_align_tiled_f32 with the wildcard and the flags above, and the
+ * same bits as ds2_ctc_align_star_f32 under every tile shape.  The two tests that skip a tile move by one pair for an utterance whose
+ * flag is set: bit 0, a tile is skipped when every state of it lies above 2t + 3 (instead of 2t + 1); bit 1, when it cannot reach state
+ * S-4 (instead of S-2) by frame T_b - 1.  Four end values per utterance are captured instead of two.
+ * Workspace: ds2_ctc_align_tiled_workspace_bytes + 8 * B (the two further end values) + 4 * B * T (g), or 0 for an illegal shape. */
+size_t ds2_ctc_align_star_tiled_workspace_bytes(int B, int T, int max_target_len, int tile_frames, int tile_pairs);
+int ds2_ctc_align_star_tiled_f32(const float* x, long long ld_b, long long ld_t, int B, int T, int C, int is_log,
+                                 const int* targets_dev, const int* tgt_off_dev, const int* in_lens_dev, const int* tgt_lens_dev,
+                                 int max_target_len, int tile_frames, int tile_pairs, float star_penalty, const int* flags_dev,
+                                 float* score, int* states, int* tok_start, int* tok_end, float* tok_logp,
+                                 void* ws, size_t ws_bytes, void* stream);
+
 /* softmax over the last dim (eval-mode InferenceBatchSoftmax, modules/blocks.py:59-64) */
 int ds2_softmax_rows_f32(const float* x, int ldx, float* y, int ldy, int rows, int C, void* stream);
 
