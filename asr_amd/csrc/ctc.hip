@@ -57,13 +57,23 @@ __global__ __launch_bounds__(256) void ctc_lse_kernel(const float* __restrict__ 
   if (lane == 0) lse[row] = m + logf(s);
 }
 
+// The STAR = true instances of the three kernels below are the wildcard loss (ds2_ctc_star_loss_f32, contract in include/ds2hip.h): a
+// label equal to C is the wildcard, whose state emits the constant star_pen instead of a log-softmax value; flags[b] bit 0 lets a path
+// start in states 2 and 3 as well, bit 1 lets it end in states S-3 and S-4 as well.  The class used for an ADDRESS is clamped to the blank
+// for a wildcard (one past the row otherwise) and the constant is selected into the loaded emission, off the dependent chain.  A label
+// outside [1, C] is found before anything is read with it.  STAR = false: none of it is compiled, the kernels are the ones they were.
+// -log of the summed end states: S-1, S-2 and, with flag bit 1, S-3, S-4 (a state that does not exist is passed as NEG_INF)
+__device__ __forceinline__ float star_end_nll(float l1, float l2, float l3, float l4) { return -lse2(lse2(l1, l2), lse2(l3, l4)); }
+__device__ __forceinline__ float star_cell(float a0, float a1, float a2, float lp, bool star);   // (below, next to lse3_sel)
+
 // blockIdx.x = utterance, blockIdx.y = 0: alpha (forward in t), 1: beta (backward in t).
 // ab layout: [2][B][T][Smax]
+template <bool STAR>
 __global__ __launch_bounds__(1024) void ctc_lattice_kernel(const float* __restrict__ logits, int ld, int T, int Bn, int C,
                                                            const int* __restrict__ targets, const int* __restrict__ tgt_off,
                                                            const int* __restrict__ in_lens, const int* __restrict__ tgt_lens,
                                                            const float* __restrict__ lse, float* __restrict__ ab, int Smax,
-                                                           float* __restrict__ nll) {
+                                                           float* __restrict__ nll, float star_pen, const int* __restrict__ flags) {
   extern __shared__ __attribute__((aligned(16))) float smem[];  // [2][S] rows
   const int b = blockIdx.x, dirn = blockIdx.y;
   const int Tb = min(in_lens[b], T), U = tgt_lens[b];
@@ -77,6 +87,18 @@ __global__ __launch_bounds__(1024) void ctc_lattice_kernel(const float* __restri
   float* row0 = smem;
   float* row1 = smem + Smax;
   const int nthr = blockDim.x;
+  int nfree0 = 2, nfree1 = 2;                                 // STAR: how many states a path may start in / end in
+  if constexpr (STAR) {
+    int bad = 0;
+    for (int u = threadIdx.x; u < U; u += nthr) bad |= (lab[u] < 1 || lab[u] > C);
+    if (__syncthreads_or(bad)) {                              // uniform: the utterance is infeasible, its lattice stays unwritten
+      if (dirn == 0 && threadIdx.x == 0) nll[b] = INFINITY;
+      return;
+    }
+    const int f = flags ? flags[b] : 0;
+    nfree0 = (f & 1) ? 4 : 2;
+    nfree1 = (f & 2) ? 4 : 2;
+  }
   // this thread owns states s = tid, tid + nthr, ... (normally exactly one)
   // generic loop for very long targets; the common case S <= blockDim.x runs one iteration.
   const int step = dirn == 0 ? 1 : -1;
@@ -84,11 +106,19 @@ __global__ __launch_bounds__(1024) void ctc_lattice_kernel(const float* __restri
 
   // init row
   for (int s = threadIdx.x; s < S; s += nthr) {
-    const int cls = (s & 1) ? lab[s >> 1] : 0;
-    const float lp = logits[((long long)tfirst * Bn + b) * ld + cls] - lse[tfirst * Bn + b];
+    int cls = (s & 1) ? lab[s >> 1] : 0;
+    bool star = false;
+    if constexpr (STAR) { star = cls == C; cls = star ? 0 : cls; }
+    float lp = logits[((long long)tfirst * Bn + b) * ld + cls] - lse[tfirst * Bn + b];
+    if constexpr (STAR) lp = star ? star_pen : lp;
     float v = NEG_INF;
-    if (dirn == 0) { if (s == 0 || s == 1) v = lp; }
-    else { if (s == S - 1 || s == S - 2) v = lp; }
+    if constexpr (STAR) {
+      if (dirn == 0) { if (s < nfree0) v = lp; }
+      else { if (s >= S - nfree1) v = lp; }
+    } else {
+      if (dirn == 0) { if (s == 0 || s == 1) v = lp; }
+      else { if (s == S - 1 || s == S - 2) v = lp; }
+    }
     row0[s] = v;
     out[(long long)tfirst * Smax + s] = v;
   }
@@ -108,6 +138,8 @@ __global__ __launch_bounds__(1024) void ctc_lattice_kernel(const float* __restri
       if (dirn == 0) skip = (s >= 2) && (s & 1) && (lab[s >> 1] != lab[(s >> 1) - 1]);
       else skip = (s + 2 < S) && (s & 1) && (lab[s >> 1] != lab[(s >> 1) + 1]);
     }
+    bool star = false;
+    if constexpr (STAR) { star = cls == C; cls = star ? 0 : cls; }
     const long long lg_stride = (long long)step * Bn * ld;
     const int ls_stride = step * Bn, out_stride = step * Smax;
     const float* lgp = logits + ((long long)tfirst * Bn + b) * ld + cls;        // frame tfirst, this state's class
@@ -119,7 +151,9 @@ __global__ __launch_bounds__(1024) void ctc_lattice_kernel(const float* __restri
     const int last = Tb - 1;
     auto emission = [&](int i) {                                                  // frame index clamped: always a valid address
       const int ii = i < last ? i : last;
-      return lgp[(long long)ii * lg_stride] - lsp[(long long)ii * ls_stride];
+      const float e = lgp[(long long)ii * lg_stride] - lsp[(long long)ii * ls_stride];
+      if constexpr (STAR) return star ? star_pen : e;           // selected 4 frames ahead of its use
+      return e;
     };
     float nx0 = emission(1), nx1 = emission(2), nx2 = emission(3), nx3 = emission(4);
     const int sa = act ? s : 0;
@@ -131,8 +165,13 @@ __global__ __launch_bounds__(1024) void ctc_lattice_kernel(const float* __restri
       const float a0 = prev[sa];
       const float a1 = has1 ? prev[s1] : NEG_INF;
       const float a2 = skip ? prev[s2] : NEG_INF;
-      const float m = lse3(a0, a1, a2);
-      const float v = (m == NEG_INF) ? NEG_INF : m + lp;
+      float v;
+      if constexpr (STAR) {
+        v = star_cell(a0, a1, a2, lp, star);
+      } else {
+        const float m = lse3(a0, a1, a2);
+        v = (m == NEG_INF) ? NEG_INF : m + lp;
+      }
       if (act) {
         cur[s] = v;
         *op = v;
@@ -144,8 +183,11 @@ __global__ __launch_bounds__(1024) void ctc_lattice_kernel(const float* __restri
     for (int i = 1; i < Tb; ++i) {
       const int t = tfirst + step * i;
       for (int s = threadIdx.x; s < S; s += nthr) {
-        const int cls = (s & 1) ? lab[s >> 1] : 0;
-        const float lp = logits[((long long)t * Bn + b) * ld + cls] - lse[t * Bn + b];
+        int cls = (s & 1) ? lab[s >> 1] : 0;
+        bool star = false;
+        if constexpr (STAR) { star = cls == C; cls = star ? 0 : cls; }
+        float lp = logits[((long long)t * Bn + b) * ld + cls] - lse[t * Bn + b];
+        if constexpr (STAR) lp = star ? star_pen : lp;
         float a0 = prev[s], a1, a2;
         if (dirn == 0) {
           const bool skip = (s >= 2) && (s & 1) && (lab[s >> 1] != lab[(s >> 1) - 1]);
@@ -156,8 +198,13 @@ __global__ __launch_bounds__(1024) void ctc_lattice_kernel(const float* __restri
           a1 = (s + 1 < S) ? prev[s + 1] : NEG_INF;
           a2 = skip ? prev[s + 2] : NEG_INF;
         }
-        const float m = lse3(a0, a1, a2);
-        const float v = (m == NEG_INF) ? NEG_INF : m + lp;
+        float v;
+        if constexpr (STAR) {
+          v = star_cell(a0, a1, a2, lp, star);
+        } else {
+          const float m = lse3(a0, a1, a2);
+          v = (m == NEG_INF) ? NEG_INF : m + lp;
+        }
         cur[s] = v;
         out[(long long)t * Smax + s] = v;
       }
@@ -168,7 +215,8 @@ __global__ __launch_bounds__(1024) void ctc_lattice_kernel(const float* __restri
   if (dirn == 0 && threadIdx.x == 0) {
     const float l1 = prev[S - 1];
     const float l2 = (S >= 2) ? prev[S - 2] : NEG_INF;
-    nll[b] = -lse2(l1, l2);
+    if (STAR && nfree1 == 4) nll[b] = star_end_nll(l1, l2, (S >= 3) ? prev[S - 3] : NEG_INF, (S >= 4) ? prev[S - 4] : NEG_INF);
+    else nll[b] = -lse2(l1, l2);
   }
 }
 
@@ -199,10 +247,24 @@ __device__ __forceinline__ float lse2_sel(float a, float b) {
   return (m == NEG_INF) ? NEG_INF : r;
 }
 
-template <int DIRN>
-__device__ __forceinline__ void ctc_lattice_wave_body(const float* __restrict__ logits, int ld, int T, int Bn, const int* __restrict__ lab,
-                                                      int b, int Tb, int U, const float* __restrict__ lse, float* __restrict__ out, int Smax,
-                                                      float* __restrict__ nll) {
+// One lattice cell of the STAR instances: lse3 of the predecessors + the emission.  For every state but a wildcard these are the
+// expressions of lse3 / lse3_sel and of the add that follows them, in their operand order: (m + log(sum)) + lp.  A wildcard's emission is
+// the SAME constant in every frame: added to the finished lse, a value of the magnitude of alpha (hundreds), it is rounded to that
+// value's grid in the same direction every frame, and the error does not average out but drifts (T = 420, U = 200: 1.5e-3 in nll, 1.2e-3
+// relative in the gradient, five times the plain loss's error).  So a wildcard adds its constant to log(sum) first, m + (log(sum) + lp):
+// the one rounding at alpha's magnitude then sees a value that differs from frame to frame, as for every other state.
+__device__ __forceinline__ float star_cell(float a0, float a1, float a2, float lp, bool star) {
+  const float m = fmaxf(a0, fmaxf(a1, a2));
+  const float lg = fast_log_(fast_exp_(a0 - m) + fast_exp_(a1 - m) + fast_exp_(a2 - m));
+  const float x = (star ? lp : m) + lg;
+  const float y = star ? m : lp;
+  return (m == NEG_INF) ? NEG_INF : x + y;
+}
+
+template <int DIRN, bool STAR>
+__device__ __forceinline__ void ctc_lattice_wave_body(const float* __restrict__ logits, int ld, int T, int Bn, int C,
+                                                      const int* __restrict__ lab, int b, int Tb, int U, const float* __restrict__ lse,
+                                                      float* __restrict__ out, int Smax, float* __restrict__ nll, float star_pen, int flag) {
   const int S = 2 * U + 1;
   const int l = threadIdx.x;
   const bool actE = 2 * l < S, actO = 2 * l + 1 < S;
@@ -214,6 +276,18 @@ __device__ __forceinline__ void ctc_lattice_wave_body(const float* __restrict__ 
     cls = lab[l];
     if (DIRN == 0) skip = (l >= 1) && (cls != lab[l - 1]);
     else skip = (l + 1 < U) && (cls != lab[l + 1]);
+  }
+  // STAR: a wildcard lane loads the blank's logit (a valid address) and never uses it: `frame` takes the odd state's emission through ONE
+  // select as before, whose arms become (loaded emission | lane constant) with the constant star_pen for a wildcard and NEG_INF for a
+  // state >= S, so a frame has the instructions it had
+  bool ldO = actO, starO = false;
+  float cstO = NEG_INF;
+  if constexpr (STAR) {
+    const bool star = actO && cls == C;
+    starO = star;
+    cls = star ? 0 : cls;
+    ldO = actO && !star;
+    cstO = star ? star_pen : NEG_INF;
   }
   const long long lg_stride = (long long)step * Bn * ld;
   const int ls_stride = step * Bn, out_stride = step * Smax;
@@ -244,27 +318,38 @@ __device__ __forceinline__ void ctc_lattice_wave_body(const float* __restrict__ 
   {
     float lgE, lgO, ls;
     fetch(0, lgE, lgO, ls);
-    const float eE = lgE - ls, eO = lgO - ls;
-    if (DIRN == 0) { if (l == 0) { E = eE; if (actO) O = eO; } }
-    else { if (2 * l == S - 1) E = eE; if (actO && 2 * l + 1 == S - 2) O = eO; }
+    const float eE = lgE - ls;
+    float eO = lgO - ls;
+    if constexpr (STAR) {
+      eO = ldO ? eO : cstO;
+      const int n0 = (flag & 1) ? 4 : 2, n1 = (flag & 2) ? 4 : 2;
+      if (DIRN == 0) { if (actE && 2 * l < n0) E = eE; if (actO && 2 * l + 1 < n0) O = eO; }
+      else { if (actE && 2 * l >= S - n1) E = eE; if (actO && 2 * l + 1 >= S - n1) O = eO; }
+    } else {
+      if (DIRN == 0) { if (l == 0) { E = eE; if (actO) O = eO; } }
+      else { if (2 * l == S - 1) E = eE; if (actO && 2 * l + 1 == S - 2) O = eO; }
+    }
     store_pair();
   }
   // one frame: a state >= S gets the emission NEG_INF, which holds it at NEG_INF without a select on the chain
   auto frame = [&](float lgE, float lgO, float ls) {
-    const float lpE = actE ? lgE - ls : NEG_INF, lpO = actO ? lgO - ls : NEG_INF;
+    const float lpE = actE ? lgE - ls : NEG_INF, lpO = STAR ? (ldO ? lgO - ls : cstO) : (actO ? lgO - ls : NEG_INF);
     op += out_stride;
-    float mE, mO;
+    float mE, mO = NEG_INF, nO = NEG_INF;                                         // (nO: the odd state's new value, STAR)
     if (DIRN == 0) {
       const float Om = wave_shift1<0x138>(O);                                   // state 2l - 1
       mE = lse2_sel(E, Om);
-      mO = lse3_sel(O, E, skip ? Om : NEG_INF);
+      if constexpr (STAR) nO = star_cell(O, E, skip ? Om : NEG_INF, lpO, starO);
+      else mO = lse3_sel(O, E, skip ? Om : NEG_INF);
     } else {
       const float Ep = wave_shift1<0x130>(E), Op = wave_shift1<0x130>(O);       // states 2l + 2, 2l + 3
       mE = lse2_sel(E, O);
-      mO = lse3_sel(O, Ep, skip ? Op : NEG_INF);
+      if constexpr (STAR) nO = star_cell(O, Ep, skip ? Op : NEG_INF, lpO, starO);
+      else mO = lse3_sel(O, Ep, skip ? Op : NEG_INF);
     }
     E = (mE == NEG_INF) ? NEG_INF : mE + lpE;
-    O = (mO == NEG_INF) ? NEG_INF : mO + lpO;
+    if constexpr (STAR) O = nO;
+    else O = (mO == NEG_INF) ? NEG_INF : mO + lpO;
     store_pair();
   };
   float rE[WPF], rO[WPF], rL[WPF];
@@ -285,16 +370,26 @@ __device__ __forceinline__ void ctc_lattice_wave_body(const float* __restrict__ 
   if (DIRN == 0) {
     const float l1 = __shfl(E, U, 64);                                          // state S - 1 = 2U
     const float l2 = __shfl(O, U >= 1 ? U - 1 : 0, 64);                         // state S - 2
-    if (l == 0) nll[b] = -lse2(l1, (S >= 2) ? l2 : NEG_INF);
+    if constexpr (STAR) {
+      const float l3 = __shfl(E, U >= 1 ? U - 1 : 0, 64);                       // state S - 3
+      const float l4 = __shfl(O, U >= 2 ? U - 2 : 0, 64);                       // state S - 4
+      if (l == 0) {
+        if (flag & 2) nll[b] = star_end_nll(l1, (S >= 2) ? l2 : NEG_INF, (S >= 3) ? l3 : NEG_INF, (S >= 4) ? l4 : NEG_INF);
+        else nll[b] = -lse2(l1, (S >= 2) ? l2 : NEG_INF);
+      }
+    } else {
+      if (l == 0) nll[b] = -lse2(l1, (S >= 2) ? l2 : NEG_INF);
+    }
   }
 }
 
 // blockIdx.x = utterance, blockIdx.y = direction; 64 threads.  Needs 2 * tgt_lens[b] + 1 <= 128 for every b (the launcher checks Smax).
+template <bool STAR>
 __global__ __launch_bounds__(64) void ctc_lattice_wave_kernel(const float* __restrict__ logits, int ld, int T, int Bn, int C,
                                                               const int* __restrict__ targets, const int* __restrict__ tgt_off,
                                                               const int* __restrict__ in_lens, const int* __restrict__ tgt_lens,
                                                               const float* __restrict__ lse, float* __restrict__ ab, int Smax,
-                                                              float* __restrict__ nll) {
+                                                              float* __restrict__ nll, float star_pen, const int* __restrict__ flags) {
   const int b = blockIdx.x, dirn = blockIdx.y;
   const int Tb = min(in_lens[b], T), U = tgt_lens[b];
   float* out = ab + (((long long)dirn * Bn + b) * T) * Smax;
@@ -303,18 +398,31 @@ __global__ __launch_bounds__(64) void ctc_lattice_wave_kernel(const float* __res
     return;
   }
   const int* lab = targets + tgt_off[b];
-  if (dirn == 0) ctc_lattice_wave_body<0>(logits, ld, T, Bn, lab, b, Tb, U, lse, out, Smax, nll);
-  else ctc_lattice_wave_body<1>(logits, ld, T, Bn, lab, b, Tb, U, lse, out, Smax, nll);
+  int flag = 0;
+  if constexpr (STAR) {
+    const int l = threadIdx.x;
+    const bool bad = l < U && (lab[l] < 1 || lab[l] > C);     // one label per lane (U <= 63)
+    if (__ballot(bad) != 0) {                                 // uniform: the utterance is infeasible, its lattice stays unwritten
+      if (dirn == 0 && l == 0) nll[b] = INFINITY;
+      return;
+    }
+    flag = flags ? flags[b] : 0;
+  }
+  if (dirn == 0) ctc_lattice_wave_body<0, STAR>(logits, ld, T, Bn, C, lab, b, Tb, U, lse, out, Smax, nll, star_pen, flag);
+  else ctc_lattice_wave_body<1, STAR>(logits, ld, T, Bn, C, lab, b, Tb, U, lse, out, Smax, nll, star_pen, flag);
 }
 
 // grid = (ceil(T / TCH), B); block = 128 threads; dynamic LDS: q[C] + val[S] + nxt[U] (ints) + lab[U]
+// STAR: q has the slot C for the wildcard's occupancy (its labels chain like any repeated label: one writer), the wildcard's emission is
+// the constant, and the softmax term is multiplied by 1 - q[C]:  grad = scale * (softmax * (1 - occ_star) - occ)
 constexpr int TCH = 8;
+template <bool STAR>
 __global__ __launch_bounds__(128) void ctc_grad_kernel(const float* __restrict__ logits, int ld, float* __restrict__ grad, int ldg, int T,
                                                        int Bn, int C, const int* __restrict__ targets,
                                                        const int* __restrict__ tgt_off, const int* __restrict__ in_lens,
                                                        const int* __restrict__ tgt_lens, const float* __restrict__ lse,
                                                        const float* __restrict__ ab, int Smax, const float* __restrict__ nll,
-                                                       float scale) {
+                                                       float scale, float star_pen) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   __shared__ float bred[2];
   const int b = blockIdx.y;
@@ -323,8 +431,9 @@ __global__ __launch_bounds__(128) void ctc_grad_kernel(const float* __restrict__
   const int S = 2 * U + 1;
   const float nl = nll[b];
   const bool feasible = (nl != INFINITY) && (nl == nl);
-  float* q = smem;                      // [C]
-  float* val = q + C;                   // [S]
+  constexpr int QX = STAR ? 1 : 0;
+  float* q = smem;                      // [C] (STAR: [C + 1])
+  float* val = q + C + QX;              // [S]
   int* nxt = (int*)(val + Smax);        // [U]
   int* labs = nxt + (Smax / 2 + 1);     // [U]
   int* hd = labs + (Smax / 2 + 1);      // [U] 1 = first occurrence of its label (the thread that sums the chain)
@@ -357,13 +466,17 @@ __global__ __launch_bounds__(128) void ctc_grad_kernel(const float* __restrict__
     }
     const float* lg = logits + ((long long)t * Bn + b) * ld;
     const float ls = lse[t * Bn + b];
-    for (int c = tid; c < C; c += nthr) q[c] = 0.f;
+    for (int c = tid; c < C + QX; c += nthr) q[c] = 0.f;
     float bsum = 0.f;
     for (int s = tid; s < S; s += nthr) {
-      const int cls = (s & 1) ? labs[s >> 1] : 0;
+      int cls = (s & 1) ? labs[s >> 1] : 0;
+      bool star = false;
+      if constexpr (STAR) { star = cls == C; cls = star ? 0 : cls; }
       const float a = alpha[(long long)t * Smax + s] + beta[(long long)t * Smax + s];
+      float e = lg[cls] - ls;
+      if constexpr (STAR) e = star ? star_pen : e;
       float v = 0.f;
-      if (a != NEG_INF) v = expf(a - (lg[cls] - ls) + nl);
+      if (a != NEG_INF) v = expf(a - e + nl);
       if (s & 1) val[s >> 1] = v;
       else bsum += v;
     }
@@ -381,7 +494,12 @@ __global__ __launch_bounds__(128) void ctc_grad_kernel(const float* __restrict__
     }
     if (tid == 0) q[0] += bred[0] + bred[1];
     __syncthreads();
-    for (int c = tid; c < C; c += nthr) g[c] = scale * (expf(lg[c] - ls) - q[c]);
+    if constexpr (STAR) {
+      const float keep = 1.f - q[C];
+      for (int c = tid; c < C; c += nthr) g[c] = scale * (expf(lg[c] - ls) * keep - q[c]);
+    } else {
+      for (int c = tid; c < C; c += nthr) g[c] = scale * (expf(lg[c] - ls) - q[c]);
+    }
     __syncthreads();
   }
 }
@@ -437,6 +555,43 @@ extern "C" size_t ds2_ctc_workspace_bytes(int T, int B, int max_target_len) {
   return align_up((size_t)T * B * sizeof(float), 256) + 2 * (size_t)B * T * Smax * sizeof(float);
 }
 
+namespace {
+template <bool STAR>
+int ctc_loss_launch(const float* logits, int ld, int T, int B, int C, const int* targets_dev, const int* tgt_off_dev, const int* in_lens_dev,
+                    const int* tgt_lens_dev, int max_target_len, float star_pen, const int* flags_dev, float* nll_dev, float* grad, int ldg,
+                    float grad_scale, int lattice, void* ws, hipStream_t s) {
+  const int Smax = 2 * max_target_len + 1;
+  float* lse = (float*)ws;
+  float* ab = (float*)((char*)ws + align_up((size_t)T * B * sizeof(float), 256));
+  // every size is checked before the first launch
+  const size_t lds = (size_t)2 * Smax * sizeof(float);
+  const bool wave = lattice == 0 && Smax <= 128;
+  DS2_REQUIRE(wave || lds <= 64 * 1024, "ds2_ctc_loss_f32: target too long for LDS lattice rows (Smax=%d)", Smax);
+  const size_t lds2 = ((size_t)C + (STAR ? 1 : 0) + Smax) * sizeof(float) + 3 * ((size_t)Smax / 2 + 1) * sizeof(int);
+  DS2_REQUIRE(!grad || lds2 <= 64 * 1024, "ds2_ctc_loss_f32: C/S too large for LDS (C=%d Smax=%d)", C, Smax);
+  hipLaunchKernelGGL(ctc_lse_kernel, dim3(ceil_div(T * B, 4)), dim3(256), 0, s, logits, ld, T, B, C, in_lens_dev, lse);
+  DS2_LAUNCH_CHECK("ctc_lse_kernel");
+  if (wave) {
+    hipLaunchKernelGGL(ctc_lattice_wave_kernel<STAR>, dim3(B, 2), dim3(64), 0, s, logits, ld, T, B, C, targets_dev, tgt_off_dev, in_lens_dev,
+                       tgt_lens_dev, (const float*)lse, ab, Smax, nll_dev, star_pen, flags_dev);
+    DS2_LAUNCH_CHECK("ctc_lattice_wave_kernel");
+  } else {
+    int threads = ceil_div(Smax, 64) * 64;
+    if (threads > 1024) threads = 1024;
+    hipLaunchKernelGGL(ctc_lattice_kernel<STAR>, dim3(B, 2), dim3(threads), lds, s, logits, ld, T, B, C, targets_dev, tgt_off_dev,
+                       in_lens_dev, tgt_lens_dev, (const float*)lse, ab, Smax, nll_dev, star_pen, flags_dev);
+    DS2_LAUNCH_CHECK("ctc_lattice_kernel");
+  }
+  if (grad) {
+    hipLaunchKernelGGL(ctc_grad_kernel<STAR>, dim3(ceil_div(T, TCH), B), dim3(128), lds2, s, logits, ld, grad, ldg, T, B, C, targets_dev,
+                       tgt_off_dev, in_lens_dev, tgt_lens_dev, (const float*)lse, (const float*)ab, Smax, (const float*)nll_dev,
+                       grad_scale, star_pen);
+    DS2_LAUNCH_CHECK("ctc_grad_kernel");
+  }
+  return 0;
+}
+}  // namespace
+
 // targets: flat labels (device int32), tgt_off[b] = start of utterance b in `targets` (device int32).
 // lattice: 0 = the launcher chooses (one wave per lattice when 2 * max_target_len + 1 <= 128, else one workgroup per lattice),
 //          1 = always one workgroup per lattice (ctc_lattice_kernel; the two produce the same bits: tests/test_gpu_ctc_wave.py)
@@ -447,34 +602,25 @@ extern "C" int ds2_ctc_loss_ex_f32(const float* logits, int ld, int T, int B, in
   DS2_REQUIRE(T > 0 && B > 0 && C > 0 && max_target_len >= 0, "ds2_ctc_loss_f32: bad dims");
   DS2_REQUIRE(lattice == 0 || lattice == 1, "ds2_ctc_loss_ex_f32: lattice must be 0 or 1");
   DS2_REQUIRE(ws && ws_bytes >= ds2_ctc_workspace_bytes(T, B, max_target_len), "ds2_ctc_loss_f32: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  const int Smax = 2 * max_target_len + 1;
-  float* lse = (float*)ws;
-  float* ab = (float*)((char*)ws + align_up((size_t)T * B * sizeof(float), 256));
-  hipLaunchKernelGGL(ctc_lse_kernel, dim3(ceil_div(T * B, 4)), dim3(256), 0, s, logits, ld, T, B, C, in_lens_dev, lse);
-  DS2_LAUNCH_CHECK("ctc_lse_kernel");
-  if (lattice == 0 && Smax <= 128) {
-    hipLaunchKernelGGL(ctc_lattice_wave_kernel, dim3(B, 2), dim3(64), 0, s, logits, ld, T, B, C, targets_dev, tgt_off_dev, in_lens_dev,
-                       tgt_lens_dev, (const float*)lse, ab, Smax, nll_dev);
-    DS2_LAUNCH_CHECK("ctc_lattice_wave_kernel");
-  } else {
-    int threads = ceil_div(Smax, 64) * 64;
-    if (threads > 1024) threads = 1024;
-    const size_t lds = (size_t)2 * Smax * sizeof(float);
-    DS2_REQUIRE(lds <= 64 * 1024, "ds2_ctc_loss_f32: target too long for LDS lattice rows (Smax=%d)", Smax);
-    hipLaunchKernelGGL(ctc_lattice_kernel, dim3(B, 2), dim3(threads), lds, s, logits, ld, T, B, C, targets_dev, tgt_off_dev,
-                       in_lens_dev, tgt_lens_dev, (const float*)lse, ab, Smax, nll_dev);
-    DS2_LAUNCH_CHECK("ctc_lattice_kernel");
-  }
-  if (grad) {
-    const size_t lds2 = ((size_t)C + Smax) * sizeof(float) + 3 * ((size_t)Smax / 2 + 1) * sizeof(int);
-    DS2_REQUIRE(lds2 <= 64 * 1024, "ds2_ctc_loss_f32: C/S too large for LDS (C=%d Smax=%d)", C, Smax);
-    hipLaunchKernelGGL(ctc_grad_kernel, dim3(ceil_div(T, TCH), B), dim3(128), lds2, s, logits, ld, grad, ldg, T, B, C, targets_dev,
-                       tgt_off_dev, in_lens_dev, tgt_lens_dev, (const float*)lse, (const float*)ab, Smax, (const float*)nll_dev,
-                       grad_scale);
-    DS2_LAUNCH_CHECK("ctc_grad_kernel");
-  }
-  return 0;
+  return ctc_loss_launch<false>(logits, ld, T, B, C, targets_dev, tgt_off_dev, in_lens_dev, tgt_lens_dev, max_target_len, 0.f, nullptr, nll_dev,
+                                grad, ldg, grad_scale, lattice, ws, (hipStream_t)stream);
+}
+
+// The wildcard loss (contract: include/ds2hip.h): the STAR = true instances of the same kernels, the same workspace.
+extern "C" size_t ds2_ctc_star_workspace_bytes(int T, int B, int max_target_len) { return ds2_ctc_workspace_bytes(T, B, max_target_len); }
+
+extern "C" int ds2_ctc_star_loss_f32(const float* logits, int ld, int T, int B, int C, const int* targets_dev, const int* tgt_off_dev,
+                                     const int* in_lens_dev, const int* tgt_lens_dev, int max_target_len, float star_penalty,
+                                     const int* flags_dev, float* nll_dev, float* grad, int ldg, float grad_scale, int lattice, void* ws,
+                                     size_t ws_bytes, void* stream) {
+  DS2_REQUIRE(logits && targets_dev && tgt_off_dev && in_lens_dev && tgt_lens_dev && nll_dev, "ds2_ctc_star_loss_f32: null pointer");
+  DS2_REQUIRE(T > 0 && B > 0 && C > 0 && max_target_len >= 0, "ds2_ctc_star_loss_f32: bad dims");
+  DS2_REQUIRE(lattice == 0 || lattice == 1, "ds2_ctc_star_loss_f32: lattice must be 0 or 1");
+  DS2_REQUIRE(star_penalty <= 0.f && star_penalty >= -3.402823466e+38f, "ds2_ctc_star_loss_f32: star_penalty must be finite and <= 0, got %g",
+              (double)star_penalty);                                                          // (NaN fails the first test)
+  DS2_REQUIRE(ws && ws_bytes >= ds2_ctc_star_workspace_bytes(T, B, max_target_len), "ds2_ctc_star_loss_f32: workspace too small");
+  return ctc_loss_launch<true>(logits, ld, T, B, C, targets_dev, tgt_off_dev, in_lens_dev, tgt_lens_dev, max_target_len, star_penalty,
+                               flags_dev, nll_dev, grad, ldg, grad_scale, lattice, ws, (hipStream_t)stream);
 }
 
 extern "C" int ds2_ctc_loss_f32(const float* logits, int ld, int T, int B, int C, const int* targets_dev, const int* tgt_off_dev,

@@ -345,14 +345,27 @@ class GpuSpectrogramFrontEnd:
                                  self.freq_mask_param, self.time_mask_param, self.freq_masks, self.time_masks)
 
 
+def _check_star(star, labels):
+    """get_loader's `star`: None, or a single character outside the label set (the rule of decoders.encode_transcripts)."""
+    if star is None:
+        return None
+    if not isinstance(star, str) or len(star) != 1:
+        raise ValueError(f"star must be a single character, got {star!r}")
+    if star in labels:
+        raise ValueError(f"star {star!r} is a label: choose a character outside the label set")
+    return star
+
+
 class SpectrogramDataset(Dataset):
-    def __init__(self, audio_conf, manifest_filepath, labels, normalize=False, spec_augment=False, caching=False, resample=False):
+    def __init__(self, audio_conf, manifest_filepath, labels, normalize=False, spec_augment=False, caching=False, resample=False,
+                 star=None):
         import pandas as pd
         self.df = pd.read_csv(manifest_filepath)
         self.size = len(self.df)
         if isinstance(labels, str):
             labels = dict([(v, k) for k, v in pd.read_csv(labels).to_dict()["label"].items()])
         self.labels_map = labels
+        self.star = _check_star(star, labels)
         self.audio_conf, self.normalize, self.caching = audio_conf, normalize, caching
         self.resample = bool(resample)                   # an off-rate WAV file is converted on the host (resample_waveform)
         self._cache = {}
@@ -383,9 +396,16 @@ class SpectrogramDataset(Dataset):
         return spect
 
     def parse_transcript(self, transcript):
-        """spectrogram_dataset.py:70-73: unknown chars and the index-0 (blank) label are dropped."""
+        """spectrogram_dataset.py:70-73: unknown chars and the index-0 (blank) label are dropped.
+        With `star` (a single character that is not a label) that character becomes the wildcard id len(labels), one past the last
+        class, for CTCLoss(star=True): every other unknown character is dropped first, then runs of wildcards collapse to one."""
         transcript = transcript.replace("\n", "")
-        return list(filter(None, [self.labels_map.get(x) for x in list(transcript)]))
+        star = getattr(self, "star", None)
+        if star is None:
+            return list(filter(None, [self.labels_map.get(x) for x in list(transcript)]))
+        star_id = len(self.labels_map)
+        ids = list(filter(None, [star_id if x == star else self.labels_map.get(x) for x in list(transcript)]))
+        return [i for k, i in enumerate(ids) if not (i == star_id and k > 0 and ids[k - 1] == star_id)]
 
     def __getitem__(self, index):
         row = self.df.iloc[index]
@@ -409,13 +429,14 @@ class WaveformDataset(Dataset):
     column is not trusted.  Raw items then carry it — `get_raw` returns `(samples, rate, ids)` and the loader converts the batch on the
     GPU (ops.wave_resample) — while `__getitem__` returns the waveform converted on the host (`resample_waveform`)."""
 
-    def __init__(self, audio_conf, manifest_filepath, labels, caching=False, perturb=False, resample=False):
+    def __init__(self, audio_conf, manifest_filepath, labels, caching=False, perturb=False, resample=False, star=None):
         import pandas as pd
         self.df = pd.read_csv(manifest_filepath)
         self.size = len(self.df)
         if isinstance(labels, str):
             labels = dict([(v, k) for k, v in pd.read_csv(labels).to_dict()["label"].items()])
         self.labels_map = labels
+        self.star = _check_star(star, labels)
         self.audio_conf, self.caching, self.resample = audio_conf, caching, bool(resample)
         self._cache, self._raw_cache = {}, {}
         for f in self.df.audio_filepath:
@@ -961,7 +982,7 @@ class AudioDataLoader(DataLoader):
 
 
 def get_loader(audio_conf, labels, manifest, batch_size, num_workers, caching=False, length_bucketing=False, front_end="host",
-               perturb=False, prefetch=0, resample=False):
+               perturb=False, prefetch=0, resample=False, star=None):
     """data/loaders/functional.py:6-24.  `length_bucketing=True` (not in the reference) sorts the manifest by its `duration` column
     before binning (LengthBucketingSampler; the distributed variant when torch.distributed is initialised).
 
@@ -985,7 +1006,10 @@ def get_loader(audio_conf, labels, manifest, batch_size, num_workers, caching=Fa
     8 kHz against 16 kHz are) — and converts each to audio_conf.sample_rate by Kaiser-windowed sinc interpolation: with front_end="gpu"
     per batch on the GPU, fused into the unpack pass (ops.wave_resample), ahead of the unchanged tempo, noise, STFT and SpecAugment
     kernels, for `prefetch=0` too; the noise bank converts its off-rate files once; with front_end="host" per item in the workers
-    (`resample_waveform`).  Parity with sox / ffmpeg is unpinned."""
+    (`resample_waveform`).  Parity with sox / ffmpeg is unpinned.
+    `star="*"` (default None: the ids are exactly the ones above): that character, any single one that is not a label, in a manifest's
+    transcript becomes the wildcard id len(labels) for `asr_amd.CTCLoss(star=True)` — "this part was not transcribed"; characters that
+    are neither a label nor the star are dropped first, then runs of wildcards collapse to one."""
     if front_end not in ("host", "gpu"):
         raise ValueError(f"front_end={front_end!r}: expected host or gpu")
     if perturb and front_end != "gpu":
@@ -996,12 +1020,13 @@ def get_loader(audio_conf, labels, manifest, batch_size, num_workers, caching=Fa
         raise ValueError("prefetch needs front_end='gpu' (the host front-end's batches are made in the workers already)")
     if front_end == "gpu":
         dataset = WaveformDataset(audio_conf=audio_conf, manifest_filepath=manifest, labels=labels, caching=caching, perturb=perturb,
-                                  resample=bool(resample))
+                                  resample=bool(resample), star=star)
         fe = GpuSpectrogramFrontEnd(audio_conf, normalize=True, augment=True, speed_volume_perturb=perturb, resample=bool(resample))
         make = lambda sampler: GpuAudioDataLoader(dataset, sampler, num_workers, fe, prefetch=int(prefetch))      # noqa: E731
     else:
         dataset = SpectrogramDataset(audio_conf=audio_conf, manifest_filepath=manifest, labels=labels, normalize=True,
-                                     spec_augment=getattr(audio_conf, "spec_augment", False), caching=caching, resample=bool(resample))
+                                     spec_augment=getattr(audio_conf, "spec_augment", False), caching=caching, resample=bool(resample),
+                                     star=star)
         make = lambda sampler: AudioDataLoader(dataset, num_workers=num_workers, batch_sampler=sampler)   # noqa: E731
     if length_bucketing and torch.distributed.is_available() and torch.distributed.is_initialized():
         sampler = DistributedLengthBucketingSampler(dataset, batch_size=batch_size)

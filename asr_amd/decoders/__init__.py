@@ -260,6 +260,26 @@ def encode_transcripts(transcripts, labels, star=None, unknown="error"):
     return out
 
 
+def wildcard_ends(targets, star_id, free_start=False, free_end=False, distinct_paths=False):
+    """The free_start / free_end rule of CTCAligner.align and asr_amd.CTCLoss on id lists: a wildcard (star_id) is put at the front /
+    back of every target unless one is there, runs of adjacent wildcards collapse to one, and the per-utterance flags say which end
+    token is optional (bit 0 the first, bit 1 the last).  Returns (targets, flags).
+    distinct_paths (the loss, which SUMS over state paths where the aligner takes the best one): a target of ONE token does not get
+    both bits — its first token is its last, and with both the all-blank path would exist twice, in state 0 and in state 2 — it
+    keeps bit 0, which already makes that token optional."""
+    out = []
+    for t in targets:
+        t = [int(i) for i in t]
+        if free_start and t[:1] != [star_id]:
+            t = [star_id] + t
+        if free_end and t[-1:] != [star_id]:
+            t = t + [star_id]
+        out.append([i for k, i in enumerate(t) if not (i == star_id and k > 0 and t[k - 1] == star_id)])
+    flag = (1 if free_start else 0) | (2 if free_end else 0)
+    flags = [1 if (distinct_paths and flag == 3 and len(t) < 2) else flag for t in out]
+    return out, flags
+
+
 def group_words(tokens, star=None):
     """tokens [(char, start, end, logp, ...)] -> words [(word, start, end, logp)]: a word is the run of tokens between space tokens
     (leading, trailing and doubled spaces make no word), from its first token's start to its last token's end, logp summed in fp64.
@@ -374,11 +394,7 @@ class CTCAligner(Decoder):
             sp = float(star_penalty)
             if not (sp <= 0.0 and math.isfinite(sp)):
                 raise ValueError(f"star_penalty must be finite and <= 0, got {star_penalty}")
-            if free_start:
-                targets = [t if t[:1] == [star_id] else [star_id] + t for t in targets]
-            if free_end:
-                targets = [t if t[-1:] == [star_id] else t + [star_id] for t in targets]
-            flags = [(1 if free_start else 0) | (2 if free_end else 0)] * B
+            targets, flags = wildcard_ends(targets, star_id, free_start, free_end)
         sizes_h = [T] * B if sizes is None else [int(v) for v in torch.as_tensor(sizes).reshape(-1).tolist()]
         if len(sizes_h) != B:
             raise ValueError(f"sizes has {len(sizes_h)} entries for a batch of {B}")

@@ -236,10 +236,10 @@ class DeepSpeech(nn.Module):
         return h, output_lengths
 
     def get_loader(self, manifest, batch_size, num_workers, caching=False, front_end="host", perturb=False, prefetch=0,
-                   resample=False):
+                   resample=False, star=None):
         from ..data import get_loader
         return get_loader(self.audio_conf, self.labels, manifest, batch_size, num_workers, caching=caching, front_end=front_end,
-                          perturb=perturb, prefetch=prefetch, resample=resample)
+                          perturb=perturb, prefetch=prefetch, resample=resample, star=star)
 
     def get_seq_lens(self, input_length: torch.Tensor) -> torch.Tensor:
         """deepspeech.py:275-288: true division per Conv2d on the time axis, one truncation at the end."""

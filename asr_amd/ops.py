@@ -1249,6 +1249,37 @@ def ctc_loss(logits: Tensor, targets_dev: Tensor, tgt_off_dev: Tensor, in_lens_d
     return nll, grad
 
 
+def ctc_star_loss(logits: Tensor, targets_dev: Tensor, tgt_off_dev: Tensor, in_lens_dev: Tensor, tgt_lens_dev: Tensor, max_tgt: int,
+                  grad_scale: float, star_penalty: float = math.log(0.5), flags: Optional[Tensor] = None, want_grad: bool = True,
+                  lattice: int = 0, return_ab: bool = False):
+    """ctc_loss for imperfect transcripts (contract: include/ds2hip.h, ds2_ctc_star_loss_f32): the label value C = logits.shape[2] is
+    the wildcard, whose state emits the constant star_penalty (<= 0, finite, natural log); flags (B) int32 on the device, or None:
+    bit 0 = the first token is optional, bit 1 = the last.  Everything else, and what is returned, as ctc_loss; without a wildcard
+    and without flags the results are its bits."""
+    _chk_f32(logits)
+    lib = _lib.load()
+    T, B, Cc = logits.shape
+    assert logits.stride(2) == 1 and logits.stride(0) == B * logits.stride(1)
+    if flags is not None:
+        assert flags.dtype == torch.int32 and flags.numel() == B and flags.is_contiguous() and flags.device == logits.device
+    ld = logits.stride(1)
+    nll = torch.empty(B, dtype=torch.float32, device=logits.device)
+    grad = torch.empty(T, B, Cc, dtype=torch.float32, device=logits.device) if want_grad else None
+    wsb = lib.ds2_ctc_star_workspace_bytes(T, B, max_tgt)
+    ws = _ws(wsb, logits.device)
+    if return_ab:
+        ws.zero_()
+    _lib.check(lib.ds2_ctc_star_loss_f32(logits.data_ptr(), ld, T, B, Cc, targets_dev.data_ptr(), tgt_off_dev.data_ptr(),
+                                         in_lens_dev.data_ptr(), tgt_lens_dev.data_ptr(), int(max_tgt), float(star_penalty), _ptr(flags),
+                                         nll.data_ptr(), _ptr(grad), Cc, float(grad_scale), int(lattice), ws.data_ptr(), wsb, _stream()),
+               "ds2_ctc_star_loss_f32")
+    if return_ab:
+        Smax = 2 * int(max_tgt) + 1
+        off = (T * B * 4 + 255) // 256 * 256
+        return nll, grad, ws[off:off + 2 * B * T * Smax * 4].view(torch.float32).view(2, B, T, Smax).clone()
+    return nll, grad
+
+
 def ctc_batch_mean(nll: Tensor) -> Tensor:
     """(1,) fp32 = nll.sum() / B, on the device in a fixed order (trainers/deepspeech_trainer.py:110-112)."""
     _chk_f32(nll)

@@ -16,7 +16,7 @@ import torch
 import torch.distributed as dist
 
 from .. import engine, ops
-from ..ctc import CTCLoss, _prep_targets, _prep_targets_host
+from ..ctc import CTCLoss, _check_star_penalty, _prep_targets, _prep_targets_host
 from ..device import autocast, make_grad_scaler, resolve_device
 from ..functional import check_loss
 from ..optim import FusedAdamW
@@ -176,6 +176,22 @@ class DeepSpeechTrainer:
             print(f"[asr_amd] step re-run on the one-launch-per-step kernels: {e}", file=sys.stderr, flush=True)
             return True
 
+    def _prep_targets_step(self, targets, target_sizes):
+        """The target half of a step's host preparation: (flat targets, offsets, lengths, longest target, flags), CPU int32.  flags is
+        None with a plain criterion (ops.ctc_loss, as ever); an asr_amd.CTCLoss with a wildcard option set has the targets prepared
+        by its own rule (a wildcard at the free ends, runs collapsed) and the step calls ops.ctc_star_loss.  A re-run (_recover) replays
+        this tuple, so it sees the same targets."""
+        crit = self.criterion
+        if isinstance(crit, CTCLoss) and crit.wildcards:
+            return crit.prepare_targets(targets, target_sizes, len(self._model.labels))
+        return _prep_targets_host(targets, target_sizes) + (None,)
+
+    def _ctc(self, logits, tg, off, lens_dev, tl, max_u, flags, B):
+        if flags is None:
+            return ops.ctc_loss(logits, tg, off, lens_dev, tl, max_u, 1.0 / B, want_grad=True)
+        return ops.ctc_star_loss(logits, tg, off, lens_dev, tl, max_u, 1.0 / B, star_penalty=_check_star_penalty(self.criterion.star_penalty),
+                                 flags=flags, want_grad=True)
+
     def _get_reducer(self):
         flat, grad = self._model.flat_parameters()
         if self._reducer is None or self._reducer.flat_grad.data_ptr() != grad.data_ptr():
@@ -212,9 +228,9 @@ class DeepSpeechTrainer:
         # every small integer operand of the step (output lengths, flat targets, their offsets and lengths) goes to the GPU in ONE
         # asynchronous copy from pinned memory: a pageable `.to(device)` is stream-ordered AND blocks the host, i.e. it would make the host
         # wait for the previous step's backward after all
-        t_h, off_h, tl_h, max_u = _prep_targets_host(targets, target_sizes)
-        prep = (inputs, output_sizes.to(torch.int32), t_h, off_h, tl_h, max_u)      # everything a re-run of this batch needs (_recover)
-        lens_dev, tg, off, tl = self._stage_ints(inputs.device, *prep[1:5])
+        t_h, off_h, tl_h, max_u, flags_h = self._prep_targets_step(targets, target_sizes)
+        prep = (inputs, output_sizes.to(torch.int32), t_h, off_h, tl_h, max_u, flags_h)      # everything a re-run of this batch needs (_recover)
+        lens_dev, tg, off, tl, *fl = self._stage_ints(inputs.device, *prep[1:5], *(() if flags_h is None else (flags_h,)))
         main = torch.cuda.current_stream()
         with torch.no_grad():
             W = model._flat.tensors(model)
@@ -222,7 +238,7 @@ class DeepSpeechTrainer:
             self._step_index = getattr(self, "_step_index", -1) + 1
             self._snapshot_bn_stats(self._step_index)                        # (restored if the device gate reports this step starved)
             logits, ctx = engine.forward(W, model._cfg, inputs, lens_dev, training=True, save=True)
-            nll, dlogits = ops.ctc_loss(logits, tg, off, lens_dev, tl, max_u, 1.0 / B, want_grad=True)
+            nll, dlogits = self._ctc(logits, tg, off, lens_dev, tl, max_u, fl[0] if fl else None, B)
             loss = ops.ctc_batch_mean(nll)                                   # (1,): sum of the per-utterance losses / B
             # the loss value travels to pinned host memory on a copy stream that waits for the CTC kernels only
             pin = self._pinned()
@@ -266,18 +282,18 @@ class DeepSpeechTrainer:
         optimizer.  A starved launch (impossible during a cooldown, possible in the host-gated path of a torch optimizer) repeats the batch.
         Returns (valid_loss, loss_value)."""
         model = self._model
-        inputs, output_sizes, t_h, off_h, tl_h, max_u = prep
+        inputs, output_sizes, t_h, off_h, tl_h, max_u, flags_h = prep
         B = inputs.size(0)
         valid_loss, loss_value = False, float("nan")
         for _attempt in range(3):
-            lens_dev, tg, off, tl = self._stage_ints(inputs.device, output_sizes, t_h, off_h, tl_h)
+            lens_dev, tg, off, tl, *fl = self._stage_ints(inputs.device, output_sizes, t_h, off_h, tl_h, *(() if flags_h is None else (flags_h,)))
             with torch.no_grad():
                 W = model._flat.tensors(model)
                 Gr = model._flat.tensors(model, grads=True)
                 self._step_index = getattr(self, "_step_index", -1) + 1
                 self._snapshot_bn_stats(self._step_index)
                 logits, ctx = engine.forward(W, model._cfg, inputs, lens_dev, training=True, save=True)
-                nll, dlogits = ops.ctc_loss(logits, tg, off, lens_dev, tl, max_u, 1.0 / B, want_grad=True)
+                nll, dlogits = self._ctc(logits, tg, off, lens_dev, tl, max_u, fl[0] if fl else None, B)
                 loss = ops.ctc_batch_mean(nll)[0]
                 red = self._get_reducer()
                 engine.backward(W, Gr, model._cfg, ctx, dlogits, on_bucket=red.on_bucket if red.active else None)
@@ -413,8 +429,7 @@ class DeepSpeechTrainer:
         inputs = inputs.to(self._device, non_blocking=True)
         output_sizes = model.get_seq_lens(input_sizes.cpu().int())
         model._ensure_flat(inputs.device)
-        t_h, off_h, tl_h, max_u = _prep_targets_host(targets, target_sizes)
-        return self._run_sync((inputs, output_sizes.to(torch.int32), t_h, off_h, tl_h, max_u))
+        return self._run_sync((inputs, output_sizes.to(torch.int32), *self._prep_targets_step(targets, target_sizes)))
 
     # -- eval / bookkeeping (deepspeech_trainer.py:119-137) ----------------------------------------
     def test(self, test_loader):

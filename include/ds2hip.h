@@ -395,6 +395,40 @@ int ds2_ctc_loss_ex_f32(const float* logits, int ld, int T, int B, int C, const 
                         const int* in_lens_dev, const int* tgt_lens_dev, int max_target_len, float* nll_dev, float* grad, int ldg,
                         float grad_scale, int lattice, void* ws, size_t ws_bytes, void* stream);
 
+/* The CTC loss for IMPERFECT transcripts: a wildcard ("star") label and optional first / last tokens, the vocabulary of
+ * ds2_ctc_align_star_f32 over (log-sum-exp, +) where the aligner has (max, +).  In the literature: wild-card CTC, star temporal
+ * classification.  The reference has no such loss: this text is the contract, restated in fp64 NumPy by tests/ctc_star_loss_oracle.py.
+ * Everything that is not named here is ds2_ctc_loss_ex_f32's: inputs, strides, the fused row log-softmax, blank = 0, in_lens,
+ * grad_scale, and the two lattice kernels chosen by `lattice` and 2 * max_target_len + 1 <= 128.
+ * Wildcard emission: a state whose label is C (one past the last class) emits the constant star_penalty in every valid frame.
+ *  star_penalty is fp32, finite and <= 0, natural log: anything else is a nonzero return before any launch.  (The aligner's wildcard
+ *  scores "max over all classes + penalty"; the softmax summed over all classes is 1, whose log is 0: no pre-pass, and a frame spent in
+ *  the wildcard yields no gradient of its own.)
+ *  In the fp32 lattice a wildcard state adds the constant to log(sum) before the max is added, m + (log(sum) + star_penalty), where
+ *  every other state computes (m + log(sum)) + emission as in the plain entry: a constant added to the finished value would be rounded
+ *  the same way in every frame and drift.
+ * Wildcard as a label: an ordinary odd state with blank states on both sides; it takes at least one frame and may repeat; the skip
+ *  rule compares label VALUES, so two adjacent C behave like a repeated label.  A target value outside [1, C] makes its utterance
+ *  infeasible: nll = +inf, gradient rows 0, nothing read out of bounds (the label is checked before anything is read with it).
+ * Flags: flags_dev (B) int32 per utterance, NULL = all 0, the aligner's bits.
+ *  bit 0: frame 0 may also start in states 2 and 3: alpha[0][s] = emission for s < min(S, 4) instead of s < 2;
+ *  bit 1: the path may also end in states S-3 and S-4: beta[T_b-1][s] = emission there too, and the likelihood is the log-sum-exp of
+ *         alpha[T_b-1][s] over the allowed end states that exist, taken as lse2(lse2(S-1, S-2), lse2(S-3, S-4)).
+ *  The likelihood is the sum over the legal STATE paths of the lattice.  With bit 1 clear nll is the expression of the plain entry in
+ *  the same operand order.
+ * Gradient, for c in [0, C):
+ *    grad[t,b,c] = grad_scale * ( softmax[t,b,c] * (1 - occ_star[t,b]) - occ[t,b,c] )
+ *  occ_star[t,b] the summed occupancy of that utterance's wildcard states at frame t, occ the occupancy of the real classes as in the
+ *  plain entry; frames beyond T_b and infeasible utterances get 0.  Repeated labels, the wildcard among them, are summed in the plain
+ *  entry's deterministic chain order; the wildcard has an accumulator slot of its own with one writer.
+ * Identity: with flags_dev = NULL and no C in the targets this entry writes the SAME BITS as ds2_ctc_loss_ex_f32 (nll, gradient and the
+ *  alpha / beta lattices of the workspace, in both lattice kernels).
+ * Workspace: that of the plain entry, ds2_ctc_star_workspace_bytes = ds2_ctc_workspace_bytes. */
+size_t ds2_ctc_star_workspace_bytes(int T, int B, int max_target_len);
+int ds2_ctc_star_loss_f32(const float* logits, int ld, int T, int B, int C, const int* targets_dev, const int* tgt_off_dev,
+                          const int* in_lens_dev, const int* tgt_lens_dev, int max_target_len, float star_penalty, const int* flags_dev,
+                          float* nll_dev, float* grad, int ldg, float grad_scale, int lattice, void* ws, size_t ws_bytes, void* stream);
+
 /* out[0] = sum_b nll[b] / B on the device, fixed summation order: `loss = criterion(...) / inputs.size(0)`,
  * trainers/deepspeech_trainer.py:110-112 */
 int ds2_ctc_batch_mean_f32(const float* nll_dev, int B, float* out_dev, void* stream);
