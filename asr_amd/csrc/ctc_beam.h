@@ -9,6 +9,9 @@
 // ctc_beam_kernel<PROF, true> is the language-model arm (ds2_ctc_beam_decode_lm_f32): the LM terms of ctc_lm.h ride in pnb of
 // each extension, every beam is extended by every kept class (no staircase) and, in word mode, the survivors are re-scored and
 // re-sorted after the last frame.  LM = false takes no extra kernel argument and compiles to the kernel without that arm.
+// ctc_beam_kernel<PROF, true, HotArgs> is the hotword arm (ds2_ctc_beam_decode_hot_f32) on the same full grid: one more int of
+// state per beam (the node of the automaton of ctc_hot.h), the term phi(n') - phi(n) added to the LM term of every extension, and
+// the end-of-utterance re-score (-phi(state)) and re-sort always run.  Its LM blob may be null (hot-only): no LM table is read.
 //
 // Per frame, inside the workgroup (256 threads, all state in LDS):
 //  1. class keys (prob bits, index) of the frame's row, block bitonic sort, running-sum cutoff by wave 0, the threshold key
@@ -48,6 +51,7 @@
 #endif
 #include "common.h"
 #include "ctc_lm.h"
+#include "ctc_hot.h"
 #include <stdio.h>
 #include <string.h>
 
@@ -306,8 +310,42 @@ __device__ inline void lm_copy(const LmArgs& a, const LmBeams& o, int src, const
   d.lmb[j] = o.lmb[src];
 }
 
+// Hotword arm: the LM arm's arguments (lm.blob null: hot-only, the LM term is 0 and no LM table is read) and the packed automaton.
+// Per-beam state: the automaton node of the prefix, one int per beam and beam buffer, after the LM arm's LDS.
+struct HotArgs {
+  LmArgs lm;
+  const void* hot;
+};
+
+__host__ __device__ inline size_t hot_state_bytes(int K) { return Layout::align_up(4 * (size_t)K, 16); }
+__host__ __device__ inline size_t hot_layout_total(const Layout& L, int nbl) {
+  return Layout::align_up(lm_layout_total(L, nbl), 16) + 2 * hot_state_bytes(L.K);
+}
+
+// LM term + hotword term of the extension of beam k (hotword state hs) by class c; -inf stays -inf
+__device__ inline float hot_bonus(const ds2lm::LmView& v, const LmArgs& a, const LmBeams& mo, int k, int len, int last, int c,
+                                  const ds2hot::HotView& hv, int hs) {
+  const float b = a.blob ? lm_bonus(v, a, mo.ctx + k * LM_CTX, mo.bow + k * LM_CTX, mo.node[k], len, last, c) : 0.f;
+  int nx;
+  float term;
+  ds2hot::hot_step(hv, hs, c, nx, term);
+  return b + term;
+}
+
 __device__ inline LmArgs lm_args() { return LmArgs{}; }
 __device__ inline LmArgs lm_args(const LmArgs& a) { return a; }
+__device__ inline LmArgs lm_args(const HotArgs& a) { return a.lm; }
+__device__ inline const void* hot_blob() { return nullptr; }
+__device__ inline const void* hot_blob(const LmArgs&) { return nullptr; }
+__device__ inline const void* hot_blob(const HotArgs& a) { return a.hot; }
+template <class... Lm>
+struct is_hot {
+  static constexpr bool value = false;
+};
+template <>
+struct is_hot<HotArgs> {
+  static constexpr bool value = true;
+};
 
 // LM = false takes no LmArgs (an empty pack): its kernel arguments, and its code, are those of the kernel without the LM arm
 template <bool PROF, bool LM, class... Lm>
@@ -316,7 +354,8 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
                                                                float cutoff_prob, int PC, int PK, int HT, int* __restrict__ labels,
                                                                int* __restrict__ offsets, int* __restrict__ lens, float* __restrict__ scores,
                                                                int* __restrict__ nodes, u64* __restrict__ prof, Lm... lm_arg) {
-  static_assert(sizeof...(Lm) == (LM ? 1 : 0), "the LM arm takes one LmArgs");
+  static_assert(sizeof...(Lm) == (LM ? 1 : 0), "the LM arm takes one LmArgs or HotArgs");
+  constexpr bool HOT = is_hot<Lm...>::value;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const LmArgs lm = lm_args(lm_arg...);
   const Layout L(K, PC, PK, HT);
@@ -343,8 +382,16 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
   LmBeams l0, l1;
   float* lnb_lp = nullptr;
   int* lnb_cls = nullptr;
+  [[maybe_unused]] ds2hot::HotView hv;
+  [[maybe_unused]] int *h0 = nullptr, *h1 = nullptr;
+  if constexpr (HOT) {
+    hv = ds2hot::hot_view(hot_blob(lm_arg...));
+    h0 = (int*)(smem + Layout::align_up(lm_layout_total(L, lm.nbl), 16));
+    h1 = (int*)((char*)h0 + hot_state_bytes(K));
+    if (tid == 0) h0[0] = 0;
+  }
   if constexpr (LM) {
-    lv = ds2lm::lm_view(lm.blob);
+    if (!HOT || lm.blob) lv = ds2lm::lm_view(lm.blob);
     l0 = lm_beams_at(smem, L, 0);
     l1 = lm_beams_at(smem, L, 1);
     lnb_lp = (float*)(smem + Layout::align_up(L.total, 16) + 2 * lm_beams_bytes(K));
@@ -385,6 +432,8 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
     if (nb_old == 0) break;
     const Beams o = cur ? b1 : b0, w = cur ? b0 : b1;
     [[maybe_unused]] const LmBeams mo = cur ? l1 : l0, mw = cur ? l0 : l1;
+    [[maybe_unused]] const int* ho = cur ? h1 : h0;
+    [[maybe_unused]] int* hw = cur ? h0 : h1;
     const float* row = probs + b * ld_b + t * ld_t;
 
     // 1. prune the classes
@@ -459,7 +508,8 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
         const int p = tab_lookup(tab, HT, o, o.ph[k], len - 1);
         if constexpr (LM) {   // the parent's extension carries the bonus of l's last label
           if (p >= 0) npnb = lae(npnb, (o.last[p] == e ? o.pb[p] : o.tot[p]) + lpe + mo.lmb[k]);
-          eb = lm_bonus(lv, lm, mo.ctx + k * LM_CTX, mo.bow + k * LM_CTX, mo.node[k], len, e, e);
+          if constexpr (HOT) eb = hot_bonus(lv, lm, mo, k, len, e, e, hv, ho[k]);
+          else eb = lm_bonus(lv, lm, mo.ctx + k * LM_CTX, mo.bow + k * LM_CTX, mo.node[k], len, e, e);
           es = pb + lpe + eb;
         } else {
           if (p >= 0) npnb = lae(npnb, (o.last[p] == e ? o.pb[p] : o.tot[p]) + lpe);
@@ -503,7 +553,12 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
         const int i = g / n_nb, r = g - i * n_nb, c = lnb_cls[r], s = 2 * nb_old + g;
         const int len = o.len[i];
         const bool rep = len > 0 && c == o.last[i];
-        const float bonus = rep ? -INFINITY : lm_bonus(lv, lm, mo.ctx + i * LM_CTX, mo.bow + i * LM_CTX, mo.node[i], len, o.last[i], c);
+        float bonus = -INFINITY;
+        if constexpr (HOT) {
+          if (!rep) bonus = hot_bonus(lv, lm, mo, i, len, o.last[i], c, hv, ho[i]);
+        } else {
+          bonus = rep ? -INFINITY : lm_bonus(lv, lm, mo.ctx + i * LM_CTX, mo.bow + i * LM_CTX, mo.node[i], len, o.last[i], c);
+        }
         const float sc = o.tot[i] + lnb_lp[r] + bonus;
         const bool real = !rep && sc > -INFINITY && tab_lookup(tab, HT, o, hash_ext(o.h[i], c), len + 1) < 0;
         keys[s] = real ? cand_key(sc, len + 1, s) : dummy_key(s);
@@ -555,6 +610,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
         w.h[j] = o.h[src];
         w.ph[j] = o.ph[src];
         if constexpr (LM) lm_copy(lm, mo, src, mw, j);
+        if constexpr (HOT) hw[j] = ho[src];
       } else {
         const int nd = t * K + j;
         n_parent[nd] = o.node[src];
@@ -568,7 +624,14 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
         w.last[j] = cls;
         w.h[j] = hash_ext(o.h[src], cls);
         w.ph[j] = o.h[src];
-        if constexpr (LM) lm_child(lv, lm, mo, src, cls, c_pb[idx], mw, j);
+        if constexpr (HOT) {
+          if (lm.blob) lm_child(lv, lm, mo, src, cls, c_pb[idx], mw, j);
+          else mw.lmb[j] = c_pb[idx];
+          float term;
+          ds2hot::hot_step(hv, ho[src], cls, hw[j], term);
+        } else if constexpr (LM) {
+          lm_child(lv, lm, mo, src, cls, c_pb[idx], mw, j);
+        }
       }
     }
     if (tid == 0) hd->nb = nb_new;
@@ -584,7 +647,8 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
   }
 
   if constexpr (LM) {
-    if (lm.mode == ds2lm::MODE_WORD && hd->nb > 0) {   // end of utterance: score the partial word, then re-sort the survivors
+    // end of utterance: score the partial word (word mode), give back the lead of a partial hotword match, re-sort the survivors
+    if ((HOT || lm.mode == ds2lm::MODE_WORD) && hd->nb > 0) {
       const int nbf = hd->nb, P = pow2_ceil(nbf);
       const Beams f = cur ? b1 : b0, w = cur ? b0 : b1;
       const LmBeams lf = cur ? l1 : l0, lw = cur ? l0 : l1;
@@ -595,10 +659,11 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
       for (int k = tid; k < P; k += BEAM_THREADS) {
         if (k < nbf) {
           float tot = f.tot[k];
-          if (f.len[k] > 0 && f.last[k] != lm.space) {
+          if ((!HOT || lm.mode == ds2lm::MODE_WORD) && f.len[k] > 0 && f.last[k] != lm.space) {
             const int wd = lv.word_of[lf.node[k]];   // an incomplete partial word is out of vocabulary
             tot += lm.alpha * (wd < 0 ? ds2lm::OOV : ds2lm::cond_score(lv, lf.ctx + k * LM_CTX, lf.bow + k * LM_CTX, lm.m, wd)) + lm.beta;
           }
+          if constexpr (HOT) tot -= hv.phi[(cur ? h1 : h0)[k]];
           keys[k] = cand_key(tot, f.len[k], k);
           c_src[k] = k;
           c_cls[k] = -1;
@@ -620,6 +685,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
         w.h[j] = f.h[idx];
         w.ph[j] = f.ph[idx];
         lm_copy(lm, lf, idx, lw, j);
+        if constexpr (HOT) (cur ? h0 : h1)[j] = (cur ? h1 : h0)[idx];
       }
       __syncthreads();
       cur ^= 1;
@@ -828,5 +894,146 @@ extern "C" int ds2_ctc_beam_decode_lm_f32(const float* probs, long long ld_b, lo
   hipLaunchKernelGGL((ctc_beam_kernel<false, true, LmArgs>), dim3(B), dim3(BEAM_THREADS), total, s, probs, ld_b, ld_t, T, C, sizes_dev, blank, K,
                      cutoff_top_n, cutoff_prob, PC, PK, HT, labels, offsets, lens, scores, (int*)ws, nullptr, la);
   DS2_LAUNCH_CHECK("ctc_beam_kernel<LM>");
+  return 0;
+}
+
+// ---- hotword arm (ds2_ctc_hot_*, ds2_ctc_beam_decode_hot_f32) ----
+
+extern "C" size_t ds2_ctc_hot_packed_bytes(int n_nodes, int n_edges) {
+  if (n_nodes < 2 || n_nodes > ds2hot::MAX_NODES || n_edges != n_nodes - 1) return 0;
+  return ds2hot::hot_bytes(pow2_ceil(2 * n_edges + 1), n_nodes);
+}
+
+extern "C" int ds2_ctc_hot_pack(int n_nodes, int n_edges, const int* edge_node, const int* edge_label, const int* edge_child,
+                                const int* fail, const float* phi, const int* terminal, int C, void* out, size_t out_bytes) {
+  using namespace ds2hot;
+  DS2_REQUIRE(n_nodes >= 2 && n_nodes <= MAX_NODES, "ds2_ctc_hot_pack: %d trie nodes outside the supported 2..%d", n_nodes, MAX_NODES);
+  DS2_REQUIRE(n_edges == n_nodes - 1, "ds2_ctc_hot_pack: a trie of %d nodes has %d edges, got %d", n_nodes, n_nodes - 1, n_edges);
+  DS2_REQUIRE(C >= 2 && C <= BEAM_MAX_C, "ds2_ctc_hot_pack: %d classes outside the supported 2..%d", C, BEAM_MAX_C);
+  const size_t need = ds2_ctc_hot_packed_bytes(n_nodes, n_edges);
+  DS2_REQUIRE(out && out_bytes >= need, "ds2_ctc_hot_pack: output buffer of %zu bytes, %zu needed", out_bytes, need);
+  DS2_REQUIRE(edge_node && edge_label && edge_child && fail && phi && terminal, "ds2_ctc_hot_pack: null pointer");
+  memset(out, 0, need);
+  HotHeader* h = (HotHeader*)out;   // the magic goes in last: a refused automaton leaves no usable blob behind
+  h->nnodes = n_nodes;
+  h->tcap = pow2_ceil(2 * n_edges + 1);
+  h->C = C;
+  const HotView v = hot_view(out);
+  ds2lm::TrieEntry* tr = (ds2lm::TrieEntry*)v.trie;
+  for (int i = 0; i < h->tcap; ++i) tr[i].node = -1;
+  int* parent = (int*)v.terminal;   // scratch until the terminal flags are copied in: the parent of every node
+  for (int i = 0; i < n_nodes; ++i) parent[i] = -1;
+  for (int i = 0; i < n_edges; ++i) {
+    DS2_REQUIRE(edge_node[i] >= 0 && edge_node[i] < n_nodes && edge_child[i] > 0 && edge_child[i] < n_nodes && edge_label[i] >= 0 &&
+                    edge_label[i] < C,
+                "ds2_ctc_hot_pack: trie edge %d out of range", i);
+    DS2_REQUIRE(parent[edge_child[i]] < 0, "ds2_ctc_hot_pack: node %d has two parents", edge_child[i]);
+    DS2_REQUIRE(hot_child(v, edge_node[i], edge_label[i]) < 0, "ds2_ctc_hot_pack: trie edge %d is listed twice", i);
+    parent[edge_child[i]] = edge_node[i];
+    int pos = (int)(ds2lm::trie_hash(edge_node[i], edge_label[i]) & (ds2lm::u64)(h->tcap - 1));
+    while (tr[pos].node >= 0) pos = (pos + 1) & (h->tcap - 1);
+    tr[pos].node = edge_node[i];
+    tr[pos].label = edge_label[i];
+    tr[pos].child = edge_child[i];
+  }
+  int* depth = (int*)v.fail;   // scratch until the links are copied in
+  int deepest = 0;
+  for (int i = 0; i < n_nodes; ++i) {   // n_nodes - 1 edges, one parent per non-root node: a tree when every node reaches the root
+    int d = 0, x = i;
+    while (x != 0 && d <= MAX_DEPTH) {
+      x = parent[x];
+      ++d;
+    }
+    DS2_REQUIRE(x == 0 && d <= MAX_DEPTH, "ds2_ctc_hot_pack: node %d lies deeper than the supported %d labels per phrase", i, MAX_DEPTH);
+    depth[i] = d;
+    deepest = d > deepest ? d : deepest;
+  }
+  DS2_REQUIRE(fail[0] == 0, "ds2_ctc_hot_pack: the root's failure link must point to the root, got %d", fail[0]);
+  int nterm = 0;
+  for (int i = 0; i < n_nodes; ++i) {
+    DS2_REQUIRE(i == 0 || (fail[i] >= 0 && fail[i] < n_nodes && depth[fail[i]] < depth[i]),
+                "ds2_ctc_hot_pack: the failure link of node %d does not point to a strictly shallower node", i);
+    DS2_REQUIRE(phi[i] >= 0.f && phi[i] < INFINITY, "ds2_ctc_hot_pack: the potential of node %d is not a finite number >= 0", i);
+    nterm += terminal[i] != 0;
+  }
+  DS2_REQUIRE(phi[0] == 0.f && !terminal[0], "ds2_ctc_hot_pack: the root has potential 0 and ends no phrase");
+  h->nterminal = nterm;
+  h->depth = deepest;
+  memcpy((int*)v.fail, fail, 4 * (size_t)n_nodes);
+  memcpy((float*)v.phi, phi, 4 * (size_t)n_nodes);
+  for (int i = 0; i < n_nodes; ++i) ((int*)v.terminal)[i] = terminal[i] != 0;
+  h->magic = MAGIC;
+  return 0;
+}
+
+// the sizes a packed automaton claims, against the bytes it was given
+static int hot_header_check(const char* who, const void* packed, size_t bytes) {
+  using namespace ds2hot;
+  DS2_REQUIRE(packed && bytes >= sizeof(HotHeader), "%s: no packed hotword automaton (%zu bytes)", who, bytes);
+  const HotHeader* h = (const HotHeader*)packed;
+  DS2_REQUIRE(h->magic == MAGIC, "%s: not a packed hotword automaton", who);
+  DS2_REQUIRE(h->nnodes >= 2 && h->nnodes <= MAX_NODES && h->tcap == pow2_ceil(2 * (h->nnodes - 1) + 1) && h->depth >= 1 &&
+                  h->depth <= MAX_DEPTH && bytes >= hot_bytes(h->tcap, h->nnodes),
+              "%s: bad hotword automaton (%d nodes, table of %d, depth %d, %zu bytes)", who, h->nnodes, h->tcap, h->depth, bytes);
+  return 0;
+}
+
+extern "C" int ds2_ctc_hot_step(const void* packed, int node, int label, int* next, float* term) {
+  using namespace ds2hot;
+  DS2_REQUIRE(packed && next && term, "ds2_ctc_hot_step: null pointer");
+  const HotHeader* h = (const HotHeader*)packed;
+  DS2_REQUIRE(h->magic == MAGIC, "ds2_ctc_hot_step: not a packed hotword automaton");
+  DS2_REQUIRE(node >= 0 && node < h->nnodes && label >= 0 && label < h->C, "ds2_ctc_hot_step: node %d or label %d out of range", node, label);
+  hot_step(hot_view(packed), node, label, *next, *term);
+  return 0;
+}
+
+extern "C" int ds2_ctc_beam_decode_hot_f32(const float* probs, long long ld_b, long long ld_t, int B, int T, int C, const int* sizes_dev,
+                                           int blank, int beam_width, int cutoff_top_n, float cutoff_prob, const void* lm_dev,
+                                           size_t lm_bytes, int lm_order, int lm_mode, int space, float alpha, float beta,
+                                           const void* hot_dev, const void* hot_host, size_t hot_bytes, int* labels, int* offsets,
+                                           int* lens, float* scores, void* ws, size_t ws_bytes, void* stream) {
+  DS2_REQUIRE(probs && labels && offsets && lens && scores && hot_dev, "ds2_ctc_beam_decode_hot_f32: null pointer");
+  DS2_REQUIRE(beam_width >= 1 && beam_width <= BEAM_MAX_K, "ds2_ctc_beam_decode_hot_f32: beam_width %d outside the supported 1..%d",
+              beam_width, BEAM_MAX_K);
+  DS2_REQUIRE(C >= 2 && C <= BEAM_MAX_C, "ds2_ctc_beam_decode_hot_f32: %d classes outside the supported 2..%d", C, BEAM_MAX_C);
+  DS2_REQUIRE(B > 0 && T > 0 && T <= BEAM_MAX_T && blank >= 0 && blank < C,
+              "ds2_ctc_beam_decode_hot_f32: bad dims (B=%d T=%d C=%d blank=%d; T <= %d)", B, T, C, blank, BEAM_MAX_T);
+  DS2_REQUIRE(cutoff_top_n >= 1 && cutoff_prob == cutoff_prob, "ds2_ctc_beam_decode_hot_f32: cutoff_top_n must be >= 1 and cutoff_prob a number");
+  DS2_REQUIRE(ws && ws_bytes >= ds2_ctc_beam_workspace_bytes(B, T, beam_width), "ds2_ctc_beam_decode_hot_f32: workspace too small");
+  if (hot_header_check("ds2_ctc_beam_decode_hot_f32", hot_host, hot_bytes)) return 1;
+  DS2_REQUIRE(((const ds2hot::HotHeader*)hot_host)->C == C, "ds2_ctc_beam_decode_hot_f32: the hotwords were packed for %d classes, probs have %d",
+              ((const ds2hot::HotHeader*)hot_host)->C, C);
+  if (lm_dev) {
+    DS2_REQUIRE(lm_order >= 1 && lm_order <= ds2lm::MAX_ORDER && (lm_mode == ds2lm::MODE_CHAR || lm_mode == ds2lm::MODE_WORD) &&
+                    lm_bytes >= sizeof(ds2lm::LmHeader),
+                "ds2_ctc_beam_decode_hot_f32: bad language model (order %d, mode %d, %zu bytes)", lm_order, lm_mode, lm_bytes);
+    DS2_REQUIRE(lm_mode == ds2lm::MODE_CHAR || (space >= 0 && space < C && space != blank),
+                "ds2_ctc_beam_decode_hot_f32: word mode needs a space label other than the blank (got %d)", space);
+    DS2_REQUIRE(alpha == alpha && beta == beta && fabsf(alpha) < INFINITY && fabsf(beta) < INFINITY,
+                "ds2_ctc_beam_decode_hot_f32: alpha and beta must be finite");
+  }
+  const int K = beam_width, nbl = min(cutoff_top_n, C - 1);
+  DS2_REQUIRE((long long)K * (nbl + 2) <= ds2_ctc_beam_lm_max_candidates(),
+              "ds2_ctc_beam_decode_hot_f32: beam_width * (min(cutoff_top_n, C - 1) + 2) = %lld exceeds the %d candidate slots (hotwords "
+              "search the full grid, with or without a language model)",
+              (long long)K * (nbl + 2), ds2_ctc_beam_lm_max_candidates());
+  const int PC = pow2_ceil(C), PK = pow2_ceil(K * (nbl + 2)), HT = 2 * pow2_ceil(K);
+  const Layout lay(K, PC, PK, HT);
+  const size_t total = hot_layout_total(lay, nbl);   // the LM arm's layout and one int of hotword state per beam and buffer
+  DS2_REQUIRE(total <= 160 * 1024,
+              "ds2_ctc_beam_decode_hot_f32: LDS layout of %zu bytes (%zu of them hotword state) does not fit the 160 KiB at beam_width %d, "
+              "%d classes",
+              total, 2 * hot_state_bytes(K), K, C);
+  hipStream_t s = (hipStream_t)stream;
+  if (total > 64 * 1024)
+    DS2_HIP(hipFuncSetAttribute((const void*)ctc_beam_kernel<false, true, HotArgs>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)total));
+  HotArgs ha;
+  ha.lm = lm_dev ? LmArgs{lm_dev, alpha, beta, lm_order - 1, lm_mode, lm_mode == ds2lm::MODE_WORD ? space : -1, nbl}
+                 : LmArgs{nullptr, 0.f, 0.f, 0, 0, -1, nbl};
+  ha.hot = hot_dev;
+  hipLaunchKernelGGL((ctc_beam_kernel<false, true, HotArgs>), dim3(B), dim3(BEAM_THREADS), total, s, probs, ld_b, ld_t, T, C, sizes_dev, blank, K,
+                     cutoff_top_n, cutoff_prob, PC, PK, HT, labels, offsets, lens, scores, (int*)ws, nullptr, ha);
+  DS2_LAUNCH_CHECK("ctc_beam_kernel<HOT>");
   return 0;
 }

@@ -171,10 +171,17 @@ class BeamCTCDecoder(Decoder):
     characters scores every label (character mode, e.g. for JSUT's unspaced transcripts); otherwise it scores words between spaces
     and keeps only prefixes spelling dictionary words (word mode, which needs a space label).  KenLM binary files raise
     NotImplementedError.  With an LM, beam_width * (min(cutoff_top_n, C - 1) + 2) must stay within 4096.  ctcdecode's min_cutoff
-    heuristic and approx_ctc score are not reproduced: `last_scores` are the fused totals, and parity with ctcdecode is not pinned."""
+    heuristic and approx_ctc score are not reproduced: `last_scores` are the fused totals, and parity with ctcdecode is not pinned.
+
+    With `hotwords` (phrases as decoders.hotwords.Hotwords takes them: `str`, `(str, weight)` or label-id sequences, or a Hotwords
+    object) the search prefers prefixes that spell those phrases (`ds2_ctc_beam_decode_hot_f32`), with or without an LM:
+    `hotword_weight` (natural log, per label, >= 0) is the weight of a phrase given without one.  A broken partial match gives its
+    lead back, a phrase that is a proper prefix of another is refused, matching knows no word boundary, and the candidate limit
+    above applies without an LM too.  `set_hotwords` changes the list between calls.  Which weight serves real recordings has not
+    been measured, and parity with pyctcdecode, WeNet or icefall biasing is not pinned."""
 
     def __init__(self, labels, lm_path=None, alpha=0, beta=0, cutoff_top_n=40, cutoff_prob=1.0, beam_width=100, num_processes=4,
-                 blank_index=0):
+                 blank_index=0, hotwords=None, hotword_weight=1.0):
         super().__init__(labels, blank_index)
         self.lm_path, self.alpha, self.beta, self.num_processes = lm_path, alpha, beta, num_processes
         self.cutoff_top_n, self.cutoff_prob, self.beam_width = int(cutoff_top_n), float(cutoff_prob), int(beam_width)
@@ -185,6 +192,24 @@ class BeamCTCDecoder(Decoder):
             space = self.space_index if self.int_to_char.get(self.space_index) == " " else next(
                 (i for i, c in sorted(self.int_to_char.items()) if c == " "), None)
             self.lm = NgramLM(lm_path, self.int_to_char, self.blank_index, space)
+        self.hotwords, self.hotword_weight = None, hotword_weight
+        self.set_hotwords(hotwords)
+
+    def set_hotwords(self, hotwords, hotword_weight=None):
+        """Replace the hotword list (None or an empty list: no hotwords); hotword_weight, when given, becomes the default weight."""
+        from .hotwords import Hotwords
+        if hotword_weight is not None:
+            self.hotword_weight = hotword_weight
+        if hotwords is None or isinstance(hotwords, Hotwords):
+            self.hotwords = hotwords
+            return
+        hotwords = [hotwords] if isinstance(hotwords, str) else list(hotwords)
+        if not hotwords:
+            self.hotwords = None
+            return
+        chars = {c: i for i, c in self.int_to_char.items()}
+        space = self.space_index if self.int_to_char.get(self.space_index) == " " else None
+        self.hotwords = Hotwords(hotwords, chars, self.blank_index, self.hotword_weight, space_index=space)
 
     def _char(self, i):
         return " " if i == self.space_index else self.int_to_char.get(i, "")
@@ -212,7 +237,7 @@ class BeamCTCDecoder(Decoder):
         if sizes is not None:
             sizes = torch.as_tensor(sizes)
         labels, offs, lens, scores = ops.ctc_beam_decode(probs, sizes, self.blank_index, self.beam_width, self.cutoff_top_n,
-                                                         self.cutoff_prob, self.lm, self.alpha, self.beta)
+                                                         self.cutoff_prob, self.lm, self.alpha, self.beta, self.hotwords)
         B, K, T = labels.shape
         host = torch.cat((labels.reshape(-1), offs.reshape(-1), lens.reshape(-1), scores.view(torch.int32).reshape(-1))).cpu()
         if ops.rnn_poison_seen(labels.device):

@@ -1522,10 +1522,14 @@ def ctc_forced_align_star_tiled(x: Tensor, targets: Tensor, tgt_off: Tensor, in_
 
 
 def ctc_beam_decode(probs: Tensor, sizes: Tensor | None = None, blank: int = 0, beam_width: int = 100, cutoff_top_n: int = 40,
-                    cutoff_prob: float = 1.0, lm=None, alpha: float = 0.0, beta: float = 0.0):
+                    cutoff_prob: float = 1.0, lm=None, alpha: float = 0.0, beta: float = 0.0, hotwords=None):
     """CTC prefix beam search of probs (B,T,C) fp32 on the GPU -> (labels (B,K,T) i32, offsets (B,K,T) i32, lengths (B,K) i32,
     scores (B,K) fp32), all on the GPU, best beam first (contract: include/ds2hip.h).  With `lm` (a decoders.lm.NgramLM bound to these
-    classes) the search fuses alpha * log10 LM scores + beta per scored token (ds2_ctc_beam_decode_lm_f32)."""
+    classes) the search fuses alpha * log10 LM scores + beta per scored token (ds2_ctc_beam_decode_lm_f32).  With `hotwords` (a
+    decoders.hotwords.Hotwords bound to these classes) it also prefers prefixes that spell those phrases, with or without `lm`
+    (ds2_ctc_beam_decode_hot_f32); the language model's candidate limit then applies without a language model too."""
+    if hotwords is not None:
+        return _ctc_beam_decode_hot(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, lm, alpha, beta, hotwords)
     _chk_f32(probs)
     if probs.dim() != 3 or probs.stride(2) != 1:
         raise ValueError("ctc_beam_decode: probs must be (B,T,C) with a contiguous class dim")
@@ -1564,6 +1568,51 @@ def ctc_beam_decode(probs: Tensor, sizes: Tensor | None = None, blank: int = 0, 
                                                   int(cutoff_top_n), float(cutoff_prob), tab.data_ptr(), tab.numel(), lm.order, lm.mode,
                                                   space, float(alpha), float(beta), labels.data_ptr(), offs.data_ptr(), lens.data_ptr(),
                                                   scores.data_ptr(), ws.data_ptr(), n, _stream()), "ds2_ctc_beam_decode_lm_f32")
+    return labels, offs, lens, scores
+
+
+def _ctc_beam_decode_hot(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, lm, alpha, beta, hotwords):
+    """ctc_beam_decode with hotwords: the full-grid kernel instance with the hotword state (ds2_ctc_beam_decode_hot_f32)"""
+    _chk_f32(probs)
+    if probs.dim() != 3 or probs.stride(2) != 1:
+        raise ValueError("ctc_beam_decode: probs must be (B,T,C) with a contiguous class dim")
+    lib = _lib.load()
+    K = int(beam_width)
+    if not 1 <= K <= lib.ds2_ctc_beam_max_width():
+        raise ValueError(f"ctc_beam_decode: beam_width {K} outside the supported 1..{lib.ds2_ctc_beam_max_width()}")
+    B, T, C = probs.shape
+    dev = probs.device
+    if hotwords.C != C:
+        raise ValueError(f"ctc_beam_decode: the hotwords were bound to {hotwords.C} classes, probs have {C}")
+    if hotwords.blank != int(blank):
+        raise ValueError(f"ctc_beam_decode: the hotwords were bound to blank {hotwords.blank}, the decode has blank {int(blank)}")
+    if lm is not None and lm.C != C:
+        raise ValueError(f"ctc_beam_decode: the language model was bound to {lm.C} classes, probs have {C}")
+    grid, cap = K * (min(int(cutoff_top_n), C - 1) + 2), lib.ds2_ctc_beam_lm_max_candidates()
+    if grid > cap:
+        raise ValueError(f"ctc_beam_decode: with hotwords every beam is extended by every kept class, with or without a language "
+                         f"model: beam_width * (min(cutoff_top_n, C - 1) + 2) = {grid} exceeds the {cap} candidate slots")
+    if sizes is not None:
+        if sizes.numel() != B:
+            raise ValueError(f"sizes has {sizes.numel()} entries for a batch of {B}")
+        sizes = sizes.to(device=dev, dtype=torch.int32).contiguous().view(-1)
+    labels = torch.empty((B, K, T), dtype=torch.int32, device=dev)
+    offs = torch.empty((B, K, T), dtype=torch.int32, device=dev)
+    lens = torch.empty((B, K), dtype=torch.int32, device=dev)
+    scores = torch.empty((B, K), dtype=torch.float32, device=dev)
+    n = lib.ds2_ctc_beam_workspace_bytes(B, T, K)
+    ws = _ws(n, dev)
+    hot = hotwords.device_tables(dev)
+    tab = lm.device_tables(dev) if lm is not None else None
+    space = lm.space if lm is not None and lm.space is not None else -1
+    _lib.check(lib.ds2_ctc_beam_decode_hot_f32(probs.data_ptr(), probs.stride(0), probs.stride(1), B, T, C,
+                                               sizes.data_ptr() if sizes is not None else None, int(blank), K, int(cutoff_top_n),
+                                               float(cutoff_prob), tab.data_ptr() if tab is not None else None,
+                                               tab.numel() if tab is not None else 0, lm.order if lm is not None else 0,
+                                               lm.mode if lm is not None else 0, space, float(alpha), float(beta), hot.data_ptr(),
+                                               hotwords.packed.ctypes.data, hotwords.packed.nbytes, labels.data_ptr(), offs.data_ptr(),
+                                               lens.data_ptr(), scores.data_ptr(), ws.data_ptr(), n, _stream()),
+               "ds2_ctc_beam_decode_hot_f32")
     return labels, offs, lens, scores
 
 

@@ -612,6 +612,47 @@ int ds2_ctc_beam_decode_lm_f32(const float* probs, long long ld_b, long long ld_
                                int lm_mode, int space, float alpha, float beta, int* labels, int* offsets, int* lens, float* scores,
                                void* ws, size_t ws_bytes, void* stream);
 
+/* The same search with hotword boosting: the caller names a few phrases and the search prefers prefixes that spell them, with or
+ * without the LM above (asr_amd/decoders/hotwords.py builds the automaton; restated by tests/ctc_beam_hot_oracle.py).  Parity with
+ * pyctcdecode, WeNet or icefall biasing is not pinned.
+ *  - phrases: N >= 1 sequences of 1..64 non-blank label ids, each with a weight w >= 0 per label, finite, in NATURAL-log units (the
+ *    units of the acoustic totals, not the LM's log10).  No two phrases are equal and none is a proper prefix of another (the host
+ *    refuses such a set); a phrase may be an infix or a suffix of another;
+ *  - automaton: the trie of the phrases, root at depth 0, with Aho-Corasick failure links.  Node n has the potential
+ *    phi(n) = depth(n) * max(w of the phrases through n), computed in fp64 and rounded once to fp32; phi(root) = 0, and the end node
+ *    of a phrase lies on that phrase only, so its phi is len * w of that phrase;
+ *  - step from state n on label c: n' = the longest suffix of path(n) + c that is a trie node (goto / failure walk; the root when
+ *    there is none).  The term of the extension is phi(n') - phi(n), in fp32; it may be negative: a broken partial match gives its
+ *    lead back.  If n' ends a phrase the new state is the root and the phrase's len * w stays banked, otherwise the new state is n';
+ *  - end of utterance: every surviving beam gets -phi(state) added to its total, then the survivors are re-sorted by the order above
+ *    (total descending, length ascending, label sequence ascending);
+ *  - invariant: the terms of a complete labeling sum to the len * w of the phrases credited by this scan: keep the longest suffix of
+ *    the labels since the last credit that is a prefix of a phrase; when that suffix is a whole phrase, credit it and restart.  So an
+ *    occurrence hidden inside a longer partial match is not credited, matching restarts at the root after a credit, and matching
+ *    is on the label stream and knows no word boundary ("CAT" also boosts "CATALOG");
+ *  - composition: the term adds to the LM term of the same extension (a -inf from word mode's dictionary stays -inf) and rides in
+ *    pnb exactly as the LM term does; the state of a prefix is a function of its labels, so merged contributions agree.  lm_dev may
+ *    be NULL ("hot-only"): the LM term is 0, no LM table is read, and lm_bytes .. beta are ignored.
+ * Every beam is extended by every kept non-blank class, with or without an LM: the LM arm's candidate limit applies, and one more
+ * int of LDS per beam and beam buffer; a shape whose layout then exceeds 160 KiB is refused with a message (at K = 256, C = 29,
+ * cutoff_top_n = 14, the LM arm's largest grid, it is 150 752 bytes).
+ * The packed automaton (csrc/ctc_hot.h): at most 2^20 trie nodes (1000 phrases of 64 labels need 64001), 64 labels per phrase,
+ * C <= 16384.  ds2_ctc_hot_packed_bytes sizes it (0: outside the limits; n_edges = n_nodes - 1), ds2_ctc_hot_pack fills it on the
+ * host from the edges (node, label) -> child (node 0 the root), fail / phi / terminal per node, and refuses a trie that is no tree, a
+ * node deeper than 64, a failure link that does not point to a strictly shallower node (the root's: to itself), and a phi that is
+ * not finite and >= 0: a walk then ends within the depth.  ds2_ctc_hot_step is one step on the host, by the device's code: next
+ * state and fp32 term.  The decode reads the packed bytes from device memory (hot_dev) and checks the magic and sizes of the host
+ * copy (hot_host, hot_bytes) before it launches. */
+size_t ds2_ctc_hot_packed_bytes(int n_nodes, int n_edges);
+int ds2_ctc_hot_pack(int n_nodes, int n_edges, const int* edge_node, const int* edge_label, const int* edge_child, const int* fail,
+                     const float* phi, const int* terminal, int C, void* out, size_t out_bytes);
+int ds2_ctc_hot_step(const void* packed, int node, int label, int* next, float* term);
+int ds2_ctc_beam_decode_hot_f32(const float* probs, long long ld_b, long long ld_t, int B, int T, int C, const int* sizes_dev, int blank,
+                                int beam_width, int cutoff_top_n, float cutoff_prob, const void* lm_dev, size_t lm_bytes, int lm_order,
+                                int lm_mode, int space, float alpha, float beta, const void* hot_dev, const void* hot_host,
+                                size_t hot_bytes, int* labels, int* offsets, int* lens, float* scores, void* ws, size_t ws_bytes,
+                                void* stream);
+
 /* Batched Levenshtein distance (unit costs: insert, delete, substitute) of P independent pairs of int32 symbol sequences, one launch;
  * the WER / CER scoring of DeepSpeech.evaluate() (replaces Decoder.wer / Decoder.cer's per-utterance DP, decoders/decoder.py:26-58,
  * whose reference uses the `Levenshtein` C package).  The host maps words / characters to ids (asr_amd/decoders), symbols compare
