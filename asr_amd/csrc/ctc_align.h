@@ -402,37 +402,43 @@ __global__ __launch_bounds__(1024) void ctc_align_block_kernel(AlignArgs a) {
   align_body<IS_LOG, MODE, STAR>(a, smem);
 }
 
-// The launch that both entries share (`who` names the entry in an error).  a.bp, a.g and a.flags are set by the caller.
+// The launch that both entries share (`who` names the entry in an error).  a.bp, a.g, a.flags and a.maxU are set by the caller.
 template <bool STAR>
 int align_launch(const char* who, AlignArgs& a, int B, int is_log, int variant, int max_target_len, void* stream) {
-  const int Smax = 2 * max_target_len + 1;
-  a.maxU = max_target_len;
   a.Wp = max_target_len + 1;
   a.NG = ceil_div(a.T, 8);
   a.stage_words = a.Wp > ALIGN_STAGE_WORDS ? a.Wp : ALIGN_STAGE_WORDS;
   const size_t stage_bytes = (size_t)a.stage_words * sizeof(unsigned);
   hipStream_t s = (hipStream_t)stream;
-  if (variant == 1 || (variant == 0 && Smax <= 128)) {
+  if (variant == 1 || (variant == 0 && 2 * max_target_len + 1 <= 128)) {
     if (is_log) hipLaunchKernelGGL((ctc_align_wave_kernel<1, STAR>), dim3(B), dim3(64), stage_bytes, s, a);
     else hipLaunchKernelGGL((ctc_align_wave_kernel<0, STAR>), dim3(B), dim3(64), stage_bytes, s, a);
     DS2_LAUNCH_CHECK("ctc_align_wave_kernel");
     return 0;
   }
-  int threads = ceil_div(a.Wp, 64) * 64;
-  if (threads > 1024) threads = 1024;
-  if (a.Wp <= threads) {
-    size_t lds = (size_t)2 * (threads + 1) * sizeof(float);
-    if (lds < stage_bytes) lds = stage_bytes;
-    if (is_log) hipLaunchKernelGGL((ctc_align_block_kernel<1, 1, STAR>), dim3(B), dim3(threads), lds, s, a);
-    else hipLaunchKernelGGL((ctc_align_block_kernel<0, 1, STAR>), dim3(B), dim3(threads), lds, s, a);
-  } else {
-    size_t lds = ((size_t)5 * a.Wp + 2) * sizeof(float);
-    if (lds < stage_bytes) lds = stage_bytes;
-    DS2_REQUIRE(lds <= 64 * 1024, "%s: target too long for LDS lattice rows (max_target_len=%d)", who, max_target_len);
-    if (is_log) hipLaunchKernelGGL((ctc_align_block_kernel<1, 2, STAR>), dim3(B), dim3(threads), lds, s, a);
-    else hipLaunchKernelGGL((ctc_align_block_kernel<0, 2, STAR>), dim3(B), dim3(threads), lds, s, a);
-  }
+  const int threads = a.Wp > 1024 ? 1024 : ceil_div(a.Wp, 64) * 64;
+  const bool loop = a.Wp > threads;                 // more pairs than threads: MODE 2, with both rows and the accumulators in LDS
+  size_t lds = (loop ? (size_t)5 * a.Wp + 2 : (size_t)2 * (threads + 1)) * sizeof(float);
+  if (lds < stage_bytes) lds = stage_bytes;
+  DS2_REQUIRE(!loop || lds <= 64 * 1024, "%s: target too long for LDS lattice rows (max_target_len=%d)", who, max_target_len);
+  if (!loop && is_log) hipLaunchKernelGGL((ctc_align_block_kernel<1, 1, STAR>), dim3(B), dim3(threads), lds, s, a);
+  else if (!loop) hipLaunchKernelGGL((ctc_align_block_kernel<0, 1, STAR>), dim3(B), dim3(threads), lds, s, a);
+  else if (is_log) hipLaunchKernelGGL((ctc_align_block_kernel<1, 2, STAR>), dim3(B), dim3(threads), lds, s, a);
+  else hipLaunchKernelGGL((ctc_align_block_kernel<0, 2, STAR>), dim3(B), dim3(threads), lds, s, a);
   DS2_LAUNCH_CHECK("ctc_align_block_kernel");
+  return 0;
+}
+
+// What all four entries share (`who` names the entry in an error): the checks of their common arguments, and those arguments' fields of
+// AlignArgs (the fields behind tok_logp: zero and null).  bp, g and flags, and every check of an entry's own, stay with the entry.
+int align_entry_args(const char* who, AlignArgs& a, const float* x, long long ld_b, long long ld_t, int B, int T, int C, int is_log,
+                     const int* targets, const int* tgt_off, const int* in_lens, const int* tgt_lens, int maxU, float* score, int* states,
+                     int* tok_start, int* tok_end, float* tok_logp) {
+  DS2_REQUIRE(x && tgt_off && tgt_lens && score && states, "%s: null pointer", who);
+  DS2_REQUIRE(B > 0 && T > 0 && C > 0 && maxU >= 0 && ld_b > 0 && ld_t > 0, "%s: bad dims (B=%d T=%d C=%d U=%d)", who, B, T, C, maxU);
+  DS2_REQUIRE(maxU == 0 || (targets && tok_start && tok_end && tok_logp), "%s: null target / token pointer", who);
+  DS2_REQUIRE(is_log == 0 || is_log == 1, "%s: is_log must be 0 or 1", who);
+  a = AlignArgs{x, ld_b, ld_t, T, C, targets, tgt_off, in_lens, tgt_lens, maxU, score, states, tok_start, tok_end, tok_logp};
   return 0;
 }
 
@@ -447,20 +453,13 @@ extern "C" int ds2_ctc_align_f32(const float* x, long long ld_b, long long ld_t,
                                  const int* tgt_off_dev, const int* in_lens_dev, const int* tgt_lens_dev, int max_target_len, int variant,
                                  float* score, int* states, int* tok_start, int* tok_end, float* tok_logp, void* ws, size_t ws_bytes,
                                  void* stream) {
-  DS2_REQUIRE(x && tgt_off_dev && tgt_lens_dev && score && states, "ds2_ctc_align_f32: null pointer");
-  DS2_REQUIRE(B > 0 && T > 0 && C > 0 && max_target_len >= 0 && ld_b > 0 && ld_t > 0, "ds2_ctc_align_f32: bad dims (B=%d T=%d C=%d U=%d)", B,
-              T, C, max_target_len);
-  DS2_REQUIRE(max_target_len == 0 || (targets_dev && tok_start && tok_end && tok_logp), "ds2_ctc_align_f32: null target / token pointer");
-  DS2_REQUIRE(is_log == 0 || is_log == 1, "ds2_ctc_align_f32: is_log must be 0 or 1");
+  AlignArgs a;
+  if (int rc = align_entry_args("ds2_ctc_align_f32", a, x, ld_b, ld_t, B, T, C, is_log, targets_dev, tgt_off_dev, in_lens_dev, tgt_lens_dev,
+                                max_target_len, score, states, tok_start, tok_end, tok_logp)) return rc;
   DS2_REQUIRE(variant >= 0 && variant <= 2, "ds2_ctc_align_f32: variant must be 0, 1 or 2");
   const int Smax = 2 * max_target_len + 1;
   DS2_REQUIRE(variant != 1 || Smax <= 128, "ds2_ctc_align_f32: variant 1 (one wavefront) needs 2 * max_target_len + 1 <= 128, got %d", Smax);
   DS2_REQUIRE(ws && ws_bytes >= ds2_ctc_align_workspace_bytes(B, T, max_target_len), "ds2_ctc_align_f32: workspace too small");
-  AlignArgs a;
-  a.x = x; a.ld_b = ld_b; a.ld_t = ld_t; a.T = T; a.C = C;
-  a.targets = targets_dev; a.tgt_off = tgt_off_dev; a.in_lens = in_lens_dev; a.tgt_lens = tgt_lens_dev;
-  a.score = score; a.states = states; a.tok_start = tok_start; a.tok_end = tok_end; a.tok_logp = tok_logp;
   a.bp = (unsigned*)ws;
-  a.g = nullptr; a.flags = nullptr;
   return align_launch<false>("ds2_ctc_align_f32", a, B, is_log, variant, max_target_len, stream);
 }

@@ -95,12 +95,9 @@ extern "C" int ds2_ctc_align_star_f32(const float* x, long long ld_b, long long 
                                       const int* tgt_off_dev, const int* in_lens_dev, const int* tgt_lens_dev, int max_target_len,
                                       int variant, float star_penalty, const int* flags_dev, float* score, int* states, int* tok_start,
                                       int* tok_end, float* tok_logp, void* ws, size_t ws_bytes, void* stream) {
-  DS2_REQUIRE(x && tgt_off_dev && tgt_lens_dev && score && states, "ds2_ctc_align_star_f32: null pointer");
-  DS2_REQUIRE(B > 0 && T > 0 && C > 0 && max_target_len >= 0 && ld_b > 0 && ld_t > 0,
-              "ds2_ctc_align_star_f32: bad dims (B=%d T=%d C=%d U=%d)", B, T, C, max_target_len);
-  DS2_REQUIRE(max_target_len == 0 || (targets_dev && tok_start && tok_end && tok_logp),
-              "ds2_ctc_align_star_f32: null target / token pointer");
-  DS2_REQUIRE(is_log == 0 || is_log == 1, "ds2_ctc_align_star_f32: is_log must be 0 or 1");
+  AlignArgs a;
+  if (int rc = align_entry_args("ds2_ctc_align_star_f32", a, x, ld_b, ld_t, B, T, C, is_log, targets_dev, tgt_off_dev, in_lens_dev,
+                                tgt_lens_dev, max_target_len, score, states, tok_start, tok_end, tok_logp)) return rc;
   DS2_REQUIRE(variant >= 0 && variant <= 2, "ds2_ctc_align_star_f32: variant must be 0, 1 or 2");
   DS2_REQUIRE(align_star_penalty_ok(star_penalty), "ds2_ctc_align_star_f32: star_penalty must be finite and <= 0, got %g",
               (double)star_penalty);
@@ -110,10 +107,6 @@ extern "C" int ds2_ctc_align_star_f32(const float* x, long long ld_b, long long 
   DS2_REQUIRE(ws && ws_bytes >= ds2_ctc_align_star_workspace_bytes(B, T, max_target_len), "ds2_ctc_align_star_f32: workspace too small");
   float* g = (float*)((char*)ws + ds2_ctc_align_workspace_bytes(B, T, max_target_len));
   if (int rc = align_star_row_launch(x, ld_b, ld_t, B, T, C, is_log, in_lens_dev, star_penalty, g, stream)) return rc;
-  AlignArgs a;
-  a.x = x; a.ld_b = ld_b; a.ld_t = ld_t; a.T = T; a.C = C;
-  a.targets = targets_dev; a.tgt_off = tgt_off_dev; a.in_lens = in_lens_dev; a.tgt_lens = tgt_lens_dev;
-  a.score = score; a.states = states; a.tok_start = tok_start; a.tok_end = tok_end; a.tok_logp = tok_logp;
   a.bp = (unsigned*)ws;
   a.g = g; a.flags = flags_dev;
   return align_launch<true>("ds2_ctc_align_star_f32", a, B, is_log, variant, max_target_len, stream);
@@ -130,12 +123,9 @@ extern "C" int ds2_ctc_align_star_tiled_f32(const float* x, long long ld_b, long
                                             int max_target_len, int tile_frames, int tile_pairs, float star_penalty, const int* flags_dev,
                                             float* score, int* states, int* tok_start, int* tok_end, float* tok_logp, void* ws,
                                             size_t ws_bytes, void* stream) {
-  DS2_REQUIRE(x && tgt_off_dev && tgt_lens_dev && score && states, "ds2_ctc_align_star_tiled_f32: null pointer");
-  DS2_REQUIRE(B > 0 && T > 0 && C > 0 && max_target_len >= 0 && ld_b > 0 && ld_t > 0,
-              "ds2_ctc_align_star_tiled_f32: bad dims (B=%d T=%d C=%d U=%d)", B, T, C, max_target_len);
-  DS2_REQUIRE(max_target_len == 0 || (targets_dev && tok_start && tok_end && tok_logp),
-              "ds2_ctc_align_star_tiled_f32: null target / token pointer");
-  DS2_REQUIRE(is_log == 0 || is_log == 1, "ds2_ctc_align_star_tiled_f32: is_log must be 0 or 1");
+  AlignArgs a;
+  if (int rc = align_entry_args("ds2_ctc_align_star_tiled_f32", a, x, ld_b, ld_t, B, T, C, is_log, targets_dev, tgt_off_dev, in_lens_dev,
+                                tgt_lens_dev, max_target_len, score, states, tok_start, tok_end, tok_logp)) return rc;
   DS2_REQUIRE(align_tiled_shape(tile_frames, tile_pairs),
               "ds2_ctc_align_star_tiled_f32: tile_frames must be a positive multiple of 8 and tile_pairs a positive multiple of 64 up to "
               "1024 (or 0 for the default), got %d x %d", tile_frames, tile_pairs);
@@ -146,10 +136,6 @@ extern "C" int ds2_ctc_align_star_tiled_f32(const float* x, long long ld_b, long
   const AlignTiledLayout L = align_tiled_layout(B, T, max_target_len, tile_frames, tile_pairs, true);
   float* g = (float*)ws + (L.bp_words + L.col_words + L.carry_words + L.fin_words);
   if (int rc = align_star_row_launch(x, ld_b, ld_t, B, T, C, is_log, in_lens_dev, star_penalty, g, stream)) return rc;
-  AlignArgs a;
-  a.x = x; a.ld_b = ld_b; a.ld_t = ld_t; a.T = T; a.C = C;
-  a.targets = targets_dev; a.tgt_off = tgt_off_dev; a.in_lens = in_lens_dev; a.tgt_lens = tgt_lens_dev;
-  a.score = score; a.states = states; a.tok_start = tok_start; a.tok_end = tok_end; a.tok_logp = tok_logp;
   a.g = g; a.flags = flags_dev;
   return align_tiled_launch<true>("ds2_ctc_align_star_tiled_f32", a, B, is_log, max_target_len, tile_frames, tile_pairs, (float*)ws, stream);
 }

@@ -329,7 +329,8 @@ inline AlignTiledLayout align_tiled_layout(int B, int T, int max_target_len, int
 }
 
 // The launches that both entries share (`who` names the entry in an error): the fill, one launch per anti-diagonal, the backtrace.
-// `ws` holds carry, fin, col and the back-pointers in this order (STAR: the caller keeps g behind them); a.g and a.flags are the caller's.
+// `ws` holds carry, fin, col and the back-pointers in this order (STAR: the caller keeps g behind them); a.g, a.flags and a.maxU are the
+// caller's.
 template <bool STAR>
 int align_tiled_launch(const char* who, const AlignArgs& a0, int B, int is_log, int max_target_len, int tile_frames, int tile_pairs,
                        float* ws, void* stream) {
@@ -337,7 +338,6 @@ int align_tiled_launch(const char* who, const AlignArgs& a0, int B, int is_log, 
   AlignTiledArgs ta;
   ta.a = a0;
   AlignArgs& a = ta.a;
-  a.maxU = max_target_len;
   ta.carry = ws;                                       // (read and written as float2: an even number of words from the aligned base)
   ta.fin = ta.carry + L.carry_words;
   ta.col = ta.fin + L.fin_words;
@@ -385,21 +385,13 @@ extern "C" int ds2_ctc_align_tiled_f32(const float* x, long long ld_b, long long
                                        const int* targets_dev, const int* tgt_off_dev, const int* in_lens_dev, const int* tgt_lens_dev,
                                        int max_target_len, int tile_frames, int tile_pairs, float* score, int* states, int* tok_start,
                                        int* tok_end, float* tok_logp, void* ws, size_t ws_bytes, void* stream) {
-  DS2_REQUIRE(x && tgt_off_dev && tgt_lens_dev && score && states, "ds2_ctc_align_tiled_f32: null pointer");
-  DS2_REQUIRE(B > 0 && T > 0 && C > 0 && max_target_len >= 0 && ld_b > 0 && ld_t > 0,
-              "ds2_ctc_align_tiled_f32: bad dims (B=%d T=%d C=%d U=%d)", B, T, C, max_target_len);
-  DS2_REQUIRE(max_target_len == 0 || (targets_dev && tok_start && tok_end && tok_logp),
-              "ds2_ctc_align_tiled_f32: null target / token pointer");
-  DS2_REQUIRE(is_log == 0 || is_log == 1, "ds2_ctc_align_tiled_f32: is_log must be 0 or 1");
+  AlignArgs a;
+  if (int rc = align_entry_args("ds2_ctc_align_tiled_f32", a, x, ld_b, ld_t, B, T, C, is_log, targets_dev, tgt_off_dev, in_lens_dev,
+                                tgt_lens_dev, max_target_len, score, states, tok_start, tok_end, tok_logp)) return rc;
   DS2_REQUIRE(align_tiled_shape(tile_frames, tile_pairs),
               "ds2_ctc_align_tiled_f32: tile_frames must be a positive multiple of 8 and tile_pairs a positive multiple of 64 up to 1024 "
               "(or 0 for the default), got %d x %d", tile_frames, tile_pairs);
   DS2_REQUIRE(ws && ws_bytes >= ds2_ctc_align_tiled_workspace_bytes(B, T, max_target_len, tile_frames, tile_pairs),
               "ds2_ctc_align_tiled_f32: workspace too small");
-  AlignArgs a;
-  a.x = x; a.ld_b = ld_b; a.ld_t = ld_t; a.T = T; a.C = C;
-  a.targets = targets_dev; a.tgt_off = tgt_off_dev; a.in_lens = in_lens_dev; a.tgt_lens = tgt_lens_dev;
-  a.score = score; a.states = states; a.tok_start = tok_start; a.tok_end = tok_end; a.tok_logp = tok_logp;
-  a.g = nullptr; a.flags = nullptr;
   return align_tiled_launch<false>("ds2_ctc_align_tiled_f32", a, B, is_log, max_target_len, tile_frames, tile_pairs, (float*)ws, stream);
 }

@@ -730,40 +730,53 @@ extern "C" size_t ds2_ctc_beam_workspace_bytes(int B, int T, int beam_width) {
   return (size_t)3 * sizeof(int) * B * T * beam_width;
 }
 
+// What the three decode entries share (`who` names the entry in an error).  `arm`: the pointer an arm cannot do without, the LM or the
+// hotword blob (the plain entry passes probs again).
+static int beam_check(const char* who, const float* probs, const void* arm, int B, int T, int C, int blank, int beam_width, int cutoff_top_n,
+                      float cutoff_prob, const int* labels, const int* offsets, const int* lens, const float* scores, const void* ws,
+                      size_t ws_bytes) {
+  DS2_REQUIRE(probs && labels && offsets && lens && scores && arm, "%s: null pointer", who);
+  DS2_REQUIRE(beam_width >= 1 && beam_width <= BEAM_MAX_K, "%s: beam_width %d outside the supported 1..%d", who, beam_width, BEAM_MAX_K);
+  DS2_REQUIRE(C >= 2 && C <= BEAM_MAX_C, "%s: %d classes outside the supported 2..%d", who, C, BEAM_MAX_C);
+  DS2_REQUIRE(B > 0 && T > 0 && T <= BEAM_MAX_T && blank >= 0 && blank < C, "%s: bad dims (B=%d T=%d C=%d blank=%d; T <= %d)", who, B, T, C,
+              blank, BEAM_MAX_T);
+  DS2_REQUIRE(cutoff_top_n >= 1 && cutoff_prob == cutoff_prob, "%s: cutoff_top_n must be >= 1 and cutoff_prob a number", who);
+  DS2_REQUIRE(ws && ws_bytes >= ds2_ctc_beam_workspace_bytes(B, T, beam_width), "%s: workspace too small", who);
+  return 0;
+}
+
+// The dynamic-LDS limit above 64 KiB, the launch of one workgroup per utterance and its check, for every instance of the kernel
+template <auto KERNEL, class... Args>
+static int beam_launch(const char* label, int B, size_t lds, void* stream, Args... args) {
+  if (lds > 64 * 1024) DS2_HIP(hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(KERNEL, dim3(B), dim3(BEAM_THREADS), lds, (hipStream_t)stream, args...);
+  DS2_LAUNCH_CHECK(label);
+  return 0;
+}
+
 extern "C" int ds2_ctc_beam_decode_f32(const float* probs, long long ld_b, long long ld_t, int B, int T, int C, const int* sizes_dev,
                                        int blank, int beam_width, int cutoff_top_n, float cutoff_prob, int* labels, int* offsets,
                                        int* lens, float* scores, void* ws, size_t ws_bytes, void* stream) {
-  DS2_REQUIRE(probs && labels && offsets && lens && scores, "ds2_ctc_beam_decode_f32: null pointer");
-  DS2_REQUIRE(beam_width >= 1 && beam_width <= BEAM_MAX_K, "ds2_ctc_beam_decode_f32: beam_width %d outside the supported 1..%d", beam_width,
-              BEAM_MAX_K);
-  DS2_REQUIRE(C >= 2 && C <= BEAM_MAX_C, "ds2_ctc_beam_decode_f32: %d classes outside the supported 2..%d", C, BEAM_MAX_C);
-  DS2_REQUIRE(B > 0 && T > 0 && T <= BEAM_MAX_T && blank >= 0 && blank < C,
-              "ds2_ctc_beam_decode_f32: bad dims (B=%d T=%d C=%d blank=%d; T <= %d)", B, T, C, blank, BEAM_MAX_T);
-  DS2_REQUIRE(cutoff_top_n >= 1 && cutoff_prob == cutoff_prob, "ds2_ctc_beam_decode_f32: cutoff_top_n must be >= 1 and cutoff_prob a number");
-  DS2_REQUIRE(ws && ws_bytes >= ds2_ctc_beam_workspace_bytes(B, T, beam_width), "ds2_ctc_beam_decode_f32: workspace too small");
+  if (int rc = beam_check("ds2_ctc_beam_decode_f32", probs, probs, B, T, C, blank, beam_width, cutoff_top_n, cutoff_prob, labels, offsets, lens,
+                          scores, ws, ws_bytes)) return rc;
   const int K = beam_width, PC = pow2_ceil(C), PK = pow2_ceil(max_candidates(K)), HT = 2 * pow2_ceil(K);
   const Layout lay(K, PC, PK, HT);
   DS2_REQUIRE(PK <= 4096 && lay.total <= 160 * 1024, "ds2_ctc_beam_decode_f32: LDS layout of %zu bytes does not fit", lay.total);
-  hipStream_t s = (hipStream_t)stream;
   const char* pe = ds2_exp_getenv("DS2_BEAM_PROFILE");
-  if (!(pe && pe[0] == '1')) {
-    if (lay.total > 64 * 1024)
-      DS2_HIP(hipFuncSetAttribute((const void*)ctc_beam_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lay.total));
-    hipLaunchKernelGGL((ctc_beam_kernel<false, false>), dim3(B), dim3(BEAM_THREADS), lay.total, s, probs, ld_b, ld_t, T, C, sizes_dev, blank, K,
-                       cutoff_top_n, cutoff_prob, PC, PK, HT, labels, offsets, lens, scores, (int*)ws, nullptr);
-    DS2_LAUNCH_CHECK("ctc_beam_kernel");
-    return 0;
-  }
+  if (!(pe && pe[0] == '1'))
+    return beam_launch<ctc_beam_kernel<false, false>>("ctc_beam_kernel", B, lay.total, stream, probs, ld_b, ld_t, T, C, sizes_dev, blank, K,
+                                                      cutoff_top_n, cutoff_prob, PC, PK, HT, labels, offsets, lens, scores, (int*)ws, nullptr);
   // profiling build of the same kernel (experiments only): per-step times averaged over the utterances' frames
-  if (lay.total > 64 * 1024)
-    DS2_HIP(hipFuncSetAttribute((const void*)ctc_beam_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lay.total));
   u64* prof = nullptr;
   DS2_HIP(hipMalloc(&prof, (size_t)B * 8 * sizeof(u64)));
-  hipLaunchKernelGGL((ctc_beam_kernel<true, false>), dim3(B), dim3(BEAM_THREADS), lay.total, s, probs, ld_b, ld_t, T, C, sizes_dev, blank, K,
-                     cutoff_top_n, cutoff_prob, PC, PK, HT, labels, offsets, lens, scores, (int*)ws, prof);
-  hipError_t e = hipGetLastError();
+  if (int rc = beam_launch<ctc_beam_kernel<true, false>>("ctc_beam_kernel (profiling)", B, lay.total, stream, probs, ld_b, ld_t, T, C, sizes_dev,
+                                                         blank, K, cutoff_top_n, cutoff_prob, PC, PK, HT, labels, offsets, lens, scores,
+                                                         (int*)ws, prof)) {
+    hipFree(prof);
+    return rc;
+  }
   u64* h = (u64*)calloc((size_t)B * 8, sizeof(u64));
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  hipError_t e = hipStreamSynchronize((hipStream_t)stream);
   if (e == hipSuccess) e = hipMemcpy(h, prof, (size_t)B * 8 * sizeof(u64), hipMemcpyDeviceToHost);
   hipFree(prof);
   if (e != hipSuccess) {
@@ -860,25 +873,24 @@ extern "C" int ds2_ctc_lm_score(const void* packed, const int* hist, int n_hist,
   return 0;
 }
 
+// The language-model arguments of the LM and hotword entries (`who` names the entry in an error)
+static int beam_lm_check(const char* who, size_t lm_bytes, int lm_order, int lm_mode, int space, int C, int blank, float alpha, float beta) {
+  DS2_REQUIRE(lm_order >= 1 && lm_order <= ds2lm::MAX_ORDER && (lm_mode == ds2lm::MODE_CHAR || lm_mode == ds2lm::MODE_WORD) &&
+                  lm_bytes >= sizeof(ds2lm::LmHeader),
+              "%s: bad language model (order %d, mode %d, %zu bytes)", who, lm_order, lm_mode, lm_bytes);
+  DS2_REQUIRE(lm_mode == ds2lm::MODE_CHAR || (space >= 0 && space < C && space != blank),
+              "%s: word mode needs a space label other than the blank (got %d)", who, space);
+  DS2_REQUIRE(alpha == alpha && beta == beta && fabsf(alpha) < INFINITY && fabsf(beta) < INFINITY, "%s: alpha and beta must be finite", who);
+  return 0;
+}
+
 extern "C" int ds2_ctc_beam_decode_lm_f32(const float* probs, long long ld_b, long long ld_t, int B, int T, int C, const int* sizes_dev,
                                           int blank, int beam_width, int cutoff_top_n, float cutoff_prob, const void* lm_dev,
                                           size_t lm_bytes, int lm_order, int lm_mode, int space, float alpha, float beta, int* labels,
                                           int* offsets, int* lens, float* scores, void* ws, size_t ws_bytes, void* stream) {
-  DS2_REQUIRE(probs && labels && offsets && lens && scores && lm_dev, "ds2_ctc_beam_decode_lm_f32: null pointer");
-  DS2_REQUIRE(beam_width >= 1 && beam_width <= BEAM_MAX_K, "ds2_ctc_beam_decode_lm_f32: beam_width %d outside the supported 1..%d",
-              beam_width, BEAM_MAX_K);
-  DS2_REQUIRE(C >= 2 && C <= BEAM_MAX_C, "ds2_ctc_beam_decode_lm_f32: %d classes outside the supported 2..%d", C, BEAM_MAX_C);
-  DS2_REQUIRE(B > 0 && T > 0 && T <= BEAM_MAX_T && blank >= 0 && blank < C,
-              "ds2_ctc_beam_decode_lm_f32: bad dims (B=%d T=%d C=%d blank=%d; T <= %d)", B, T, C, blank, BEAM_MAX_T);
-  DS2_REQUIRE(cutoff_top_n >= 1 && cutoff_prob == cutoff_prob, "ds2_ctc_beam_decode_lm_f32: cutoff_top_n must be >= 1 and cutoff_prob a number");
-  DS2_REQUIRE(ws && ws_bytes >= ds2_ctc_beam_workspace_bytes(B, T, beam_width), "ds2_ctc_beam_decode_lm_f32: workspace too small");
-  DS2_REQUIRE(lm_order >= 1 && lm_order <= ds2lm::MAX_ORDER && (lm_mode == ds2lm::MODE_CHAR || lm_mode == ds2lm::MODE_WORD) &&
-                  lm_bytes >= sizeof(ds2lm::LmHeader),
-              "ds2_ctc_beam_decode_lm_f32: bad language model (order %d, mode %d, %zu bytes)", lm_order, lm_mode, lm_bytes);
-  DS2_REQUIRE(lm_mode == ds2lm::MODE_CHAR || (space >= 0 && space < C && space != blank),
-              "ds2_ctc_beam_decode_lm_f32: word mode needs a space label other than the blank (got %d)", space);
-  DS2_REQUIRE(alpha == alpha && beta == beta && fabsf(alpha) < INFINITY && fabsf(beta) < INFINITY,
-              "ds2_ctc_beam_decode_lm_f32: alpha and beta must be finite");
+  if (int rc = beam_check("ds2_ctc_beam_decode_lm_f32", probs, lm_dev, B, T, C, blank, beam_width, cutoff_top_n, cutoff_prob, labels, offsets,
+                          lens, scores, ws, ws_bytes)) return rc;
+  if (int rc = beam_lm_check("ds2_ctc_beam_decode_lm_f32", lm_bytes, lm_order, lm_mode, space, C, blank, alpha, beta)) return rc;
   const int K = beam_width, nbl = min(cutoff_top_n, C - 1);
   DS2_REQUIRE((long long)K * (nbl + 2) <= ds2_ctc_beam_lm_max_candidates(),
               "ds2_ctc_beam_decode_lm_f32: beam_width * (min(cutoff_top_n, C - 1) + 2) = %lld exceeds the %d candidate slots",
@@ -887,14 +899,10 @@ extern "C" int ds2_ctc_beam_decode_lm_f32(const float* probs, long long ld_b, lo
   const Layout lay(K, PC, PK, HT);
   const size_t total = lm_layout_total(lay, nbl);
   DS2_REQUIRE(total <= 160 * 1024, "ds2_ctc_beam_decode_lm_f32: LDS layout of %zu bytes does not fit", total);
-  hipStream_t s = (hipStream_t)stream;
-  if (total > 64 * 1024)
-    DS2_HIP(hipFuncSetAttribute((const void*)ctc_beam_kernel<false, true, LmArgs>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)total));
   const LmArgs la{lm_dev, alpha, beta, lm_order - 1, lm_mode, lm_mode == ds2lm::MODE_WORD ? space : -1, nbl};
-  hipLaunchKernelGGL((ctc_beam_kernel<false, true, LmArgs>), dim3(B), dim3(BEAM_THREADS), total, s, probs, ld_b, ld_t, T, C, sizes_dev, blank, K,
-                     cutoff_top_n, cutoff_prob, PC, PK, HT, labels, offsets, lens, scores, (int*)ws, nullptr, la);
-  DS2_LAUNCH_CHECK("ctc_beam_kernel<LM>");
-  return 0;
+  return beam_launch<ctc_beam_kernel<false, true, LmArgs>>("ctc_beam_kernel<LM>", B, total, stream, probs, ld_b, ld_t, T, C, sizes_dev, blank, K,
+                                                           cutoff_top_n, cutoff_prob, PC, PK, HT, labels, offsets, lens, scores, (int*)ws,
+                                                           nullptr, la);
 }
 
 // ---- hotword arm (ds2_ctc_hot_*, ds2_ctc_beam_decode_hot_f32) ----
@@ -993,26 +1001,13 @@ extern "C" int ds2_ctc_beam_decode_hot_f32(const float* probs, long long ld_b, l
                                            size_t lm_bytes, int lm_order, int lm_mode, int space, float alpha, float beta,
                                            const void* hot_dev, const void* hot_host, size_t hot_bytes, int* labels, int* offsets,
                                            int* lens, float* scores, void* ws, size_t ws_bytes, void* stream) {
-  DS2_REQUIRE(probs && labels && offsets && lens && scores && hot_dev, "ds2_ctc_beam_decode_hot_f32: null pointer");
-  DS2_REQUIRE(beam_width >= 1 && beam_width <= BEAM_MAX_K, "ds2_ctc_beam_decode_hot_f32: beam_width %d outside the supported 1..%d",
-              beam_width, BEAM_MAX_K);
-  DS2_REQUIRE(C >= 2 && C <= BEAM_MAX_C, "ds2_ctc_beam_decode_hot_f32: %d classes outside the supported 2..%d", C, BEAM_MAX_C);
-  DS2_REQUIRE(B > 0 && T > 0 && T <= BEAM_MAX_T && blank >= 0 && blank < C,
-              "ds2_ctc_beam_decode_hot_f32: bad dims (B=%d T=%d C=%d blank=%d; T <= %d)", B, T, C, blank, BEAM_MAX_T);
-  DS2_REQUIRE(cutoff_top_n >= 1 && cutoff_prob == cutoff_prob, "ds2_ctc_beam_decode_hot_f32: cutoff_top_n must be >= 1 and cutoff_prob a number");
-  DS2_REQUIRE(ws && ws_bytes >= ds2_ctc_beam_workspace_bytes(B, T, beam_width), "ds2_ctc_beam_decode_hot_f32: workspace too small");
+  if (int rc = beam_check("ds2_ctc_beam_decode_hot_f32", probs, hot_dev, B, T, C, blank, beam_width, cutoff_top_n, cutoff_prob, labels, offsets,
+                          lens, scores, ws, ws_bytes)) return rc;
   if (hot_header_check("ds2_ctc_beam_decode_hot_f32", hot_host, hot_bytes)) return 1;
   DS2_REQUIRE(((const ds2hot::HotHeader*)hot_host)->C == C, "ds2_ctc_beam_decode_hot_f32: the hotwords were packed for %d classes, probs have %d",
               ((const ds2hot::HotHeader*)hot_host)->C, C);
-  if (lm_dev) {
-    DS2_REQUIRE(lm_order >= 1 && lm_order <= ds2lm::MAX_ORDER && (lm_mode == ds2lm::MODE_CHAR || lm_mode == ds2lm::MODE_WORD) &&
-                    lm_bytes >= sizeof(ds2lm::LmHeader),
-                "ds2_ctc_beam_decode_hot_f32: bad language model (order %d, mode %d, %zu bytes)", lm_order, lm_mode, lm_bytes);
-    DS2_REQUIRE(lm_mode == ds2lm::MODE_CHAR || (space >= 0 && space < C && space != blank),
-                "ds2_ctc_beam_decode_hot_f32: word mode needs a space label other than the blank (got %d)", space);
-    DS2_REQUIRE(alpha == alpha && beta == beta && fabsf(alpha) < INFINITY && fabsf(beta) < INFINITY,
-                "ds2_ctc_beam_decode_hot_f32: alpha and beta must be finite");
-  }
+  if (lm_dev)
+    if (int rc = beam_lm_check("ds2_ctc_beam_decode_hot_f32", lm_bytes, lm_order, lm_mode, space, C, blank, alpha, beta)) return rc;
   const int K = beam_width, nbl = min(cutoff_top_n, C - 1);
   DS2_REQUIRE((long long)K * (nbl + 2) <= ds2_ctc_beam_lm_max_candidates(),
               "ds2_ctc_beam_decode_hot_f32: beam_width * (min(cutoff_top_n, C - 1) + 2) = %lld exceeds the %d candidate slots (hotwords "
@@ -1025,15 +1020,11 @@ extern "C" int ds2_ctc_beam_decode_hot_f32(const float* probs, long long ld_b, l
               "ds2_ctc_beam_decode_hot_f32: LDS layout of %zu bytes (%zu of them hotword state) does not fit the 160 KiB at beam_width %d, "
               "%d classes",
               total, 2 * hot_state_bytes(K), K, C);
-  hipStream_t s = (hipStream_t)stream;
-  if (total > 64 * 1024)
-    DS2_HIP(hipFuncSetAttribute((const void*)ctc_beam_kernel<false, true, HotArgs>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)total));
   HotArgs ha;
   ha.lm = lm_dev ? LmArgs{lm_dev, alpha, beta, lm_order - 1, lm_mode, lm_mode == ds2lm::MODE_WORD ? space : -1, nbl}
                  : LmArgs{nullptr, 0.f, 0.f, 0, 0, -1, nbl};
   ha.hot = hot_dev;
-  hipLaunchKernelGGL((ctc_beam_kernel<false, true, HotArgs>), dim3(B), dim3(BEAM_THREADS), total, s, probs, ld_b, ld_t, T, C, sizes_dev, blank, K,
-                     cutoff_top_n, cutoff_prob, PC, PK, HT, labels, offsets, lens, scores, (int*)ws, nullptr, ha);
-  DS2_LAUNCH_CHECK("ctc_beam_kernel<HOT>");
-  return 0;
+  return beam_launch<ctc_beam_kernel<false, true, HotArgs>>("ctc_beam_kernel<HOT>", B, total, stream, probs, ld_b, ld_t, T, C, sizes_dev, blank, K,
+                                                            cutoff_top_n, cutoff_prob, PC, PK, HT, labels, offsets, lens, scores, (int*)ws,
+                                                            nullptr, ha);
 }

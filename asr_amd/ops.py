@@ -1223,30 +1223,35 @@ def rnn_bias_grads(gates: int, bias_part: Tensor, dbih: Tensor, dbhh: Tensor):
 # ------------------------------------------------------------------------------------------------
 # CTC
 # ------------------------------------------------------------------------------------------------
+def _ctc_loss(entry, logits, targets_dev, tgt_off_dev, in_lens_dev, tgt_lens_dev, max_tgt, grad_scale, want_grad, lattice, return_ab, star=()):
+    """ctc_loss and ctc_star_loss: `entry` is the C entry, star = (star_penalty, flags pointer) the two arguments only the wildcard one takes"""
+    _chk_f32(logits)
+    lib = _lib.load()
+    T, B, Cc = logits.shape
+    assert logits.stride(2) == 1 and logits.stride(0) == B * logits.stride(1)
+    nll = torch.empty(B, dtype=torch.float32, device=logits.device)
+    grad = torch.empty(T, B, Cc, dtype=torch.float32, device=logits.device) if want_grad else None
+    wsb = (lib.ds2_ctc_star_workspace_bytes if star else lib.ds2_ctc_workspace_bytes)(T, B, max_tgt)
+    ws = _ws(wsb, logits.device)
+    if return_ab:
+        ws.zero_()
+    _lib.check(getattr(lib, entry)(logits.data_ptr(), logits.stride(1), T, B, Cc, targets_dev.data_ptr(), tgt_off_dev.data_ptr(),
+                                   in_lens_dev.data_ptr(), tgt_lens_dev.data_ptr(), int(max_tgt), *star, nll.data_ptr(), _ptr(grad), Cc,
+                                   float(grad_scale), int(lattice), ws.data_ptr(), wsb, _stream()), entry)
+    if return_ab:                                        # the lattices follow the (T, B) row of the workspace, as the C entries lay it out
+        Smax = 2 * int(max_tgt) + 1
+        off = (T * B * 4 + 255) // 256 * 256
+        return nll, grad, ws[off:off + 2 * B * T * Smax * 4].view(torch.float32).view(2, B, T, Smax).clone()
+    return nll, grad
+
+
 def ctc_loss(logits: Tensor, targets_dev: Tensor, tgt_off_dev: Tensor, in_lens_dev: Tensor, tgt_lens_dev: Tensor, max_tgt: int,
              grad_scale: float, want_grad: bool = True, lattice: int = 0, return_ab: bool = False):
     """logits (T,B,C) (last dim contiguous, uniform row pitch).  Returns (nll (B,), grad (T,B,C) or None).
     lattice: 0 = the library chooses the lattice kernel, 1 = one workgroup per lattice whatever the target length (the two write the same
     bits).  return_ab: also a copy of the alpha / beta lattices (2, B, T, 2 * max_tgt + 1), zero outside an utterance's (T_b, S_b)."""
-    _chk_f32(logits)
-    lib = _lib.load()
-    T, B, Cc = logits.shape
-    assert logits.stride(2) == 1 and logits.stride(0) == B * logits.stride(1)
-    ld = logits.stride(1)
-    nll = torch.empty(B, dtype=torch.float32, device=logits.device)
-    grad = torch.empty(T, B, Cc, dtype=torch.float32, device=logits.device) if want_grad else None
-    wsb = lib.ds2_ctc_workspace_bytes(T, B, max_tgt)
-    ws = _ws(wsb, logits.device)
-    if return_ab:
-        ws.zero_()
-    _lib.check(lib.ds2_ctc_loss_ex_f32(logits.data_ptr(), ld, T, B, Cc, targets_dev.data_ptr(), tgt_off_dev.data_ptr(),
-                                       in_lens_dev.data_ptr(), tgt_lens_dev.data_ptr(), int(max_tgt), nll.data_ptr(), _ptr(grad), Cc,
-                                       float(grad_scale), int(lattice), ws.data_ptr(), wsb, _stream()), "ds2_ctc_loss_ex_f32")
-    if return_ab:
-        Smax = 2 * int(max_tgt) + 1
-        off = (T * B * 4 + 255) // 256 * 256
-        return nll, grad, ws[off:off + 2 * B * T * Smax * 4].view(torch.float32).view(2, B, T, Smax).clone()
-    return nll, grad
+    return _ctc_loss("ds2_ctc_loss_ex_f32", logits, targets_dev, tgt_off_dev, in_lens_dev, tgt_lens_dev, max_tgt, grad_scale, want_grad, lattice,
+                     return_ab)
 
 
 def ctc_star_loss(logits: Tensor, targets_dev: Tensor, tgt_off_dev: Tensor, in_lens_dev: Tensor, tgt_lens_dev: Tensor, max_tgt: int,
@@ -1256,28 +1261,10 @@ def ctc_star_loss(logits: Tensor, targets_dev: Tensor, tgt_off_dev: Tensor, in_l
     the wildcard, whose state emits the constant star_penalty (<= 0, finite, natural log); flags (B) int32 on the device, or None:
     bit 0 = the first token is optional, bit 1 = the last.  Everything else, and what is returned, as ctc_loss; without a wildcard
     and without flags the results are its bits."""
-    _chk_f32(logits)
-    lib = _lib.load()
-    T, B, Cc = logits.shape
-    assert logits.stride(2) == 1 and logits.stride(0) == B * logits.stride(1)
     if flags is not None:
-        assert flags.dtype == torch.int32 and flags.numel() == B and flags.is_contiguous() and flags.device == logits.device
-    ld = logits.stride(1)
-    nll = torch.empty(B, dtype=torch.float32, device=logits.device)
-    grad = torch.empty(T, B, Cc, dtype=torch.float32, device=logits.device) if want_grad else None
-    wsb = lib.ds2_ctc_star_workspace_bytes(T, B, max_tgt)
-    ws = _ws(wsb, logits.device)
-    if return_ab:
-        ws.zero_()
-    _lib.check(lib.ds2_ctc_star_loss_f32(logits.data_ptr(), ld, T, B, Cc, targets_dev.data_ptr(), tgt_off_dev.data_ptr(),
-                                         in_lens_dev.data_ptr(), tgt_lens_dev.data_ptr(), int(max_tgt), float(star_penalty), _ptr(flags),
-                                         nll.data_ptr(), _ptr(grad), Cc, float(grad_scale), int(lattice), ws.data_ptr(), wsb, _stream()),
-               "ds2_ctc_star_loss_f32")
-    if return_ab:
-        Smax = 2 * int(max_tgt) + 1
-        off = (T * B * 4 + 255) // 256 * 256
-        return nll, grad, ws[off:off + 2 * B * T * Smax * 4].view(torch.float32).view(2, B, T, Smax).clone()
-    return nll, grad
+        assert flags.dtype == torch.int32 and flags.numel() == logits.shape[1] and flags.is_contiguous() and flags.device == logits.device
+    return _ctc_loss("ds2_ctc_star_loss_f32", logits, targets_dev, tgt_off_dev, in_lens_dev, tgt_lens_dev, max_tgt, grad_scale, want_grad,
+                     lattice, return_ab, star=(float(star_penalty), _ptr(flags)))
 
 
 def ctc_batch_mean(nll: Tensor) -> Tensor:
@@ -1304,6 +1291,15 @@ def softmax_rows(x: Tensor) -> Tensor:
     return y
 
 
+def _sizes_i32(sizes, B: int, dev):
+    """the decoders' optional per-utterance frame counts (any integer dtype, any device) as (B) int32 on dev, or None"""
+    if sizes is None:
+        return None
+    if sizes.numel() != B:
+        raise ValueError(f"sizes has {sizes.numel()} entries for a batch of {B}")
+    return sizes.to(device=dev, dtype=torch.int32).contiguous().view(-1)
+
+
 def greedy_decode(probs: Tensor, sizes: Tensor | None = None, blank: int = 0):
     """probs (B,T,C) fp32 on the GPU -> (ids (B,T) i32, offsets (B,T) i32, lengths (B) i32), all on the GPU."""
     _chk_f32(probs)
@@ -1311,10 +1307,7 @@ def greedy_decode(probs: Tensor, sizes: Tensor | None = None, blank: int = 0):
         raise ValueError("greedy_decode: probs must be (B,T,C) with a contiguous class dim")
     B, T, C = probs.shape
     dev = probs.device
-    if sizes is not None:
-        if sizes.numel() != B:
-            raise ValueError(f"sizes has {sizes.numel()} entries for a batch of {B}")
-        sizes = sizes.to(device=dev, dtype=torch.int32).contiguous().view(-1)
+    sizes = _sizes_i32(sizes, B, dev)
     ids = torch.empty((B, T), dtype=torch.int32, device=dev)
     offs = torch.empty((B, T), dtype=torch.int32, device=dev)
     lens = torch.empty((B,), dtype=torch.int32, device=dev)
@@ -1322,7 +1315,7 @@ def greedy_decode(probs: Tensor, sizes: Tensor | None = None, blank: int = 0):
     n = lib.ds2_greedy_decode_workspace_bytes(B, T)
     ws = torch.empty(n, dtype=torch.uint8, device=dev)
     _lib.check(lib.ds2_greedy_decode_f32(probs.data_ptr(), probs.stride(0), probs.stride(1), B, T, C,
-                                         sizes.data_ptr() if sizes is not None else None, blank, ids.data_ptr(), offs.data_ptr(),
+                                         _ptr(sizes), blank, ids.data_ptr(), offs.data_ptr(),
                                          lens.data_ptr(), ws.data_ptr(), n, _stream()), "ds2_greedy_decode_f32")
     return ids, offs, lens
 
@@ -1364,6 +1357,51 @@ def edit_distance(seq: Tensor, a_off, a_len, b_off, b_len, max_len: int | None =
     return dist
 
 
+def _chk_align_args(who, x, ints, star_penalty=None):
+    """The checks of the aligner wrappers, a malformed argument before a tensor off the GPU.  ints: name -> int32 tensor or None, all of
+    them but `targets` with one entry per utterance.  Returns star_penalty as a float (None without one)."""
+    if x.dim() != 3 or x.stride(2) != 1:
+        raise ValueError(f"{who}: x must be (B,T,C) with a contiguous class dim")
+    B, dev = x.shape[0], x.device
+    for name, t in ints.items():
+        if t is not None and (t.dtype != torch.int32 or t.device != dev or not t.is_contiguous()):
+            raise ValueError(f"{who}: {name} must be a contiguous int32 tensor on {dev}")
+    if any(t is not None and t.numel() != B for name, t in ints.items() if name != "targets"):
+        raise ValueError(f"{who}: offsets / lengths{' / flags' if 'flags' in ints else ''} do not match the batch of {B}")
+    p = None if star_penalty is None else float(star_penalty)
+    if p is not None and not (p <= 0.0 and math.isfinite(p)):
+        raise ValueError(f"{who}: star_penalty must be finite and <= 0, got {star_penalty}")
+    _chk_f32(x)
+    return p
+
+
+def _ctc_align(who, entry, x, targets, tgt_off, in_lens, tgt_lens, max_u, is_log, shape, star=None):
+    """The four aligner wrappers.  entry: the C entry, sized by its own *_workspace_bytes; shape: (variant,) or (tile_frames, tile_pairs),
+    of which only a tile shape sizes the workspace (an illegal one sizes nothing: the entry refuses it); star: (star_penalty, flags)."""
+    ints = dict(targets=targets, tgt_off=tgt_off, tgt_lens=tgt_lens, in_lens=in_lens)
+    if star is not None:
+        ints["flags"] = star[1]
+    p = _chk_align_args(who, x, ints, star[0] if star is not None else None)
+    B, T, Cc = x.shape
+    dev = x.device
+    shape = tuple(int(v) for v in shape)
+    n_tok = targets.numel()
+    score = torch.empty(B, dtype=torch.float32, device=dev)
+    states = torch.empty((B, T), dtype=torch.int32, device=dev)
+    tok_start = torch.empty(n_tok, dtype=torch.int32, device=dev)
+    tok_end = torch.empty(n_tok, dtype=torch.int32, device=dev)
+    tok_logp = torch.empty(n_tok, dtype=torch.float32, device=dev)
+    tok = _ptr if n_tok else (lambda t: None)            # no token: null pointers, which the entries accept with max_u == 0 only
+    lib = _lib.load()
+    wsb = getattr(lib, entry[:-len("f32")] + "workspace_bytes")(B, T, int(max_u), *(shape if len(shape) == 2 else ()))
+    ws = _ws(wsb, dev)
+    _lib.check(getattr(lib, entry)(x.data_ptr(), x.stride(0), x.stride(1), B, T, Cc, 1 if is_log else 0, tok(targets), tgt_off.data_ptr(),
+                                   _ptr(in_lens), tgt_lens.data_ptr(), int(max_u), *shape, *(() if star is None else (p, _ptr(star[1]))),
+                                   score.data_ptr(), states.data_ptr(), tok(tok_start), tok(tok_end), tok(tok_logp), ws.data_ptr(), wsb,
+                                   _stream()), entry)
+    return score, states, tok_start, tok_end, tok_logp
+
+
 def ctc_forced_align(x: Tensor, targets: Tensor, tgt_off: Tensor, in_lens: Tensor | None, tgt_lens: Tensor, max_u: int, is_log: bool,
                      variant: int = 0):
     """CTC forced alignment of x (B,T,C) fp32 on the GPU (any batch / frame strides, classes contiguous: the model's (T,B,C)-backed eval
@@ -1372,30 +1410,7 @@ def ctc_forced_align(x: Tensor, targets: Tensor, tgt_off: Tensor, in_lens: Tenso
     frames each) are int32 device tensors; max_u >= every target length (host-known: nothing is copied back to size anything).
     is_log: x holds log-probabilities (else probabilities).  variant: 0 = the library chooses, 1 = one wavefront per utterance
     (2 * max_u + 1 <= 128), 2 = one workgroup per utterance.  One launch on the current stream."""
-    _chk_f32(x)
-    if x.dim() != 3 or x.stride(2) != 1:
-        raise ValueError("ctc_forced_align: x must be (B,T,C) with a contiguous class dim")
-    B, T, Cc = x.shape
-    dev = x.device
-    for name, t in (("targets", targets), ("tgt_off", tgt_off), ("tgt_lens", tgt_lens), ("in_lens", in_lens)):
-        if t is not None and (t.dtype != torch.int32 or t.device != dev or not t.is_contiguous()):
-            raise ValueError(f"ctc_forced_align: {name} must be a contiguous int32 tensor on {dev}")
-    if tgt_off.numel() != B or tgt_lens.numel() != B or (in_lens is not None and in_lens.numel() != B):
-        raise ValueError(f"ctc_forced_align: offsets / lengths do not match the batch of {B}")
-    n_tok = targets.numel()
-    score = torch.empty(B, dtype=torch.float32, device=dev)
-    states = torch.empty((B, T), dtype=torch.int32, device=dev)
-    tok_start = torch.empty(n_tok, dtype=torch.int32, device=dev)
-    tok_end = torch.empty(n_tok, dtype=torch.int32, device=dev)
-    tok_logp = torch.empty(n_tok, dtype=torch.float32, device=dev)
-    lib = _lib.load()
-    wsb = lib.ds2_ctc_align_workspace_bytes(B, T, int(max_u))
-    ws = _ws(max(wsb, 1), dev)
-    _lib.check(lib.ds2_ctc_align_f32(x.data_ptr(), x.stride(0), x.stride(1), B, T, Cc, 1 if is_log else 0, _ptr(targets) if n_tok else None,
-                                     tgt_off.data_ptr(), _ptr(in_lens), tgt_lens.data_ptr(), int(max_u), int(variant), score.data_ptr(),
-                                     states.data_ptr(), _ptr(tok_start) if n_tok else None, _ptr(tok_end) if n_tok else None,
-                                     _ptr(tok_logp) if n_tok else None, ws.data_ptr(), wsb, _stream()), "ds2_ctc_align_f32")
-    return score, states, tok_start, tok_end, tok_logp
+    return _ctc_align("ctc_forced_align", "ds2_ctc_align_f32", x, targets, tgt_off, in_lens, tgt_lens, max_u, is_log, (variant,))
 
 
 def ctc_forced_align_tiled(x: Tensor, targets: Tensor, tgt_off: Tensor, in_lens: Tensor | None, tgt_lens: Tensor, max_u: int, is_log: bool,
@@ -1404,62 +1419,14 @@ def ctc_forced_align_tiled(x: Tensor, targets: Tensor, tgt_off: Tensor, in_lens:
     over (frames x state pairs) and spread over the GPU, one launch per anti-diagonal of tiles (contract: include/ds2hip.h,
     ds2_ctc_align_tiled_f32).  No limit on T or max_u beyond the workspace (back-pointers: B * ceil(T/8) * (max_u+1) dwords).
     tile_frames / tile_pairs: 0 = the library's default, else a positive multiple of 8 / of 64 up to 1024 (DS2LibraryError otherwise)."""
-    _chk_f32(x)
-    if x.dim() != 3 or x.stride(2) != 1:
-        raise ValueError("ctc_forced_align_tiled: x must be (B,T,C) with a contiguous class dim")
-    B, T, Cc = x.shape
-    dev = x.device
-    for name, t in (("targets", targets), ("tgt_off", tgt_off), ("tgt_lens", tgt_lens), ("in_lens", in_lens)):
-        if t is not None and (t.dtype != torch.int32 or t.device != dev or not t.is_contiguous()):
-            raise ValueError(f"ctc_forced_align_tiled: {name} must be a contiguous int32 tensor on {dev}")
-    if tgt_off.numel() != B or tgt_lens.numel() != B or (in_lens is not None and in_lens.numel() != B):
-        raise ValueError(f"ctc_forced_align_tiled: offsets / lengths do not match the batch of {B}")
-    lib = _lib.load()
-    wsb = lib.ds2_ctc_align_tiled_workspace_bytes(B, T, int(max_u), int(tile_frames), int(tile_pairs))
-    n_tok = targets.numel()
-    score = torch.empty(B, dtype=torch.float32, device=dev)
-    states = torch.empty((B, T), dtype=torch.int32, device=dev)
-    tok_start = torch.empty(n_tok, dtype=torch.int32, device=dev)
-    tok_end = torch.empty(n_tok, dtype=torch.int32, device=dev)
-    tok_logp = torch.empty(n_tok, dtype=torch.float32, device=dev)
-    ws = _ws(wsb, dev)                                   # (an illegal tile shape sizes nothing: the entry refuses it below)
-    _lib.check(lib.ds2_ctc_align_tiled_f32(x.data_ptr(), x.stride(0), x.stride(1), B, T, Cc, 1 if is_log else 0,
-                                           _ptr(targets) if n_tok else None, tgt_off.data_ptr(), _ptr(in_lens), tgt_lens.data_ptr(),
-                                           int(max_u), int(tile_frames), int(tile_pairs), score.data_ptr(), states.data_ptr(),
-                                           _ptr(tok_start) if n_tok else None, _ptr(tok_end) if n_tok else None,
-                                           _ptr(tok_logp) if n_tok else None, ws.data_ptr(), wsb, _stream()), "ds2_ctc_align_tiled_f32")
-    return score, states, tok_start, tok_end, tok_logp
-
-
-def _chk_star_args(who, x, targets, tgt_off, in_lens, tgt_lens, flags, star_penalty):
-    if x.dim() != 3 or x.stride(2) != 1:
-        raise ValueError(f"{who}: x must be (B,T,C) with a contiguous class dim")
-    B, dev = x.shape[0], x.device
-    for name, t in (("targets", targets), ("tgt_off", tgt_off), ("tgt_lens", tgt_lens), ("in_lens", in_lens), ("flags", flags)):
-        if t is not None and (t.dtype != torch.int32 or t.device != dev or not t.is_contiguous()):
-            raise ValueError(f"{who}: {name} must be a contiguous int32 tensor on {dev}")
-    if tgt_off.numel() != B or tgt_lens.numel() != B or (in_lens is not None and in_lens.numel() != B) or \
-            (flags is not None and flags.numel() != B):
-        raise ValueError(f"{who}: offsets / lengths / flags do not match the batch of {B}")
-    p = float(star_penalty)
-    if not (p <= 0.0 and math.isfinite(p)):
-        raise ValueError(f"{who}: star_penalty must be finite and <= 0, got {star_penalty}")
-    _chk_f32(x)
-    return p
+    return _ctc_align("ctc_forced_align_tiled", "ds2_ctc_align_tiled_f32", x, targets, tgt_off, in_lens, tgt_lens, max_u, is_log,
+                      (tile_frames, tile_pairs))
 
 
 def ctc_star_row(x: Tensor, in_lens: Tensor | None, is_log: bool, star_penalty: float):
     """The wildcard's emission of ctc_forced_align_star alone: g (B,T) f32 with g[b,t] = max_c e[b,t,c] + star_penalty for t < T_b and
     -inf beyond (the library leaves those frames unwritten).  One launch that reads x once (ds2_ctc_align_star_row_f32)."""
-    if x.dim() != 3 or x.stride(2) != 1:
-        raise ValueError("ctc_star_row: x must be (B,T,C) with a contiguous class dim")
-    if in_lens is not None and (in_lens.dtype != torch.int32 or in_lens.device != x.device or not in_lens.is_contiguous()
-                                or in_lens.numel() != x.shape[0]):
-        raise ValueError(f"ctc_star_row: in_lens must be a contiguous int32 tensor of {x.shape[0]} entries on {x.device}")
-    p = float(star_penalty)
-    if not (p <= 0.0 and math.isfinite(p)):
-        raise ValueError(f"ctc_star_row: star_penalty must be finite and <= 0, got {star_penalty}")
-    _chk_f32(x)
+    p = _chk_align_args("ctc_star_row", x, dict(in_lens=in_lens), star_penalty)
     B, T, Cc = x.shape
     g = torch.full((B, T), float("-inf"), dtype=torch.float32, device=x.device)
     lib = _lib.load()
@@ -1475,24 +1442,8 @@ def ctc_forced_align_star(x: Tensor, targets: Tensor, tgt_off: Tensor, in_lens: 
     per utterance, the start in the second token's states (bit 0) and the end in the last but one token's (bit 1).  The same five
     results; a skipped first / last token has the span (-1, -1) and tok_logp 0.  Two launches (the wildcard row, the lattice) on the
     current stream.  With flags None and no wildcard label: the bits of ctc_forced_align."""
-    p = _chk_star_args("ctc_forced_align_star", x, targets, tgt_off, in_lens, tgt_lens, flags, star_penalty)
-    B, T, Cc = x.shape
-    dev = x.device
-    n_tok = targets.numel()
-    score = torch.empty(B, dtype=torch.float32, device=dev)
-    states = torch.empty((B, T), dtype=torch.int32, device=dev)
-    tok_start = torch.empty(n_tok, dtype=torch.int32, device=dev)
-    tok_end = torch.empty(n_tok, dtype=torch.int32, device=dev)
-    tok_logp = torch.empty(n_tok, dtype=torch.float32, device=dev)
-    lib = _lib.load()
-    wsb = lib.ds2_ctc_align_star_workspace_bytes(B, T, int(max_u))
-    ws = _ws(max(wsb, 1), dev)
-    _lib.check(lib.ds2_ctc_align_star_f32(x.data_ptr(), x.stride(0), x.stride(1), B, T, Cc, 1 if is_log else 0,
-                                          _ptr(targets) if n_tok else None, tgt_off.data_ptr(), _ptr(in_lens), tgt_lens.data_ptr(),
-                                          int(max_u), int(variant), p, _ptr(flags), score.data_ptr(), states.data_ptr(),
-                                          _ptr(tok_start) if n_tok else None, _ptr(tok_end) if n_tok else None,
-                                          _ptr(tok_logp) if n_tok else None, ws.data_ptr(), wsb, _stream()), "ds2_ctc_align_star_f32")
-    return score, states, tok_start, tok_end, tok_logp
+    return _ctc_align("ctc_forced_align_star", "ds2_ctc_align_star_f32", x, targets, tgt_off, in_lens, tgt_lens, max_u, is_log, (variant,),
+                      star=(star_penalty, flags))
 
 
 def ctc_forced_align_star_tiled(x: Tensor, targets: Tensor, tgt_off: Tensor, in_lens: Tensor | None, tgt_lens: Tensor, max_u: int,
@@ -1500,25 +1451,8 @@ def ctc_forced_align_star_tiled(x: Tensor, targets: Tensor, tgt_off: Tensor, in_
                                 flags: Tensor | None = None):
     """ctc_forced_align_star for long recordings: the same tensors in, the same five results out and the same bits, on the tiled lattice
     of ctc_forced_align_tiled (contract: include/ds2hip.h, ds2_ctc_align_star_tiled_f32).  tile_frames / tile_pairs as there."""
-    p = _chk_star_args("ctc_forced_align_star_tiled", x, targets, tgt_off, in_lens, tgt_lens, flags, star_penalty)
-    B, T, Cc = x.shape
-    dev = x.device
-    lib = _lib.load()
-    wsb = lib.ds2_ctc_align_star_tiled_workspace_bytes(B, T, int(max_u), int(tile_frames), int(tile_pairs))
-    n_tok = targets.numel()
-    score = torch.empty(B, dtype=torch.float32, device=dev)
-    states = torch.empty((B, T), dtype=torch.int32, device=dev)
-    tok_start = torch.empty(n_tok, dtype=torch.int32, device=dev)
-    tok_end = torch.empty(n_tok, dtype=torch.int32, device=dev)
-    tok_logp = torch.empty(n_tok, dtype=torch.float32, device=dev)
-    ws = _ws(wsb, dev)                                   # (an illegal tile shape sizes nothing: the entry refuses it below)
-    _lib.check(lib.ds2_ctc_align_star_tiled_f32(x.data_ptr(), x.stride(0), x.stride(1), B, T, Cc, 1 if is_log else 0,
-                                                _ptr(targets) if n_tok else None, tgt_off.data_ptr(), _ptr(in_lens), tgt_lens.data_ptr(),
-                                                int(max_u), int(tile_frames), int(tile_pairs), p, _ptr(flags), score.data_ptr(),
-                                                states.data_ptr(), _ptr(tok_start) if n_tok else None, _ptr(tok_end) if n_tok else None,
-                                                _ptr(tok_logp) if n_tok else None, ws.data_ptr(), wsb, _stream()),
-               "ds2_ctc_align_star_tiled_f32")
-    return score, states, tok_start, tok_end, tok_logp
+    return _ctc_align("ctc_forced_align_star_tiled", "ds2_ctc_align_star_tiled_f32", x, targets, tgt_off, in_lens, tgt_lens, max_u, is_log,
+                      (tile_frames, tile_pairs), star=(star_penalty, flags))
 
 
 def ctc_beam_decode(probs: Tensor, sizes: Tensor | None = None, blank: int = 0, beam_width: int = 100, cutoff_top_n: int = 40,
@@ -1528,8 +1462,6 @@ def ctc_beam_decode(probs: Tensor, sizes: Tensor | None = None, blank: int = 0, 
     classes) the search fuses alpha * log10 LM scores + beta per scored token (ds2_ctc_beam_decode_lm_f32).  With `hotwords` (a
     decoders.hotwords.Hotwords bound to these classes) it also prefers prefixes that spell those phrases, with or without `lm`
     (ds2_ctc_beam_decode_hot_f32); the language model's candidate limit then applies without a language model too."""
-    if hotwords is not None:
-        return _ctc_beam_decode_hot(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, lm, alpha, beta, hotwords)
     _chk_f32(probs)
     if probs.dim() != 3 or probs.stride(2) != 1:
         raise ValueError("ctc_beam_decode: probs must be (B,T,C) with a contiguous class dim")
@@ -1539,80 +1471,37 @@ def ctc_beam_decode(probs: Tensor, sizes: Tensor | None = None, blank: int = 0, 
         raise ValueError(f"ctc_beam_decode: beam_width {K} outside the supported 1..{lib.ds2_ctc_beam_max_width()}")
     B, T, C = probs.shape
     dev = probs.device
-    if lm is not None:
-        if lm.C != C:
-            raise ValueError(f"ctc_beam_decode: the language model was bound to {lm.C} classes, probs have {C}")
-        grid, cap = K * (min(int(cutoff_top_n), C - 1) + 2), lib.ds2_ctc_beam_lm_max_candidates()
-        if grid > cap:
-            raise ValueError(f"ctc_beam_decode: with a language model beam_width * (min(cutoff_top_n, C - 1) + 2) = {grid} exceeds "
-                             f"the {cap} candidate slots")
-    if sizes is not None:
-        if sizes.numel() != B:
-            raise ValueError(f"sizes has {sizes.numel()} entries for a batch of {B}")
-        sizes = sizes.to(device=dev, dtype=torch.int32).contiguous().view(-1)
-    labels = torch.empty((B, K, T), dtype=torch.int32, device=dev)
-    offs = torch.empty((B, K, T), dtype=torch.int32, device=dev)
-    lens = torch.empty((B, K), dtype=torch.int32, device=dev)
-    scores = torch.empty((B, K), dtype=torch.float32, device=dev)
-    n = lib.ds2_ctc_beam_workspace_bytes(B, T, K)
-    ws = _ws(n, dev)
-    sz_ptr = sizes.data_ptr() if sizes is not None else None
-    if lm is None:
-        _lib.check(lib.ds2_ctc_beam_decode_f32(probs.data_ptr(), probs.stride(0), probs.stride(1), B, T, C, sz_ptr, int(blank), K,
-                                               int(cutoff_top_n), float(cutoff_prob), labels.data_ptr(), offs.data_ptr(), lens.data_ptr(),
-                                               scores.data_ptr(), ws.data_ptr(), n, _stream()), "ds2_ctc_beam_decode_f32")
-    else:
-        tab = lm.device_tables(dev)
-        space = lm.space if lm.space is not None else -1
-        _lib.check(lib.ds2_ctc_beam_decode_lm_f32(probs.data_ptr(), probs.stride(0), probs.stride(1), B, T, C, sz_ptr, int(blank), K,
-                                                  int(cutoff_top_n), float(cutoff_prob), tab.data_ptr(), tab.numel(), lm.order, lm.mode,
-                                                  space, float(alpha), float(beta), labels.data_ptr(), offs.data_ptr(), lens.data_ptr(),
-                                                  scores.data_ptr(), ws.data_ptr(), n, _stream()), "ds2_ctc_beam_decode_lm_f32")
-    return labels, offs, lens, scores
-
-
-def _ctc_beam_decode_hot(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, lm, alpha, beta, hotwords):
-    """ctc_beam_decode with hotwords: the full-grid kernel instance with the hotword state (ds2_ctc_beam_decode_hot_f32)"""
-    _chk_f32(probs)
-    if probs.dim() != 3 or probs.stride(2) != 1:
-        raise ValueError("ctc_beam_decode: probs must be (B,T,C) with a contiguous class dim")
-    lib = _lib.load()
-    K = int(beam_width)
-    if not 1 <= K <= lib.ds2_ctc_beam_max_width():
-        raise ValueError(f"ctc_beam_decode: beam_width {K} outside the supported 1..{lib.ds2_ctc_beam_max_width()}")
-    B, T, C = probs.shape
-    dev = probs.device
-    if hotwords.C != C:
+    if hotwords is not None and hotwords.C != C:
         raise ValueError(f"ctc_beam_decode: the hotwords were bound to {hotwords.C} classes, probs have {C}")
-    if hotwords.blank != int(blank):
+    if hotwords is not None and hotwords.blank != int(blank):
         raise ValueError(f"ctc_beam_decode: the hotwords were bound to blank {hotwords.blank}, the decode has blank {int(blank)}")
     if lm is not None and lm.C != C:
         raise ValueError(f"ctc_beam_decode: the language model was bound to {lm.C} classes, probs have {C}")
     grid, cap = K * (min(int(cutoff_top_n), C - 1) + 2), lib.ds2_ctc_beam_lm_max_candidates()
-    if grid > cap:
-        raise ValueError(f"ctc_beam_decode: with hotwords every beam is extended by every kept class, with or without a language "
-                         f"model: beam_width * (min(cutoff_top_n, C - 1) + 2) = {grid} exceeds the {cap} candidate slots")
-    if sizes is not None:
-        if sizes.numel() != B:
-            raise ValueError(f"sizes has {sizes.numel()} entries for a batch of {B}")
-        sizes = sizes.to(device=dev, dtype=torch.int32).contiguous().view(-1)
+    if (lm is not None or hotwords is not None) and grid > cap:          # (the plain search has its staircase: no full grid, no limit)
+        why = "with a language model " if hotwords is None else \
+            "with hotwords every beam is extended by every kept class, with or without a language model: "
+        raise ValueError(f"ctc_beam_decode: {why}beam_width * (min(cutoff_top_n, C - 1) + 2) = {grid} exceeds the {cap} candidate slots")
+    sizes = _sizes_i32(sizes, B, dev)
     labels = torch.empty((B, K, T), dtype=torch.int32, device=dev)
     offs = torch.empty((B, K, T), dtype=torch.int32, device=dev)
     lens = torch.empty((B, K), dtype=torch.int32, device=dev)
     scores = torch.empty((B, K), dtype=torch.float32, device=dev)
     n = lib.ds2_ctc_beam_workspace_bytes(B, T, K)
     ws = _ws(n, dev)
-    hot = hotwords.device_tables(dev)
+    search = (probs.data_ptr(), probs.stride(0), probs.stride(1), B, T, C, _ptr(sizes), int(blank), K, int(cutoff_top_n), float(cutoff_prob))
+    out = (labels.data_ptr(), offs.data_ptr(), lens.data_ptr(), scores.data_ptr(), ws.data_ptr(), n, _stream())
     tab = lm.device_tables(dev) if lm is not None else None
-    space = lm.space if lm is not None and lm.space is not None else -1
-    _lib.check(lib.ds2_ctc_beam_decode_hot_f32(probs.data_ptr(), probs.stride(0), probs.stride(1), B, T, C,
-                                               sizes.data_ptr() if sizes is not None else None, int(blank), K, int(cutoff_top_n),
-                                               float(cutoff_prob), tab.data_ptr() if tab is not None else None,
-                                               tab.numel() if tab is not None else 0, lm.order if lm is not None else 0,
-                                               lm.mode if lm is not None else 0, space, float(alpha), float(beta), hot.data_ptr(),
-                                               hotwords.packed.ctypes.data, hotwords.packed.nbytes, labels.data_ptr(), offs.data_ptr(),
-                                               lens.data_ptr(), scores.data_ptr(), ws.data_ptr(), n, _stream()),
-               "ds2_ctc_beam_decode_hot_f32")
+    lm_args = (None, 0, 0, 0, -1) if lm is None else (tab.data_ptr(), tab.numel(), lm.order, lm.mode, lm.space if lm.space is not None else -1)
+    lm_args += (float(alpha), float(beta))
+    if hotwords is not None:
+        hot = hotwords.device_tables(dev)
+        _lib.check(lib.ds2_ctc_beam_decode_hot_f32(*search, *lm_args, hot.data_ptr(), hotwords.packed.ctypes.data, hotwords.packed.nbytes, *out),
+                   "ds2_ctc_beam_decode_hot_f32")
+    elif lm is not None:
+        _lib.check(lib.ds2_ctc_beam_decode_lm_f32(*search, *lm_args, *out), "ds2_ctc_beam_decode_lm_f32")
+    else:
+        _lib.check(lib.ds2_ctc_beam_decode_f32(*search, *out), "ds2_ctc_beam_decode_f32")
     return labels, offs, lens, scores
 
 

@@ -312,5 +312,12 @@ def test_ops_wrappers_check_their_arguments():
             fn(x, i(1), i(0, 1), None, i(1, 0), 1, True, flags=i(0, 0, 0))
         with pytest.raises(ValueError, match="contiguous class dim"):
             fn(x.transpose(1, 2), i(1), i(0, 1), None, i(1, 0), 1, True)
+    for fn in (ops.ctc_forced_align, ops.ctc_forced_align_tiled, ops.ctc_forced_align_star, ops.ctc_forced_align_star_tiled):
+        with pytest.raises(ValueError, match="batch"):
+            fn(x, i(1), i(0, 1, 2), None, i(1, 0), 1, True)
+        with pytest.raises(ValueError, match="contiguous class dim"):
+            fn(x.transpose(1, 2), i(1), i(0, 1), None, i(1, 0), 1, True)
+        with pytest.raises(ValueError, match="tgt_lens must be a contiguous int32"):
+            fn(x, i(1), i(0, 1), None, torch.tensor([1, 0]), 1, True)
     with pytest.raises(ValueError, match="star_penalty"):
         ops.ctc_star_row(x, None, True, 1.0)
