@@ -25,6 +25,10 @@ struct AugNoise {
 };
 
 // ypad[b*R*hop + i] = padded waveform of utterance b (i in [0, R*hop)), zero beyond n_b + 2*half.
+// Reflect padding follows np.pad(mode="reflect") (what librosa.stft calls) for every n >= 1: the index is folded into [0, 2(n-1)) and the
+// upper half mirrored, so an utterance of n <= n_fft/2 samples is reflected as often as the pad needs.  For n > n_fft/2 one reflection
+// lands inside the signal (-j <= half <= n-1, 2(n-1)-j >= n-1-half >= 0) and the fold picks that same sample: same bits as the
+// one-reflection rule this replaced; zero padding does not pass through the fold at all.
 // MIX: the padded signal is that of the mixed waveform x[j] + gain_b * noise_seg[j], read at the already reflected index j.
 template <bool MIX>
 __global__ __launch_bounds__(256) void stft_pad_kernel(const float* __restrict__ audio, long long ld_audio, const int* __restrict__ n_samples,
@@ -37,9 +41,16 @@ __global__ __launch_bounds__(256) void stft_pad_kernel(const float* __restrict__
       const int n = n_samples[b];
       long long j = i - b * row_len - half;            // index into the un-padded waveform
       if (j >= -(long long)half && j < (long long)n + half && n > 0) {
-        if (j < 0) j = reflect ? -j : -1;
-        else if (j >= n) j = reflect ? 2LL * (n - 1) - j : -1;
-        if (j >= 0 && j < n) {
+        if (j < 0 || j >= n) {
+          if (!reflect) j = -1;
+          else {
+            const long long P = 2LL * (n - 1);         // numpy's reflect: mirror-periodic with period 2(n-1); n == 1: every index is sample 0
+            j = P > 0 ? j % P : 0;
+            if (j < 0) j += P;
+            if (j >= n) j = P - j;
+          }
+        }
+        if (j >= 0) {
           v = audio[b * ld_audio + j];
           if constexpr (MIX) {
             const float g = nz.gain[b];

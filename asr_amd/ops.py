@@ -1508,21 +1508,26 @@ def ctc_beam_decode(probs: Tensor, sizes: Tensor | None = None, blank: int = 0, 
 _BASIS_CACHE = {}
 
 
+def dft_basis_host(n_fft: int, window: str):
+    """The numpy half of `dft_basis` (no device needed): the (n_fft, 2*(n_fft/2+1)) float32 array, computed in float64 and rounded once."""
+    import numpy as np
+    from scipy.signal import get_window
+    w = get_window(window, n_fft, fftbins=True).astype(np.float64)
+    k = np.arange(n_fft)[:, None]
+    j = np.arange(n_fft // 2 + 1)[None, :]
+    ang = 2.0 * np.pi * ((k * j) % n_fft) / n_fft
+    basis = np.empty((n_fft, 2 * (n_fft // 2 + 1)))
+    basis[:, 0::2] = w[:, None] * np.cos(ang)
+    basis[:, 1::2] = -w[:, None] * np.sin(ang)
+    return basis.astype(np.float32)
+
+
 def dft_basis(n_fft: int, window: str, device) -> Tensor:
     """(n_fft, 2*(n_fft/2+1)) fp32: column 2j = w[k] cos(2 pi k j / n_fft), column 2j+1 = -w[k] sin(...); w = scipy's periodic window
     (what librosa.filters.get_window returns for a name), computed in float64 once per (n_fft, window, device)."""
     key = (n_fft, window, str(device))
     if key not in _BASIS_CACHE:
-        import numpy as np
-        from scipy.signal import get_window
-        w = get_window(window, n_fft, fftbins=True).astype(np.float64)
-        k = np.arange(n_fft)[:, None]
-        j = np.arange(n_fft // 2 + 1)[None, :]
-        ang = 2.0 * np.pi * ((k * j) % n_fft) / n_fft
-        basis = np.empty((n_fft, 2 * (n_fft // 2 + 1)))
-        basis[:, 0::2] = w[:, None] * np.cos(ang)
-        basis[:, 1::2] = -w[:, None] * np.sin(ang)
-        _BASIS_CACHE[key] = torch.from_numpy(basis.astype(np.float32)).to(device)
+        _BASIS_CACHE[key] = torch.from_numpy(dft_basis_host(n_fft, window)).to(device)
     return _BASIS_CACHE[key]
 
 

@@ -149,32 +149,103 @@ def _wave(seed, n):
     return (0.3 * np.sin(2 * np.pi * 440.0 * t) + 0.1 * det.unitvar((n,), seed)).astype(np.float32)
 
 
-@pytest.mark.parametrize("n,pad_mode", [(16000, "constant"), (16000, "reflect"), (4321, "constant"), (161, "constant")])
-def test_stft_oracle_vs_torch_and_scipy(n, pad_mode):
+def _stft_grid():
+    """The four 320 / 160 / hamming cases this test began with (their ids kept), then the front-end shape grid of
+    tests/frontend_cases.py: per shape the lengths around n_fft/2 where reflect padding folds more than once, one sample, a multiple of
+    the hop (the scipy comparison) and one short of it, and a length past a 64-frame block."""
+    import frontend_cases as F
+    out = [pytest.param(n, pad_mode, 320, 160, "hamming", id=f"{n}-{pad_mode}")
+           for n, pad_mode in [(16000, "constant"), (16000, "reflect"), (4321, "constant"), (161, "constant")]]
+    for n_fft, hop, window in F.GRID:
+        h = n_fft // 2
+        for n, pad_mode in [(h + 1, "reflect"), (h, "reflect"), (h - 1, "reflect"), (1, "reflect"), (1, "constant"), (hop - 1, "reflect"),
+                            (5 * hop, "constant"), (5 * hop - 1, "reflect"), (64 * hop, "constant"), (64 * hop, "reflect")]:
+            out.append(pytest.param(n, pad_mode, n_fft, hop, window, id=f"{n_fft}-{hop}-{window}-{n}-{pad_mode}"))
+    return out
+
+
+@pytest.mark.parametrize("n,pad_mode,n_fft,hop,window", _stft_grid())
+def test_stft_oracle_vs_torch_and_scipy(n, pad_mode, n_fft, hop, window):
     from scipy.signal import stft as sp_stft, get_window
     from oracle import stft_oracle as S
     y = _wave(3, n)
-    ref = S.stft_log_spectrogram(y, 320, 160, "hamming", pad_mode)
-    assert ref.shape == (161, 1 + n // 160)                                      # tests/test_spectrogram_dataset.py:37-46
-    win = torch.from_numpy(get_window("hamming", 320, fftbins=True))
-    D = torch.stft(torch.from_numpy(y).double(), 320, hop_length=160, win_length=320, window=win, center=True, pad_mode=pad_mode,
-                   normalized=False, onesided=True, return_complex=True)
-    assert np.allclose(np.log1p(D.abs().numpy()), ref, rtol=1e-9, atol=1e-9)
-    if pad_mode == "constant" and n % 160 == 0:
+    ref = S.stft_log_spectrogram(y, n_fft, hop, window, pad_mode)
+    assert ref.shape == (n_fft // 2 + 1, 1 + n // hop)                            # tests/test_spectrogram_dataset.py:37-46
+    win = get_window(window, n_fft, fftbins=True)
+    if pad_mode == "constant" or n > n_fft // 2:
+        D = torch.stft(torch.from_numpy(y).double(), n_fft, hop_length=hop, win_length=n_fft, window=torch.from_numpy(win), center=True,
+                       pad_mode=pad_mode, normalized=False, onesided=True, return_complex=True)
+        assert np.allclose(np.log1p(D.abs().numpy()), ref, rtol=1e-9, atol=1e-9)
+    else:
+        # torch refuses to reflect by n_fft/2 >= n samples.  librosa.stft pads with np.pad(y, n_fft // 2, mode="reflect") — this is
+        # librosa's own call — and transforms the windowed frames of the result: restated here frame by frame, independent of the oracle's loop
+        with pytest.raises(RuntimeError):
+            torch.stft(torch.from_numpy(y).double(), n_fft, hop_length=hop, win_length=n_fft, window=torch.from_numpy(win), center=True,
+                       pad_mode=pad_mode, return_complex=True)
+        yp = np.pad(y.astype(np.float64), n_fft // 2, "reflect")
+        D = np.array([np.fft.rfft(yp[t * hop: t * hop + n_fft] * win) for t in range(1 + n // hop)]).T
+        assert np.allclose(np.log1p(np.abs(D)), ref, rtol=1e-9, atol=1e-9)
+    if pad_mode == "constant" and n % hop == 0:
         # scipy: boundary="zeros" is the same centring; it scales by 1/sum(window) and appends whole padded segments
-        _, _, Z = sp_stft(y.astype(np.float64), window="hamming", nperseg=320, noverlap=160, boundary="zeros", padded=False)
-        Z = np.abs(Z) * get_window("hamming", 320, fftbins=True).sum()
+        _, _, Z = sp_stft(y.astype(np.float64), window=window, nperseg=n_fft, noverlap=n_fft - hop, boundary="zeros", padded=False)
+        Z = np.abs(Z) * win.sum()
         assert np.allclose(np.log1p(Z[:, :ref.shape[1]]), ref, rtol=1e-9, atol=1e-9)
-    norm = S.stft_log_spectrogram(y, 320, 160, "hamming", pad_mode, normalize=True)
+    import frontend_cases as F
+    if not F.has_two_values(ref):
+        assert n == 1 and pad_mode == "constant"   # one sample under zero padding: a constant spectrogram has no normalised form (0 / 0)
+        return
+    norm = S.stft_log_spectrogram(y, n_fft, hop, window, pad_mode, normalize=True)
     t = torch.from_numpy(ref).float()
     assert np.allclose(norm, ((t - t.mean()) / t.std()).numpy(), atol=2e-5)      # spectrogram_parser.py:56-60 (torch: unbiased std)
     assert abs(norm.mean()) < 1e-3 and np.isfinite(norm).all()                    # tests/test_spectrogram_dataset.py:49-58
 
 
+@pytest.mark.parametrize("n_fft", [320, 8])
+def test_reflect_index_rule_equals_np_pad(n_fft):
+    """The index rule of stft_pad_kernel (fold into [0, 2(n-1)), mirror the upper half; n == 1: sample 0), restated in numpy, against
+    np.pad(mode="reflect") for every utterance length up to just past n_fft/2, where one reflection is enough again; the rule it
+    replaced (one reflection, zero beyond) agrees from n_fft/2 + 1 on and nowhere below."""
+    import frontend_cases as F
+    half = n_fft // 2
+    for n in range(1, half + 3):
+        y = np.arange(1, n + 1, dtype=np.float64)                                  # distinct, non-zero: the value names its index
+        want = np.pad(y, half, mode="reflect")
+        j = np.arange(-half, n + half)
+        assert np.array_equal(y[F.reflect_index(j, n)], want), n
+        old = F.one_reflection_index(j, n)
+        assert np.array_equal(np.where(old >= 0, y[np.clip(old, 0, n - 1)], 0.0), want) == (n > half), n
+        assert np.array_equal(F.padded_fp32(y, half, "reflect"), want.astype(np.float32))
+        assert np.array_equal(F.padded_fp32(y, half, "constant"), np.pad(y, half).astype(np.float32))
+
+
+def test_frontend_case_table_and_teeth():
+    """tests/frontend_cases.py: the recorded e32 of every case is what the fp32 restatement gives against the fp64 oracle (host BLAS
+    summation order may move it: within a factor 2, and 4 * e32 below the 2e-5 floor either way), the restatement itself meets every
+    tolerance, and each mutation — frames shifted by one sample, a symmetric window, the one-reflection pad rule, biased variance — misses
+    the tolerance of at least one case."""
+    import frontend_cases as F
+    cases = list(F.cases())
+    assert {c[:4] for c in cases} == set(F.E32)
+    for c in cases:
+        e = F.measure_e32(*c)
+        e32, tol = F.E32[c[:4]]
+        assert 0.0 < e <= 2.0 * e32 and 4.0 * e < 2e-5, (c[:4], e)
+        assert F.tolerance(*c[:4]) == tol == max(2e-5, 4.0 * e32)
+        for normalize in (False, True):
+            assert not F.misses(*c, normalize), (c[:4], normalize)
+    for mutation, normalize, pads in ((dict(shift=1), False, ("constant", "reflect")), (dict(fftbins=False), False, ("constant", "reflect")),
+                                      (dict(pad_rule=F.one_reflection_index), False, ("reflect",)), (dict(ddof=0), True, ("constant", "reflect"))):
+        hit = [c[:4] for c in cases if c[3] in pads and F.misses(*c, normalize, **mutation)]
+        assert hit, mutation
+    assert not F.misses(*cases[0], False, ddof=0)                                  # (biased variance cannot show un-normalised)
+
+
 def test_host_dataset_stft_matches_oracle():
     from asr_amd.data import _stft_spectrogram
     from oracle import stft_oracle as S
-    y = _wave(5, 12345)
-    for pad_mode in ("constant", "reflect"):
-        got = _stft_spectrogram(y, 16000, 0.02, 0.01, "hamming", pad_mode)
-        assert got.dtype == np.float32 and np.allclose(got, S.stft_log_spectrogram(y, 320, 160, "hamming", pad_mode), atol=2e-5)
+    for (sr, size, stride), n_fft, hop in (((16000, 0.02, 0.01), 320, 160), ((8000, 0.025, 0.01), 200, 80)):
+        for y, pad_modes in ((_wave(5, 12345), ("constant", "reflect")), (_wave(6, 50), ("reflect",))):   # 50 samples: reflected more than once
+            for pad_mode in pad_modes:
+                got = _stft_spectrogram(y, sr, size, stride, "hamming", pad_mode)
+                assert got.dtype == np.float32 and got.shape == (n_fft // 2 + 1, 1 + len(y) // hop)
+                assert np.allclose(got, S.stft_log_spectrogram(y, n_fft, hop, "hamming", pad_mode), atol=2e-5)
