@@ -66,24 +66,37 @@ __global__ __launch_bounds__(256) void ctc_lse_kernel(const float* __restrict__ 
 __device__ __forceinline__ float star_end_nll(float l1, float l2, float l3, float l4) { return -lse2(lse2(l1, l2), lse2(l3, l4)); }
 __device__ __forceinline__ float star_cell(float a0, float a1, float a2, float lp, bool star);   // (below, next to lse3_sel)
 
+// MW = true instances of the two lattice kernels are the n-best lattices of ds2_ctc_mwer_f32 (ctc_mwer.h, contract in include/ds2hip.h):
+// blockIdx.x is the lattice n of B * K, which reads the logits, lse and in_lens of utterance n / K; labels, lengths, nll and the ab rows
+// are indexed by n, the label offsets are 64-bit (off64; tgt_off is unused), and a slot that is not valid (valid, NULL = all valid),
+// whose length lies outside [0, (Smax - 1) / 2] or whose labels leave [1, C - 1] gets nll = +inf before anything is read through it.
+// MW = false: none of it is compiled, n = b and the kernels are the ones they were.
 // blockIdx.x = utterance, blockIdx.y = 0: alpha (forward in t), 1: beta (backward in t).
-// ab layout: [2][B][T][Smax]
-template <bool STAR>
+// ab layout: [2][B][T][Smax]  (MW: [2][B * K][T][Smax])
+template <bool STAR, bool MW = false>
 __global__ __launch_bounds__(1024) void ctc_lattice_kernel(const float* __restrict__ logits, int ld, int T, int Bn, int C,
                                                            const int* __restrict__ targets, const int* __restrict__ tgt_off,
                                                            const int* __restrict__ in_lens, const int* __restrict__ tgt_lens,
                                                            const float* __restrict__ lse, float* __restrict__ ab, int Smax,
-                                                           float* __restrict__ nll, float star_pen, const int* __restrict__ flags) {
+                                                           float* __restrict__ nll, float star_pen, const int* __restrict__ flags,
+                                                           int K, const long long* __restrict__ off64, const int* __restrict__ valid) {
   extern __shared__ __attribute__((aligned(16))) float smem[];  // [2][S] rows
-  const int b = blockIdx.x, dirn = blockIdx.y;
-  const int Tb = min(in_lens[b], T), U = tgt_lens[b];
+  const int n = blockIdx.x, dirn = blockIdx.y;                  // n: the lattice, b: the utterance whose frames it reads
+  const int b = MW ? n / K : n;
+  const int Tb = min(in_lens[b], T), U = tgt_lens[n];
   const int S = 2 * U + 1;
-  float* out = ab + (((long long)dirn * Bn + b) * T) * Smax;
+  float* out = ab + (((long long)dirn * (MW ? Bn * K : Bn) + n) * T) * Smax;
+  if constexpr (MW) {
+    if ((valid && !valid[n]) || U < 0 || S > Smax) {            // uniform
+      if (dirn == 0 && threadIdx.x == 0) nll[n] = INFINITY;
+      return;
+    }
+  }
   if (Tb <= 0) {
-    if (dirn == 0 && threadIdx.x == 0) nll[b] = (U == 0) ? 0.f : INFINITY;
+    if (dirn == 0 && threadIdx.x == 0) nll[n] = (U == 0) ? 0.f : INFINITY;
     return;
   }
-  const int* lab = targets + tgt_off[b];
+  const int* lab = MW ? targets + off64[n] : targets + tgt_off[n];
   float* row0 = smem;
   float* row1 = smem + Smax;
   const int nthr = blockDim.x;
@@ -92,12 +105,20 @@ __global__ __launch_bounds__(1024) void ctc_lattice_kernel(const float* __restri
     int bad = 0;
     for (int u = threadIdx.x; u < U; u += nthr) bad |= (lab[u] < 1 || lab[u] > C);
     if (__syncthreads_or(bad)) {                              // uniform: the utterance is infeasible, its lattice stays unwritten
-      if (dirn == 0 && threadIdx.x == 0) nll[b] = INFINITY;
+      if (dirn == 0 && threadIdx.x == 0) nll[n] = INFINITY;
       return;
     }
     const int f = flags ? flags[b] : 0;
     nfree0 = (f & 1) ? 4 : 2;
     nfree1 = (f & 2) ? 4 : 2;
+  }
+  if constexpr (MW) {
+    int bad = 0;
+    for (int u = threadIdx.x; u < U; u += nthr) bad |= (lab[u] < 1 || lab[u] >= C);
+    if (__syncthreads_or(bad)) {                              // uniform
+      if (dirn == 0 && threadIdx.x == 0) nll[n] = INFINITY;
+      return;
+    }
   }
   // this thread owns states s = tid, tid + nthr, ... (normally exactly one)
   // generic loop for very long targets; the common case S <= blockDim.x runs one iteration.
@@ -215,8 +236,8 @@ __global__ __launch_bounds__(1024) void ctc_lattice_kernel(const float* __restri
   if (dirn == 0 && threadIdx.x == 0) {
     const float l1 = prev[S - 1];
     const float l2 = (S >= 2) ? prev[S - 2] : NEG_INF;
-    if (STAR && nfree1 == 4) nll[b] = star_end_nll(l1, l2, (S >= 3) ? prev[S - 3] : NEG_INF, (S >= 4) ? prev[S - 4] : NEG_INF);
-    else nll[b] = -lse2(l1, l2);
+    if (STAR && nfree1 == 4) nll[n] = star_end_nll(l1, l2, (S >= 3) ? prev[S - 3] : NEG_INF, (S >= 4) ? prev[S - 4] : NEG_INF);
+    else nll[n] = -lse2(l1, l2);
   }
 }
 
@@ -263,8 +284,9 @@ __device__ __forceinline__ float star_cell(float a0, float a1, float a2, float l
 
 template <int DIRN, bool STAR>
 __device__ __forceinline__ void ctc_lattice_wave_body(const float* __restrict__ logits, int ld, int T, int Bn, int C,
-                                                      const int* __restrict__ lab, int b, int Tb, int U, const float* __restrict__ lse,
+                                                      const int* __restrict__ lab, int b, int n, int Tb, int U, const float* __restrict__ lse,
                                                       float* __restrict__ out, int Smax, float* __restrict__ nll, float star_pen, int flag) {
+  // b: the utterance (logits, lse); n: the lattice (nll[n]; n = b but for the MW instances); out: this lattice's rows
   const int S = 2 * U + 1;
   const int l = threadIdx.x;
   const bool actE = 2 * l < S, actO = 2 * l + 1 < S;
@@ -374,42 +396,58 @@ __device__ __forceinline__ void ctc_lattice_wave_body(const float* __restrict__ 
       const float l3 = __shfl(E, U >= 1 ? U - 1 : 0, 64);                       // state S - 3
       const float l4 = __shfl(O, U >= 2 ? U - 2 : 0, 64);                       // state S - 4
       if (l == 0) {
-        if (flag & 2) nll[b] = star_end_nll(l1, (S >= 2) ? l2 : NEG_INF, (S >= 3) ? l3 : NEG_INF, (S >= 4) ? l4 : NEG_INF);
-        else nll[b] = -lse2(l1, (S >= 2) ? l2 : NEG_INF);
+        if (flag & 2) nll[n] = star_end_nll(l1, (S >= 2) ? l2 : NEG_INF, (S >= 3) ? l3 : NEG_INF, (S >= 4) ? l4 : NEG_INF);
+        else nll[n] = -lse2(l1, (S >= 2) ? l2 : NEG_INF);
       }
     } else {
-      if (l == 0) nll[b] = -lse2(l1, (S >= 2) ? l2 : NEG_INF);
+      if (l == 0) nll[n] = -lse2(l1, (S >= 2) ? l2 : NEG_INF);
     }
   }
 }
 
 // blockIdx.x = utterance, blockIdx.y = direction; 64 threads.  Needs 2 * tgt_lens[b] + 1 <= 128 for every b (the launcher checks Smax).
-template <bool STAR>
+template <bool STAR, bool MW = false>
 __global__ __launch_bounds__(64) void ctc_lattice_wave_kernel(const float* __restrict__ logits, int ld, int T, int Bn, int C,
                                                               const int* __restrict__ targets, const int* __restrict__ tgt_off,
                                                               const int* __restrict__ in_lens, const int* __restrict__ tgt_lens,
                                                               const float* __restrict__ lse, float* __restrict__ ab, int Smax,
-                                                              float* __restrict__ nll, float star_pen, const int* __restrict__ flags) {
-  const int b = blockIdx.x, dirn = blockIdx.y;
-  const int Tb = min(in_lens[b], T), U = tgt_lens[b];
-  float* out = ab + (((long long)dirn * Bn + b) * T) * Smax;
+                                                              float* __restrict__ nll, float star_pen, const int* __restrict__ flags,
+                                                              int K, const long long* __restrict__ off64, const int* __restrict__ valid) {
+  const int n = blockIdx.x, dirn = blockIdx.y;                // n: the lattice, b: the utterance whose frames it reads (see ctc_lattice_kernel)
+  const int b = MW ? n / K : n;
+  const int Tb = min(in_lens[b], T), U = tgt_lens[n];
+  float* out = ab + (((long long)dirn * (MW ? Bn * K : Bn) + n) * T) * Smax;
+  if constexpr (MW) {
+    if ((valid && !valid[n]) || U < 0 || 2 * U + 1 > Smax) {  // uniform (Smax <= 128 here: U <= 63)
+      if (dirn == 0 && threadIdx.x == 0) nll[n] = INFINITY;
+      return;
+    }
+  }
   if (Tb <= 0) {
-    if (dirn == 0 && threadIdx.x == 0) nll[b] = (U == 0) ? 0.f : INFINITY;
+    if (dirn == 0 && threadIdx.x == 0) nll[n] = (U == 0) ? 0.f : INFINITY;
     return;
   }
-  const int* lab = targets + tgt_off[b];
+  const int* lab = MW ? targets + off64[n] : targets + tgt_off[n];
   int flag = 0;
   if constexpr (STAR) {
     const int l = threadIdx.x;
     const bool bad = l < U && (lab[l] < 1 || lab[l] > C);     // one label per lane (U <= 63)
     if (__ballot(bad) != 0) {                                 // uniform: the utterance is infeasible, its lattice stays unwritten
-      if (dirn == 0 && l == 0) nll[b] = INFINITY;
+      if (dirn == 0 && l == 0) nll[n] = INFINITY;
       return;
     }
     flag = flags ? flags[b] : 0;
   }
-  if (dirn == 0) ctc_lattice_wave_body<0, STAR>(logits, ld, T, Bn, C, lab, b, Tb, U, lse, out, Smax, nll, star_pen, flag);
-  else ctc_lattice_wave_body<1, STAR>(logits, ld, T, Bn, C, lab, b, Tb, U, lse, out, Smax, nll, star_pen, flag);
+  if constexpr (MW) {
+    const int l = threadIdx.x;
+    const bool bad = l < U && (lab[l] < 1 || lab[l] >= C);    // one label per lane
+    if (__ballot(bad) != 0) {                                 // uniform
+      if (dirn == 0 && l == 0) nll[n] = INFINITY;
+      return;
+    }
+  }
+  if (dirn == 0) ctc_lattice_wave_body<0, STAR>(logits, ld, T, Bn, C, lab, b, n, Tb, U, lse, out, Smax, nll, star_pen, flag);
+  else ctc_lattice_wave_body<1, STAR>(logits, ld, T, Bn, C, lab, b, n, Tb, U, lse, out, Smax, nll, star_pen, flag);
 }
 
 // grid = (ceil(T / TCH), B); block = 128 threads; dynamic LDS: q[C] + val[S] + nxt[U] (ints) + lab[U]
@@ -573,13 +611,15 @@ int ctc_loss_launch(const float* logits, int ld, int T, int B, int C, const int*
   DS2_LAUNCH_CHECK("ctc_lse_kernel");
   if (wave) {
     hipLaunchKernelGGL(ctc_lattice_wave_kernel<STAR>, dim3(B, 2), dim3(64), 0, s, logits, ld, T, B, C, targets_dev, tgt_off_dev, in_lens_dev,
-                       tgt_lens_dev, (const float*)lse, ab, Smax, nll_dev, star_pen, flags_dev);
+                       tgt_lens_dev, (const float*)lse, ab, Smax, nll_dev, star_pen, flags_dev, 1, (const long long*)nullptr,
+                       (const int*)nullptr);
     DS2_LAUNCH_CHECK("ctc_lattice_wave_kernel");
   } else {
     int threads = ceil_div(Smax, 64) * 64;
     if (threads > 1024) threads = 1024;
     hipLaunchKernelGGL(ctc_lattice_kernel<STAR>, dim3(B, 2), dim3(threads), lds, s, logits, ld, T, B, C, targets_dev, tgt_off_dev,
-                       in_lens_dev, tgt_lens_dev, (const float*)lse, ab, Smax, nll_dev, star_pen, flags_dev);
+                       in_lens_dev, tgt_lens_dev, (const float*)lse, ab, Smax, nll_dev, star_pen, flags_dev, 1, (const long long*)nullptr,
+                       (const int*)nullptr);
     DS2_LAUNCH_CHECK("ctc_lattice_kernel");
   }
   if (grad) {
@@ -638,3 +678,6 @@ extern "C" int ds2_ctc_loss_f32(const float* logits, int ld, int T, int B, int C
 #include "ctc_align_tiled.h"
 // ... and the wildcard / free-ends entries (ds2_ctc_align_star_*), which instantiate both with STAR = true behind a pre-pass
 #include "ctc_align_star.h"
+// Minimum-error-rate training on an n-best list (ds2_ctc_mwer_*): the MW = true instances of the two lattice kernels above, a weights
+// launch and a gradient kernel that folds the K occupancies of an utterance into one row
+#include "ctc_mwer.h"

@@ -9,6 +9,8 @@ produces for log-softmaxed input.
 
 Imperfect transcripts (`CTCLoss(star=..., star_penalty=..., free_start=..., free_end=...)`): the wildcard loss of
 ds2_ctc_star_loss_f32 (contract in include/ds2hip.h), the vocabulary of `CTCAligner.align`'s options over log-sum-exp.
+
+`MWERLoss` — minimum-error-rate training on the n-best list of a `BeamCTCDecoder` (ds2_ctc_mwer_f32, contract in include/ds2hip.h).
 """
 from __future__ import annotations
 
@@ -175,3 +177,144 @@ class CTCLoss(torch.nn.Module):
             return nll.sum()
         tl = torch.as_tensor(target_lengths).to(nll.device).clamp_min(1).to(nll.dtype)
         return (nll / tl).mean()
+
+
+class _MWERFunction(torch.autograd.Function):
+    """_CTCFunction on MWERLoss.run: the gradient is stored in forward and scaled per utterance in backward."""
+
+    @staticmethod
+    def forward(ctx, acts, crit, targets, input_lengths, target_lengths, want_grad):
+        T, B, C = acts.shape
+        dev = acts.device
+        il = torch.as_tensor(input_lengths).to(torch.int32).to(dev)
+        tg, off, tl, max_u = _prep_targets(targets, target_lengths, dev)
+        x = acts.float()
+        if not (x.stride(2) == 1 and x.stride(0) == B * x.stride(1)):
+            x = x.contiguous()
+        value, grad = crit.run(x, tg, off, il, tl, max_u, 1.0, want_grad, targets_host=(targets, target_lengths))
+        ctx.grad = grad
+        return value
+
+    @staticmethod
+    def backward(ctx, g):
+        grad = ctx.grad
+        ctx.grad = None
+        if grad is None:
+            raise RuntimeError("MWER gradient was not requested in forward")
+        return grad * g.view(1, -1, 1), None, None, None, None, None
+
+
+class MWERLoss(torch.nn.Module):
+    """Minimum-error-rate training: the expected risk of the decoder's n-best list under the model, per utterance
+        sum_k p_k R_k,   p_k = p_ctc(y_k | x) / sum_j p_ctc(y_j | x)   over the `nbest` best beams of `decoder`,
+    plus ctc_weight * nll of the reference (the usual interpolation that keeps the model from drifting off the transcripts).
+    Called like CTCLoss: forward(log_probs_or_logits (T,B,C), targets, input_lengths, target_lengths).  Without gradient
+    tracking it runs: ops.softmax_rows, ops.ctc_beam_decode with the decoder's own settings (its language model and hotwords
+    included), the risks, then — when ctc_weight > 0 — ops.ctc_loss on the reference, which writes ctc_weight * (softmax - occ), and
+    ops.ctc_mwer, which adds its gradient to that.
+
+    The posteriors p_k come from the CTC likelihood RECOMPUTED for each hypothesis (ds2_ctc_mwer_f32's lattices), not from the
+    decoder's scores: those hold language-model and hotword terms and are no function of the logits alone.  The search only chooses
+    the list.  A slot is valid when its score is > -inf (the beam search fills fewer slots than beam_width on short utterances).
+
+      nbest         slots kept, <= decoder.beam_width
+      risk="label"  Levenshtein distance between the hypothesis' and the reference's label ids, spaces included (ops.edit_distance
+                    on the device: the call makes no host synchronisation)
+      risk="word"   Decoder.wer's word distance, packed by decoders.pack_scoring on the HOST: the hypotheses are copied to the host
+                    first, one synchronisation per call (DeepSpeechTrainer.step refuses it for that reason)
+      max_hyp_len   bound on a hypothesis' length, None = T (a beam search emits nothing longer than T_b).  It sizes the
+                    workspace: 8 B nbest T (2 max_hyp_len + 1) bytes, about 1 GB at B = 64, nbest = 4, T = 501; a hypothesis longer
+                    than the bound counts as infeasible.
+      reduction     "sum" (default), "none" or "mean" (over the batch)
+    `last_nbest` = (labels (B,nbest,T), lens, valid, risk, post (B,nbest)) of the last call, on the GPU.
+    Whether this lowers the WER of a real corpus, and which nbest / ctc_weight serve it, is not measured here."""
+
+    def __init__(self, decoder, nbest: int = 4, ctc_weight: float = 0.01, risk: str = "label", max_hyp_len=None, reduction: str = "sum"):
+        super().__init__()
+        if risk not in ("label", "word"):
+            raise ValueError(f"MWERLoss: risk must be 'label' or 'word', got {risk!r}")
+        if reduction not in ("none", "mean", "sum"):
+            raise ValueError(reduction)
+        if not hasattr(decoder, "beam_width"):
+            raise TypeError("MWERLoss needs a BeamCTCDecoder: the n-best list is its beam")
+        if not 1 <= int(nbest) <= int(decoder.beam_width):
+            raise ValueError(f"MWERLoss: nbest = {nbest} must lie in 1 .. decoder.beam_width = {decoder.beam_width}")
+        if decoder.blank_index != 0:
+            raise ValueError("the HIP CTC kernels fix blank = 0")
+        cw = float(ctc_weight)
+        if not (cw >= 0.0 and math.isfinite(cw)):
+            raise ValueError(f"MWERLoss: ctc_weight must be finite and >= 0, got {ctc_weight}")
+        if max_hyp_len is not None and int(max_hyp_len) < 0:
+            raise ValueError(f"MWERLoss: max_hyp_len must be >= 0, got {max_hyp_len}")
+        self.decoder, self.nbest, self.ctc_weight, self.risk = decoder, int(nbest), cw, risk
+        self.max_hyp_len = None if max_hyp_len is None else int(max_hyp_len)
+        self.reduction = reduction
+        self.last_nbest = None
+
+    def _word_risk(self, labels, lens, targets_host, B, K, dev):
+        """Decoder.wer's distance of every kept beam to its reference -> (B, K) fp32 on dev.  Copies the beams to the host."""
+        from .decoders import pack_scoring
+        if targets_host is None:
+            raise ValueError("MWERLoss(risk='word') needs the host targets")
+        t_h, off_h, tl_h, _ = _prep_targets_host(*targets_host)
+        dec = self.decoder
+        lab_h, len_h = labels[:, :K].cpu(), lens.cpu()                       # the synchronisation
+        refs = ["".join(dec._char(int(i)) for i in t_h[int(off_h[b]):int(off_h[b]) + int(tl_h[b])].tolist()) for b in range(B)]
+        hyps = dec.convert_to_strings(lab_h, len_h)
+        seq, a_off, a_len, b_off, b_len, _, _ = pack_scoring([h for b in range(B) for h in hyps[b]], [refs[b] for b in range(B) for _ in range(K)])
+        P = B * K                                                            # the first P problems are the word problems
+        seq_dev = torch.from_numpy(seq).to(dev) if seq.size else torch.zeros(1, dtype=torch.int32, device=dev)
+        dist = ops.edit_distance(seq_dev, torch.from_numpy(a_off[:P]), torch.from_numpy(a_len[:P]), torch.from_numpy(b_off[:P]),
+                                 torch.from_numpy(b_len[:P]))
+        return dist.to(torch.float32).view(B, K)
+
+    def run(self, x, tg, off, il, tl, max_u, scale, want_grad, targets_host=None):
+        """The device half of a call (also DeepSpeechTrainer.step's): x (T,B,C) fp32 logits or log-probabilities as ops.ctc_loss
+        takes them; tg / off / il / tl the flat targets, their offsets, the input and the target lengths as int32 GPU tensors;
+        max_u the longest target.  Returns (value (B) = loss_b + ctc_weight * nll_ref_b, gradient of sum_b value_b times `scale`
+        or None).  With risk="label" nothing here waits for the device."""
+        T, B, C = x.shape
+        dev = x.device
+        dec, K, Kw = self.decoder, self.nbest, int(self.decoder.beam_width)
+        if K > Kw:
+            raise ValueError(f"MWERLoss: nbest = {K} exceeds decoder.beam_width = {Kw}")
+        rows = x.view(T * B, C) if x.is_contiguous() else x.as_strided((T * B, C), (x.stride(1), 1))
+        probs = ops.softmax_rows(rows).view(T, B, C)
+        # one int32 buffer: the beams' labels (B, Kw, T) in front, the flat references behind, so that every offset is affine in
+        # (b, k) and one edit-distance launch sees both sides
+        n_hyp = B * Kw * T
+        if n_hyp + tg.numel() >= 2 ** 31:
+            raise ValueError("MWERLoss: B * beam_width * T too large")
+        buf = torch.empty(n_hyp + tg.numel(), dtype=torch.int32, device=dev)
+        buf[n_hyp:].copy_(tg)
+        labels = buf[:n_hyp].view(B, Kw, T)
+        _, _, lens, scores = ops.ctc_beam_decode(probs.transpose(0, 1), il, dec.blank_index, Kw, dec.cutoff_top_n, dec.cutoff_prob, dec.lm,
+                                                 dec.alpha, dec.beta, dec.hotwords, labels_out=labels)
+        hyp_lens = lens[:, :K].contiguous()
+        valid = (scores[:, :K] > -math.inf).to(torch.int32).contiguous()
+        slot = torch.arange(B * K, device=dev, dtype=torch.int64)
+        hyp_off = ((torch.div(slot, K, rounding_mode="floor") * Kw + slot % K) * T).view(B, K)
+        if self.risk == "label":
+            ref_off = (off.to(torch.int64) + n_hyp).repeat_interleave(K)
+            ref_len = tl.repeat_interleave(K)
+            dist = ops.edit_distance(buf, hyp_off.view(-1), hyp_lens.view(-1), ref_off, ref_len, max_len=max(T, int(max_u)))
+            risk = dist.to(torch.float32).view(B, K)
+        else:
+            risk = self._word_risk(labels, hyp_lens, targets_host, B, K, dev)
+        grad, nll_ref = None, None
+        if self.ctc_weight > 0:
+            nll_ref, grad = ops.ctc_loss(x, tg, off, il, tl, max_u, self.ctc_weight * scale, want_grad=want_grad)
+        mh = T if self.max_hyp_len is None else self.max_hyp_len
+        loss, _, post, grad = ops.ctc_mwer(x, buf, hyp_off, hyp_lens, valid, il, mh, risk, scale, want_grad=want_grad, grad=grad)
+        self.last_nbest = (labels[:, :K], hyp_lens, valid, risk, post)
+        value = loss if nll_ref is None else torch.add(loss, nll_ref, alpha=self.ctc_weight)
+        return value, grad
+
+    def forward(self, log_probs, targets, input_lengths, target_lengths):
+        if not log_probs.is_cuda:
+            raise _lib.DS2LibraryError("asr_amd.MWERLoss needs GPU input (no CPU fallback; the CPU oracle is test-only)")
+        want_grad = torch.is_grad_enabled() and log_probs.requires_grad
+        value = _MWERFunction.apply(log_probs, self, targets, input_lengths, target_lengths, want_grad)
+        if self.reduction == "none":
+            return value
+        return value.sum() if self.reduction == "sum" else value.mean()

@@ -1267,6 +1267,45 @@ def ctc_star_loss(logits: Tensor, targets_dev: Tensor, tgt_off_dev: Tensor, in_l
                      lattice, return_ab, star=(float(star_penalty), _ptr(flags)))
 
 
+def ctc_mwer(logits: Tensor, hyps_dev: Tensor, hyp_off_dev: Tensor, hyp_lens_dev: Tensor, hyp_valid_dev: Optional[Tensor], in_lens_dev: Tensor,
+             max_hyp_len: int, risk_dev: Tensor, grad_scale: float = 1.0, want_grad: bool = True, grad: Optional[Tensor] = None,
+             lattice: int = 0):
+    """Minimum-error-rate loss on an n-best list (contract: include/ds2hip.h, ds2_ctc_mwer_f32).  logits (T,B,C) as ctc_loss takes
+    them; hyps_dev flat int32 labels, hyp_off_dev (B,K) int64 offsets into it, hyp_lens_dev (B,K) int32, hyp_valid_dev (B,K) int32 or
+    None = all valid, risk_dev (B,K) fp32, all on the GPU; max_hyp_len bounds every hypothesis and sizes the workspace (8 B K T
+    (2 max_hyp_len + 1) bytes).  Returns (loss (B), nll_hyp (B,K), post (B,K), grad (T,B,C) or None).  With `grad` given (fp32,
+    contiguous, (T,B,C)) the gradient is ADDED to it (accumulate = 1) and it is the tensor returned; otherwise want_grad decides."""
+    _chk_f32(logits, risk_dev, grad)
+    lib = _lib.load()
+    T, B, Cc = logits.shape
+    dev = logits.device
+    assert logits.stride(2) == 1 and logits.stride(0) == B * logits.stride(1)
+    if hyp_off_dev.dim() != 2 or hyp_off_dev.shape[0] != B:
+        raise ValueError(f"ctc_mwer: hyp_off_dev must be (B, K) with B = {B}, got {tuple(hyp_off_dev.shape)}")
+    K = hyp_off_dev.shape[1]
+    for name, t, dt in (("hyps_dev", hyps_dev, torch.int32), ("hyp_off_dev", hyp_off_dev, torch.int64), ("hyp_lens_dev", hyp_lens_dev, torch.int32),
+                        ("hyp_valid_dev", hyp_valid_dev, torch.int32), ("in_lens_dev", in_lens_dev, torch.int32), ("risk_dev", risk_dev, torch.float32)):
+        if t is not None and (t.dtype != dt or t.device != dev or not t.is_contiguous()):
+            raise ValueError(f"ctc_mwer: {name} must be a contiguous {dt} tensor on {dev}")
+    if any(t is not None and t.numel() != B * K for t in (hyp_lens_dev, hyp_valid_dev, risk_dev)) or in_lens_dev.numel() != B:
+        raise ValueError(f"ctc_mwer: lengths / validity / risks do not match (B, K) = ({B}, {K})")
+    if grad is not None and (grad.shape != (T, B, Cc) or not grad.is_contiguous() or grad.device != dev):
+        raise ValueError("ctc_mwer: grad must be a contiguous (T, B, C) tensor on the logits' device")
+    accumulate = grad is not None
+    if grad is None and want_grad:
+        grad = torch.empty(T, B, Cc, dtype=torch.float32, device=dev)
+    loss = torch.empty(B, dtype=torch.float32, device=dev)
+    nll_hyp = torch.empty(B, K, dtype=torch.float32, device=dev)
+    post = torch.empty(B, K, dtype=torch.float32, device=dev)
+    wsb = lib.ds2_ctc_mwer_workspace_bytes(T, B, K, int(max_hyp_len))
+    ws = _ws(wsb, dev)
+    _lib.check(lib.ds2_ctc_mwer_f32(logits.data_ptr(), logits.stride(1), T, B, Cc, K, hyps_dev.data_ptr(), hyp_off_dev.data_ptr(),
+                                    hyp_lens_dev.data_ptr(), _ptr(hyp_valid_dev), in_lens_dev.data_ptr(), int(max_hyp_len), risk_dev.data_ptr(),
+                                    loss.data_ptr(), nll_hyp.data_ptr(), post.data_ptr(), _ptr(grad), Cc, float(grad_scale), int(accumulate),
+                                    int(lattice), ws.data_ptr(), wsb, _stream()), "ds2_ctc_mwer_f32")
+    return loss, nll_hyp, post, grad
+
+
 def ctc_batch_mean(nll: Tensor) -> Tensor:
     """(1,) fp32 = nll.sum() / B, on the device in a fixed order (trainers/deepspeech_trainer.py:110-112)."""
     _chk_f32(nll)
@@ -1456,12 +1495,14 @@ def ctc_forced_align_star_tiled(x: Tensor, targets: Tensor, tgt_off: Tensor, in_
 
 
 def ctc_beam_decode(probs: Tensor, sizes: Tensor | None = None, blank: int = 0, beam_width: int = 100, cutoff_top_n: int = 40,
-                    cutoff_prob: float = 1.0, lm=None, alpha: float = 0.0, beta: float = 0.0, hotwords=None):
+                    cutoff_prob: float = 1.0, lm=None, alpha: float = 0.0, beta: float = 0.0, hotwords=None, labels_out: Tensor | None = None):
     """CTC prefix beam search of probs (B,T,C) fp32 on the GPU -> (labels (B,K,T) i32, offsets (B,K,T) i32, lengths (B,K) i32,
     scores (B,K) fp32), all on the GPU, best beam first (contract: include/ds2hip.h).  With `lm` (a decoders.lm.NgramLM bound to these
     classes) the search fuses alpha * log10 LM scores + beta per scored token (ds2_ctc_beam_decode_lm_f32).  With `hotwords` (a
     decoders.hotwords.Hotwords bound to these classes) it also prefers prefixes that spell those phrases, with or without `lm`
-    (ds2_ctc_beam_decode_hot_f32); the language model's candidate limit then applies without a language model too."""
+    (ds2_ctc_beam_decode_hot_f32); the language model's candidate limit then applies without a language model too.
+    labels_out: a contiguous (B,K,T) int32 GPU tensor to receive the labels instead of a fresh one (MWERLoss passes the front of the
+    buffer that also holds the references, so that one edit-distance launch sees both)."""
     _chk_f32(probs)
     if probs.dim() != 3 or probs.stride(2) != 1:
         raise ValueError("ctc_beam_decode: probs must be (B,T,C) with a contiguous class dim")
@@ -1483,7 +1524,10 @@ def ctc_beam_decode(probs: Tensor, sizes: Tensor | None = None, blank: int = 0, 
             "with hotwords every beam is extended by every kept class, with or without a language model: "
         raise ValueError(f"ctc_beam_decode: {why}beam_width * (min(cutoff_top_n, C - 1) + 2) = {grid} exceeds the {cap} candidate slots")
     sizes = _sizes_i32(sizes, B, dev)
-    labels = torch.empty((B, K, T), dtype=torch.int32, device=dev)
+    if labels_out is not None and (labels_out.shape != (B, K, T) or labels_out.dtype != torch.int32 or labels_out.device != dev
+                                   or not labels_out.is_contiguous()):
+        raise ValueError(f"ctc_beam_decode: labels_out must be a contiguous ({B}, {K}, {T}) int32 tensor on {dev}")
+    labels = labels_out if labels_out is not None else torch.empty((B, K, T), dtype=torch.int32, device=dev)
     offs = torch.empty((B, K, T), dtype=torch.int32, device=dev)
     lens = torch.empty((B, K), dtype=torch.int32, device=dev)
     scores = torch.empty((B, K), dtype=torch.float32, device=dev)

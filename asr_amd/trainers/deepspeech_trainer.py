@@ -16,7 +16,7 @@ import torch
 import torch.distributed as dist
 
 from .. import engine, ops
-from ..ctc import CTCLoss, _check_star_penalty, _prep_targets, _prep_targets_host
+from ..ctc import CTCLoss, MWERLoss, _check_star_penalty, _prep_targets, _prep_targets_host
 from ..device import autocast, make_grad_scaler, resolve_device
 from ..functional import check_loss
 from ..optim import FusedAdamW
@@ -145,9 +145,9 @@ class DeepSpeechTrainer:
             out, output_sizes = self._model.forward(inputs, input_sizes)
             out = out.transpose(0, 1)                                        # TxNxC
             float_out = out.float()
-            if not isinstance(self.criterion, CTCLoss):
+            if not isinstance(self.criterion, (CTCLoss, MWERLoss)):
                 float_out = float_out.log_softmax(2)    # torch criterion: keep the reference's op sequence
-            # (asr_amd.CTCLoss fuses the row log-softmax into the CTC kernels)
+            # (asr_amd.CTCLoss and asr_amd.MWERLoss fuse the row log-softmax into the CTC kernels)
             loss = self.criterion(float_out, targets, output_sizes, target_sizes).to(self._device)
             loss = loss / inputs.size(0)
             loss_value = loss.item()
@@ -180,13 +180,20 @@ class DeepSpeechTrainer:
         """The target half of a step's host preparation: (flat targets, offsets, lengths, longest target, flags), CPU int32.  flags is
         None with a plain criterion (ops.ctc_loss, as ever); an asr_amd.CTCLoss with a wildcard option set has the targets prepared
         by its own rule (a wildcard at the free ends, runs collapsed) and the step calls ops.ctc_star_loss.  A re-run (_recover) replays
-        this tuple, so it sees the same targets."""
+        this tuple, so it sees the same targets.  An asr_amd.MWERLoss takes the plain targets; its word risk copies the beams to the
+        host, which the step does not do."""
         crit = self.criterion
+        if isinstance(crit, MWERLoss) and crit.risk != "label":
+            raise NotImplementedError("DeepSpeechTrainer.step with MWERLoss(risk='word'): the word risk is packed on the host from the decoded "
+                                      "beams, one host synchronisation between forward and backward; use risk='label', or fit() + backward()")
         if isinstance(crit, CTCLoss) and crit.wildcards:
             return crit.prepare_targets(targets, target_sizes, len(self._model.labels))
         return _prep_targets_host(targets, target_sizes) + (None,)
 
     def _ctc(self, logits, tg, off, lens_dev, tl, max_u, flags, B):
+        if isinstance(self.criterion, MWERLoss):
+            # decode, risks, the optional CTC term and the MWER kernels, all enqueued: (per-utterance value, gradient of their mean)
+            return self.criterion.run(logits, tg, off, lens_dev, tl, max_u, 1.0 / B, True)
         if flags is None:
             return ops.ctc_loss(logits, tg, off, lens_dev, tl, max_u, 1.0 / B, want_grad=True)
         return ops.ctc_star_loss(logits, tg, off, lens_dev, tl, max_u, 1.0 / B, star_penalty=_check_star_penalty(self.criterion.star_penalty),

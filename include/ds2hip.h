@@ -429,6 +429,41 @@ int ds2_ctc_star_loss_f32(const float* logits, int ld, int T, int B, int C, cons
                           const int* in_lens_dev, const int* tgt_lens_dev, int max_target_len, float star_penalty, const int* flags_dev,
                           float* nll_dev, float* grad, int ldg, float grad_scale, int lattice, void* ws, size_t ws_bytes, void* stream);
 
+/* Minimum-error-rate (MWER) training on an n-best list: the expected risk of K hypotheses per utterance under their renormalised CTC
+ * posteriors, and its gradient with respect to the logits.  The reference has no such loss: this text is the contract, restated in
+ * fp64 NumPy by tests/ctc_mwer_oracle.py.  Inputs, strides, the fused row log-softmax, blank = 0, in_lens and the two lattice kernels
+ * chosen by `lattice` and 2 * max_hyp_len + 1 <= 128 (which write the same bits) are ds2_ctc_loss_ex_f32's.
+ * For utterance b with T_b valid frames there are K hypothesis slots; slot k of utterance b is n = b * K + k in every (B, K) array:
+ *  hyps_dev: int32 labels; slot n is hyps_dev[hyp_off_dev[n] ..][: hyp_lens_dev[n]], offsets int64, lengths a device array the host
+ *  never learns; hyp_valid_dev (B, K) int32, nonzero = valid, NULL = all valid; risk_dev (B, K) fp32, R_k >= 0, given by the caller:
+ *  the kernels do not know what the risk counts.  Labels are classes 1 .. C-1.  An EMPTY sequence is a legal hypothesis (the beam
+ *  search's empty prefix): one blank state.
+ * Quantities:
+ *  nll_k  = -log p_ctc(y_k | x_b), the plain loss's lattice; +inf when the slot is invalid, when a label lies outside [1, C-1], when
+ *           its length lies outside [0, max_hyp_len], or when the lattice is infeasible (T_b <= 0 with a non-empty sequence included);
+ *           an invalid slot and a bad label are found before anything is read through them.
+ *  p_k    = exp(-nll_k) / sum_j exp(-nll_j) over the slots with finite nll, a max-subtracted softmax formed in slot order; 0 for the
+ *           other slots.
+ *  loss_b = sum_k p_k R_k in slot order; 0 when no slot is finite or when T_b <= 0.
+ *  w_k    = p_k (R_k - loss_b)  (0 for a slot that is not finite, and for every slot when T_b <= 0).
+ *  grad[t,b,c] = prior + grad_scale * sum_k w_k occ_k[t,c] for t < T_b, summed in slot order; occ_k is the plain loss's occupancy of
+ *           hypothesis k (repeated labels in its deterministic chain order); prior is the buffer's content when accumulate = 1 and 0
+ *           when accumulate = 0.  Rows with t >= T_b get prior: accumulate = 0 writes 0 there, accumulate = 1 leaves the row alone.
+ *  The softmax terms of the K CTC gradients cancel because sum_k w_k = 0; this is the cancelled form and no softmax is computed.
+ *  Every gradient row sums to 0 over the classes, up to rounding.
+ * Outputs: loss_dev (B), nll_hyp_dev (B, K), post_dev (B, K) = p, grad (T, B, C) at row pitch ldg, or NULL for the values alone.
+ * Refused with a nonzero return before any launch: a null pointer, T, B <= 0, C <= 1, K < 1, max_hyp_len < 0, a row pitch below C,
+ *  accumulate or lattice outside {0, 1}, a grad_scale that is not finite, hypotheses too long for the LDS rows of the chosen kernels,
+ *  a workspace below ds2_ctc_mwer_workspace_bytes.
+ * Workspace: lse (T, B) + alpha / beta for B * K lattices at pitch 2 * max_hyp_len + 1 + the repeated-label chains + the weights.  The
+ *  lattices dominate: 8 B K T (2 max_hyp_len + 1) bytes, about 1 GB at B = 64, K = 4, T = 501 with max_hyp_len = T.  A caller that
+ *  knows a tighter bound on the hypothesis lengths passes it. */
+size_t ds2_ctc_mwer_workspace_bytes(int T, int B, int K, int max_hyp_len);
+int ds2_ctc_mwer_f32(const float* logits, int ld, int T, int B, int C, int K, const int* hyps_dev, const long long* hyp_off_dev,
+                     const int* hyp_lens_dev, const int* hyp_valid_dev, const int* in_lens_dev, int max_hyp_len, const float* risk_dev,
+                     float* loss_dev, float* nll_hyp_dev, float* post_dev, float* grad, int ldg, float grad_scale, int accumulate,
+                     int lattice, void* ws, size_t ws_bytes, void* stream);
+
 /* out[0] = sum_b nll[b] / B on the device, fixed summation order: `loss = criterion(...) / inputs.size(0)`,
  * trainers/deepspeech_trainer.py:110-112 */
 int ds2_ctc_batch_mean_f32(const float* nll_dev, int B, float* out_dev, void* stream);
