@@ -169,6 +169,10 @@ SIGNATURES = {
     "ds2_resample_out_samples": (i64, [i64, i32, i32]),
     "ds2_resample_tile_samples": (i32, []),
     "ds2_wave_resample_f32": (i32, [vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, vp, i64, vp]),
+    "ds2_reverb_max_taps": (i32, []),
+    "ds2_reverb_tile_samples": (i32, []),
+    "ds2_reverb_tap_chunk": (i32, []),
+    "ds2_reverb_f32": (i32, [vp, i64, vp, vp, i64, vp, vp, i32, i32, vp, i64, vp]),
     "ds2_adamw_f32": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, vp]),
     "ds2_adamw_gated_f32": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, vp, vp]),
     "ds2_scale_f32": (i32, [vp, i64, f32, vp]),

@@ -491,3 +491,6 @@ extern "C" int ds2_wave_unpack_f32(const void* packed, long long packed_elems, i
 // ---- packed waveform feed: unpack with a sample-rate conversion in it (ds2_wave_resample_f32) --------------------------------------
 #define DS2_STFT_UNPACK_DEFS 1
 #include "resample.h"
+
+// ---- reverberation of the waveform batch (ds2_reverb_f32): built with the feed's other passes ------------------------------------------
+#include "reverb.h"

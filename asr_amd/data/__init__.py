@@ -190,6 +190,119 @@ class NoiseInjection:
         return (x + noise_level * seg * data_energy / noise_energy).astype(np.asarray(data).dtype)
 
 
+class ImpulseResponses:
+    """A bank of room impulse responses (RIRs) for reverberation, modelled on NoiseInjection: every `.wav` under `path` (recursively,
+    sorted) is read once and the prepared responses are kept concatenated — `taps` (fp32, host) plus `starts` / `lengths` per file;
+    `device_taps(device)` is the same bank in one device buffer (uploaded once per device) for ops.reverb.  Of a multi-channel file
+    CHANNEL 0 is taken (averaging the channels of an RIR would smear it).  Files must be at `sample_rate`, unless `resample=True`: an
+    off-rate file is then converted once, here, on the host (`resample_waveform`).
+
+    Preparation of one response, in fp64 on the host (`prepare`; tests/reverb_oracle.py restates it):
+      1. d = argmax |h|, the lowest index on ties; h[d:] is kept, so the direct path sits at lag 0 and a reverberated utterance is not
+         shifted in time.  THE SAMPLES BEFORE THE PEAK ARE DROPPED.
+      2. the length P is the smallest P >= 1 with sum_{k >= P} h[k]^2 <= 10^(tail_db / 10) * sum h^2, capped at
+         int(max_seconds * sample_rate) and at ops.reverb_max_taps() (16384): a longer response is truncated.
+      3. h /= sqrt(sum h^2): unit energy.  This is the level convention here: the loader's spectrograms are normalised per utterance and
+         the noise is mixed relative to the rms of the reverberated signal, so no device-side level pass is needed.
+      4. rounded to fp32.
+    A file that is all zeros (or empty) raises."""
+
+    def __init__(self, path, sample_rate=16000, max_seconds=0.5, tail_db=-60.0, resample=False):
+        if path is None or not os.path.exists(path):
+            raise IOError(f"impulse-response directory does not exist: {path}")
+        found = []
+        for root, _dirs, files in os.walk(path):
+            for f in files:
+                if f.lower().endswith(".wav"):
+                    found.append(os.path.abspath(os.path.join(root, f)))
+        found.sort()
+        if not found:
+            raise ValueError(f"ImpulseResponses: no .wav file under {path}")
+        from scipy.io import wavfile
+        responses = []
+        for f in found:
+            sr, y = wavfile.read(f)
+            y = _mono_float32(y[:, 0] if y.ndim > 1 else y)
+            if sr != int(sample_rate):
+                if not resample:
+                    raise ValueError(f"ImpulseResponses: {f} is sampled at {sr} Hz, expected {int(sample_rate)} Hz (pass resample=True)")
+                y = resample_waveform(y, sr, int(sample_rate))
+            try:
+                responses.append(self.prepare(y, sample_rate, max_seconds, tail_db))
+            except ValueError as e:
+                raise ValueError(f"ImpulseResponses: {f}: {e}") from None
+        self._set(responses, found, sample_rate, max_seconds, tail_db)
+
+    def _set(self, responses, paths, sample_rate, max_seconds, tail_db):
+        self.paths = list(paths)
+        self.sample_rate, self.max_seconds, self.tail_db = int(sample_rate), float(max_seconds), float(tail_db)
+        self.lengths = np.array([len(h) for h in responses], dtype=np.int64)
+        self.starts = np.concatenate([[0], np.cumsum(self.lengths)[:-1]]).astype(np.int64)
+        self.taps = np.concatenate(responses).astype(np.float32)
+        self._device = {}
+
+    @staticmethod
+    def prepare(h, sample_rate=16000, max_seconds=0.5, tail_db=-60.0):
+        """Steps 1 to 4 of the class docstring on one raw response: the prepared fp32 taps."""
+        from .. import ops
+        h = np.asarray(h, dtype=np.float64).reshape(-1)
+        if h.size == 0 or not np.any(h):
+            raise ValueError("an impulse response must hold a non-zero sample")
+        h = h[int(np.argmax(np.abs(h))):]
+        e = h * h
+        tail = np.concatenate([np.cumsum(e[::-1])[::-1][1:], [0.0]])         # tail[P - 1] = sum_{k >= P} h[k]^2
+        P = int(np.argmax(tail <= 10.0 ** (tail_db / 10.0) * e.sum())) + 1
+        P = max(1, min(P, int(max_seconds * sample_rate), ops.reverb_max_taps()))
+        h = h[:P]
+        return (h / np.sqrt((h * h).sum())).astype(np.float32)
+
+    @classmethod
+    def synthetic(cls, count, sample_rate=16000, t60_range=(0.2, 0.8), drr_db_range=(-2.0, 12.0), seed=0, **kw):
+        """`count` synthetic responses, for users without an RIR corpus and for the tests: h[0] = 1 (the direct path) and, for k >= 1,
+        h[k] = g N(0, 1) exp(-6.9078 k / (T60 sample_rate)) — exponentially decaying Gaussian noise, 60 dB down after T60 seconds — with g
+        set so that the direct-to-reverberant energy ratio equals the drawn DRR; 2 T60 seconds are synthesised.  Per response, from ONE
+        np.random.default_rng(seed): T60 ~ U(*t60_range), then DRR ~ U(*drr_db_range) dB, then the Gaussian block.  The result goes through
+        `prepare` (`max_seconds`, `tail_db` in **kw).  A CRUDE MODEL — no early reflections, no room geometry; whether training on it helps
+        far-field WER is UNMEASURED."""
+        rng = np.random.default_rng(seed)
+        max_seconds, tail_db = float(kw.pop("max_seconds", 0.5)), float(kw.pop("tail_db", -60.0))
+        if kw:
+            raise TypeError(f"ImpulseResponses.synthetic: unexpected arguments {sorted(kw)}")
+        responses = []
+        for _ in range(int(count)):
+            t60 = rng.uniform(*t60_range)
+            drr_db = rng.uniform(*drr_db_range)
+            n = max(int(2.0 * t60 * sample_rate), 2)
+            tail = rng.standard_normal(n - 1) * np.exp(-6.9078 * np.arange(1, n, dtype=np.float64) / (t60 * sample_rate))
+            g = np.sqrt(10.0 ** (-drr_db / 10.0) / (tail * tail).sum())
+            responses.append(cls.prepare(np.concatenate([[1.0], g * tail]), sample_rate, max_seconds, tail_db))
+        self = cls.__new__(cls)
+        self._set(responses, [f"synthetic:{seed}:{i}" for i in range(int(count))], sample_rate, max_seconds, tail_db)
+        return self
+
+    def __len__(self):
+        return len(self.paths)
+
+    def device_taps(self, device) -> torch.Tensor:
+        key = str(device)
+        if key not in self._device:
+            self._device[key] = torch.from_numpy(self.taps).to(device)
+        return self._device[key]
+
+
+def draw_reverb(rng, B, bank, prob):
+    """Which impulse response each utterance of one batch gets, drawn from `rng` (numpy Generator) on the host: per utterance in batch
+    order, coin = rng.binomial(1, prob); if coin: file = rng.integers(len(bank)).  One block, drawn AFTER draw_perturbation's and BEFORE
+    draw_augmentation's for the same batch.  Returns (file (B,) int64, -1 = not reverberated; base (B,) int64; taps (B,) int32): the
+    arguments of ops.reverb."""
+    file, base, taps = np.full(B, -1, np.int64), np.zeros(B, np.int64), np.zeros(B, np.int32)
+    for b in range(B):
+        if rng.binomial(1, prob):
+            i = int(rng.integers(len(bank)))
+            file[b], base[b], taps[b] = i, int(bank.starts[i]), int(bank.lengths[i])
+    return file, base, taps
+
+
 def draw_perturbation(rng, B, tempo_range=(0.85, 1.15), gain_range=(-6, 8)):
     """Tempo factors and gains (dB) of one batch, drawn from `rng` (numpy Generator) on the host: per utterance, in the order given,
     tempo = rng.uniform(*tempo_range) then gain = rng.uniform(*gain_range) (load_randomly_augmented_audio's ranges, audio/functional.py:94-104).
@@ -253,6 +366,13 @@ class GpuSpectrogramFrontEnd:
         all (ops.tempo_gain, ds2_tempo_gain_f32) — noise and masks then follow the perturbed utterance of floor(n / tempo + 0.5) samples.
         Modelled on sox's `tempo` / `gain` effects that the reference runs per file; parity with sox is unpinned, and its 16-bit
         requantisation with dither is not reproduced.  Its draws (draw_perturbation) come as one block before draw_augmentation's.
+      * reverberation when a bank of room impulse responses is given (`reverb=`, an ImpulseResponses, or `audio_conf.rir_dir`, from which
+        one is built): with probability `audio_conf.reverb_prob` (default 0.5: a starting point — which value serves real recordings is
+        UNMEASURED) an utterance is convolved with a response of the bank (ops.reverb, ds2_reverb_f32), cut to its own length, after
+        tempo / gain and before the noise: the noise is then scaled by the rms of the REVERBERATED signal.  The responses have unit
+        energy and the spectrograms are normalised per utterance, so there is no level pass.
+    DRAW ORDER per batch: the perturbation block (draw_perturbation), the reverb block (draw_reverb), then draw_augmentation's.  Without
+    a bank there is no reverb draw and no launch: the Generator's stream and the batches are what they are without the feature.
     The draws are made on the host from the front-end's own numpy Generator, in the order documented at `draw_augmentation`; `seed=None`
     takes the seed from numpy's global state (offset by the rank under torch.distributed; only when there is something to draw), a fixed
     seed gives bit-identical batches.
@@ -261,13 +381,14 @@ class GpuSpectrogramFrontEnd:
 
     def __init__(self, audio_conf, normalize=False, pad_mode="constant", device=None, augment=False, seed=None, freq_mask_param=27,
                  time_mask_param=70, freq_masks=1, time_masks=1, noise=None, speed_volume_perturb=False, tempo_range=(0.85, 1.15),
-                 gain_range=(-6, 8), resample=False):
+                 gain_range=(-6, 8), resample=False, reverb=None):
         self.sample_rate = int(audio_conf.sample_rate)
         self.n_fft = int(audio_conf.sample_rate * audio_conf.window_size)
         self.hop = int(audio_conf.sample_rate * audio_conf.window_stride)
         self.window, self.normalize, self.pad_mode, self.device = audio_conf.window, normalize, pad_mode, device
         self.augment = bool(augment)
         self.noise, self.noise_prob, self.spec_augment, self.perturb = None, 0.0, False, False
+        self.reverb, self.reverb_prob = None, 0.0
         if self.augment:
             self.perturb = bool(speed_volume_perturb) and bool(getattr(audio_conf, "speed_volume_perturb", False))
             self.tempo_range = (float(tempo_range[0]), float(tempo_range[1]))
@@ -283,7 +404,13 @@ class GpuSpectrogramFrontEnd:
                 noise = NoiseInjection(audio_conf.noise_dir, audio_conf.sample_rate, noise_levels_of(audio_conf), resample=resample)
             self.noise = noise
             self.noise_prob = float(getattr(audio_conf, "noise_prob", 0.4)) if noise is not None else 0.0
-            if seed is None and (noise is not None or self.spec_augment or self.perturb):     # (nothing to draw: numpy's global state is left alone)
+            if reverb is None and getattr(audio_conf, "rir_dir", None) is not None:
+                reverb = ImpulseResponses(audio_conf.rir_dir, audio_conf.sample_rate, resample=resample)
+            if reverb is not None and reverb.sample_rate != self.sample_rate:
+                raise ValueError(f"reverb: the bank is at {reverb.sample_rate} Hz, the front-end at {self.sample_rate} Hz")
+            self.reverb = reverb
+            self.reverb_prob = float(getattr(audio_conf, "reverb_prob", 0.5)) if reverb is not None else 0.0
+            if seed is None and (noise is not None or self.spec_augment or self.perturb or reverb is not None):     # (nothing to draw: numpy's global state is left alone)
                 seed = int(np.random.randint(0, 2 ** 31 - 1))
                 if torch.distributed.is_available() and torch.distributed.is_initialized():
                     seed += torch.distributed.get_rank()
@@ -316,6 +443,10 @@ class GpuSpectrogramFrontEnd:
             n = self.perturbed_lengths(n, tempo)
         elif perturb is not None:
             raise ValueError("perturb= given, but this front-end does not perturb (augment, speed_volume_perturb and audio_conf.speed_volume_perturb)")
+        if self.reverb is not None:
+            _, base, taps = self.draw_reverb(len(n))
+            if max(n) > 0:
+                batch = ops.reverb(batch, n, self.reverb.device_taps(dev), base, taps, max(n))
         if self.augment and (self.noise is not None or self.spec_augment):
             p = self.draw(n)
             nz = {}
@@ -332,6 +463,10 @@ class GpuSpectrogramFrontEnd:
     def draw_perturbation(self, B):
         """The next batch's (tempo, gain dB) arrays (draw_perturbation with this front-end's ranges and Generator)."""
         return draw_perturbation(self.rng, B, self.tempo_range, self.gain_range)
+
+    def draw_reverb(self, B):
+        """The next batch's (file, base, taps) arrays (draw_reverb with this front-end's bank, probability and Generator)."""
+        return draw_reverb(self.rng, B, self.reverb, self.reverb_prob)
 
     @staticmethod
     def perturbed_lengths(n_samples, tempo):
@@ -372,6 +507,7 @@ class SpectrogramDataset(Dataset):
         # spectrogram_parser.py:29-44 / :64-80: noise injection, tempo/gain perturbation and SpecAugment are host-side augmentations of
         # the reference's parser that this loader does not implement — say so instead of training silently without them
         unsupported = [k for k, on in (("noise_dir", getattr(audio_conf, "noise_dir", None) is not None),
+                                       ("rir_dir", getattr(audio_conf, "rir_dir", None) is not None),
                                        ("speed_volume_perturb", bool(getattr(audio_conf, "speed_volume_perturb", False))),
                                        ("spec_augment", bool(spec_augment))) if on]
         if unsupported:
@@ -1007,6 +1143,10 @@ def get_loader(audio_conf, labels, manifest, batch_size, num_workers, caching=Fa
     per batch on the GPU, fused into the unpack pass (ops.wave_resample), ahead of the unchanged tempo, noise, STFT and SpecAugment
     kernels, for `prefetch=0` too; the noise bank converts its off-rate files once; with front_end="host" per item in the workers
     (`resample_waveform`).  Parity with sox / ffmpeg is unpinned.
+    `audio_conf.rir_dir` (front_end="gpu"; needs no parameter here, works with `prefetch` too): a directory of room impulse responses —
+    with probability `audio_conf.reverb_prob` (default 0.5, a starting point: which value serves real recordings is unmeasured) an
+    utterance is reverberated on the GPU (ImpulseResponses, ops.reverb) after tempo / gain and before the noise; `resample` is passed on to
+    the bank.  With front_end="host" a set `rir_dir` is ignored with a warning, like the other augmentations.
     `star="*"` (default None: the ids are exactly the ones above): that character, any single one that is not a label, in a manifest's
     transcript becomes the wildcard id len(labels) for `asr_amd.CTCLoss(star=True)` — "this part was not transcribed"; characters that
     are neither a label nor the star are dropped first, then runs of wildcards collapse to one."""

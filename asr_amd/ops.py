@@ -1882,6 +1882,49 @@ def wave_resample(packed: Tensor, offsets, lengths, rates, src_index=None, targe
     return out, n_out
 
 
+def reverb_max_taps() -> int:
+    """The longest impulse response ops.reverb takes (ds2_reverb_max_taps; a host function, no GPU needed)."""
+    return int(_lib.load().ds2_reverb_max_taps())
+
+
+def reverb(audio: Tensor, n_samples, rir: Optional[Tensor], rir_base, rir_taps, n_max: Optional[int] = None) -> Tensor:
+    """Reverberation of a waveform batch (ds2_reverb_f32, contract in include/ds2hip.h): row b becomes the truncated causal convolution
+    y[i] = sum_{k <= min(i, P - 1)} h[k] x[i - k], i < n_b, of its n_b samples with the P_b = rir_taps[b] taps at rir[rir_base[b]:]; the tail
+    beyond n_b is dropped, so every utterance keeps its length.  rir_taps[b] == 0 copies the row bit for bit.
+    audio (B, L) fp32 GPU rows (garbage allowed beyond n_samples); rir: ONE 1-D fp32 GPU bank of concatenated responses (None: no bank,
+    every rir_taps is then 0); n_samples, rir_base, rir_taps: (B) HOST integers.  The description is checked here, on the host (ValueError:
+    a length outside [0, n_max], taps outside [0, reverb_max_taps()], a slice outside the bank), then uploaded from pinned memory as one
+    int32 image with one asynchronous copy.  Returns a new (B, n_max) fp32 GPU tensor, exact zeros beyond each n_b; n_max defaults to
+    max(n_samples)."""
+    import numpy as np
+    if audio.dtype != torch.float32 or not audio.is_cuda or audio.dim() != 2 or audio.stride(1) != 1 or audio.size(0) == 0:
+        raise ValueError("reverb: audio must be a (B >= 1, L) fp32 GPU tensor with contiguous rows")
+    if rir is not None and (rir.dtype != torch.float32 or not rir.is_cuda or rir.dim() != 1 or not rir.is_contiguous()):
+        raise ValueError("reverb: rir must be a contiguous 1-D fp32 GPU tensor")
+    B, dev = audio.size(0), audio.device
+    n, base, taps = (np.asarray(v.tolist() if isinstance(v, Tensor) else v, dtype=np.int64).reshape(-1) for v in (n_samples, rir_base, rir_taps))
+    if n.size != B or base.size != B or taps.size != B:
+        raise ValueError(f"reverb: n_samples ({n.size}), rir_base ({base.size}) and rir_taps ({taps.size}): one value per row ({B})")
+    if n_max is None:
+        n_max = int(n.max())
+    n_max = int(n_max)
+    elems = 0 if rir is None else int(rir.numel())
+    if (n < 0).any() or (n > n_max).any() or n_max > audio.size(1) or n_max > 2 ** 30:
+        raise ValueError(f"reverb: lengths lie in [0, n_max = {n_max}], n_max within the rows ({audio.size(1)}) and 2^30, got {n.tolist()}")
+    if (taps < 0).any() or (taps > reverb_max_taps()).any():
+        raise ValueError(f"reverb: taps lie in [0, {reverb_max_taps()}], got {taps.tolist()}")
+    if elems > 2 ** 31 - 1 or (base < 0).any() or (base + taps > elems).any():
+        raise ValueError(f"reverb: an impulse response lies outside the bank of {elems} taps (at most 2^31 - 1)")
+    if n_max == 0:
+        return torch.zeros((B, 0), dtype=torch.float32, device=dev)
+    meta = torch.from_numpy(np.concatenate([n.astype(np.int32), taps.astype(np.int32), base.view(np.int32)])).pin_memory().to(dev, non_blocking=True)
+    out = torch.empty((B, n_max), dtype=torch.float32, device=dev)
+    _lib.check(_lib.load().ds2_reverb_f32(audio.data_ptr(), audio.stride(0), meta[:B].data_ptr(), rir.data_ptr() if elems else None, elems,
+                                          meta[2 * B:].data_ptr(), meta[B:2 * B].data_ptr(), B, n_max, out.data_ptr(), out.stride(0),
+                                          _stream()), "ds2_reverb_f32")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 # optimizer
 # ------------------------------------------------------------------------------------------------

@@ -837,6 +837,39 @@ int ds2_wave_resample_f32(const void* packed, long long packed_elems, int dtype,
                           const int* src_index_dev, const int* L_dev, const int* M_dev, const int* J_dev, const int* tab_base_dev,
                           const float* tab, long long tab_elems, int B, int n_out_max, float* out, long long ld_out, void* stream);
 
+/* ---- reverberation of the waveform batch (GpuSpectrogramFrontEnd(reverb=...), audio_conf.rir_dir) ---------------
+ * Multi-condition training (Ko et al. 2017, "A study on data augmentation of reverberant speech for robust speech recognition"): an
+ * utterance is convolved with a room impulse response (RIR) before the noise goes in.  The reference has no such step; the contract
+ * below is what tests/reverb_oracle.py restates in fp64.
+ * Per row b: x = the n_b samples of audio[b], h = the P_b taps rir[rir_base[b] .. rir_base[b] + P_b).  The truncated causal convolution
+ *      y[i] = sum_{k = 0 .. min(i, P_b - 1)} h[k] * x[i - k],   i in [0, n_b)
+ *  out[b][i] = y[i] for i < n_b, exact 0 for n_b <= i < n_max; columns n_max .. ld_out are not written.  The tail beyond n_b is dropped:
+ *  the utterance keeps its length (sort, frame counts and CTC sizes stay valid); the bank (asr_amd.data.ImpulseResponses) puts the direct
+ *  path at lag 0, so nothing shifts in time.
+ *  Arithmetic: fp32 products, fp32 accumulation, one fused multiply-add per tap in a FIXED order (tap chunks of ds2_reverb_tap_chunk()
+ *  ascending, inside a chunk the taps descending); no atomics; reruns are bit-identical, and a row's bits depend only on (x, h) — not on
+ *  its position in the batch, on B or on n_max.  DENORMALS: subnormal products and sums may be flushed to zero (today's kernel keeps
+ *  them; callers must not rely on either).  Non-finite samples inside [0, n_b) are outside the contract (0 * inf).
+ *  P_b == 0: "not reverberated" — the row is copied bit for bit and zero-filled to n_max.
+ *  Samples of audio[b] at and beyond n_b may hold anything, NaN included: they never reach the output (ds2_tempo_gain_f32's input rule).
+ *  out must not alias audio.
+ * ds2_reverb_f32: audio (B, ld_audio) fp32 device; n_samples_dev (B) int32 device; rir (rir_elems) fp32 device, ONE bank of concatenated
+ *  responses; rir_base_dev (B) int64 device; rir_taps_dev (B) int32 device; out (B, ld_out) fp32 device.
+ *  Rejected (non-zero, nothing launched): null pointers (rir may be NULL when rir_elems == 0), pointers not aligned to their element
+ *  size, out == audio, B outside [1, 65535], n_max outside [0, 2^30], ld_out < n_max, ld_audio < n_max, rir_elems outside [0, 2^31).
+ *  n_max == 0 is accepted and launches nothing.
+ *  The per-row arrays live on the device, so the CALLER checks them (asr_amd.ops.reverb does, on the host values it uploads); the kernel
+ *  re-checks each row — n_b in [0, n_max], P_b in [0, ds2_reverb_max_taps()], rir_base >= 0, rir_base + P_b <= rir_elems — and writes
+ *  a row that fails as zeros: nothing outside the three buffers is read or written.
+ *  One kernel (reverb_kernel, csrc/reverb.h) on v_mfma_f32_16x16x4_f32, a FIR filter being a GEMM with a Toeplitz operand: one
+ *  workgroup per (row, tile of ds2_reverb_tile_samples() outputs), looping over tap chunks; the tile's x window and the chunk's taps
+ *  are staged in LDS.  ds2_reverb_max_taps() = 16384 (1.02 s at 16 kHz). */
+int ds2_reverb_max_taps(void);
+int ds2_reverb_tile_samples(void);
+int ds2_reverb_tap_chunk(void);
+int ds2_reverb_f32(const float* audio, long long ld_audio, const int* n_samples_dev, const float* rir, long long rir_elems,
+                   const long long* rir_base_dev, const int* rir_taps_dev, int B, int n_max, float* out, long long ld_out, void* stream);
+
 /* ---- optimizer ----------------------------------------------------------------------------------
  * torch.optim.AdamW.step over one flat parameter buffer, trainers/__main__.py:41-47. */
 int ds2_adamw_f32(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps,
