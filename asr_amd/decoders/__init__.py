@@ -4,7 +4,8 @@ reference uses for TARGET strings.  Eval-only, not on the t
 `wer` / `cer` keep a small pure-Python DP (the reference imports the `Levenshtein` C package) as the reference API; evaluate()
 scores a whole batch with `Decoder.score_batch`, one HIP launch (csrc/edit_distance.h) on ids packed by `pack_scoring`.
 `CTCAligner.align` places a KNOWN transcript in time (csrc/ctc_align.h); its record assembly is the pure host function
-`assemble_alignments`."""
+`assemble_alignments`.  `KeywordSpotter.search` finds WHERE keywords were said without a decode or a transcript (csrc/ctc_kws.h); its
+record assembly is `assemble_detections`."""
 from __future__ import annotations
 
 import math
@@ -364,8 +365,12 @@ def assemble_alignments(score, states, tok_start, tok_end, tok_logp, targets, si
 
 def add_seconds(records, frame_seconds):
     """Every token and word tuple of the records gains (start_s, end_s) = (start, end) * frame_seconds, and so does every (start, end)
-    span of "unaligned" where a record has that key."""
+    span of "unaligned" where a record has that key.  An utterance's list of KeywordSpotter detections gains "start_s" / "end_s"."""
     for r in records:
+        if isinstance(r, list):                          # KeywordSpotter.search: a list of detections per utterance
+            for d in r:
+                d["start_s"], d["end_s"] = d["start"] * frame_seconds, d["end"] * frame_seconds
+            continue
         for key in ("tokens", "words"):
             r[key] = [t + (t[1] * frame_seconds, t[2] * frame_seconds) for t in r[key]]
         if "unaligned" in r:
@@ -461,6 +466,128 @@ class CTCAligner(Decoder):
         return assemble_alignments(o[:B].view(np.float32), o[B:n].reshape(B, T), o[n:n + n_tok], o[n + n_tok:n + 2 * n_tok],
                                    o[n + 2 * n_tok:].view(np.float32), targets, sizes_h, self.int_to_char, self.space_index,
                                    star_id if wild else None, star or "*")
+
+
+KWS_MAX_LEN, KWS_MAX_HITS = 63, 1024
+
+
+def assemble_detections(hit_start, hit_end, hit_score, n_hits, keywords, kw_lens, max_hits):
+    """Pure host half of KeywordSpotter.search: the kernel's hit arrays ((B,K,max_hits) each, n_hits (B,K)) -> per utterance the list
+    of {"keyword", "start", "end" (exclusive), "score", "confidence": exp(score / U)} over all keywords, sorted by (start, end,
+    keyword index).  Returns (records, overflowed): overflowed lists the (utterance, keyword) pairs whose n_hits is max_hits + 1."""
+    hit_start, hit_end = np.asarray(hit_start), np.asarray(hit_end)
+    hit_score, n_hits = np.asarray(hit_score, np.float32), np.asarray(n_hits)
+    records, overflowed = [], []
+    for b in range(n_hits.shape[0]):
+        found = []
+        for k, kw in enumerate(keywords):
+            n = int(n_hits[b, k])
+            if n > max_hits:
+                overflowed.append((b, kw))
+            for h in range(min(n, max_hits)):
+                sc = float(hit_score[b, k, h])
+                found.append((int(hit_start[b, k, h]), int(hit_end[b, k, h]), k, sc))
+        records.append([{"keyword": keywords[k], "start": s, "end": e, "score": sc, "confidence": math.exp(sc / kw_lens[k])}
+                        for s, e, k, sc in sorted(found)])
+    return records, overflowed
+
+
+class KeywordSpotter(Decoder):
+    """Keyword search on CTC posteriors: WHERE a phrase was said, and whether at all, without a decode and without a transcript
+    (Lengerich & Hannun 2016).  `search` runs every keyword against every utterance as one library call (`ds2_ctc_kws_f32`, contract in
+    include/ds2hip.h; restated by tests/ctc_kws_oracle.py): a Viterbi lattice entered at any frame whose scores are log-likelihood
+    ratios against the frame-wise best path (0 = the keyword's labels are the best class of every frame they take), then a greedy pick
+    of non-overlapping detections.  The reference has no keyword search.
+    keywords: strings over the labels (encode_transcripts, unknown="error"), 1 .. 63 labels each, no duplicates.
+    threshold: a per-label probability ratio in (0, 1]: a detection of a keyword of U labels needs score >= U * log(threshold).  The
+    default 0.5 mirrors the aligner's star_penalty and is a starting point, NOT a measured one: which value serves real recordings has
+    not been measured.
+    Matching is on the label stream and knows no word boundary: "cat" fires inside "catalog", as with the beam search's hotwords."""
+
+    def __init__(self, labels, keywords, threshold=0.5, max_hits=32, blank_index=0):
+        if blank_index != 0:
+            raise ValueError("KeywordSpotter: the kernel takes class 0 as the blank (blank_index must be 0)")
+        super().__init__(labels, blank_index)
+        if isinstance(max_hits, bool) or int(max_hits) != max_hits or not 1 <= int(max_hits) <= KWS_MAX_HITS:
+            raise ValueError(f"KeywordSpotter: max_hits must be an integer in [1, {KWS_MAX_HITS}], got {max_hits!r}")
+        self.max_hits = int(max_hits)
+        self.set_keywords(keywords, threshold)
+
+    def set_keywords(self, keywords, threshold=None):
+        """Replace the keyword list (and the threshold, unless None).  Nothing is kept on a refusal."""
+        thr = self.threshold if threshold is None else float(threshold)
+        if not (0.0 < thr <= 1.0):                       # (NaN fails too)
+            raise ValueError(f"KeywordSpotter: threshold must lie in (0, 1], got {threshold!r}")
+        if isinstance(keywords, str):
+            raise ValueError("KeywordSpotter: keywords must be a list of strings, not one string")
+        keywords = list(keywords)
+        if not keywords:
+            raise ValueError("KeywordSpotter: no keyword")
+        if not all(isinstance(k, str) for k in keywords):
+            raise ValueError("KeywordSpotter: keywords must be strings")
+        ids = encode_transcripts(keywords, self.labels, unknown="error")
+        for kw, i in zip(keywords, ids):
+            if not i:
+                raise ValueError("KeywordSpotter: empty keyword")
+            if len(i) > KWS_MAX_LEN:
+                raise ValueError(f"KeywordSpotter: keyword {kw!r} has {len(i)} labels, the kernel holds at most {KWS_MAX_LEN}")
+            if self.blank_index in i:
+                raise ValueError(f"KeywordSpotter: keyword {kw!r} contains the blank label")
+        if len(set(keywords)) != len(keywords):
+            dup = sorted(k for k in set(keywords) if keywords.count(k) > 1)
+            raise ValueError(f"KeywordSpotter: duplicate keyword {dup[0]!r}")
+        self.threshold, self.keywords, self.kw_ids = thr, keywords, ids
+        self.kw_lens = [len(i) for i in ids]
+        self.thr = np.array([u * math.log(thr) for u in self.kw_lens], np.float64).astype(np.float32)
+
+    def search(self, probs, sizes=None, is_log=False, frame_seconds=None):
+        """probs (B,T,C) as decode() takes them (probabilities, or log-probabilities with is_log=True), sizes (B) valid frames or None.
+        One pinned upload of the packed keywords, one library call, one device-to-host copy of the hits.  Returns, per utterance, the
+        detections of all keywords sorted by start: {"keyword", "start", "end" (frames, end exclusive), "score" (the path's
+        log-likelihood ratio, <= 0), "confidence" (exp(score / U), the geometric mean per label, in (0, 1])}; with frame_seconds every
+        record gains "start_s" / "end_s" (add_seconds).  Detections of ONE keyword never overlap; those of different keywords may.
+        Warns when a keyword had more than max_hits detections in an utterance (the best max_hits in greedy order are kept).
+        Host tensors are uploaded first: there is no CPU implementation.  T has no limit beyond the (B,K,T) frame arrays."""
+        import warnings
+
+        from .. import ops
+        probs = torch.as_tensor(probs)
+        if probs.dim() != 3:
+            raise ValueError(f"KeywordSpotter.search: probs must be (B,T,C), got {tuple(probs.shape)}")
+        B, T = int(probs.shape[0]), int(probs.shape[1])
+        sizes_h = [T] * B if sizes is None else [int(v) for v in torch.as_tensor(sizes).reshape(-1).tolist()]
+        if len(sizes_h) != B:
+            raise ValueError(f"sizes has {len(sizes_h)} entries for a batch of {B}")
+        if not probs.is_cuda:
+            probs = probs.to(_device("KeywordSpotter", ".search"))
+        probs = probs.float()
+        if probs.stride(2) != 1:
+            probs = probs.contiguous()
+        dev = probs.device
+        K, n_lab = len(self.keywords), sum(self.kw_lens)
+        # one int32 image: kw_off, kw_lens, thr (its bits), in_lens, labels
+        host = torch.empty(3 * K + B + n_lab, dtype=torch.int32, pin_memory=True)
+        h = host.numpy()
+        h[:K] = np.cumsum([0] + self.kw_lens[:-1])
+        h[K:2 * K], h[2 * K:3 * K] = self.kw_lens, self.thr.view(np.int32)
+        h[3 * K:3 * K + B] = np.clip(sizes_h, -1, T)
+        h[3 * K + B:] = [i for ids in self.kw_ids for i in ids]
+        d = host.to(dev, non_blocking=True)
+        _, _, hs, he, hsc, nh = ops.ctc_keyword_search(probs, d[3 * K + B:], d[:K], d[K:2 * K], max(self.kw_lens), d[2 * K:3 * K].view(torch.float32),
+                                                       d[3 * K:3 * K + B], is_log, self.max_hits)
+        out = torch.cat((hs.reshape(-1), he.reshape(-1), hsc.view(torch.int32).reshape(-1), nh.reshape(-1))).cpu()
+        if ops.rnn_poison_seen(dev):
+            # as in GreedyDecoder.decode: a poisoned forward (a starved persistent recurrence launch) raises here
+            ops.rnn_persistent_check(dev)
+        o, n = out.numpy(), B * K * self.max_hits
+        shape = (B, K, self.max_hits)
+        records, overflowed = assemble_detections(o[:n].reshape(shape), o[n:2 * n].reshape(shape), o[2 * n:3 * n].view(np.float32).reshape(shape),
+                                                  o[3 * n:].reshape(B, K), self.keywords, self.kw_lens, self.max_hits)
+        if overflowed:
+            b, kw = overflowed[0]
+            warnings.warn(f"KeywordSpotter.search: more than max_hits={self.max_hits} detections for {len(overflowed)} (utterance, keyword) "
+                          f"pair(s), the first: utterance {b}, keyword {kw!r}; the rest were dropped", RuntimeWarning, stacklevel=2)
+        return records if frame_seconds is None else add_seconds(records, float(frame_seconds))
 
 
 def _device(who="GreedyDecoder", what=".decode"):

@@ -314,6 +314,30 @@ class DeepSpeech(nn.Module):
                                                 unknown=unknown, free_start=free_start, free_end=free_end)
         return add_seconds(records, 2.0 * float(self.audio_conf.window_stride))[0]
 
+    # -- keyword search (no counterpart in the reference) -----------------------------------------
+    def spot(self, inputs, input_sizes, keywords, threshold=0.5, max_hits=32):
+        """Where the keywords were said: the eval-mode forward, then KeywordSpotter on its output.  inputs (B,1,F,T) and input_sizes
+        (B) as forward() takes them, keywords a list of strings.  Returns KeywordSpotter.search's records per utterance with
+        "start_s" / "end_s" added, seconds = frame * 2 * audio_conf.window_stride as in align().  threshold / max_hits: see
+        KeywordSpotter, also for what the default threshold is not (a measured one) and for the missing word boundary.  The model is
+        left in eval mode."""
+        from ..decoders import KeywordSpotter
+        spotter = KeywordSpotter(self.labels, keywords, threshold=threshold, max_hits=max_hits)
+        self.eval()
+        with torch.no_grad():
+            out, output_sizes = self.forward(inputs, input_sizes)
+            return spotter.search(out, output_sizes, frame_seconds=2.0 * float(self.audio_conf.window_stride))
+
+    def spot_long(self, spect, keywords, window=2000, overlap=200, batch_size=32, threshold=0.5, max_hits=32):
+        """Where the keywords were said in ONE recording of any length: posteriors_long (see there for the windows and for what is not
+        claimed about their edges), then KeywordSpotter.search on the whole recording as one lattice per keyword: the kernel keeps no
+        back-pointers, so nothing is tiled and the frames have no limit beyond device memory (12 bytes per keyword and frame).  Returns
+        the recording's list of records as spot() does."""
+        from ..decoders import KeywordSpotter
+        spotter = KeywordSpotter(self.labels, keywords, threshold=threshold, max_hits=max_hits)
+        probs = self.posteriors_long(spect, window, overlap, batch_size)
+        return spotter.search(probs[None], None, frame_seconds=2.0 * float(self.audio_conf.window_stride))[0]
+
     # -- evaluation loop (deepspeech.py:161-273) --------------------------------------------------
     def evaluate(self, loader=None, manifest=None, batch_size=None, device="auto", num_workers=32, verbose=False, half=False,
                  output_file=None, main_proc=True, **_unused):

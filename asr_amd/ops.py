@@ -1494,6 +1494,54 @@ def ctc_forced_align_star_tiled(x: Tensor, targets: Tensor, tgt_off: Tensor, in_
                       (tile_frames, tile_pairs), star=(star_penalty, flags))
 
 
+KWS_MAX_LEN, KWS_MAX_HITS = 63, 1024
+
+
+def ctc_keyword_search(x: Tensor, kw_labels: Tensor, kw_off: Tensor, kw_lens: Tensor, max_kw_len: int, thr: Tensor,
+                       in_lens: Tensor | None = None, is_log: bool = False, max_hits: int = 32):
+    """Keyword search over CTC posteriors x (B,T,C) fp32 on the GPU (any batch / frame strides, classes contiguous), K keywords against
+    every utterance (contract: include/ds2hip.h, ds2_ctc_kws_f32) -> (frame_score (B,K,T) f32, frame_start (B,K,T) i32, hit_start,
+    hit_end (B,K,max_hits) i32, hit_score (B,K,max_hits) f32, n_hits (B,K) i32), all on the GPU.  kw_labels (flat), kw_off (K),
+    kw_lens (K) are int32 device tensors, thr (K) fp32 on the device, in_lens (B) int32 or None (= T frames each); max_kw_len >= every
+    keyword length, at most 63; max_hits in [1, 1024] (n_hits == max_hits + 1: more detections than slots).  No limit on T: the
+    workspace is 4 B T (1 + K) bytes.  Three launches on the current stream, nothing is copied back."""
+    who = "ctc_keyword_search"
+    if not all(torch.is_tensor(t) for t in (x, kw_labels, kw_off, kw_lens, thr)):
+        raise ValueError(f"{who}: x, kw_labels, kw_off, kw_lens and thr must be tensors")
+    if not 0 <= int(max_kw_len) <= KWS_MAX_LEN:
+        raise ValueError(f"{who}: max_kw_len must lie in [0, {KWS_MAX_LEN}] (one wavefront holds a keyword), got {max_kw_len}")
+    if not 1 <= int(max_hits) <= KWS_MAX_HITS:
+        raise ValueError(f"{who}: max_hits must lie in [1, {KWS_MAX_HITS}], got {max_hits}")
+    if not x.is_cuda:
+        raise ValueError(f"{who}: x must be a GPU tensor (no CPU fallback exists)")
+    K = kw_lens.numel()
+    if K < 1 or kw_off.numel() != K or thr.numel() != K:
+        raise ValueError(f"{who}: {kw_off.numel()} offsets / {K} lengths / {thr.numel()} thresholds (one each per keyword, at least one)")
+    _chk_align_args(who, x, dict(in_lens=in_lens))
+    for name, t, dt in (("kw_labels", kw_labels, torch.int32), ("kw_off", kw_off, torch.int32), ("kw_lens", kw_lens, torch.int32),
+                        ("thr", thr, torch.float32)):
+        if t.dtype != dt or t.device != x.device or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous {str(dt).replace('torch.', '')} tensor on {x.device}")
+    B, T, Cc = x.shape
+    dev = x.device
+    max_hits = int(max_hits)
+    fscore = torch.empty((B, K, T), dtype=torch.float32, device=dev)
+    fstart = torch.empty((B, K, T), dtype=torch.int32, device=dev)
+    hstart = torch.empty((B, K, max_hits), dtype=torch.int32, device=dev)
+    hend = torch.empty((B, K, max_hits), dtype=torch.int32, device=dev)
+    hscore = torch.empty((B, K, max_hits), dtype=torch.float32, device=dev)
+    nhits = torch.empty((B, K), dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    wsb = lib.ds2_ctc_kws_workspace_bytes(B, T, K, max_hits)
+    ws = _ws(wsb, dev)
+    ld_b, ld_t = (x.stride(d) if x.size(d) > 1 else max(x.stride(d), 1) for d in (0, 1))      # (a dim of one entry may carry the stride 0)
+    _lib.check(lib.ds2_ctc_kws_f32(x.data_ptr(), ld_b, ld_t, B, T, Cc, 1 if is_log else 0, _ptr(in_lens),
+                                   _ptr(kw_labels) if kw_labels.numel() else None, kw_off.data_ptr(), kw_lens.data_ptr(), K, int(max_kw_len),
+                                   thr.data_ptr(), max_hits, fscore.data_ptr(), fstart.data_ptr(), hstart.data_ptr(), hend.data_ptr(),
+                                   hscore.data_ptr(), nhits.data_ptr(), ws.data_ptr(), wsb, _stream()), "ds2_ctc_kws_f32")
+    return fscore, fstart, hstart, hend, hscore, nhits
+
+
 def ctc_beam_decode(probs: Tensor, sizes: Tensor | None = None, blank: int = 0, beam_width: int = 100, cutoff_top_n: int = 40,
                     cutoff_prob: float = 1.0, lm=None, alpha: float = 0.0, beta: float = 0.0, hotwords=None, labels_out: Tensor | None = None):
     """CTC prefix beam search of probs (B,T,C) fp32 on the GPU -> (labels (B,K,T) i32, offsets (B,K,T) i32, lengths (B,K) i32,

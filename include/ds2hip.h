@@ -575,6 +575,47 @@ int ds2_ctc_align_star_tiled_f32(const float* x, long long ld_b, long long ld_t,
                                  float* score, int* states, int* tok_start, int* tok_end, float* tok_logp,
                                  void* ws, size_t ws_bytes, void* stream);
 
+/* Keyword search over CTC posteriors: WHERE a phrase was said, and whether it was said at all (csrc/ctc_kws.h; in the literature:
+ * Lengerich & Hannun 2016).  The (max, +) lattice of ds2_ctc_align_f32 entered at any frame, on emissions taken relative to the
+ * frame's best class, for K keywords against every utterance of a batch in one call.  The reference has nothing like it: this text is
+ * the contract, restated in NumPy by tests/ctc_kws_oracle.py.
+ * Inputs: x, ld_b, ld_t, is_log and in_lens_dev mean what they mean for ds2_ctc_align_f32 (blank is class 0, in_lens_dev NULL = T
+ *  frames).  The keywords are shared by the batch: kw_labels_dev flat int32 labels, kw_off_dev (K) the start of keyword k in it,
+ *  kw_lens_dev (K) its length U_k; max_kw_len >= every U_k and <= 63 (one wavefront holds a keyword, two states per lane; a larger value
+ *  is a nonzero return, and a kw_lens entry above max_kw_len makes that keyword one without a hit).  thr_dev (K) fp32: one threshold
+ *  per keyword.  max_hits in [1, 1024].
+ * Emission: with e the emission of that contract, g[t] = (max over all classes c of e[t][c]) + 0.0f is the wildcard row of
+ *  ds2_ctc_align_star_f32 with penalty 0 (with is_log = 0 the max is taken on x, as there), and d[t][c] = e[t][c] - g[t] is ONE fp32
+ *  subtract, -inf where e is -inf.  So d <= 0, and a path's value is its log-likelihood ratio against the frame-wise best path.  A
+ *  frame whose classes are all -inf is unspecified, and so is NaN.
+ * States: the aligner's numbering; a keyword l[0..U) has the live states 1 .. 2U-1, odd state 2u+1 the label l[u], even state 2u the
+ *  blank between two labels.  State 0 and a trailing blank do not exist: a detection begins on the first label's first frame and ends
+ *  on the last label's last frame.  Every state carries a value v and the start frame s of its path.
+ * Recurrence: before frame 0 every value is -inf.  For each frame t < T_b and state q, the max over the moves
+ *    stay  v[t-1][q];   step  v[t-1][q-1], q >= 2;   skip  v[t-1][q-2], q odd, q >= 3, l[q>>1] != l[(q>>1)-1];
+ *    enter the value 0 with the start t, q == 1 only
+ *  then ONE fp32 add of d[t][class(q)]; nothing else touches the values.  Ties: the smallest move wins (stay beats step beats skip)
+ *  and enter loses every tie, so an existing path, which has the earlier start, is kept.  The start travels with the chosen move; a
+ *  state whose value is -inf has the start -1.
+ * Per-frame outputs, (B,K,T) each: frame_score[b][k][t] = v[t][2U-1], frame_start[b][k][t] = s[t][2U-1]; (-inf, -1) for t >= T_b, and
+ *  in every frame for a keyword with U = 0 or a label outside [1, C), which has no hit.
+ * Pick, per (b, k): greedy non-maximum suppression.  Candidates are the frames with a finite frame_score >= thr[k].  A round takes
+ *  the live candidate with the largest score (a tie: the smallest t), writes (hit_start = frame_start[t], hit_end = t + 1, hit_score)
+ *  to the next slot and kills every candidate t' whose closed span [frame_start[t'], t'] intersects [frame_start[t], t].  It stops
+ *  when no candidate is live or max_hits are written; n_hits[b][k] is the number written, or max_hits + 1 if a live candidate
+ *  remained.  hit_start / hit_end / hit_score are (B,K,max_hits), in order of acceptance, unused slots (-1, -1, -inf); n_hits (B,K).
+ * With is_log = 1 every output is pinned bit for bit by a float32 restatement (scores compared after + 0.0f: -0 and +0 are equal).
+ * Workspace, from host-known sizes only: g (B * T floats), then the pick's compacted candidate frames (B * K * T int32):
+ *  ds2_ctc_kws_workspace_bytes = 4 * B * T * (1 + K), or 0 for B, T, K <= 0 or max_hits outside [1, 1024].  There is no back-pointer
+ *  array and no limit on T.  Three launches on the stream (the g row, the lattice, the pick).  Nonzero return on bad arguments or a
+ *  short workspace, before any launch. */
+size_t ds2_ctc_kws_workspace_bytes(int B, int T, int K, int max_hits);
+int ds2_ctc_kws_f32(const float* x, long long ld_b, long long ld_t, int B, int T, int C, int is_log, const int* in_lens_dev,
+                    const int* kw_labels_dev, const int* kw_off_dev, const int* kw_lens_dev, int K, int max_kw_len,
+                    const float* thr_dev, int max_hits,
+                    float* frame_score, int* frame_start, int* hit_start, int* hit_end, float* hit_score, int* n_hits,
+                    void* ws, size_t ws_bytes, void* stream);
+
 /* softmax over the last dim (eval-mode InferenceBatchSoftmax, modules/blocks.py:59-64) */
 int ds2_softmax_rows_f32(const float* x, int ldx, float* y, int ldy, int rows, int C, void* stream);
 
