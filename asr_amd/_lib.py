@@ -134,6 +134,9 @@ SIGNATURES = {
     "ds2_softmax_rows_f32": (i32, [vp, i32, vp, i32, i32, i32, vp]),
     "ds2_greedy_decode_workspace_bytes": (sz, [i32, i32]),
     "ds2_greedy_decode_f32": (i32, [vp, i64, i64, i32, i32, i32, vp, i32, vp, vp, vp, vp, sz, vp]),
+    "ds2_ctc_segment_workspace_bytes": (sz, [i32, i32]),
+    "ds2_ctc_segment_f32": (i32, [vp, i64, i64, i32, i32, i32, vp, i32, f32, i32, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
+    "ds2_ctc_segment_gather_f32": (i32, [vp, i64, i64, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp]),
     "ds2_ctc_beam_max_width": (i32, []),
     "ds2_ctc_beam_workspace_bytes": (sz, [i32, i32, i32]),
     "ds2_ctc_beam_decode_f32": (i32, [vp, i64, i64, i32, i32, i32, vp, i32, i32, i32, f32, vp, vp, vp, vp, vp, sz, vp]),

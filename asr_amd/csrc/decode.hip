@@ -97,3 +97,7 @@ extern "C" int ds2_greedy_decode_f32(const float* probs, long long ld_b, long lo
 // The batched edit distance of the WER / CER scoring (ds2_edit_distance_*) is compiled here as well, for the same reason.
 #define DS2_EDIT_DISTANCE_TU
 #include "edit_distance.h"
+
+// The pause segmentation of long recordings and the packing of its segments into decode batches (ds2_ctc_segment_*), likewise.
+#define DS2_CTC_SEGMENT_TU
+#include "ctc_segment.h"

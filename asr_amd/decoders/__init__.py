@@ -5,7 +5,9 @@ reference uses for TARGET strings.  Eval-only, not on the t
 scores a whole batch with `Decoder.score_batch`, one HIP launch (csrc/edit_distance.h) on ids packed by `pack_scoring`.
 `CTCAligner.align` places a KNOWN transcript in time (csrc/ctc_align.h); its record assembly is the pure host function
 `assemble_alignments`.  `KeywordSpotter.search` finds WHERE keywords were said without a decode or a transcript (csrc/ctc_kws.h); its
-record assembly is `assemble_detections`."""
+record assembly is `assemble_detections`.  `transcribe_posteriors` turns ONE long recording's posteriors into timed segments: cut at
+pauses and packed into decode batches on the GPU (csrc/ctc_segment.h); its host half is `plan_segment_batches`, `words_from_offsets`
+and `assemble_transcript`."""
 from __future__ import annotations
 
 import math
@@ -588,6 +590,109 @@ class KeywordSpotter(Decoder):
             warnings.warn(f"KeywordSpotter.search: more than max_hits={self.max_hits} detections for {len(overflowed)} (utterance, keyword) "
                           f"pair(s), the first: utterance {b}, keyword {kw!r}; the rest were dropped", RuntimeWarning, stacklevel=2)
         return records if frame_seconds is None else add_seconds(records, float(frame_seconds))
+
+
+def plan_segment_batches(lengths, batch_size):
+    """Host half of DeepSpeech.transcribe_long: the segments, given by their lengths, ordered longest first (ties by index) and cut into
+    batches of at most batch_size -> a list of index lists.  A batch's t_max is its first segment's length, so a batch pads only up to
+    its own longest segment and the decoder's (S, K, t_max) outputs stay bounded."""
+    if isinstance(batch_size, bool) or int(batch_size) != batch_size or int(batch_size) < 1:
+        raise ValueError(f"plan_segment_batches: batch_size must be a positive integer, got {batch_size!r}")
+    lengths = [int(n) for n in lengths]
+    order = sorted(range(len(lengths)), key=lambda i: (-lengths[i], i))
+    return [order[i:i + int(batch_size)] for i in range(0, len(order), int(batch_size))]
+
+
+def words_from_offsets(text, offsets, shift=0):
+    """A decoded string and its per-character offsets -> [(word, start, end)]: a word is the run of characters between spaces (leading,
+    trailing and doubled spaces make no word), start = its first character's offset + shift, end = its last character's offset +
+    shift + 1.  The offsets of decode() are the frames where a label was FIRST EMITTED, not spans: a word's end is one past the frame
+    where its last character appeared, not where that character's sound ended.  CTCAligner.align() gives spans."""
+    offsets = [int(o) for o in (offsets.tolist() if hasattr(offsets, "tolist") else offsets)]
+    if len(offsets) != len(text):
+        raise ValueError(f"words_from_offsets: {len(offsets)} offsets for {len(text)} characters")
+    words, first = [], None
+    for i, ch in enumerate(text + " "):
+        if ch == " ":
+            if first is not None:
+                words.append((text[first:i], offsets[first] + shift, offsets[i - 1] + shift + 1))
+            first = None
+        elif first is None:
+            first = i
+    return words
+
+
+def assemble_transcript(texts, offsets, seg_start, seg_end, seg_flags, order, scores=None, frame_seconds=None):
+    """Pure host half of DeepSpeech.transcribe_long.  texts / offsets (/ scores): one decoded string, its per-character offsets (frames
+    inside the segment) and optionally its score per segment, IN DECODE ORDER; order[i] is the index of the i-th decoded segment in the
+    time-ordered arrays seg_start / seg_end / seg_flags (the flattened plan_segment_batches).  Returns {"text": the stripped non-empty
+    segment texts joined by single spaces, "segments": [{"start", "end" (global frames, end exclusive), "text" (the decoder's raw
+    string), "words": [(word, start, end)] (words_from_offsets, global frames), "forced": flags (1 = starts at a forced cut, 2 = ends at
+    one), "score" with scores}]} in time order; with frame_seconds every segment gains "start_s" / "end_s" and every word tuple
+    (start_s, end_s)."""
+    n = len(seg_start)
+    order = [int(i) for i in order]
+    if sorted(order) != list(range(n)) or len(texts) != n or len(offsets) != n or (scores is not None and len(scores) != n):
+        raise ValueError(f"assemble_transcript: {len(texts)} texts / {len(offsets)} offsets / an order of {len(order)} for {n} segments")
+    segments = [None] * n
+    for i, k in enumerate(order):
+        s, e = int(seg_start[k]), int(seg_end[k])
+        rec = {"start": s, "end": e, "text": texts[i], "words": words_from_offsets(texts[i], offsets[i], s), "forced": int(seg_flags[k])}
+        if frame_seconds is not None:
+            rec["start_s"], rec["end_s"] = s * frame_seconds, e * frame_seconds
+            rec["words"] = [w + (w[1] * frame_seconds, w[2] * frame_seconds) for w in rec["words"]]
+        if scores is not None:
+            rec["score"] = float(scores[i])
+        segments[k] = rec
+    return {"text": " ".join(t for t in (r["text"].strip() for r in segments) if t), "segments": segments}
+
+
+def check_segment_options(who, threshold, min_gap, pad, max_len, decode_batch):
+    """The argument checks of transcribe_posteriors / DeepSpeech.transcribe_long: ValueError naming the option."""
+    if isinstance(decode_batch, bool) or int(decode_batch) != decode_batch or int(decode_batch) < 1:
+        raise ValueError(f"{who}: decode_batch must be a positive integer, got {decode_batch!r}")
+    if not (0.0 < float(threshold) <= 1.0):              # (NaN fails too)
+        raise ValueError(f"{who}: threshold must lie in (0, 1], got {threshold!r}")
+    for name, v, lo in (("min_gap", min_gap, 1), ("pad", pad, 0), ("max_len", max_len, 2)):
+        if isinstance(v, bool) or int(v) != v or int(v) < lo:
+            raise ValueError(f"{who}: {name} must be an integer >= {lo}, got {v!r}")
+
+
+def transcribe_posteriors(probs, decoder, threshold=0.9, min_gap=25, pad=5, max_len=1000, decode_batch=64, frame_seconds=None):
+    """The device half of DeepSpeech.transcribe_long on posteriors you already have: probs (T, C) fp32 probabilities of ONE recording
+    (uploaded first if on the host; there is no CPU implementation).  ops.ctc_segment with the decoder's blank, one device-to-host copy
+    of the segment list, plan_segment_batches, per batch one ops.ctc_segment_gather and one decoder.decode, assemble_transcript (see
+    there for the record; "score" per segment with a BeamCTCDecoder, its best beam's).  The options and what is not measured about
+    their defaults: DeepSpeech.transcribe_long."""
+    from .. import ops
+    check_segment_options("transcribe_posteriors", threshold, min_gap, pad, max_len, decode_batch)
+    probs = torch.as_tensor(probs)
+    if probs.dim() != 2:
+        raise ValueError(f"transcribe_posteriors: probs must be (T, C), got {tuple(probs.shape)}")
+    if not probs.is_cuda:
+        probs = probs.to(_device("transcribe_posteriors", ""))
+    probs = probs.float()
+    if probs.stride(1) != 1:
+        probs = probs.contiguous()
+    probs = probs[None]
+    start, end, flags, n_segs = ops.ctc_segment(probs, None, decoder.blank_index, threshold, min_gap, pad, max_len)
+    seg = torch.cat((n_segs, start[0], end[0], flags[0])).cpu().numpy()
+    n, m = int(seg[0]), start.size(1)
+    start_h, end_h, flags_h = seg[1:1 + n], seg[1 + m:1 + m + n], seg[1 + 2 * m:1 + 2 * m + n]
+    batches = plan_segment_batches(end_h - start_h, decode_batch)
+    beam = isinstance(decoder, BeamCTCDecoder)
+    texts, offsets, scores = [], [], [] if beam else None
+    for idx in batches:
+        host = torch.zeros((3, len(idx)), dtype=torch.int32)          # one int32 image: utterance indices (all 0), starts, lengths
+        host[1], host[2] = torch.from_numpy(start_h[idx]), torch.from_numpy(end_h[idx] - start_h[idx])
+        d = host.to(probs.device)
+        packed, sizes = ops.ctc_segment_gather(probs, d[0], d[1], d[2], int(host[2, 0]))
+        strings, offs = decoder.decode(packed, sizes)
+        texts += [s[0] for s in strings]
+        offsets += [o[0] for o in offs]
+        if beam:
+            scores += decoder.last_scores[:, 0].tolist()
+    return assemble_transcript(texts, offsets, start_h, end_h, flags_h, [i for idx in batches for i in idx], scores, frame_seconds)
 
 
 def _device(who="GreedyDecoder", what=".decode"):

@@ -338,6 +338,44 @@ class DeepSpeech(nn.Module):
         probs = self.posteriors_long(spect, window, overlap, batch_size)
         return spotter.search(probs[None], None, frame_seconds=2.0 * float(self.audio_conf.window_stride))[0]
 
+    # -- transcription with times (no counterpart in the reference) -------------------------------
+    def transcribe(self, inputs, input_sizes, decoder=None):
+        """The text of each utterance with word times: the eval-mode forward, then `decoder or self.decoder or GreedyDecoder(labels)`
+        on its output.  inputs (B,1,F,T) and input_sizes (B) as forward() takes them.  Returns one {"text", "words"} record per
+        utterance: the best string and [(word, start, end, start_s, end_s)] (decoders.words_from_offsets: the frames are where a
+        character was first emitted, not spans; align() gives spans), seconds = frame * 2 * audio_conf.window_stride as in align().
+        The model is left in eval mode."""
+        from ..decoders import GreedyDecoder, words_from_offsets
+        dec = decoder or self.decoder or GreedyDecoder(self.labels)
+        fs = 2.0 * float(self.audio_conf.window_stride)
+        self.eval()
+        with torch.no_grad():
+            out, output_sizes = self.forward(inputs, input_sizes)
+            strings, offsets = dec.decode(out, output_sizes)
+        return [{"text": s[0], "words": [w + (w[1] * fs, w[2] * fs) for w in words_from_offsets(s[0], o[0])]}
+                for s, o in zip(strings, offsets)]
+
+    def transcribe_long(self, spect, window=2000, overlap=200, batch_size=32, decoder=None, threshold=0.9, min_gap=25, pad=5, max_len=1000,
+                        decode_batch=64):
+        """The text of ONE recording of any length, in timed segments: posteriors_long (see there for the windows and for what is not
+        claimed about their edges), ops.ctc_segment (a frame whose blank probability is >= threshold is silent; silent runs of min_gap
+        frames are pauses; segments are padded by up to `pad` frames and cut at their most silent frame when longer than max_len; the
+        contract: include/ds2hip.h, ds2_ctc_segment_f32), one device-to-host copy of the segment list, then per batch of at most
+        decode_batch segments (decoders.plan_segment_batches: longest first, so a batch pads to its own longest segment) one
+        ops.ctc_segment_gather and one decoder.decode, spread over the GPU instead of one workgroup walking the whole recording.
+        decoder: `decoder or self.decoder or GreedyDecoder(labels)`.  Returns {"text", "segments": [{"start", "end", "start_s", "end_s",
+        "text", "words": [(word, start, end, start_s, end_s)], "forced"}]} (decoders.assemble_transcript), frames counted in the whole
+        recording, seconds = frame * 2 * window_stride; with a BeamCTCDecoder every segment has "score", its best beam's.
+        NOT MEASURED: the defaults are starting points — the threshold 0.9, the 0.5 s pause, the 0.1 s pad and the 20 s cap (at a 10 ms
+        stride; the cap sits at the model's training lengths) have not been tuned, and which values serve real recordings is unmeasured;
+        so is what the window edges cost (inherited from posteriors_long).  With a language model every segment starts from the <s>
+        context; what that costs in WER against a whole-recording decode is unmeasured.  The model is left in eval mode."""
+        from ..decoders import GreedyDecoder, check_segment_options, transcribe_posteriors
+        dec = decoder or self.decoder or GreedyDecoder(self.labels)
+        check_segment_options("transcribe_long", threshold, min_gap, pad, max_len, decode_batch)     # before the forward passes
+        probs = self.posteriors_long(spect, window, overlap, batch_size)
+        return transcribe_posteriors(probs, dec, threshold, min_gap, pad, max_len, decode_batch, 2.0 * float(self.audio_conf.window_stride))
+
     # -- evaluation loop (deepspeech.py:161-273) --------------------------------------------------
     def evaluate(self, loader=None, manifest=None, batch_size=None, device="auto", num_workers=32, verbose=False, half=False,
                  output_file=None, main_proc=True, **_unused):

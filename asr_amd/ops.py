@@ -1542,6 +1542,94 @@ def ctc_keyword_search(x: Tensor, kw_labels: Tensor, kw_off: Tensor, kw_lens: Te
     return fscore, fstart, hstart, hend, hscore, nhits
 
 
+def segment_max_segs(T: int, min_gap: int, max_len: int) -> int:
+    """The most segments ctc_segment can give an utterance of T frames: at most (T + min_gap) // (min_gap + 1) regions (two regions are
+    min_gap silent frames and a frame apart, an end's pause may be shorter) and at most T // ((max_len + 1) // 2) forced cuts (a piece
+    that ends at one has that many frames)."""
+    return max(1, (T + min_gap) // (min_gap + 1) + T // ((max_len + 1) // 2))
+
+
+def ctc_segment(probs: Tensor, sizes: Tensor | None = None, blank: int = 0, threshold: float = 0.9, min_gap: int = 25, pad: int = 5,
+                max_len: int = 1000, is_log: bool = False, max_segs: int | None = None):
+    """Pause segmentation of CTC posteriors probs (B,T,C) fp32 on the GPU (any batch / frame strides, classes contiguous; contract:
+    include/ds2hip.h, ds2_ctc_segment_f32) -> (seg_start, seg_end (B, max_segs) i32, seg_flags (B, max_segs) i32, n_segs (B) i32), all
+    on the GPU.  A frame is silent when its blank probability is >= threshold (in (0, 1]; with is_log the input holds log-probabilities
+    and log(threshold) is compared); silent runs of at least min_gap frames, and those at either end, are pauses; what lies between them,
+    padded by up to `pad` frames into the pauses, is a segment; one longer than max_len is cut at its most silent frame in the second
+    half of each max_len frames (flags: 1 = starts at such a cut, 2 = ends at one).  sizes (B) valid frames, any integer dtype and
+    device, or None.  max_segs: None = segment_max_segs(T, min_gap, max_len), which no utterance exceeds; a smaller value keeps the
+    first max_segs segments while n_segs still reports the full count.  Unused slots hold (-1, -1, 0).  Two launches on the current
+    stream, nothing is copied back."""
+    who = "ctc_segment"
+    if not torch.is_tensor(probs):
+        raise ValueError(f"{who}: probs must be a tensor")
+    for name, v, lo in (("min_gap", min_gap, 1), ("pad", pad, 0), ("max_len", max_len, 2)):
+        if isinstance(v, bool) or int(v) != v or int(v) < lo or int(v) > 0x7fffffff:
+            raise ValueError(f"{who}: {name} must be an integer >= {lo}, got {v!r}")
+    thr = float(threshold)
+    if not (0.0 < thr <= 1.0):                           # (NaN fails too)
+        raise ValueError(f"{who}: threshold must lie in (0, 1], got {threshold!r}")
+    if not probs.is_cuda:
+        raise ValueError(f"{who}: probs must be a GPU tensor (no CPU fallback exists)")
+    if probs.dim() != 3 or probs.stride(2) != 1:
+        raise ValueError(f"{who}: probs must be (B,T,C) with a contiguous class dim")
+    B, T, Cc = probs.shape
+    if min(B, T, Cc) < 1:
+        raise ValueError(f"{who}: empty probs {tuple(probs.shape)}")
+    if not 0 <= int(blank) < Cc:
+        raise ValueError(f"{who}: blank {blank} outside the {Cc} classes")
+    _chk_f32(probs)
+    dev = probs.device
+    sizes = _sizes_i32(sizes, B, dev)
+    min_gap, pad, max_len = int(min_gap), int(pad), int(max_len)
+    max_segs = segment_max_segs(T, min_gap, max_len) if max_segs is None else int(max_segs)
+    if max_segs < 1:
+        raise ValueError(f"{who}: max_segs must be positive, got {max_segs}")
+    seg = torch.empty((3, B, max_segs), dtype=torch.int32, device=dev)
+    n_segs = torch.empty((B,), dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    wsb = lib.ds2_ctc_segment_workspace_bytes(B, T)
+    ws = _ws(wsb, dev)
+    ld_b, ld_t = (probs.stride(d) if probs.size(d) > 1 else max(probs.stride(d), 1) for d in (0, 1))
+    _lib.check(lib.ds2_ctc_segment_f32(probs.data_ptr(), ld_b, ld_t, B, T, Cc, _ptr(sizes), int(blank), math.log(thr) if is_log else thr,
+                                       min_gap, pad, max_len, max_segs, seg[0].data_ptr(), seg[1].data_ptr(), seg[2].data_ptr(),
+                                       n_segs.data_ptr(), ws.data_ptr(), wsb, _stream()), "ds2_ctc_segment_f32")
+    return seg[0], seg[1], seg[2], n_segs
+
+
+def ctc_segment_gather(probs: Tensor, seg_b: Tensor, seg_start: Tensor, seg_len: Tensor, t_max: int):
+    """Packs S segments of probs (B,T,C) fp32 on the GPU (strides as ctc_segment takes them) into one padded batch, one launch (contract:
+    include/ds2hip.h, ds2_ctc_segment_gather_f32) -> (out (S, t_max, C) fp32: row s = probs[seg_b[s], seg_start[s]:][:seg_len[s]], then
+    zeros; out_sizes (S) i32 = seg_len).  seg_b, seg_start, seg_len: (S) int32 tensors on the GPU.  A segment outside probs or longer
+    than t_max gives a zero row and the size 0."""
+    who = "ctc_segment_gather"
+    if not all(torch.is_tensor(t) for t in (probs, seg_b, seg_start, seg_len)):
+        raise ValueError(f"{who}: probs, seg_b, seg_start and seg_len must be tensors")
+    if isinstance(t_max, bool) or int(t_max) != t_max or not 1 <= int(t_max) <= 0x7fffffff:
+        raise ValueError(f"{who}: t_max must be a positive integer, got {t_max!r}")
+    if not probs.is_cuda:
+        raise ValueError(f"{who}: probs must be a GPU tensor (no CPU fallback exists)")
+    if probs.dim() != 3 or probs.stride(2) != 1 or min(probs.shape) < 1:
+        raise ValueError(f"{who}: probs must be a non-empty (B,T,C) with a contiguous class dim")
+    S = seg_b.numel()
+    if seg_start.numel() != S or seg_len.numel() != S:
+        raise ValueError(f"{who}: {S} / {seg_start.numel()} / {seg_len.numel()} utterances, starts and lengths")
+    for name, t in (("seg_b", seg_b), ("seg_start", seg_start), ("seg_len", seg_len)):
+        if t.dtype != torch.int32 or t.device != probs.device or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous int32 tensor on {probs.device}")
+    _chk_f32(probs)
+    B, T, Cc = probs.shape
+    out = torch.empty((S, int(t_max), Cc), dtype=torch.float32, device=probs.device)
+    out_sizes = torch.empty((S,), dtype=torch.int32, device=probs.device)
+    if S == 0:
+        return out, out_sizes
+    ld_b, ld_t = (probs.stride(d) if probs.size(d) > 1 else max(probs.stride(d), 1) for d in (0, 1))
+    _lib.check(_lib.load().ds2_ctc_segment_gather_f32(probs.data_ptr(), ld_b, ld_t, B, T, Cc, seg_b.data_ptr(), seg_start.data_ptr(),
+                                                      seg_len.data_ptr(), S, int(t_max), out.data_ptr(), out_sizes.data_ptr(), _stream()),
+               "ds2_ctc_segment_gather_f32")
+    return out, out_sizes
+
+
 def ctc_beam_decode(probs: Tensor, sizes: Tensor | None = None, blank: int = 0, beam_width: int = 100, cutoff_top_n: int = 40,
                     cutoff_prob: float = 1.0, lm=None, alpha: float = 0.0, beta: float = 0.0, hotwords=None, labels_out: Tensor | None = None):
     """CTC prefix beam search of probs (B,T,C) fp32 on the GPU -> (labels (B,K,T) i32, offsets (B,K,T) i32, lengths (B,K) i32,

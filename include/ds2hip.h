@@ -743,6 +743,46 @@ size_t ds2_edit_distance_workspace_bytes(int P, long long max_len);
 int ds2_edit_distance_i32(const int* seq, long long n_seq, const long long* a_off, const int* a_len, const long long* b_off,
                           const int* b_len, int P, long long max_len, int* dist, void* ws, size_t ws_bytes, void* stream);
 
+/* Pause segmentation of CTC posteriors (csrc/ctc_segment.h): where to cut a long recording so that its pieces can be decoded as one
+ * batch.  Integer work on the blank column; every output is pinned to the integer by tests/ctc_segment_oracle.py, which restates this
+ * text.  The reference has nothing like it.
+ * Inputs: x (B,T,C) fp32 with element strides ld_b / ld_t (class dim contiguous); in_lens_dev (B) int32 or NULL (= T),
+ *  T_b = clamp(in_lens[b], 0, T); blank in [0, C); thr fp32, compared against the raw value: silent(t) := x[b][t][blank] >= thr, which
+ *  is false for NaN (for log-probabilities pass the logarithm of the threshold: there is no is_log); min_gap >= 1, pad >= 0,
+ *  max_len >= 2, max_segs >= 1.
+ * Pauses: a pause is a maximal run [a, b) of silent frames of [0, T_b) with b - a >= min_gap, or a == 0, or b == T_b (a silent run at
+ *  either end of the utterance is a pause at any length).
+ * Regions: the maximal intervals of [0, T_b) that no pause covers, in order; shorter silent runs stay inside their region.  No region:
+ *  0 segments.
+ * Padding: with m(a, b) = a + (b - a) / 2 (integer division) for a pause [a, b), a region [s, e) becomes [s', e'):
+ *    s' = max(s - pad, lo), lo = 0 if s == 0 or the pause in front starts at frame 0, else m of the pause in front;
+ *    e' = min(e + pad, hi), hi = T_b if e == T_b or the pause behind ends at T_b, else m of the pause behind.
+ *  Segments therefore never overlap.
+ * Forced cuts: a padded region longer than max_len is split left to right.  cur = s'; while e' - cur > max_len: the cut c is the frame
+ *  of [cur + (max_len + 1) / 2, cur + max_len] (both ends included) with the greatest x[b][c][blank], scanned upwards with a strict >
+ *  (the smallest c wins a tie; which frame wins among NaN values is unspecified); emit [cur, c) with flag bit 1 (value 2: ends at a
+ *  forced cut); cur = c, and the next piece carries flag bit 0 (value 1: starts at a forced cut).  The last piece is [cur, e').  So
+ *  every segment has 1 <= length <= max_len, and a piece that ends at a forced cut has at least (max_len + 1) / 2 frames.
+ * Outputs: seg_start, seg_end (exclusive), seg_flags (B, max_segs) int32, ascending in time, unused slots (-1, -1, 0); n_segs (B) the
+ *  full count, which may exceed max_segs: then only the first max_segs are written.
+ * Workspace, from host-known sizes only: ds2_ctc_segment_workspace_bytes(B, T) = B * (8 * ceil(T / 64) + 4 * (4 * (T / 2 + 1) + T))
+ *  bytes (the silence bits, the run and pause lists, the forced cuts), or 0 for B, T <= 0; ws 8-byte aligned.  Two launches on the
+ *  stream: one lane per frame writes a 64-bit ballot word per 64 frames, spread over the GPU; then one workgroup per utterance works
+ *  on the words.  Nonzero return on bad arguments or a short workspace, before any launch. */
+size_t ds2_ctc_segment_workspace_bytes(int B, int T);
+int ds2_ctc_segment_f32(const float* x, long long ld_b, long long ld_t, int B, int T, int C, const int* in_lens_dev, int blank, float thr,
+                        int min_gap, int pad, int max_len, int max_segs, int* seg_start, int* seg_end, int* seg_flags, int* n_segs,
+                        void* ws, size_t ws_bytes, void* stream);
+
+/* Packs S segments of x (the same x, ld_b, ld_t, B, T, C as above) into one padded batch, one launch: out (S, T_max, C) contiguous,
+ * row s a bit-exact copy of x[seg_b[s]][seg_start[s] : seg_start[s] + seg_len[s]] followed by zeros up to T_max, and out_sizes[s] =
+ * seg_len[s].  seg_b_dev, seg_start_dev, seg_len_dev (S) int32 device arrays.  A segment with seg_b outside [0, B), seg_start < 0,
+ * seg_len < 0, seg_start + seg_len > T or seg_len > T_max is rejected: an all-zero row and out_sizes[s] = 0.  Nonzero return on bad
+ * arguments, before the launch. */
+int ds2_ctc_segment_gather_f32(const float* x, long long ld_b, long long ld_t, int B, int T, int C, const int* seg_b_dev,
+                               const int* seg_start_dev, const int* seg_len_dev, int S, int T_max, float* out, int* out_sizes,
+                               void* stream);
+
 /* conv1 in bf16 mode (Conv2d(1,32,(41,11),s=(2,2),p=(20,5)), deepspeech.py:61, forward + weight gradient; conv1 has no data
  * gradient).  ds2_conv1_gather_bf16 builds the two bf16 operand images from the spectrogram batch: XB (B,F,P) = the rows themselves as
  * bf16, XB[..][7 + s] = x[..][s] with zeros in front and behind (P = ds2_conv1_bf16_row_pitch(T)) for the forward — the 16 taps of an output
