@@ -23,6 +23,7 @@ from torch.utils.data import DataLoader, Dataset
 from torch.utils.data.sampler import Sampler
 
 from ..functional import _collate_fn
+from ..ops import WAVE_ALIGN, WAVE_MAX_ELEMS      # the packed layout: offsets are multiples of WAVE_ALIGN elements and fit the device's int32
 
 
 def _stft_spectrogram(y: np.ndarray, sample_rate: int, window_size: float, window_stride: float, window: str = "hamming",
@@ -491,9 +492,11 @@ def _check_star(star, labels):
     return star
 
 
-class SpectrogramDataset(Dataset):
-    def __init__(self, audio_conf, manifest_filepath, labels, normalize=False, spec_augment=False, caching=False, resample=False,
-                 star=None):
+class _ManifestDataset(Dataset):
+    """What SpectrogramDataset and WaveformDataset share: the manifest, the label map, the star check, the transcript parser and the
+    cached item (a subclass's parse_audio, parse_transcript)."""
+
+    def __init__(self, audio_conf, manifest_filepath, labels, caching, resample, star):
         import pandas as pd
         self.df = pd.read_csv(manifest_filepath)
         self.size = len(self.df)
@@ -501,9 +504,42 @@ class SpectrogramDataset(Dataset):
             labels = dict([(v, k) for k, v in pd.read_csv(labels).to_dict()["label"].items()])
         self.labels_map = labels
         self.star = _check_star(star, labels)
-        self.audio_conf, self.normalize, self.caching = audio_conf, normalize, caching
-        self.resample = bool(resample)                   # an off-rate WAV file is converted on the host (resample_waveform)
+        self.audio_conf, self.caching, self.resample = audio_conf, caching, bool(resample)
         self._cache = {}
+
+    def parse_transcript(self, transcript):
+        """spectrogram_dataset.py:70-73: unknown chars and the index-0 (blank) label are dropped.
+        With `star` (a single character that is not a label) that character becomes the wildcard id len(labels), one past the last
+        class, for CTCLoss(star=True): every other unknown character is dropped first, then runs of wildcards collapse to one."""
+        transcript = transcript.replace("\n", "")
+        star = getattr(self, "star", None)
+        if star is None:
+            return list(filter(None, [self.labels_map.get(x) for x in list(transcript)]))
+        star_id = len(self.labels_map)
+        ids = list(filter(None, [star_id if x == star else self.labels_map.get(x) for x in list(transcript)]))
+        return [i for k, i in enumerate(ids) if not (i == star_id and k > 0 and ids[k - 1] == star_id)]
+
+    def _cached(self, cache, index, make):
+        """item `index` = make(its manifest row), kept in `cache` with caching=True"""
+        if self.caching and index in cache:
+            return cache[index]
+        item = make(self.df.iloc[index])
+        if self.caching:
+            cache[index] = item
+        return item
+
+    def __getitem__(self, index):
+        return self._cached(self._cache, index, lambda row: (self.parse_audio(row.audio_filepath), self.parse_transcript(row.text)))
+
+    def __len__(self):
+        return self.size
+
+
+class SpectrogramDataset(_ManifestDataset):
+    def __init__(self, audio_conf, manifest_filepath, labels, normalize=False, spec_augment=False, caching=False, resample=False,
+                 star=None):
+        super().__init__(audio_conf, manifest_filepath, labels, caching, resample, star)
+        self.normalize = normalize                       # (resample: an off-rate WAV file is converted on the host, resample_waveform)
         # spectrogram_parser.py:29-44 / :64-80: noise injection, tempo/gain perturbation and SpecAugment are host-side augmentations of
         # the reference's parser that this loader does not implement — say so instead of training silently without them
         unsupported = [k for k, on in (("noise_dir", getattr(audio_conf, "noise_dir", None) is not None),
@@ -531,32 +567,8 @@ class SpectrogramDataset(Dataset):
             spect = (spect - spect.mean()) / spect.std()
         return spect
 
-    def parse_transcript(self, transcript):
-        """spectrogram_dataset.py:70-73: unknown chars and the index-0 (blank) label are dropped.
-        With `star` (a single character that is not a label) that character becomes the wildcard id len(labels), one past the last
-        class, for CTCLoss(star=True): every other unknown character is dropped first, then runs of wildcards collapse to one."""
-        transcript = transcript.replace("\n", "")
-        star = getattr(self, "star", None)
-        if star is None:
-            return list(filter(None, [self.labels_map.get(x) for x in list(transcript)]))
-        star_id = len(self.labels_map)
-        ids = list(filter(None, [star_id if x == star else self.labels_map.get(x) for x in list(transcript)]))
-        return [i for k, i in enumerate(ids) if not (i == star_id and k > 0 and ids[k - 1] == star_id)]
 
-    def __getitem__(self, index):
-        row = self.df.iloc[index]
-        if self.caching and index in self._cache:
-            return self._cache[index]
-        item = (self.parse_audio(row.audio_filepath), self.parse_transcript(row.text))
-        if self.caching:
-            self._cache[index] = item
-        return item
-
-    def __len__(self):
-        return self.size
-
-
-class WaveformDataset(Dataset):
+class WaveformDataset(_ManifestDataset):
     """The dataset behind `get_loader(front_end="gpu")`: the manifest and labels of SpectrogramDataset, but an item is `(waveform (n,) float32
     CPU tensor, transcript ids)` — workers only read WAV files (same scaling as SpectrogramDataset.parse_audio) and transcripts; the
     spectrogram is made per batch on the GPU.  Pre-computed spectrograms (`.npy` / `.pt`) cannot be augmented as waveforms and are refused.
@@ -566,15 +578,8 @@ class WaveformDataset(Dataset):
     GPU (ops.wave_resample) — while `__getitem__` returns the waveform converted on the host (`resample_waveform`)."""
 
     def __init__(self, audio_conf, manifest_filepath, labels, caching=False, perturb=False, resample=False, star=None):
-        import pandas as pd
-        self.df = pd.read_csv(manifest_filepath)
-        self.size = len(self.df)
-        if isinstance(labels, str):
-            labels = dict([(v, k) for k, v in pd.read_csv(labels).to_dict()["label"].items()])
-        self.labels_map = labels
-        self.star = _check_star(star, labels)
-        self.audio_conf, self.caching, self.resample = audio_conf, caching, bool(resample)
-        self._cache, self._raw_cache = {}, {}
+        super().__init__(audio_conf, manifest_filepath, labels, caching, resample, star)
+        self._raw_cache = {}
         for f in self.df.audio_filepath:
             if str(f).endswith((".npy", ".pt")):
                 raise ValueError(f"front_end='gpu' reads waveforms, but the manifest lists a pre-computed spectrogram: {f} "
@@ -583,8 +588,6 @@ class WaveformDataset(Dataset):
             warnings.warn("asr_amd.data (front_end='gpu'): speed_volume_perturb is not implemented, ignored — its sox tempo time-stretch "
                           "needs a resampling kernel of its own and is a separate issue; noise_dir and spec_augment are applied on the GPU")
 
-    parse_transcript = SpectrogramDataset.parse_transcript
-
     def parse_audio(self, path):
         sr, y = _read_wav(path)
         if sr != self.audio_conf.sample_rate:
@@ -592,18 +595,6 @@ class WaveformDataset(Dataset):
                 raise ValueError(f"{path}: {sr} Hz, expected {self.audio_conf.sample_rate} Hz audio")
             y = resample_waveform(y, sr, self.audio_conf.sample_rate)
         return torch.from_numpy(np.ascontiguousarray(y, dtype=np.float32))
-
-    def __getitem__(self, index):
-        if self.caching and index in self._cache:
-            return self._cache[index]
-        row = self.df.iloc[index]
-        item = (self.parse_audio(row.audio_filepath), self.parse_transcript(row.text))
-        if self.caching:
-            self._cache[index] = item
-        return item
-
-    def __len__(self):
-        return self.size
 
     def parse_audio_raw(self, path):
         """`parse_audio` for the packed feed: a numpy array, int16 for a 16-bit mono file (its raw samples), float32 otherwise; with
@@ -620,14 +611,10 @@ class WaveformDataset(Dataset):
     def get_raw(self, index):
         """Item `index` as `(parse_audio_raw's array, transcript ids)`, with resample=True `(samples, rate, transcript ids)`; `caching=True`
         keeps these arrays (a cache of their own)."""
-        if self.caching and index in self._raw_cache:
-            return self._raw_cache[index]
-        row = self.df.iloc[index]
-        audio = self.parse_audio_raw(row.audio_filepath)
-        item = (*audio, self.parse_transcript(row.text)) if self.resample else (audio, self.parse_transcript(row.text))
-        if self.caching:
-            self._raw_cache[index] = item
-        return item
+        def make(row):
+            audio = self.parse_audio_raw(row.audio_filepath)
+            return (*audio, self.parse_transcript(row.text)) if self.resample else (audio, self.parse_transcript(row.text))
+        return self._cached(self._raw_cache, index, make)
 
     def raw_items(self):
         """A Dataset over the same manifest whose items are `get_raw`'s: what the workers of the packed feed read."""
@@ -647,10 +634,6 @@ class _RawWaveforms(Dataset):
 
 def _waveform_batch(batch):
     return batch
-
-
-WAVE_ALIGN = 8                     # every utterance of a packed batch starts at a multiple of 8 elements: 128-bit loads on the device
-WAVE_MAX_ELEMS = 2 ** 31 - 1       # offsets are int64 on the host and int32 on the device
 
 
 def packed_layout(lengths, limit=WAVE_MAX_ELEMS):

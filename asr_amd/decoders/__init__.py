@@ -649,12 +649,13 @@ def assemble_transcript(texts, offsets, seg_start, seg_end, seg_flags, order, sc
 
 def check_segment_options(who, threshold, min_gap, pad, max_len, decode_batch):
     """The argument checks of transcribe_posteriors / DeepSpeech.transcribe_long: ValueError naming the option."""
-    if isinstance(decode_batch, bool) or int(decode_batch) != decode_batch or int(decode_batch) < 1:
+    from ..ops import _is_int
+    if not _is_int(decode_batch, 1):
         raise ValueError(f"{who}: decode_batch must be a positive integer, got {decode_batch!r}")
     if not (0.0 < float(threshold) <= 1.0):              # (NaN fails too)
         raise ValueError(f"{who}: threshold must lie in (0, 1], got {threshold!r}")
     for name, v, lo in (("min_gap", min_gap, 1), ("pad", pad, 0), ("max_len", max_len, 2)):
-        if isinstance(v, bool) or int(v) != v or int(v) < lo:
+        if not _is_int(v, lo):
             raise ValueError(f"{who}: {name} must be an integer >= {lo}, got {v!r}")
 
 

@@ -11,6 +11,7 @@ import math
 import threading
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1339,13 +1340,45 @@ def _sizes_i32(sizes, B: int, dev):
     return sizes.to(device=dev, dtype=torch.int32).contiguous().view(-1)
 
 
+def _posteriors(who, x, name="probs", off_gpu=ValueError, what="(B,T,C)", empty=None):
+    """The host path of every consumer of posteriors: x is (B,T,C) fp32 on the GPU with contiguous classes -> (B, T, C, device, ld_b,
+    ld_t), the strides as the C entries take them (a dimension of one entry may carry the stride 0, which they refuse: it becomes 1).
+    off_gpu: how a tensor off the GPU is refused.  ValueError: by name, like a non-tensor, before the shape; DS2LibraryError: with
+    _chk_f32's text; None: not here, the caller does it after its other checks (_chk_align_args).  what: the shape as the refusal
+    spells it.  empty: the refusal of an empty dimension ({shape}: x's), None = left to the C entry."""
+    if off_gpu is ValueError:
+        if not torch.is_tensor(x):
+            raise ValueError(f"{who}: {name} must be a tensor")
+        if not x.is_cuda:
+            raise ValueError(f"{who}: {name} must be a GPU tensor (no CPU fallback exists)")
+    if x.dim() != 3 or x.stride(2) != 1:
+        raise ValueError(f"{who}: {name} must be {what} with a contiguous class dim")
+    B, T, Cc = x.shape
+    if empty is not None and min(B, T, Cc) < 1:
+        raise ValueError(f"{who}: " + empty.format(shape=(B, T, Cc)))
+    if off_gpu is not None:
+        _chk_f32(x)
+    ld_b, ld_t = x.stride(0), x.stride(1)
+    if B <= 1 or T <= 1:                                 # (the common case costs nothing: these wrappers front kernels of 20 us)
+        ld_b, ld_t = ld_b if B > 1 else max(ld_b, 1), ld_t if T > 1 else max(ld_t, 1)
+    return B, T, Cc, x.device, ld_b, ld_t
+
+
+def _chk_on_dev(who, dev, dtype, tensors):
+    """tensors: name -> tensor or None; each one given must be contiguous, of `dtype` and on `dev`"""
+    for name, t in tensors.items():
+        if t is not None and (t.dtype != dtype or t.device != dev or not t.is_contiguous()):
+            raise ValueError(f"{who}: {name} must be a contiguous {str(dtype).replace('torch.', '')} tensor on {dev}")
+
+
+def _is_int(v, lo, hi=None) -> bool:
+    """v is an integer (an int, or a float or array scalar that equals one; not a bool) in [lo, hi]"""
+    return not (isinstance(v, bool) or int(v) != v or int(v) < lo or (hi is not None and int(v) > hi))
+
+
 def greedy_decode(probs: Tensor, sizes: Tensor | None = None, blank: int = 0):
     """probs (B,T,C) fp32 on the GPU -> (ids (B,T) i32, offsets (B,T) i32, lengths (B) i32), all on the GPU."""
-    _chk_f32(probs)
-    if probs.dim() != 3 or probs.stride(2) != 1:
-        raise ValueError("greedy_decode: probs must be (B,T,C) with a contiguous class dim")
-    B, T, C = probs.shape
-    dev = probs.device
+    B, T, C, dev, ld_b, ld_t = _posteriors("greedy_decode", probs, off_gpu=_lib.DS2LibraryError)
     sizes = _sizes_i32(sizes, B, dev)
     ids = torch.empty((B, T), dtype=torch.int32, device=dev)
     offs = torch.empty((B, T), dtype=torch.int32, device=dev)
@@ -1353,7 +1386,7 @@ def greedy_decode(probs: Tensor, sizes: Tensor | None = None, blank: int = 0):
     lib = _lib.load()
     n = lib.ds2_greedy_decode_workspace_bytes(B, T)
     ws = torch.empty(n, dtype=torch.uint8, device=dev)
-    _lib.check(lib.ds2_greedy_decode_f32(probs.data_ptr(), probs.stride(0), probs.stride(1), B, T, C,
+    _lib.check(lib.ds2_greedy_decode_f32(probs.data_ptr(), ld_b, ld_t, B, T, C,
                                          _ptr(sizes), blank, ids.data_ptr(), offs.data_ptr(),
                                          lens.data_ptr(), ws.data_ptr(), n, _stream()), "ds2_greedy_decode_f32")
     return ids, offs, lens
@@ -1396,22 +1429,21 @@ def edit_distance(seq: Tensor, a_off, a_len, b_off, b_len, max_len: int | None =
     return dist
 
 
-def _chk_align_args(who, x, ints, star_penalty=None):
-    """The checks of the aligner wrappers, a malformed argument before a tensor off the GPU.  ints: name -> int32 tensor or None, all of
-    them but `targets` with one entry per utterance.  Returns star_penalty as a float (None without one)."""
-    if x.dim() != 3 or x.stride(2) != 1:
-        raise ValueError(f"{who}: x must be (B,T,C) with a contiguous class dim")
-    B, dev = x.shape[0], x.device
-    for name, t in ints.items():
-        if t is not None and (t.dtype != torch.int32 or t.device != dev or not t.is_contiguous()):
-            raise ValueError(f"{who}: {name} must be a contiguous int32 tensor on {dev}")
+def _chk_align_args(who, x, ints, star_penalty=None, off_gpu=None):
+    """The checks of the aligner wrappers, a malformed argument before a tensor off the GPU (off_gpu None; else as _posteriors takes it).
+    ints: name -> int32 tensor or None, all of them but `targets` with one entry per utterance.  Returns _posteriors' six and
+    star_penalty as a float (None without one)."""
+    geo = _posteriors(who, x, "x", off_gpu)
+    B, dev = geo[0], geo[3]
+    _chk_on_dev(who, dev, torch.int32, ints)
     if any(t is not None and t.numel() != B for name, t in ints.items() if name != "targets"):
         raise ValueError(f"{who}: offsets / lengths{' / flags' if 'flags' in ints else ''} do not match the batch of {B}")
     p = None if star_penalty is None else float(star_penalty)
     if p is not None and not (p <= 0.0 and math.isfinite(p)):
         raise ValueError(f"{who}: star_penalty must be finite and <= 0, got {star_penalty}")
-    _chk_f32(x)
-    return p
+    if off_gpu is None:
+        _chk_f32(x)
+    return (*geo, p)
 
 
 def _ctc_align(who, entry, x, targets, tgt_off, in_lens, tgt_lens, max_u, is_log, shape, star=None):
@@ -1420,9 +1452,7 @@ def _ctc_align(who, entry, x, targets, tgt_off, in_lens, tgt_lens, max_u, is_log
     ints = dict(targets=targets, tgt_off=tgt_off, tgt_lens=tgt_lens, in_lens=in_lens)
     if star is not None:
         ints["flags"] = star[1]
-    p = _chk_align_args(who, x, ints, star[0] if star is not None else None)
-    B, T, Cc = x.shape
-    dev = x.device
+    B, T, Cc, dev, ld_b, ld_t, p = _chk_align_args(who, x, ints, star[0] if star is not None else None)
     shape = tuple(int(v) for v in shape)
     n_tok = targets.numel()
     score = torch.empty(B, dtype=torch.float32, device=dev)
@@ -1434,7 +1464,7 @@ def _ctc_align(who, entry, x, targets, tgt_off, in_lens, tgt_lens, max_u, is_log
     lib = _lib.load()
     wsb = getattr(lib, entry[:-len("f32")] + "workspace_bytes")(B, T, int(max_u), *(shape if len(shape) == 2 else ()))
     ws = _ws(wsb, dev)
-    _lib.check(getattr(lib, entry)(x.data_ptr(), x.stride(0), x.stride(1), B, T, Cc, 1 if is_log else 0, tok(targets), tgt_off.data_ptr(),
+    _lib.check(getattr(lib, entry)(x.data_ptr(), ld_b, ld_t, B, T, Cc, 1 if is_log else 0, tok(targets), tgt_off.data_ptr(),
                                    _ptr(in_lens), tgt_lens.data_ptr(), int(max_u), *shape, *(() if star is None else (p, _ptr(star[1]))),
                                    score.data_ptr(), states.data_ptr(), tok(tok_start), tok(tok_end), tok(tok_logp), ws.data_ptr(), wsb,
                                    _stream()), entry)
@@ -1465,11 +1495,10 @@ def ctc_forced_align_tiled(x: Tensor, targets: Tensor, tgt_off: Tensor, in_lens:
 def ctc_star_row(x: Tensor, in_lens: Tensor | None, is_log: bool, star_penalty: float):
     """The wildcard's emission of ctc_forced_align_star alone: g (B,T) f32 with g[b,t] = max_c e[b,t,c] + star_penalty for t < T_b and
     -inf beyond (the library leaves those frames unwritten).  One launch that reads x once (ds2_ctc_align_star_row_f32)."""
-    p = _chk_align_args("ctc_star_row", x, dict(in_lens=in_lens), star_penalty)
-    B, T, Cc = x.shape
-    g = torch.full((B, T), float("-inf"), dtype=torch.float32, device=x.device)
+    B, T, Cc, dev, ld_b, ld_t, p = _chk_align_args("ctc_star_row", x, dict(in_lens=in_lens), star_penalty)
+    g = torch.full((B, T), float("-inf"), dtype=torch.float32, device=dev)
     lib = _lib.load()
-    _lib.check(lib.ds2_ctc_align_star_row_f32(x.data_ptr(), x.stride(0), x.stride(1), B, T, Cc, 1 if is_log else 0, _ptr(in_lens), p,
+    _lib.check(lib.ds2_ctc_align_star_row_f32(x.data_ptr(), ld_b, ld_t, B, T, Cc, 1 if is_log else 0, _ptr(in_lens), p,
                                               g.data_ptr(), _stream()), "ds2_ctc_align_star_row_f32")
     return g
 
@@ -1512,18 +1541,12 @@ def ctc_keyword_search(x: Tensor, kw_labels: Tensor, kw_off: Tensor, kw_lens: Te
         raise ValueError(f"{who}: max_kw_len must lie in [0, {KWS_MAX_LEN}] (one wavefront holds a keyword), got {max_kw_len}")
     if not 1 <= int(max_hits) <= KWS_MAX_HITS:
         raise ValueError(f"{who}: max_hits must lie in [1, {KWS_MAX_HITS}], got {max_hits}")
-    if not x.is_cuda:
-        raise ValueError(f"{who}: x must be a GPU tensor (no CPU fallback exists)")
+    B, T, Cc, dev, ld_b, ld_t, _ = _chk_align_args(who, x, dict(in_lens=in_lens), off_gpu=ValueError)
     K = kw_lens.numel()
     if K < 1 or kw_off.numel() != K or thr.numel() != K:
         raise ValueError(f"{who}: {kw_off.numel()} offsets / {K} lengths / {thr.numel()} thresholds (one each per keyword, at least one)")
-    _chk_align_args(who, x, dict(in_lens=in_lens))
-    for name, t, dt in (("kw_labels", kw_labels, torch.int32), ("kw_off", kw_off, torch.int32), ("kw_lens", kw_lens, torch.int32),
-                        ("thr", thr, torch.float32)):
-        if t.dtype != dt or t.device != x.device or not t.is_contiguous():
-            raise ValueError(f"{who}: {name} must be a contiguous {str(dt).replace('torch.', '')} tensor on {x.device}")
-    B, T, Cc = x.shape
-    dev = x.device
+    _chk_on_dev(who, dev, torch.int32, dict(kw_labels=kw_labels, kw_off=kw_off, kw_lens=kw_lens))
+    _chk_on_dev(who, dev, torch.float32, dict(thr=thr))
     max_hits = int(max_hits)
     fscore = torch.empty((B, K, T), dtype=torch.float32, device=dev)
     fstart = torch.empty((B, K, T), dtype=torch.int32, device=dev)
@@ -1534,7 +1557,6 @@ def ctc_keyword_search(x: Tensor, kw_labels: Tensor, kw_off: Tensor, kw_lens: Te
     lib = _lib.load()
     wsb = lib.ds2_ctc_kws_workspace_bytes(B, T, K, max_hits)
     ws = _ws(wsb, dev)
-    ld_b, ld_t = (x.stride(d) if x.size(d) > 1 else max(x.stride(d), 1) for d in (0, 1))      # (a dim of one entry may carry the stride 0)
     _lib.check(lib.ds2_ctc_kws_f32(x.data_ptr(), ld_b, ld_t, B, T, Cc, 1 if is_log else 0, _ptr(in_lens),
                                    _ptr(kw_labels) if kw_labels.numel() else None, kw_off.data_ptr(), kw_lens.data_ptr(), K, int(max_kw_len),
                                    thr.data_ptr(), max_hits, fscore.data_ptr(), fstart.data_ptr(), hstart.data_ptr(), hend.data_ptr(),
@@ -1561,25 +1583,15 @@ def ctc_segment(probs: Tensor, sizes: Tensor | None = None, blank: int = 0, thre
     first max_segs segments while n_segs still reports the full count.  Unused slots hold (-1, -1, 0).  Two launches on the current
     stream, nothing is copied back."""
     who = "ctc_segment"
-    if not torch.is_tensor(probs):
-        raise ValueError(f"{who}: probs must be a tensor")
     for name, v, lo in (("min_gap", min_gap, 1), ("pad", pad, 0), ("max_len", max_len, 2)):
-        if isinstance(v, bool) or int(v) != v or int(v) < lo or int(v) > 0x7fffffff:
+        if not _is_int(v, lo, 0x7fffffff):
             raise ValueError(f"{who}: {name} must be an integer >= {lo}, got {v!r}")
     thr = float(threshold)
     if not (0.0 < thr <= 1.0):                           # (NaN fails too)
         raise ValueError(f"{who}: threshold must lie in (0, 1], got {threshold!r}")
-    if not probs.is_cuda:
-        raise ValueError(f"{who}: probs must be a GPU tensor (no CPU fallback exists)")
-    if probs.dim() != 3 or probs.stride(2) != 1:
-        raise ValueError(f"{who}: probs must be (B,T,C) with a contiguous class dim")
-    B, T, Cc = probs.shape
-    if min(B, T, Cc) < 1:
-        raise ValueError(f"{who}: empty probs {tuple(probs.shape)}")
+    B, T, Cc, dev, ld_b, ld_t = _posteriors(who, probs, empty="empty probs {shape}")
     if not 0 <= int(blank) < Cc:
         raise ValueError(f"{who}: blank {blank} outside the {Cc} classes")
-    _chk_f32(probs)
-    dev = probs.device
     sizes = _sizes_i32(sizes, B, dev)
     min_gap, pad, max_len = int(min_gap), int(pad), int(max_len)
     max_segs = segment_max_segs(T, min_gap, max_len) if max_segs is None else int(max_segs)
@@ -1590,7 +1602,6 @@ def ctc_segment(probs: Tensor, sizes: Tensor | None = None, blank: int = 0, thre
     lib = _lib.load()
     wsb = lib.ds2_ctc_segment_workspace_bytes(B, T)
     ws = _ws(wsb, dev)
-    ld_b, ld_t = (probs.stride(d) if probs.size(d) > 1 else max(probs.stride(d), 1) for d in (0, 1))
     _lib.check(lib.ds2_ctc_segment_f32(probs.data_ptr(), ld_b, ld_t, B, T, Cc, _ptr(sizes), int(blank), math.log(thr) if is_log else thr,
                                        min_gap, pad, max_len, max_segs, seg[0].data_ptr(), seg[1].data_ptr(), seg[2].data_ptr(),
                                        n_segs.data_ptr(), ws.data_ptr(), wsb, _stream()), "ds2_ctc_segment_f32")
@@ -1605,25 +1616,18 @@ def ctc_segment_gather(probs: Tensor, seg_b: Tensor, seg_start: Tensor, seg_len:
     who = "ctc_segment_gather"
     if not all(torch.is_tensor(t) for t in (probs, seg_b, seg_start, seg_len)):
         raise ValueError(f"{who}: probs, seg_b, seg_start and seg_len must be tensors")
-    if isinstance(t_max, bool) or int(t_max) != t_max or not 1 <= int(t_max) <= 0x7fffffff:
+    if not _is_int(t_max, 1, 0x7fffffff):
         raise ValueError(f"{who}: t_max must be a positive integer, got {t_max!r}")
-    if not probs.is_cuda:
-        raise ValueError(f"{who}: probs must be a GPU tensor (no CPU fallback exists)")
-    if probs.dim() != 3 or probs.stride(2) != 1 or min(probs.shape) < 1:
-        raise ValueError(f"{who}: probs must be a non-empty (B,T,C) with a contiguous class dim")
+    what = "a non-empty (B,T,C)"
+    B, T, Cc, dev, ld_b, ld_t = _posteriors(who, probs, what=what, empty=f"probs must be {what} with a contiguous class dim")
     S = seg_b.numel()
     if seg_start.numel() != S or seg_len.numel() != S:
         raise ValueError(f"{who}: {S} / {seg_start.numel()} / {seg_len.numel()} utterances, starts and lengths")
-    for name, t in (("seg_b", seg_b), ("seg_start", seg_start), ("seg_len", seg_len)):
-        if t.dtype != torch.int32 or t.device != probs.device or not t.is_contiguous():
-            raise ValueError(f"{who}: {name} must be a contiguous int32 tensor on {probs.device}")
-    _chk_f32(probs)
-    B, T, Cc = probs.shape
-    out = torch.empty((S, int(t_max), Cc), dtype=torch.float32, device=probs.device)
-    out_sizes = torch.empty((S,), dtype=torch.int32, device=probs.device)
+    _chk_on_dev(who, dev, torch.int32, dict(seg_b=seg_b, seg_start=seg_start, seg_len=seg_len))
+    out = torch.empty((S, int(t_max), Cc), dtype=torch.float32, device=dev)
+    out_sizes = torch.empty((S,), dtype=torch.int32, device=dev)
     if S == 0:
         return out, out_sizes
-    ld_b, ld_t = (probs.stride(d) if probs.size(d) > 1 else max(probs.stride(d), 1) for d in (0, 1))
     _lib.check(_lib.load().ds2_ctc_segment_gather_f32(probs.data_ptr(), ld_b, ld_t, B, T, Cc, seg_b.data_ptr(), seg_start.data_ptr(),
                                                       seg_len.data_ptr(), S, int(t_max), out.data_ptr(), out_sizes.data_ptr(), _stream()),
                "ds2_ctc_segment_gather_f32")
@@ -1639,15 +1643,11 @@ def ctc_beam_decode(probs: Tensor, sizes: Tensor | None = None, blank: int = 0, 
     (ds2_ctc_beam_decode_hot_f32); the language model's candidate limit then applies without a language model too.
     labels_out: a contiguous (B,K,T) int32 GPU tensor to receive the labels instead of a fresh one (MWERLoss passes the front of the
     buffer that also holds the references, so that one edit-distance launch sees both)."""
-    _chk_f32(probs)
-    if probs.dim() != 3 or probs.stride(2) != 1:
-        raise ValueError("ctc_beam_decode: probs must be (B,T,C) with a contiguous class dim")
+    B, T, C, dev, ld_b, ld_t = _posteriors("ctc_beam_decode", probs, off_gpu=_lib.DS2LibraryError)
     lib = _lib.load()
     K = int(beam_width)
     if not 1 <= K <= lib.ds2_ctc_beam_max_width():
         raise ValueError(f"ctc_beam_decode: beam_width {K} outside the supported 1..{lib.ds2_ctc_beam_max_width()}")
-    B, T, C = probs.shape
-    dev = probs.device
     if hotwords is not None and hotwords.C != C:
         raise ValueError(f"ctc_beam_decode: the hotwords were bound to {hotwords.C} classes, probs have {C}")
     if hotwords is not None and hotwords.blank != int(blank):
@@ -1669,7 +1669,7 @@ def ctc_beam_decode(probs: Tensor, sizes: Tensor | None = None, blank: int = 0, 
     scores = torch.empty((B, K), dtype=torch.float32, device=dev)
     n = lib.ds2_ctc_beam_workspace_bytes(B, T, K)
     ws = _ws(n, dev)
-    search = (probs.data_ptr(), probs.stride(0), probs.stride(1), B, T, C, _ptr(sizes), int(blank), K, int(cutoff_top_n), float(cutoff_prob))
+    search = (probs.data_ptr(), ld_b, ld_t, B, T, C, _ptr(sizes), int(blank), K, int(cutoff_top_n), float(cutoff_prob))
     out = (labels.data_ptr(), offs.data_ptr(), lens.data_ptr(), scores.data_ptr(), ws.data_ptr(), n, _stream())
     tab = lm.device_tables(dev) if lm is not None else None
     lm_args = (None, 0, 0, 0, -1) if lm is None else (tab.data_ptr(), tab.numel(), lm.order, lm.mode, lm.space if lm.space is not None else -1)
@@ -1690,7 +1690,6 @@ _BASIS_CACHE = {}
 
 def dft_basis_host(n_fft: int, window: str):
     """The numpy half of `dft_basis` (no device needed): the (n_fft, 2*(n_fft/2+1)) float32 array, computed in float64 and rounded once."""
-    import numpy as np
     from scipy.signal import get_window
     w = get_window(window, n_fft, fftbins=True).astype(np.float64)
     k = np.arange(n_fft)[:, None]
@@ -1711,24 +1710,53 @@ def dft_basis(n_fft: int, window: str, device) -> Tensor:
     return _BASIS_CACHE[key]
 
 
-def spectrogram(audio: Tensor, n_samples: Tensor, n_fft: int, hop: int, window: str = "hamming", pad_mode: str = "constant",
-                normalize: bool = False, frames: int = 0):
-    """audio (B, L) fp32 GPU waveforms (rows zero/garbage beyond n_samples) -> (spect (B,1,n_fft/2+1,T), frames (B,) int32 CPU)."""
+def _spectrogram(entry, audio, n_samples, n_fft, hop, window, pad_mode, normalize, frames, aug=None):
+    """spectrogram and spectrogram_augmented.  entry: the C entry, sized by its own *_workspace_bytes; aug: what the second one adds,
+    (noise, (noise_base, noise_period, noise_start, noise_level), (freq_masks, time_masks))."""
     _chk_f32(audio)
     assert audio.dim() == 2 and audio.stride(1) == 1
     lib = _lib.load()
-    B = audio.size(0)
+    B, dev = audio.size(0), audio.device
     n_host = [int(v) for v in n_samples.tolist()]
     fr = [lib.ds2_spectrogram_frames(n, hop) for n in n_host]
     T = frames or max(max(fr), 1)
-    n_dev = torch.as_tensor(n_host, dtype=torch.int32).to(audio.device)
-    out = torch.empty((B, 1, n_fft // 2 + 1, T), dtype=torch.float32, device=audio.device)
-    wsb = lib.ds2_spectrogram_workspace_bytes(B, T, n_fft, hop)
-    ws = _ws(wsb, audio.device)
-    _lib.check(lib.ds2_spectrogram_f32(audio.data_ptr(), audio.stride(0), n_dev.data_ptr(), B, T, n_fft, hop,
-                                       dft_basis(n_fft, window, audio.device).data_ptr(), {"constant": 0, "reflect": 1}[pad_mode],
-                                       int(bool(normalize)), out.data_ptr(), ws.data_ptr(), wsb, _stream()), "ds2_spectrogram_f32")
+    n_dev = torch.as_tensor(n_host, dtype=torch.int32).to(dev)
+    extra, keep = (), []                                 # device copies stay alive until the call is enqueued
+    if aug is not None:
+        noise, nz, masks = aug
+
+        def per_utt(x, dtype, shape):
+            t = torch.as_tensor(x, dtype=dtype).to(dev).contiguous()
+            assert tuple(t.shape) == shape, f"expected shape {shape}, got {tuple(t.shape)}"
+            return t
+        extra = (None, 0, None, None, None, None)
+        if any(a is not None for a in nz):
+            assert all(a is not None for a in nz) and noise is not None, "noise_base, noise_period, noise_start, noise_level and noise go together"
+            _chk_f32(noise)
+            assert noise.dim() == 1 and noise.device == dev
+            keep = [per_utt(a, dtype, (B,)) for a, dtype in zip(nz, (torch.int64, torch.int32, torch.int32, torch.float32))]
+            extra = (noise.data_ptr(), noise.numel(), *[t.data_ptr() for t in keep])
+        for m in masks:
+            if m is None:
+                extra += (None, 0)
+            else:
+                mt = torch.as_tensor(m, dtype=torch.int32).to(dev).contiguous()
+                assert mt.dim() == 3 and mt.size(0) == B and mt.size(2) == 2, f"masks: expected (B, M, 2), got {tuple(mt.shape)}"
+                keep.append(mt)
+                extra += (mt.data_ptr() if mt.size(1) else None, mt.size(1))
+    out = torch.empty((B, 1, n_fft // 2 + 1, T), dtype=torch.float32, device=dev)
+    wsb = getattr(lib, entry[:-len("f32")] + "workspace_bytes")(B, T, n_fft, hop)
+    ws = _ws(wsb, dev)
+    _lib.check(getattr(lib, entry)(audio.data_ptr(), audio.stride(0), n_dev.data_ptr(), B, T, n_fft, hop, dft_basis(n_fft, window, dev).data_ptr(),
+                                   {"constant": 0, "reflect": 1}[pad_mode], int(bool(normalize)), *extra, out.data_ptr(), ws.data_ptr(), wsb,
+                                   _stream()), entry)
     return out, torch.tensor([min(f, T) for f in fr], dtype=torch.int32)
+
+
+def spectrogram(audio: Tensor, n_samples: Tensor, n_fft: int, hop: int, window: str = "hamming", pad_mode: str = "constant",
+                normalize: bool = False, frames: int = 0):
+    """audio (B, L) fp32 GPU waveforms (rows zero/garbage beyond n_samples) -> (spect (B,1,n_fft/2+1,T), frames (B,) int32 CPU)."""
+    return _spectrogram("ds2_spectrogram_f32", audio, n_samples, n_fft, hop, window, pad_mode, normalize, frames)
 
 
 def spectrogram_augmented(audio: Tensor, n_samples: Tensor, n_fft: int, hop: int, window: str = "hamming", pad_mode: str = "constant",
@@ -1738,47 +1766,8 @@ def spectrogram_augmented(audio: Tensor, n_samples: Tensor, n_fft: int, hop: int
     include/ds2hip.h).  noise: 1-D fp32 GPU noise bank (or None); noise_base (B) int64, noise_period / noise_start (B) int32, noise_level
     (B) fp32 (0 = no noise for that utterance), all four given or none; freq_masks / time_masks: (B, M, 2) int32 [lo, hi) bin / frame ranges,
     M <= 8, or None.  Per-utterance arrays may live on the host: they are copied to audio's device.  Returns (spect, frames) as `spectrogram`."""
-    _chk_f32(audio)
-    assert audio.dim() == 2 and audio.stride(1) == 1
-    lib = _lib.load()
-    B, dev = audio.size(0), audio.device
-    n_host = [int(v) for v in n_samples.tolist()]
-    fr = [lib.ds2_spectrogram_frames(n, hop) for n in n_host]
-    T = frames or max(max(fr), 1)
-    n_dev = torch.as_tensor(n_host, dtype=torch.int32).to(dev)
-
-    def per_utt(x, dtype, shape):
-        t = torch.as_tensor(x, dtype=dtype).to(dev).contiguous()
-        assert tuple(t.shape) == shape, f"expected shape {shape}, got {tuple(t.shape)}"
-        return t
-    keep = []                                            # device copies stay alive until the call is enqueued
-    nz = (noise_base, noise_period, noise_start, noise_level)
-    if any(a is not None for a in nz):
-        assert all(a is not None for a in nz) and noise is not None, "noise_base, noise_period, noise_start, noise_level and noise go together"
-        _chk_f32(noise)
-        assert noise.dim() == 1 and noise.device == dev
-        keep = [per_utt(noise_base, torch.int64, (B,)), per_utt(noise_period, torch.int32, (B,)), per_utt(noise_start, torch.int32, (B,)),
-                per_utt(noise_level, torch.float32, (B,))]
-        nz_ptrs, noise_ptr, noise_len = [t.data_ptr() for t in keep], noise.data_ptr(), noise.numel()
-    else:
-        nz_ptrs, noise_ptr, noise_len = [None] * 4, None, 0
-    masks = []
-    for m in (freq_masks, time_masks):
-        if m is None:
-            masks.append((None, 0))
-        else:
-            mt = torch.as_tensor(m, dtype=torch.int32).to(dev).contiguous()
-            assert mt.dim() == 3 and mt.size(0) == B and mt.size(2) == 2, f"masks: expected (B, M, 2), got {tuple(mt.shape)}"
-            keep.append(mt)
-            masks.append((mt.data_ptr() if mt.size(1) else None, mt.size(1)))
-    out = torch.empty((B, 1, n_fft // 2 + 1, T), dtype=torch.float32, device=dev)
-    wsb = lib.ds2_spectrogram_aug_workspace_bytes(B, T, n_fft, hop)
-    ws = _ws(wsb, dev)
-    _lib.check(lib.ds2_spectrogram_aug_f32(audio.data_ptr(), audio.stride(0), n_dev.data_ptr(), B, T, n_fft, hop,
-                                           dft_basis(n_fft, window, dev).data_ptr(), {"constant": 0, "reflect": 1}[pad_mode],
-                                           int(bool(normalize)), noise_ptr, noise_len, *nz_ptrs, masks[0][0], masks[0][1], masks[1][0],
-                                           masks[1][1], out.data_ptr(), ws.data_ptr(), wsb, _stream()), "ds2_spectrogram_aug_f32")
-    return out, torch.tensor([min(f, T) for f in fr], dtype=torch.int32)
+    return _spectrogram("ds2_spectrogram_aug_f32", audio, n_samples, n_fft, hop, window, pad_mode, normalize, frames,
+                        aug=(noise, (noise_base, noise_period, noise_start, noise_level), (freq_masks, time_masks)))
 
 
 TEMPO_SEGMENT_MS, TEMPO_SEARCH_MS, TEMPO_OVERLAP_MS = 82.0, 14.68, 12.0
@@ -1801,6 +1790,12 @@ def tempo_out_samples(n: int, tempo: float) -> int:
     return n_out
 
 
+def _host_array(x, dtype=np.int64):
+    """A per-utterance host description (a list, a numpy array or a tensor of any device) as a contiguous numpy array: int64, or float64
+    for tempo_gain's factors and gains."""
+    return np.ascontiguousarray(x.tolist() if isinstance(x, Tensor) else x, dtype=dtype)
+
+
 def tempo_gain(audio: Tensor, n_samples, tempo, gain, sample_rate: int, segment_ms: float = TEMPO_SEGMENT_MS,
                search_ms: float = TEMPO_SEARCH_MS, overlap_ms: float = TEMPO_OVERLAP_MS):
     """Tempo (WSOLA time-stretch, pitch kept) and gain perturbation of a waveform batch (ds2_tempo_gain_f32, contract in include/ds2hip.h;
@@ -1809,16 +1804,14 @@ def tempo_gain(audio: Tensor, n_samples, tempo, gain, sample_rate: int, segment_
     host values; the kernel is given G = float32(10 ** (gain / 20)).
     Returns (out (B, max n_out) fp32 GPU, exact zeros beyond each n_out; n_out (B) int32 GPU; offsets (B, Kmax) int32 GPU: the search
     result d_k of every segment, 0 beyond an utterance's own segments).  The host-side lengths are `tempo_out_samples(n, tempo)`."""
-    import numpy as np
     _chk_f32(audio)
     assert audio.dim() == 2 and audio.stride(1) == 1
     lib = _lib.load()
     B, dev = audio.size(0), audio.device
-    n_host = np.ascontiguousarray([int(v) for v in (n_samples.tolist() if isinstance(n_samples, Tensor) else n_samples)], dtype=np.int32)
-    f_host = np.ascontiguousarray(tempo.tolist() if isinstance(tempo, Tensor) else tempo, dtype=np.float64)
-    g_db = np.ascontiguousarray(gain.tolist() if isinstance(gain, Tensor) else gain, dtype=np.float64)
+    n_host, f_host, g_db = _host_array(n_samples), _host_array(tempo, np.float64), _host_array(gain, np.float64)
     assert n_host.shape == f_host.shape == g_db.shape == (B,), f"n_samples, tempo and gain: one value per utterance ({B})"
     assert B == 0 or int(n_host.max()) <= audio.size(1), "n_samples exceeds the batch's row length"
+    n_host = n_host.astype(np.int32)
     g_host = np.ascontiguousarray(np.float32(10.0 ** (g_db / 20.0)))
     S, _, O = tempo_sizes(sample_rate, segment_ms, search_ms, overlap_ms)
     n_out = [tempo_out_samples(n, f) for n, f in zip(n_host.tolist(), f_host.tolist())]
@@ -1835,8 +1828,41 @@ def tempo_gain(audio: Tensor, n_samples, tempo, gain, sample_rate: int, segment_
     return out, n_out_dev, offsets
 
 
-WAVE_ALIGN = 8                     # every utterance of a packed waveform buffer starts at a multiple of this many ELEMENTS
-WAVE_MAX_ELEMS = 2 ** 31 - 1       # device offsets are int32
+WAVE_ALIGN = 8                     # every utterance of a packed waveform buffer starts at a multiple of this many ELEMENTS: 128-bit loads
+WAVE_MAX_ELEMS = 2 ** 31 - 1       # offsets are int64 on the host and int32 on the device (asr_amd.data lays batches out by these two)
+
+
+def _packed_description(who, packed, offsets, lengths, src_index, rates=None):
+    """The checks that wave_unpack and wave_resample share: the packed buffer and its host description -> (offsets, lengths, src_index as
+    (B) int64 arrays, B, the buffer's elements).  rates: wave_resample's, a list that is counted with the others.  The lengths' own
+    bounds are the caller's: they differ."""
+    if packed.dtype not in (torch.int16, torch.float32) or not packed.is_cuda or packed.dim() != 1 or not packed.is_contiguous():
+        raise ValueError(f"{who}: packed must be a contiguous 1-D int16 or fp32 GPU tensor")
+    off, ln = _host_array(offsets).reshape(-1), _host_array(lengths).reshape(-1)
+    B, total = int(ln.size), int(packed.numel())
+    src = np.arange(B, dtype=np.int64) if src_index is None else _host_array(src_index).reshape(-1)
+    counts = [("offsets", off.size), ("lengths", B)] + ([] if rates is None else [("rates", len(rates))])
+    if B == 0 or any(n != B for _, n in counts) or src.size != B:
+        raise ValueError(f"{who}: " + ", ".join(f"{k} ({n})" for k, n in counts) + f" and src_index ({src.size}): one value per utterance, "
+                         "at least one")
+    if total % WAVE_ALIGN or total > WAVE_MAX_ELEMS:
+        raise ValueError(f"{who}: packed holds {total} elements: a multiple of {WAVE_ALIGN}, at most 2^31 - 1")
+    if (off < 0).any() or (off % WAVE_ALIGN).any():
+        raise ValueError(f"{who}: every offset is a non-negative multiple of {WAVE_ALIGN} elements, got {off.tolist()}")
+    if (off + (ln + WAVE_ALIGN - 1) // WAVE_ALIGN * WAVE_ALIGN > total).any():
+        raise ValueError(f"{who}: an utterance (rounded up to {WAVE_ALIGN} elements) ends beyond the {total} packed elements")
+    if (src < 0).any() or (src >= B).any():
+        raise ValueError(f"{who}: src_index outside [0, {B})")
+    return off, ln, src, B, total
+
+
+def _upload_i32(dev, rows, wide=None):
+    """Per-utterance host integers for a kernel: rows (B values each) -> one (len(rows), B) int32 image on dev, from pinned memory with
+    one asynchronous copy.  wide: a (B) int64 array that travels whole, as int32 pairs, in two more rows."""
+    img = np.stack([np.asarray(r, dtype=np.int64) for r in rows]).astype(np.int32)
+    if wide is not None:
+        img = np.concatenate([img, wide.view(np.int32).reshape(2, -1)])
+    return torch.from_numpy(img).pin_memory().to(dev, non_blocking=True)
 
 
 def wave_unpack(packed: Tensor, offsets, lengths, src_index=None, n_max: Optional[int] = None) -> Tensor:
@@ -1846,33 +1872,16 @@ def wave_unpack(packed: Tensor, offsets, lengths, src_index=None, n_max: Optiona
     src_index[b] (default: b); n_max defaults to max(lengths).  The description is checked here, on the host (ValueError: an offset that
     is negative or not a multiple of 8, a length below 0 or above n_max, an utterance whose 8-aligned end passes the buffer, an index outside
     [0, B)), then uploaded from pinned memory with one asynchronous copy: the call does not block the host."""
-    import numpy as np
-    if packed.dtype not in (torch.int16, torch.float32) or not packed.is_cuda or packed.dim() != 1 or not packed.is_contiguous():
-        raise ValueError("wave_unpack: packed must be a contiguous 1-D int16 or fp32 GPU tensor")
-    off = np.asarray(offsets.tolist() if isinstance(offsets, Tensor) else offsets, dtype=np.int64).reshape(-1)
-    ln = np.asarray(lengths.tolist() if isinstance(lengths, Tensor) else lengths, dtype=np.int64).reshape(-1)
-    B, total = int(ln.size), int(packed.numel())
-    src = np.arange(B, dtype=np.int64) if src_index is None else np.asarray(
-        src_index.tolist() if isinstance(src_index, Tensor) else src_index, dtype=np.int64).reshape(-1)
-    if B == 0 or off.size != B or src.size != B:
-        raise ValueError(f"wave_unpack: offsets ({off.size}), lengths ({B}) and src_index ({src.size}): one value per utterance, at least one")
+    off, ln, src, B, total = _packed_description("wave_unpack", packed, offsets, lengths, src_index)
     if n_max is None:
         n_max = int(ln.max())
     n_max = int(n_max)
-    if total % WAVE_ALIGN or total > WAVE_MAX_ELEMS:
-        raise ValueError(f"wave_unpack: packed holds {total} elements: a multiple of {WAVE_ALIGN}, at most 2^31 - 1")
-    if (off < 0).any() or (off % WAVE_ALIGN).any():
-        raise ValueError(f"wave_unpack: every offset is a non-negative multiple of {WAVE_ALIGN} elements, got {off.tolist()}")
     if (ln < 0).any() or (ln > n_max).any():
         raise ValueError(f"wave_unpack: lengths lie in [0, n_max = {n_max}], got {ln.tolist()}")
-    if (off + (ln + WAVE_ALIGN - 1) // WAVE_ALIGN * WAVE_ALIGN > total).any():
-        raise ValueError(f"wave_unpack: an utterance (rounded up to {WAVE_ALIGN} elements) ends beyond the {total} packed elements")
-    if (src < 0).any() or (src >= B).any():
-        raise ValueError(f"wave_unpack: src_index outside [0, {B})")
     dev = packed.device
     if n_max == 0:
         return torch.zeros((B, 0), dtype=torch.float32, device=dev)
-    meta = torch.from_numpy(np.stack([off, ln, src]).astype(np.int32)).pin_memory().to(dev, non_blocking=True)
+    meta = _upload_i32(dev, (off, ln, src))
     out = torch.empty((B, n_max), dtype=torch.float32, device=dev)
     _lib.check(_lib.load().ds2_wave_unpack_f32(packed.data_ptr() if total else None, total, 0 if packed.dtype == torch.int16 else 1,
                                                meta[0].data_ptr(), meta[1].data_ptr(), meta[2].data_ptr(), B, n_max, out.data_ptr(),
@@ -1892,8 +1901,7 @@ _TAPS_DEVICE_CACHE = {}
 def resample_ratio(fs: int, ft: int, zeros: int = RESAMPLE_ZEROS, rolloff: float = RESAMPLE_ROLLOFF) -> Tuple[int, int, int]:
     """(L, M, J) of a rate pair: L = ft / gcd, M = fs / gcd, J = ceil(zeros / (rolloff * min(1, L / M))) taps per side.  ValueError for a
     pair outside what the resampler supports: a ratio outside [1/8, 8] or a table of more than RESAMPLE_MAX_TAPS taps."""
-    import math
-    if isinstance(fs, bool) or isinstance(ft, bool) or int(fs) != fs or int(ft) != ft or fs < 1 or ft < 1:
+    if not (_is_int(fs, 1) and _is_int(ft, 1)):
         raise ValueError(f"resample: sample rates are positive integers, got {fs!r} -> {ft!r}")
     fs, ft = int(fs), int(ft)
     g = math.gcd(fs, ft)
@@ -1913,7 +1921,6 @@ def resample_taps(fs: int, ft: int, zeros: int = RESAMPLE_ZEROS, rolloff: float 
     """The (L, P = 2 J) fp32 polyphase table of the contract in include/ds2hip.h (a host numpy array, cached per argument tuple):
     tab[p][j] = fp32(s sinc(s tau) w(tau)), tau = p / L + J - 1 - j, s = rolloff min(1, L / M), w the Kaiser window of half-width
     zeros / s — computed in fp64, rounded once.  fs == ft has no table: ValueError."""
-    import numpy as np
     key = (int(fs), int(ft), int(zeros), float(rolloff), float(beta))
     if key not in _TAPS_CACHE:
         L, M, J = resample_ratio(fs, ft, zeros, rolloff)
@@ -1931,7 +1938,6 @@ def resample_taps(fs: int, ft: int, zeros: int = RESAMPLE_ZEROS, rolloff: float 
 
 def resample_out_samples(n: int, fs: int, ft: int) -> int:
     """ceil(n L / M): the length of an n-sample utterance at fs after conversion to ft (ds2_resample_out_samples; a host function)."""
-    import math
     g = math.gcd(int(fs), int(ft))
     n_out = _lib.load().ds2_resample_out_samples(int(n), int(ft) // g, int(fs) // g)
     if n_out < 0:
@@ -1943,7 +1949,6 @@ def _resample_tables(pairs, device):
     """(table buffer, {pair: base}) on `device` covering the rate pairs of one call.  ONE buffer per device holds the tables of every
     pair seen so far, in order of first use (so it is bounded by RESAMPLE_MAX_TABLE taps = 16 MiB however the rates mix in the batches);
     a new pair makes a longer buffer, the old one stays alive for the launches that hold it.  No pair: (None, {})."""
-    import numpy as np
     key = str(device)
     buf, bases = _TAPS_DEVICE_CACHE.get(key, (None, {}))
     new = [p for p in pairs if p not in bases]
@@ -1969,28 +1974,10 @@ def wave_resample(packed: Tensor, offsets, lengths, rates, src_index=None, targe
     once per rate pair and device, everything is sized on the host and uploaded from pinned memory with one asynchronous copy: nothing is
     copied back.  `n_out`: the resampled lengths when the caller has them already (resample_out_samples per utterance; the loader has).
     Returns (batch (B, n_out_max) fp32 GPU in src_index order, n_out: a list of B ints in UTTERANCE order)."""
-    import numpy as np
-    if packed.dtype not in (torch.int16, torch.float32) or not packed.is_cuda or packed.dim() != 1 or not packed.is_contiguous():
-        raise ValueError("wave_resample: packed must be a contiguous 1-D int16 or fp32 GPU tensor")
-    off = np.asarray(offsets.tolist() if isinstance(offsets, Tensor) else offsets, dtype=np.int64).reshape(-1)
-    ln = np.asarray(lengths.tolist() if isinstance(lengths, Tensor) else lengths, dtype=np.int64).reshape(-1)
-    fs = [int(v) for v in (rates.tolist() if isinstance(rates, (Tensor, np.ndarray)) else rates)]
-    B, total = int(ln.size), int(packed.numel())
-    src = np.arange(B, dtype=np.int64) if src_index is None else np.asarray(
-        src_index.tolist() if isinstance(src_index, Tensor) else src_index, dtype=np.int64).reshape(-1)
-    if B == 0 or off.size != B or src.size != B or len(fs) != B:
-        raise ValueError(f"wave_resample: offsets ({off.size}), lengths ({B}), rates ({len(fs)}) and src_index ({src.size}): one value per "
-                         "utterance, at least one")
-    if total % WAVE_ALIGN or total > WAVE_MAX_ELEMS:
-        raise ValueError(f"wave_resample: packed holds {total} elements: a multiple of {WAVE_ALIGN}, at most 2^31 - 1")
-    if (off < 0).any() or (off % WAVE_ALIGN).any():
-        raise ValueError(f"wave_resample: every offset is a non-negative multiple of {WAVE_ALIGN} elements, got {off.tolist()}")
+    fs = _host_array(rates).reshape(-1).tolist()
+    off, ln, src, B, total = _packed_description("wave_resample", packed, offsets, lengths, src_index, fs)
     if (ln < 0).any():
         raise ValueError(f"wave_resample: negative length in {ln.tolist()}")
-    if (off + (ln + WAVE_ALIGN - 1) // WAVE_ALIGN * WAVE_ALIGN > total).any():
-        raise ValueError(f"wave_resample: an utterance (rounded up to {WAVE_ALIGN} elements) ends beyond the {total} packed elements")
-    if (src < 0).any() or (src >= B).any():
-        raise ValueError(f"wave_resample: src_index outside [0, {B})")
     target_rate = int(target_rate)
     lmj = {r: resample_ratio(r, target_rate) for r in sorted(set(fs))}
     if n_out is None:
@@ -2009,7 +1996,7 @@ def wave_resample(packed: Tensor, offsets, lengths, rates, src_index=None, targe
     tab, bases = _resample_tables(tuple((r, target_rate) for r in lmj if lmj[r][:2] != (1, 1)), dev)
     rows = [off, ln, src, [lmj[r][0] for r in fs], [lmj[r][1] for r in fs], [lmj[r][2] for r in fs],
             [bases.get((r, target_rate), 0) for r in fs]]
-    meta = torch.from_numpy(np.stack([np.asarray(r, dtype=np.int64) for r in rows]).astype(np.int32)).pin_memory().to(dev, non_blocking=True)
+    meta = _upload_i32(dev, rows)
     out = torch.empty((B, n_out_max), dtype=torch.float32, device=dev)
     _lib.check(_lib.load().ds2_wave_resample_f32(packed.data_ptr() if total else None, total, 0 if packed.dtype == torch.int16 else 1,
                                                  *[meta[i].data_ptr() for i in range(7)], tab.data_ptr() if tab is not None else None,
@@ -2032,13 +2019,12 @@ def reverb(audio: Tensor, n_samples, rir: Optional[Tensor], rir_base, rir_taps, 
     a length outside [0, n_max], taps outside [0, reverb_max_taps()], a slice outside the bank), then uploaded from pinned memory as one
     int32 image with one asynchronous copy.  Returns a new (B, n_max) fp32 GPU tensor, exact zeros beyond each n_b; n_max defaults to
     max(n_samples)."""
-    import numpy as np
     if audio.dtype != torch.float32 or not audio.is_cuda or audio.dim() != 2 or audio.stride(1) != 1 or audio.size(0) == 0:
         raise ValueError("reverb: audio must be a (B >= 1, L) fp32 GPU tensor with contiguous rows")
     if rir is not None and (rir.dtype != torch.float32 or not rir.is_cuda or rir.dim() != 1 or not rir.is_contiguous()):
         raise ValueError("reverb: rir must be a contiguous 1-D fp32 GPU tensor")
     B, dev = audio.size(0), audio.device
-    n, base, taps = (np.asarray(v.tolist() if isinstance(v, Tensor) else v, dtype=np.int64).reshape(-1) for v in (n_samples, rir_base, rir_taps))
+    n, base, taps = (_host_array(v).reshape(-1) for v in (n_samples, rir_base, rir_taps))
     if n.size != B or base.size != B or taps.size != B:
         raise ValueError(f"reverb: n_samples ({n.size}), rir_base ({base.size}) and rir_taps ({taps.size}): one value per row ({B})")
     if n_max is None:
@@ -2053,10 +2039,10 @@ def reverb(audio: Tensor, n_samples, rir: Optional[Tensor], rir_base, rir_taps, 
         raise ValueError(f"reverb: an impulse response lies outside the bank of {elems} taps (at most 2^31 - 1)")
     if n_max == 0:
         return torch.zeros((B, 0), dtype=torch.float32, device=dev)
-    meta = torch.from_numpy(np.concatenate([n.astype(np.int32), taps.astype(np.int32), base.view(np.int32)])).pin_memory().to(dev, non_blocking=True)
+    meta = _upload_i32(dev, (n, taps), wide=base)                # rows: n, taps, and base's int32 pairs in two
     out = torch.empty((B, n_max), dtype=torch.float32, device=dev)
-    _lib.check(_lib.load().ds2_reverb_f32(audio.data_ptr(), audio.stride(0), meta[:B].data_ptr(), rir.data_ptr() if elems else None, elems,
-                                          meta[2 * B:].data_ptr(), meta[B:2 * B].data_ptr(), B, n_max, out.data_ptr(), out.stride(0),
+    _lib.check(_lib.load().ds2_reverb_f32(audio.data_ptr(), audio.stride(0), meta[0].data_ptr(), rir.data_ptr() if elems else None, elems,
+                                          meta[2].data_ptr(), meta[1].data_ptr(), B, n_max, out.data_ptr(), out.stride(0),
                                           _stream()), "ds2_reverb_f32")
     return out
 
