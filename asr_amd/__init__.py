@@ -3,7 +3,7 @@ zakuro-ai/asr (`asr_deepspeech`).  See DESIGN.md / INTEGRATION.md."""
 __version__ = "0.1.0"
 
 from .ctc import CTCLoss, MWERLoss
-from .decoders import BeamCTCDecoder, CTCAligner, GreedyDecoder, KeywordSpotter
+from .decoders import BeamCTCDecoder, CTCAligner, CTCConfidence, GreedyDecoder, KeywordSpotter
 from .functional import _collate_fn, check_loss, reduce_tensor, to_np
 from .modules import DeepSpeech
 from .optim import FusedAdamW

@@ -117,6 +117,9 @@ SIGNATURES = {
     "ds2_ctc_star_loss_f32": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, f32, vp, vp, vp, i32, f32, i32, vp, sz, vp]),
     "ds2_ctc_mwer_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "ds2_ctc_mwer_f32": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, f32, i32, i32, vp, sz, vp]),
+    "ds2_ctc_conf_max_unit_labels": (i32, []),
+    "ds2_ctc_conf_workspace_bytes": (sz, [i32, i32, i32]),
+    "ds2_ctc_conf_f32": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, i32, vp, sz, vp]),
     "ds2_ctc_batch_mean_f32": (i32, [vp, i32, vp, vp]),
     "ds2_ctc_align_workspace_bytes": (sz, [i32, i32, i32]),
     "ds2_ctc_align_f32": (i32, [vp, i64, i64, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),

@@ -684,3 +684,5 @@ extern "C" int ds2_ctc_loss_f32(const float* logits, int ld, int T, int B, int C
 // Minimum-error-rate training on an n-best list (ds2_ctc_mwer_*): the MW = true instances of the two lattice kernels above, a weights
 // launch and a gradient kernel that folds the K occupancies of an utterance into one row
 #include "ctc_mwer.h"
+// Word and character confidences (ds2_ctc_conf_*): the MW = true lattices at K = 1 and one short masked backward sweep per unit
+#include "ctc_conf.h"

@@ -7,7 +7,8 @@ scores a whole batch with `Decoder.score_batch`, one HIP launch (csrc/edit_dista
 `assemble_alignments`.  `KeywordSpotter.search` finds WHERE keywords were said without a decode or a transcript (csrc/ctc_kws.h); its
 record assembly is `assemble_detections`.  `transcribe_posteriors` turns ONE long recording's posteriors into timed segments: cut at
 pauses and packed into decode batches on the GPU (csrc/ctc_segment.h); its host half is `plan_segment_batches`, `words_from_offsets`
-and `assemble_transcript`."""
+and `assemble_transcript`.  `CTCConfidence.score` says HOW SURE a text is of each word or character, as a conditional probability
+(csrc/ctc_conf.h); its host half is `confidence_units`."""
 from __future__ import annotations
 
 import math
@@ -590,6 +591,97 @@ class KeywordSpotter(Decoder):
             warnings.warn(f"KeywordSpotter.search: more than max_hits={self.max_hits} detections for {len(overflowed)} (utterance, keyword) "
                           f"pair(s), the first: utterance {b}, keyword {kw!r}; the rest were dropped", RuntimeWarning, stacklevel=2)
         return records if frame_seconds is None else add_seconds(records, float(frame_seconds))
+
+
+CONF_MAX_UNIT_LABELS = 63
+
+
+def confidence_units(text, spans, n_frames, unit="word", margin=0):
+    """Pure host half of CTCConfidence.score: a hypothesis `text` (one character per label) and the aligner's (start, end) span of
+    every label (end exclusive) -> [(text, lo, hi, start, end)], the units ds2_ctc_conf_f32 scores: the labels [lo, hi) in the frames
+    [start, end).  unit="word": the runs of characters between spaces (leading, trailing and doubled spaces make no word), from the
+    first label's start to the last label's end; unit="char": every label, the spaces among them.  The window is the span widened by
+    `margin` frames on each side and clipped to [0, n_frames]."""
+    if unit not in ("word", "char"):
+        raise ValueError(f"unit must be 'word' or 'char', got {unit!r}")
+    if isinstance(margin, bool) or int(margin) != margin or int(margin) < 0:
+        raise ValueError(f"margin must be an integer >= 0, got {margin!r}")
+    if len(spans) != len(text):
+        raise ValueError(f"confidence_units: {len(spans)} spans for {len(text)} characters")
+    margin, n_frames = int(margin), int(n_frames)
+    if unit == "char":
+        ranges = [(i, i + 1) for i in range(len(text))]
+    else:
+        ranges, first = [], None
+        for i, ch in enumerate(text + " "):
+            if ch == " ":
+                if first is not None:
+                    ranges.append((first, i))
+                first = None
+            elif first is None:
+                first = i
+    return [(text[lo:hi], lo, hi, max(int(spans[lo][0]) - margin, 0), min(int(spans[hi - 1][1]) + margin, n_frames)) for lo, hi in ranges]
+
+
+class CTCConfidence(Decoder):
+    """HOW SURE a transcript is of each of its words or characters.  `score` aligns the texts (CTCAligner.align), turns every word or
+    character into a unit (its labels, and its span as a frame window) and runs one library call (`ds2_ctc_conf_f32`, contract in
+    include/ds2hip.h; restated by tests/ctc_conf_oracle.py): the two lattices of the loss and one short masked backward sweep per unit.
+    A unit's confidence is a true conditional probability in [0, 1]: that the whole utterance spells the text, given that the audio
+    outside the unit's window spells the rest of the text.  It is exact and needs no calibration set.  The reference has nothing like it.
+    NOT MEASURED: how the number calibrates on real recordings (whether the words at 0.9 are right nine times in ten), and which
+    `margin` serves them: no margin was tuned, the default 0 takes the aligner's span as it is.  A widened window takes frames from
+    its neighbours, which lowers what the frames outside can account for; one that reaches the first or last frame while labels of
+    the text remain outside it has no possible context (NaN).  A unit of more than 63 labels is not scored (NaN)."""
+
+    def __init__(self, labels, blank_index=0):
+        if blank_index != 0:
+            raise ValueError("CTCConfidence: the kernels take class 0 as the blank (blank_index must be 0)")
+        super().__init__(labels, blank_index)
+
+    def score(self, probs, sizes, texts, is_log=False, unit="word", margin=0):
+        """probs (B,T,C) as decode() takes them (probabilities, or log-probabilities with is_log=True), sizes (B) valid frames or None,
+        texts: B strings over the labels.  CTCAligner.align on the same posteriors gives the spans; the units, offsets and lengths go
+        up in one pinned upload; one library call; one device-to-host copy.  Returns per utterance {"nll": -log p(text), "units":
+        [(text, start, end, confidence)]} (frames, end exclusive: the unit's window; confidence = exp(logconf), NaN for a unit that was
+        not scored); an utterance whose alignment is infeasible has "units": [].  Host tensors are uploaded first: there is no CPU
+        implementation."""
+        from .. import ops
+        confidence_units("", [], 0, unit, margin)          # the options, before any work
+        probs = torch.as_tensor(probs)
+        if probs.dim() != 3:
+            raise ValueError(f"CTCConfidence.score: probs must be (B,T,C), got {tuple(probs.shape)}")
+        B, T = int(probs.shape[0]), int(probs.shape[1])
+        if len(texts) != B or not all(isinstance(t, str) for t in texts):
+            raise ValueError(f"CTCConfidence.score: texts must be {B} strings")
+        if not probs.is_cuda:
+            probs = probs.to(_device("CTCConfidence", ".score"))
+        probs = probs.float()
+        records = CTCAligner(self.labels).align(probs, sizes, texts, is_log=is_log)
+        sizes_h = [T] * B if sizes is None else [int(v) for v in torch.as_tensor(sizes).reshape(-1).tolist()]
+        frames = [min(max(n, 0), T) for n in sizes_h]
+        targets = encode_transcripts(texts, self.labels)
+        units = [confidence_units(texts[b], [(t[1], t[2]) for t in r["tokens"]], frames[b], unit, margin) if r["tokens"] else []
+                 for b, r in enumerate(records)]
+        lens = [len(t) for t in targets]
+        W = max([len(u) for u in units] + [1])
+        n_tok, max_u = sum(lens), max(lens, default=0)
+        grid = np.zeros((4, B, W), np.int64)
+        for b, us in enumerate(units):
+            for w, (_, lo, hi, s, e) in enumerate(us):
+                grid[:, b, w] = lo, hi, s, e
+        # one int32 image: hyp_off (int64, as int32 pairs), hyp_lens, in_lens, n_units, unit_lo / unit_hi / win_start / win_end, labels
+        off = np.cumsum([0] + lens[:-1]).astype(np.int64) if B else np.zeros(0, np.int64)
+        flat = np.concatenate([off.view(np.int32), lens, frames, [len(u) for u in units], grid.reshape(-1), [i for t in targets for i in t], [0]])   # (a last 0: the label array is never empty)
+        d = ops._upload_i32(probs.device, (flat,))[0]
+        logits = (probs if is_log else torch.log(probs)).transpose(0, 1).contiguous()
+        g0 = 5 * B
+        arr = d[g0:g0 + 4 * B * W].view(4, B, W)
+        nll, logconf = ops.ctc_confidence(logits, d[g0 + 4 * B * W:], d[:2 * B].view(torch.int64), d[2 * B:3 * B], d[3 * B:4 * B], max_u,
+                                          d[4 * B:5 * B], arr[0], arr[1], arr[2], arr[3])
+        out = torch.cat((nll, logconf.reshape(-1))).cpu().numpy().astype(np.float64)
+        conf = np.exp(out[B:].reshape(B, W))
+        return [{"nll": float(out[b]), "units": [(u[0], u[3], u[4], float(conf[b, w])) for w, u in enumerate(us)]} for b, us in enumerate(units)]
 
 
 def plan_segment_batches(lengths, batch_size):

@@ -376,6 +376,61 @@ class DeepSpeech(nn.Module):
         probs = self.posteriors_long(spect, window, overlap, batch_size)
         return transcribe_posteriors(probs, dec, threshold, min_gap, pad, max_len, decode_batch, 2.0 * float(self.audio_conf.window_stride))
 
+    # -- word and character confidences (no counterpart in the reference) -------------------------
+    def confidence(self, inputs, input_sizes, decoder=None, unit="word", margin=0):
+        """How sure the text of each utterance is of its words: what transcribe() does, then CTCConfidence.score on the same
+        posteriors with the decoded texts.  Returns one {"text", "words", "confidence"} record per utterance, "text" and "words" as
+        transcribe() gives them; with unit="word", "confidence" is a list parallel to "words"; with unit="char" it has one entry per
+        character of "text".  An entry is the probability that the utterance spells the text, given that the audio outside the unit's
+        aligned span (widened by `margin` frames) spells the rest; NaN where it was not scored (a unit above 63 labels, a text whose
+        alignment is infeasible).  NOT MEASURED: how the number calibrates on real recordings and which margin serves them (see
+        decoders.CTCConfidence).  The model is left in eval mode."""
+        from ..decoders import CTCConfidence, GreedyDecoder, words_from_offsets
+        dec = decoder or self.decoder or GreedyDecoder(self.labels)
+        fs = 2.0 * float(self.audio_conf.window_stride)
+        self.eval()
+        with torch.no_grad():
+            out, output_sizes = self.forward(inputs, input_sizes)
+            strings, offsets = dec.decode(out, output_sizes)
+            scored = CTCConfidence(self.labels).score(out, output_sizes, [s[0] for s in strings], unit=unit, margin=margin)
+        records = []
+        for s, o, r in zip(strings, offsets, scored):
+            words = [w + (w[1] * fs, w[2] * fs) for w in words_from_offsets(s[0], o[0])]
+            want = len(words) if unit == "word" else len(s[0])
+            conf = [u[3] for u in r["units"]] if r["units"] else [float("nan")] * want
+            assert len(conf) == want, (len(conf), want)
+            records.append({"text": s[0], "words": words, "confidence": conf})
+        return records
+
+    def confidence_long(self, spect, window=2000, overlap=200, batch_size=32, decoder=None, threshold=0.9, min_gap=25, pad=5, max_len=1000,
+                        decode_batch=64, unit="word", margin=0):
+        """transcribe_long() with confidences: posteriors_long once, decoders.transcribe_posteriors for the segments and their texts,
+        then per batch of decoders.plan_segment_batches one ops.ctc_segment_gather and one CTCConfidence.score.  Returns
+        transcribe_long's record in which every segment gains "confidence" (as in confidence(): parallel to the segment's "words", or
+        one entry per character of its "text") and "units": [(text, start, end, confidence)] with the frames counted in the whole
+        recording.  What is not measured about transcribe_long's defaults and about the confidence holds here too."""
+        from ..decoders import CTCConfidence, GreedyDecoder, check_segment_options, plan_segment_batches, transcribe_posteriors
+        dec = decoder or self.decoder or GreedyDecoder(self.labels)
+        check_segment_options("confidence_long", threshold, min_gap, pad, max_len, decode_batch)     # before the forward passes
+        probs = self.posteriors_long(spect, window, overlap, batch_size)
+        result = transcribe_posteriors(probs, dec, threshold, min_gap, pad, max_len, decode_batch, 2.0 * float(self.audio_conf.window_stride))
+        segs = result["segments"]
+        scorer = CTCConfidence(self.labels)
+        for idx in plan_segment_batches([s["end"] - s["start"] for s in segs], decode_batch):
+            host = torch.zeros((3, len(idx)), dtype=torch.int32)          # one int32 image: utterance indices (all 0), starts, lengths
+            host[1] = torch.tensor([segs[i]["start"] for i in idx], dtype=torch.int32)
+            host[2] = torch.tensor([segs[i]["end"] - segs[i]["start"] for i in idx], dtype=torch.int32)
+            d = host.to(probs.device)
+            packed, sizes = ops.ctc_segment_gather(probs[None], d[0], d[1], d[2], int(host[2, 0]))
+            for i, r in zip(idx, scorer.score(packed, sizes, [segs[i]["text"] for i in idx], unit=unit, margin=margin)):
+                seg = segs[i]
+                want = len(seg["words"]) if unit == "word" else len(seg["text"])
+                conf = [u[3] for u in r["units"]] if r["units"] else [float("nan")] * want
+                assert len(conf) == want, (len(conf), want)
+                seg["confidence"] = conf
+                seg["units"] = [(u[0], u[1] + seg["start"], u[2] + seg["start"], u[3]) for u in r["units"]]
+        return result
+
     # -- evaluation loop (deepspeech.py:161-273) --------------------------------------------------
     def evaluate(self, loader=None, manifest=None, batch_size=None, device="auto", num_workers=32, verbose=False, half=False,
                  output_file=None, main_proc=True, **_unused):

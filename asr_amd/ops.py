@@ -1307,6 +1307,47 @@ def ctc_mwer(logits: Tensor, hyps_dev: Tensor, hyp_off_dev: Tensor, hyp_lens_dev
     return loss, nll_hyp, post, grad
 
 
+def ctc_confidence(logits: Tensor, hyps_dev: Tensor, hyp_off_dev: Tensor, hyp_lens_dev: Tensor, in_lens_dev: Tensor, max_hyp_len: int,
+                   n_units: Tensor, unit_lo: Tensor, unit_hi: Tensor, win_start: Tensor, win_end: Tensor, lattice: int = 0):
+    """Word and character confidences (contract: include/ds2hip.h, ds2_ctc_conf_f32).  logits (T,B,C) as ctc_loss takes them; one
+    hypothesis per utterance as ctc_mwer's slots with K = 1: hyps_dev flat int32 labels, hyp_off_dev (B) int64 offsets into it,
+    hyp_lens_dev (B) int32; n_units (B) int32 and unit_lo / unit_hi / win_start / win_end (B, W_max) int32: unit w of utterance b covers
+    the labels [lo, hi) (at most 63) and the frames [start, end); all on the GPU.  max_hyp_len bounds every hypothesis and sizes the
+    workspace (8 B T (2 max_hyp_len + 1) bytes).  Returns (nll (B), logconf (B, W_max)): log of the probability that the utterance
+    spells its hypothesis given that the frames outside the unit's window spell the rest; NaN for a slot beyond n_units, a unit out of
+    bounds or an impossible context, -inf where the unit cannot be spelled in its window."""
+    _chk_f32(logits)
+    lib = _lib.load()
+    if logits.dim() != 3:
+        raise ValueError(f"ctc_confidence: logits must be (T, B, C), got {tuple(logits.shape)}")
+    T, B, Cc = logits.shape
+    dev = logits.device
+    ld = logits.stride(1) if B > 1 else logits.stride(0)     # (the stride of a dimension of one entry says nothing)
+    if logits.stride(2) != 1 or logits.stride(0) != B * ld or ld < Cc:
+        raise ValueError("ctc_confidence: logits must be (T, B, C) with contiguous classes and a uniform row pitch")
+    if unit_lo.dim() != 2 or unit_lo.shape[0] != B or unit_lo.shape[1] < 1:
+        raise ValueError(f"ctc_confidence: unit_lo must be (B, W_max) with B = {B} and W_max >= 1, got {tuple(unit_lo.shape)}")
+    W = unit_lo.shape[1]
+    _chk_on_dev("ctc_confidence", dev, torch.int32, dict(hyps_dev=hyps_dev, hyp_lens_dev=hyp_lens_dev, in_lens_dev=in_lens_dev, n_units=n_units,
+                                                        unit_lo=unit_lo, unit_hi=unit_hi, win_start=win_start, win_end=win_end))
+    _chk_on_dev("ctc_confidence", dev, torch.int64, dict(hyp_off_dev=hyp_off_dev))
+    if any(t.numel() != B for t in (hyp_off_dev, hyp_lens_dev, in_lens_dev, n_units)):
+        raise ValueError(f"ctc_confidence: offsets / lengths / unit counts do not match B = {B}")
+    if any(tuple(t.shape) != (B, W) for t in (unit_hi, win_start, win_end)):
+        raise ValueError(f"ctc_confidence: the unit arrays do not match (B, W_max) = ({B}, {W})")
+    if not _is_int(max_hyp_len, 0):
+        raise ValueError(f"ctc_confidence: max_hyp_len must be an integer >= 0, got {max_hyp_len!r}")
+    nll = torch.empty(B, dtype=torch.float32, device=dev)
+    logconf = torch.empty(B, W, dtype=torch.float32, device=dev)
+    wsb = lib.ds2_ctc_conf_workspace_bytes(T, B, int(max_hyp_len))
+    ws = _ws(wsb, dev)
+    _lib.check(lib.ds2_ctc_conf_f32(logits.data_ptr(), ld, T, B, Cc, hyps_dev.data_ptr(), hyp_off_dev.data_ptr(),
+                                    hyp_lens_dev.data_ptr(), in_lens_dev.data_ptr(), int(max_hyp_len), n_units.data_ptr(), unit_lo.data_ptr(),
+                                    unit_hi.data_ptr(), win_start.data_ptr(), win_end.data_ptr(), W, nll.data_ptr(), logconf.data_ptr(),
+                                    int(lattice), ws.data_ptr(), wsb, _stream()), "ds2_ctc_conf_f32")
+    return nll, logconf
+
+
 def ctc_batch_mean(nll: Tensor) -> Tensor:
     """(1,) fp32 = nll.sum() / B, on the device in a fixed order (trainers/deepspeech_trainer.py:110-112)."""
     _chk_f32(nll)

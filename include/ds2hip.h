@@ -464,6 +464,48 @@ int ds2_ctc_mwer_f32(const float* logits, int ld, int T, int B, int C, int K, co
                      float* loss_dev, float* nll_hyp_dev, float* post_dev, float* grad, int ldg, float grad_scale, int accumulate,
                      int lattice, void* ws, size_t ws_bytes, void* stream);
 
+/* Word and character confidences: HOW SURE a hypothesis is of one of its parts.  For a hypothesis y and a unit (a label range of y and a
+ * frame window) the result is a true conditional probability in [0, 1]: the probability that the whole utterance spells y, given that
+ * the audio outside the window spells the rest of y.  It is exact and needs no calibration set.  The reference has nothing like it: this
+ * text is the contract, restated in fp64 NumPy by tests/ctc_conf_oracle.py.  Inputs, strides, the fused row log-softmax, blank = 0,
+ * in_lens and the two lattice kernels chosen by `lattice` and 2 * max_hyp_len + 1 <= 128 (which write the same bits) are
+ * ds2_ctc_loss_ex_f32's; the hypotheses are ds2_ctc_mwer_f32's slots with K = 1: hyps_dev int32 labels, utterance b's hypothesis is
+ * hyps_dev[hyp_off_dev[b] ..][: hyp_lens_dev[b]], offsets int64.
+ * Utterance b has T_b valid frames, log-softmax rows e[t][c], a hypothesis y[0..U) with labels in [1, C-1] and S = 2U + 1 states.
+ *  alpha and beta are the plain loss's lattices, the emission of frame t included in both, as the workspace of ds2_ctc_loss_ex_f32
+ *  holds them.  A unit is (lo, hi, ts, te): the labels [lo, hi), 0 <= lo < hi <= U, and the frames [ts, te), 0 <= ts < te <= T_b.
+ *  A     = lse(alpha[ts-1][2lo-1], alpha[ts-1][2lo]), a state that does not exist being -inf; for ts = 0: 0 if lo = 0, else -inf.
+ *          The probability that the frames before the window spell y[:lo].
+ *  Bq    = lse(beta[te][2hi], beta[te][2hi+1]); for te = T_b: 0 if hi = U, else -inf.  The probability that the frames from te on
+ *          spell y[hi:].
+ *  beta' = the plain beta recurrence, the same moves and the same skip rule on label values, started at frame te from beta[te] with
+ *          every state except 2hi and 2hi+1 set to -inf (for te = T_b: started from beta[T_b-1] itself) and run back to frame ts.
+ *  num   = lse over s in {2lo-1, 2lo} of ( alpha[ts-1][s] + lse over the legal moves s -> s' of beta'[ts][s'] );
+ *          for ts = 0: lse(beta'[0][0], beta'[0][1]).
+ *  logconf = NaN if A or Bq is -inf (the context is impossible); else -inf if num is -inf; else min(0, num - (A + Bq)).
+ *  Every lse takes its operands in the order state, state + 1, state + 2 (csrc/ctc_conf.h lists each one), so the bits are defined.
+ * Units: n_units_dev (B) int32 and four (B, W_max) int32 arrays unit_lo / unit_hi / win_start / win_end.  Units are independent of one
+ *  another and may overlap: one call may score words and characters together.  A unit has at most ds2_ctc_conf_max_unit_labels = 63
+ *  labels (one wavefront holds its states).
+ * Outputs: nll_dev (B), the plain loss's value (+inf for an infeasible hypothesis, a label outside [1, C-1] or a length outside
+ *  [0, max_hyp_len], found before anything is read with them); logconf_dev (B, W_max).
+ *  NaN goes to: a unit that breaks a bound (a label range outside [0, U], empty or above 63 labels, a window outside [0, T_b]) — that unit
+ *  alone; the slots w >= n_units[b]; every slot of an utterance whose n_units lies outside [0, W_max], whose hypothesis has a label
+ *  outside [1, C-1] or a length outside [0, max_hyp_len], or which has no frames.  With nll = +inf the rules above hold as they stand.
+ *  Nothing at t >= T_b is read into a result.
+ * Determinism: no float atomics; the bits depend neither on B, nor on the utterance's place in the batch, nor on the slot, nor on the
+ *  lattice kernel, and reruns repeat them.
+ * Refused with a nonzero return before any launch: a null pointer, T, B <= 0, C <= 1, W_max < 1, max_hyp_len < 0, a row pitch below C,
+ *  lattice outside {0, 1}, hypotheses too long for the LDS rows of the chosen lattice kernel, B above 65535, a workspace below
+ *  ds2_ctc_conf_workspace_bytes.
+ * Workspace: lse (T, B) + alpha / beta at pitch 2 * max_hyp_len + 1: 8 B T (2 max_hyp_len + 1) bytes and a row. */
+int ds2_ctc_conf_max_unit_labels(void);
+size_t ds2_ctc_conf_workspace_bytes(int T, int B, int max_hyp_len);
+int ds2_ctc_conf_f32(const float* logits, int ld, int T, int B, int C, const int* hyps_dev, const long long* hyp_off_dev,
+                     const int* hyp_lens_dev, const int* in_lens_dev, int max_hyp_len, const int* n_units_dev, const int* unit_lo_dev,
+                     const int* unit_hi_dev, const int* win_start_dev, const int* win_end_dev, int W_max, float* nll_dev,
+                     float* logconf_dev, int lattice, void* ws, size_t ws_bytes, void* stream);
+
 /* out[0] = sum_b nll[b] / B on the device, fixed summation order: `loss = criterion(...) / inputs.size(0)`,
  * trainers/deepspeech_trainer.py:110-112 */
 int ds2_ctc_batch_mean_f32(const float* nll_dev, int B, float* out_dev, void* stream);
