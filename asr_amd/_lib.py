@@ -156,6 +156,8 @@ SIGNATURES = {
                                           vp, vp, vp, vp, vp, sz, vp]),
     "ds2_edit_distance_workspace_bytes": (sz, [i32, i64]),
     "ds2_edit_distance_i32": (i32, [vp, i64, vp, vp, vp, vp, i32, i64, vp, vp, sz, vp]),
+    "ds2_edit_align_workspace_bytes": (sz, [i32, i64]),
+    "ds2_edit_align_i32": (i32, [vp, i64, vp, vp, vp, vp, i32, i64, vp, vp, vp, vp, sz, vp]),
     "ds2_conv1_bf16_row_pitch": (i32, [i32]),
     "ds2_conv1_bf16_bytes": (sz, [i32, i32, i32, i32]),
     "ds2_conv1_pack_bf16": (i32, [vp, vp, vp]),

@@ -98,6 +98,10 @@ extern "C" int ds2_greedy_decode_f32(const float* probs, long long ld_b, long lo
 #define DS2_EDIT_DISTANCE_TU
 #include "edit_distance.h"
 
+// The edit alignment behind the error breakdown (ds2_edit_align_*): the same column step with its columns kept, and a traceback.
+#define DS2_EDIT_ALIGN_TU
+#include "edit_align.h"
+
 // The pause segmentation of long recordings and the packing of its segments into decode batches (ds2_ctc_segment_*), likewise.
 #define DS2_CTC_SEGMENT_TU
 #include "ctc_segment.h"

@@ -8,7 +8,9 @@ scores a whole batch with `Decoder.score_batch`, one HIP launch (csrc/edit_dista
 record assembly is `assemble_detections`.  `transcribe_posteriors` turns ONE long recording's posteriors into timed segments: cut at
 pauses and packed into decode batches on the GPU (csrc/ctc_segment.h); its host half is `plan_segment_batches`, `words_from_offsets`
 and `assemble_transcript`.  `CTCConfidence.score` says HOW SURE a text is of each word or character, as a conditional probability
-(csrc/ctc_conf.h); its host half is `confidence_units`."""
+(csrc/ctc_conf.h); its host half is `confidence_units`.  `Decoder.align_batch` says WHICH words and characters are wrong: the edit
+alignment behind the distances (csrc/edit_align.h); its host half is `assemble_edit_alignments`, `ErrorReport` adds the records up and
+`reliability` bins confidences against their right / wrong flags."""
 from __future__ import annotations
 
 import math
@@ -54,6 +56,163 @@ def pack_scoring(hypotheses, references):
     return seq, offs[0::2].copy(), lens[0::2].astype(np.int32), offs[1::2].copy(), lens[1::2].astype(np.int32), ref_w, ref_c
 
 
+def _upload_scoring(dev, seq, a_off, a_len, b_off, b_len):
+    """pack_scoring's arrays on the device, as ops.edit_distance / ops.edit_align take them: one pinned int32 image (a_off, b_off as
+    int64, 8-byte aligned at the front, then a_len, b_len, the symbols), one asynchronous copy -> (seq, a_off, a_len, b_off, b_len)."""
+    P = len(a_len)
+    host = torch.empty(6 * P + len(seq), dtype=torch.int32, pin_memory=True)
+    h = host.numpy()
+    h[:2 * P], h[2 * P:4 * P] = a_off.view(np.int32), b_off.view(np.int32)
+    h[4 * P:5 * P], h[5 * P:6 * P], h[6 * P:] = a_len, b_len, seq
+    d = host.to(dev, non_blocking=True)
+    return d[6 * P:], d[:2 * P].view(torch.int64), d[4 * P:5 * P], d[2 * P:4 * P].view(torch.int64), d[5 * P:6 * P]
+
+
+def _check_align_unit(unit):
+    if unit not in ("word", "char", "both"):
+        raise ValueError(f"unit must be 'word', 'char' or 'both', got {unit!r}")
+
+
+def _edit_ops(hyp, ref, a_map, b_map):
+    """The path in forward order from the two maps: every unpaired token in front of the next pair.  (Between two pairs an optimal
+    path leaves tokens of one side only unpaired: one of each would be a cheaper substitution.)"""
+    ops, i, j = [], 0, 0
+    m, n = len(hyp), len(ref)
+    while i < m or j < n:
+        if j < n and int(b_map[j]) < 0:
+            ops.append(("del", None, ref[j], None, j))
+            j += 1
+        elif i < m and int(a_map[i]) < 0:
+            ops.append(("ins", hyp[i], None, i, None))
+            i += 1
+        else:
+            if not (i < m and j < n and int(a_map[i]) == j and int(b_map[j]) == i):
+                raise ValueError(f"assemble_edit_alignments: the maps do not describe one path (hypothesis token {i}, reference token {j})")
+            ops.append(("hit" if hyp[i] == ref[j] else "sub", hyp[i], ref[j], i, j))
+            i, j = i + 1, j + 1
+    return ops
+
+
+def assemble_edit_alignments(hypotheses, references, counts, a_map, b_map, unit="both"):
+    """Pure host half of Decoder.align_batch: the strings + ops.edit_align's arrays on pack_scoring's 2B problems (problem b: pair b's
+    words, problem B + b: its characters; counts (2B,4), a_map / b_map (2B,max_len)) -> one record per pair, {"words": {...}, "chars":
+    {...}} cut to `unit`.  A unit holds "hits", "substitutions", "deletions", "insertions", "distance" (their last three summed),
+    "ref_len", "ops": the path in forward order as (op, hyp_token | None, ref_token | None, hyp_index | None, ref_index | None) with op
+    one of "hit" / "sub" / "del" / "ins", and "hyp_correct": one bool per hypothesis token, True for a hit.  Tokens are `s.split()` and
+    the code points of `s.replace(" ", "")`, as in wer / cer."""
+    _check_align_unit(unit)
+    if len(hypotheses) != len(references):
+        raise ValueError(f"{len(hypotheses)} hypotheses for {len(references)} references")
+    B = len(hypotheses)
+    counts, a_map, b_map = np.asarray(counts), np.asarray(a_map), np.asarray(b_map)
+    if counts.shape != (2 * B, 4) or a_map.shape[0] != 2 * B or b_map.shape[0] != 2 * B:
+        raise ValueError(f"assemble_edit_alignments: arrays of {counts.shape} / {a_map.shape} / {b_map.shape} for {B} pairs")
+    records = []
+    for b, (h, r) in enumerate(zip(hypotheses, references)):
+        rec = {}
+        for key, p, hyp, ref in (("words", b, h.split(), r.split()), ("chars", B + b, list(h.replace(" ", "")), list(r.replace(" ", "")))):
+            if unit != "both" and not key.startswith(unit):
+                continue
+            hits, subs, dels, ins = (int(v) for v in counts[p])
+            path = _edit_ops(hyp, ref, a_map[p], b_map[p])
+            if [sum(o[0] == k for o in path) for k in ("hit", "sub", "del", "ins")] != [hits, subs, dels, ins]:
+                raise ValueError(f"assemble_edit_alignments: the counts of pair {b} ({key}) do not match its maps")
+            correct = [False] * len(hyp)
+            for o in path:
+                if o[0] == "hit":
+                    correct[o[3]] = True
+            rec[key] = {"hits": hits, "substitutions": subs, "deletions": dels, "insertions": ins, "distance": subs + dels + ins,
+                        "ref_len": len(ref), "ops": path, "hyp_correct": correct}
+        records.append(rec)
+    return records
+
+
+class ErrorReport:
+    """The error breakdown over an evaluation: feed it Decoder.align_batch's records batch by batch (`add`), read `summary()` or the text
+    block `format()`.  Host code only.  `top`: how many of the most frequent substitution pairs, deleted tokens and inserted tokens
+    are listed; equal counts are ordered by token, so the output is deterministic."""
+
+    def __init__(self, top=20):
+        if isinstance(top, bool) or int(top) != top or int(top) < 0:
+            raise ValueError(f"ErrorReport: top must be an integer >= 0, got {top!r}")
+        self.top = int(top)
+        self.units = {}
+
+    def add(self, records):
+        for rec in records:
+            for key, u in rec.items():
+                t = self.units.setdefault(key, {"hits": 0, "substitutions": 0, "deletions": 0, "insertions": 0, "ref_len": 0,
+                                                "sub": {}, "del": {}, "ins": {}})
+                for k in ("hits", "substitutions", "deletions", "insertions", "ref_len"):
+                    t[k] += u[k]
+                for op, hyp, ref, _, _ in u["ops"]:
+                    if op != "hit":
+                        tok = (ref, hyp) if op == "sub" else ref if op == "del" else hyp
+                        t[op][tok] = t[op].get(tok, 0) + 1
+        return self
+
+    def summary(self):
+        """Per unit fed so far ("words", "chars"): the four totals, "ref_len", "rate" = (S + D + I) / ref_len and the three partial
+        rates (a ref_len of 0 divides as 1, as in evaluate()), "top_substitutions" [(ref, hyp, count)], "top_deletions" and
+        "top_insertions" [(token, count)]."""
+        out = {}
+        for key in sorted(self.units, reverse=True):      # words before chars
+            t = self.units[key]
+            n = max(t["ref_len"], 1)
+            s, d, i = t["substitutions"], t["deletions"], t["insertions"]
+            first = lambda table: sorted(table.items(), key=lambda kv: (-kv[1], kv[0]))[:self.top]   # noqa: E731
+            out[key] = {"hits": t["hits"], "substitutions": s, "deletions": d, "insertions": i, "ref_len": t["ref_len"],
+                        "rate": (s + d + i) / n, "substitution_rate": s / n, "deletion_rate": d / n, "insertion_rate": i / n,
+                        "top_substitutions": [(ref, hyp, c) for (ref, hyp), c in first(t["sub"])],
+                        "top_deletions": first(t["del"]), "top_insertions": first(t["ins"])}
+        return out
+
+    def format(self):
+        lines = []
+        for key, u in self.summary().items():
+            lines += [f"----- ERRORS: {key} -----",
+                      f"rate {100 * u['rate']:.2f} = substitutions {100 * u['substitution_rate']:.2f} + deletions {100 * u['deletion_rate']:.2f}"
+                      f" + insertions {100 * u['insertion_rate']:.2f}",
+                      f"hits {u['hits']}  substitutions {u['substitutions']}  deletions {u['deletions']}  insertions {u['insertions']}"
+                      f"  reference {key} {u['ref_len']}"]
+            if u["top_substitutions"]:
+                lines += ["substitutions (reference -> hypothesis):"] + [f"{c:>7}  {ref!r} -> {hyp!r}" for ref, hyp, c in u["top_substitutions"]]
+            for name in ("deletions", "insertions"):
+                if u["top_" + name]:
+                    lines += [name + ":"] + [f"{c:>7}  {tok!r}" for tok, c in u["top_" + name]]
+        return "\n".join(lines) + ("\n" if lines else "")
+
+
+def reliability(confidences, correct, bins=10):
+    """A reliability table: do the tokens with confidence near c turn out right a fraction c of the time?  confidences: floats in
+    [0, 1] (e.g. DeepSpeech.confidence's), correct: one bool each (e.g. align_batch's "hyp_correct").  `bins` equal-width bins over
+    [0, 1], the last one closed at 1.  Returns {"bins": [(lo, hi, count, mean_conf, accuracy)] (NaN for an empty bin), "ece": the
+    expected calibration error sum_k count_k / N * |accuracy_k - mean_conf_k| (NaN without a token), "skipped": how many NaN
+    confidences (units that were not scored) were dropped}."""
+    if isinstance(bins, bool) or int(bins) != bins or int(bins) < 1:
+        raise ValueError(f"reliability: bins must be a positive integer, got {bins!r}")
+    bins = int(bins)
+    conf = np.asarray(list(confidences), np.float64).reshape(-1)
+    right = np.asarray(list(correct), bool).reshape(-1)
+    if conf.shape != right.shape:
+        raise ValueError(f"reliability: {conf.size} confidences for {right.size} flags")
+    keep = ~np.isnan(conf)
+    skipped = int(conf.size - keep.sum())
+    conf, right = conf[keep], right[keep]
+    if conf.size and (conf.min() < 0.0 or conf.max() > 1.0):
+        raise ValueError("reliability: a confidence lies outside [0, 1]")
+    which = np.minimum((conf * bins).astype(np.int64), bins - 1)
+    rows, ece = [], 0.0
+    for k in range(bins):
+        sel = which == k
+        cnt = int(sel.sum())
+        mean, acc = (float(conf[sel].mean()), float(right[sel].mean())) if cnt else (float("nan"), float("nan"))
+        rows.append((k / bins, (k + 1) / bins, cnt, mean, acc))
+        if cnt:
+            ece += cnt / conf.size * abs(acc - mean)
+    return {"bins": rows, "ece": ece if conf.size else float("nan"), "skipped": skipped}
+
+
 class Decoder:
     """decoder.py:4-72: labels is {char: index}; index 0 is the CTC blank."""
 
@@ -85,24 +244,39 @@ class Decoder:
         from .. import ops
         dev = _device("Decoder.score_batch", "")
         seq, a_off, a_len, b_off, b_len, ref_w, ref_c = pack_scoring(hypotheses, references)
-        B, P = len(ref_w), 2 * len(ref_w)
+        B = len(ref_w)
         out = torch.empty((B, 4), dtype=torch.int64)
         if B == 0:
             return out
         max_len = int(max(a_len.max(), b_len.max()))
-        # one int32 image: a_off, b_off (int64, 8-byte aligned at the front), a_len, b_len, symbols
-        host = torch.empty(6 * P + len(seq), dtype=torch.int32, pin_memory=True)
-        h = host.numpy()
-        h[:2 * P], h[2 * P:4 * P] = a_off.view(np.int32), b_off.view(np.int32)
-        h[4 * P:5 * P], h[5 * P:6 * P], h[6 * P:] = a_len, b_len, seq
-        d = host.to(dev, non_blocking=True)
-        dist = ops.edit_distance(d[6 * P:], d[:2 * P].view(torch.int64), d[4 * P:5 * P], d[2 * P:4 * P].view(torch.int64),
-                                 d[5 * P:6 * P], max_len=max_len).cpu().long()
+        dist = ops.edit_distance(*_upload_scoring(dev, seq, a_off, a_len, b_off, b_len), max_len=max_len).cpu().long()
         if int(dist.min()) < 0:
             raise RuntimeError("Decoder.score_batch: the edit-distance kernel rejected a problem")
         out[:, 0], out[:, 2] = dist[:B], dist[B:]
         out[:, 1], out[:, 3] = torch.from_numpy(ref_w), torch.from_numpy(ref_c)
         return out
+
+    def align_batch(self, hypotheses, references, unit="both"):
+        """WHICH words and characters of B (hypothesis, reference) pairs are right: the edit alignment behind score_batch's distances,
+        in one HIP launch -> one record per pair, {"words": {...}, "chars": {...}} cut to `unit` ("word", "char" or "both"); the unit
+        records are assemble_edit_alignments'.  One pinned host-to-device copy of the packed ids (pack_scoring), one launch
+        (ops.edit_align), one device-to-host copy.  The tie rule among equally cheap alignments is ds2_edit_align_i32's
+        (include/ds2hip.h).  There is no CPU implementation: without a GPU this raises."""
+        from .. import ops
+        _check_align_unit(unit)
+        dev = _device("Decoder.align_batch", "")
+        seq, a_off, a_len, b_off, b_len, ref_w, _ = pack_scoring(hypotheses, references)
+        B, P = len(ref_w), 2 * len(ref_w)
+        if B == 0:
+            return []
+        max_len = int(max(a_len.max(), b_len.max()))
+        counts, a_map, b_map = ops.edit_align(*_upload_scoring(dev, seq, a_off, a_len, b_off, b_len), max_len=max_len)
+        out = torch.cat((counts.reshape(-1), a_map.reshape(-1), b_map.reshape(-1))).cpu().numpy()
+        n = P * max_len
+        counts_h, a_map_h, b_map_h = out[:4 * P].reshape(P, 4), out[4 * P:4 * P + n].reshape(P, max_len), out[4 * P + n:].reshape(P, max_len)
+        if int(counts_h.min()) < 0:
+            raise RuntimeError("Decoder.align_batch: the edit-alignment kernel rejected a problem")
+        return assemble_edit_alignments(hypotheses, references, counts_h, a_map_h, b_map_h, unit)
 
     def decode(self, probs, sizes=None):
         raise NotImplementedError

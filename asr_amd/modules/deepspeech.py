@@ -433,9 +433,16 @@ class DeepSpeech(nn.Module):
 
     # -- evaluation loop (deepspeech.py:161-273) --------------------------------------------------
     def evaluate(self, loader=None, manifest=None, batch_size=None, device="auto", num_workers=32, verbose=False, half=False,
-                 output_file=None, main_proc=True, **_unused):
+                 output_file=None, main_proc=True, errors=None, **_unused):
+        """errors: a decoders.ErrorReport (None, the default: nothing below happens).  Every batch is then also aligned
+        (decoder.align_batch: which words and characters are hits, substitutions, deletions, insertions) and fed to it, and
+        errors.format() is appended to output_file's report.  The return value is the same either way.  A decoder that overrides
+        wer or cer refuses it (ValueError): its own scoring is not what the kernel aligns."""
         from ..decoders import BeamCTCDecoder, Decoder, GreedyDecoder
         device = resolve_device(device)
+        if errors is not None and not (type(self.decoder).wer is Decoder.wer and type(self.decoder).cer is Decoder.cer):
+            raise ValueError("evaluate: errors= needs the built-in scoring; this decoder overrides wer or cer, which the alignment kernel "
+                             "does not follow")
         with torch.no_grad():
             if loader is None:
                 loader, _ = self.get_loader(manifest=manifest, batch_size=batch_size, num_workers=num_workers)
@@ -471,6 +478,9 @@ class DeepSpeech(nn.Module):
                 if gpu_scoring:
                     scores = decoder.score_batch([decoded_output[i][0] for i in range(len(target_strings))],
                                                  [target_strings[i][0] for i in range(len(target_strings))]).tolist()
+                if errors is not None:
+                    errors.add(decoder.align_batch([decoded_output[i][0] for i in range(len(target_strings))],
+                                                   [target_strings[i][0] for i in range(len(target_strings))]))
                 for i in range(len(target_strings)):
                     transcript, reference = decoded_output[i][0], target_strings[i][0]
                     if scores is not None:
@@ -503,6 +513,8 @@ class DeepSpeech(nn.Module):
                     f.write("\n".join([f"===== {wer * 100:.2f}/{cer * 100:.2f} =====", "----- BEST -----", best[1], "----- LAST -----", last_str,
                                        "----- WORST -----", worst[1], "CER histogram"] + bars
                                       + ["=============================================\n"]))
+                    if errors is not None:
+                        f.write(errors.format())
                 print(f"saved output to {output_file}")
             return wer * 100, cer * 100, output_data
 

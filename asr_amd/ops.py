@@ -1433,41 +1433,71 @@ def greedy_decode(probs: Tensor, sizes: Tensor | None = None, blank: int = 0):
     return ids, offs, lens
 
 
-def edit_distance(seq: Tensor, a_off, a_len, b_off, b_len, max_len: int | None = None) -> Tensor:
-    """Levenshtein distances (unit costs) of P pairs of int32 symbol sequences, one launch -> dist (P) int32 on the GPU (contract:
-    include/ds2hip.h, ds2_edit_distance_i32).  seq: flat int32 symbols on the GPU; pair p compares seq[a_off[p]:][:a_len[p]] with
-    seq[b_off[p]:][:b_len[p]].  Offsets (int64) and lengths (int32) may live on the host or the GPU.  max_len bounds every pair's
-    longer side and sizes the workspace; when omitted it is taken from host lengths, or from device lengths at the cost of one
-    synchronising reduction.  Host lengths and offsets are checked against seq here; a device-side pair outside seq gets -1."""
+def _edit_problems(who, seq, a_off, a_len, b_off, b_len, max_len):
+    """The host path of edit_distance and edit_align: seq flat int32 on the GPU, offsets (int64) and lengths (int32) on the host or the
+    GPU, host ones checked against seq -> (seq, device, a_off, a_len, b_off, b_len on the device, P, max_len).  With P == 0 the four
+    arrays come back as they are: nothing is launched."""
     if not torch.is_tensor(seq) or not seq.is_cuda:
-        raise _lib.DS2LibraryError("edit_distance: seq must be a GPU tensor (no CPU fallback exists)")
+        raise _lib.DS2LibraryError(f"{who}: seq must be a GPU tensor (no CPU fallback exists)")
     if seq.dtype != torch.int32:
-        raise TypeError(f"edit_distance: expected int32 symbols, got {seq.dtype}")
+        raise TypeError(f"{who}: expected int32 symbols, got {seq.dtype}")
     seq = seq.contiguous().view(-1)
     dev = seq.device
     a_off, a_len, b_off, b_len = (torch.as_tensor(t).reshape(-1) for t in (a_off, a_len, b_off, b_len))
     P = a_len.numel()
     if not a_off.numel() == b_off.numel() == b_len.numel() == P:
-        raise ValueError(f"edit_distance: {a_off.numel()} / {P} / {b_off.numel()} / {b_len.numel()} offsets and lengths")
+        raise ValueError(f"{who}: {a_off.numel()} / {P} / {b_off.numel()} / {b_len.numel()} offsets and lengths")
     host = not any(t.is_cuda for t in (a_off, a_len, b_off, b_len))
     if host and P:
         lo = torch.stack((a_off.long(), b_off.long())).min()
         ln = torch.stack((a_len.long(), b_len.long()))
         hi = (torch.stack((a_off.long(), b_off.long())) + ln).max()
         if int(lo) < 0 or int(ln.min()) < 0 or int(hi) > seq.numel():
-            raise ValueError("edit_distance: a pair lies outside the symbol buffer")
+            raise ValueError(f"{who}: a pair lies outside the symbol buffer")
     if max_len is None:
         max_len = 0 if P == 0 else int(torch.maximum(a_len.max(), b_len.max()))
+    if P:
+        a_off, b_off = (t.to(device=dev, dtype=torch.int64).contiguous() for t in (a_off, b_off))
+        a_len, b_len = (t.to(device=dev, dtype=torch.int32).contiguous() for t in (a_len, b_len))
+    return seq, dev, a_off, a_len, b_off, b_len, P, int(max_len)
+
+
+def edit_distance(seq: Tensor, a_off, a_len, b_off, b_len, max_len: int | None = None) -> Tensor:
+    """Levenshtein distances (unit costs) of P pairs of int32 symbol sequences, one launch -> dist (P) int32 on the GPU (contract:
+    include/ds2hip.h, ds2_edit_distance_i32).  seq: flat int32 symbols on the GPU; pair p compares seq[a_off[p]:][:a_len[p]] with
+    seq[b_off[p]:][:b_len[p]].  Offsets (int64) and lengths (int32) may live on the host or the GPU.  max_len bounds every pair's
+    longer side and sizes the workspace; when omitted it is taken from host lengths, or from device lengths at the cost of one
+    synchronising reduction.  Host lengths and offsets are checked against seq here; a device-side pair outside seq gets -1."""
+    seq, dev, a_off, a_len, b_off, b_len, P, max_len = _edit_problems("edit_distance", seq, a_off, a_len, b_off, b_len, max_len)
     dist = torch.empty((P,), dtype=torch.int32, device=dev)
     if P == 0:
         return dist
-    a_off, b_off = (t.to(device=dev, dtype=torch.int64).contiguous() for t in (a_off, b_off))
-    a_len, b_len = (t.to(device=dev, dtype=torch.int32).contiguous() for t in (a_len, b_len))
     lib = _lib.load()
-    ws = _ws(lib.ds2_edit_distance_workspace_bytes(P, int(max_len)), dev)
+    ws = _ws(lib.ds2_edit_distance_workspace_bytes(P, max_len), dev)
     _lib.check(lib.ds2_edit_distance_i32(seq.data_ptr(), seq.numel(), a_off.data_ptr(), a_len.data_ptr(), b_off.data_ptr(), b_len.data_ptr(),
-                                         P, int(max_len), dist.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "ds2_edit_distance_i32")
+                                         P, max_len, dist.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "ds2_edit_distance_i32")
     return dist
+
+
+def edit_align(seq: Tensor, a_off, a_len, b_off, b_len, max_len: int | None = None):
+    """Edit alignments (unit costs) of P pairs of int32 symbol sequences, one launch -> (counts (P,4), a_map (P,max_len), b_map
+    (P,max_len)), int32 on the GPU (contract and tie rule: include/ds2hip.h, ds2_edit_align_i32).  Side a is the hypothesis, side b the
+    reference; counts[p] = (hits, substitutions, deletions, insertions); a_map[p][i] is the index in b paired with a[i] or -1 (an
+    insertion), b_map[p][j] the index in a paired with b[j] or -1 (a deletion); -1 beyond a side's length.  The arguments are
+    edit_distance's, checked the same way; a device-side pair outside seq, or with a side above max_len, gets -1 everywhere.  The
+    workspace grows with max_len squared (16 bytes per 64 DP cells and problem)."""
+    seq, dev, a_off, a_len, b_off, b_len, P, max_len = _edit_problems("edit_align", seq, a_off, a_len, b_off, b_len, max_len)
+    counts = torch.empty((P, 4), dtype=torch.int32, device=dev)
+    a_map = torch.empty((P, max_len), dtype=torch.int32, device=dev)
+    b_map = torch.empty((P, max_len), dtype=torch.int32, device=dev)
+    if P == 0:
+        return counts, a_map, b_map
+    lib = _lib.load()
+    ws = _ws(lib.ds2_edit_align_workspace_bytes(P, max_len), dev)
+    _lib.check(lib.ds2_edit_align_i32(seq.data_ptr(), seq.numel(), a_off.data_ptr(), a_len.data_ptr(), b_off.data_ptr(), b_len.data_ptr(),
+                                      P, max_len, counts.data_ptr(), a_map.data_ptr(), b_map.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+               "ds2_edit_align_i32")
+    return counts, a_map, b_map
 
 
 def _chk_align_args(who, x, ints, star_penalty=None, off_gpu=None):

@@ -785,6 +785,31 @@ size_t ds2_edit_distance_workspace_bytes(int P, long long max_len);
 int ds2_edit_distance_i32(const int* seq, long long n_seq, const long long* a_off, const int* a_len, const long long* b_off,
                           const int* b_len, int P, long long max_len, int* dist, void* ws, size_t ws_bytes, void* stream);
 
+/* Batched edit ALIGNMENT: the hits, substitutions, deletions and insertions behind each of those distances, and which symbol pairs
+ * with which (csrc/edit_align.h); every output is pinned to the integer by tests/edit_align_oracle.py, which restates this text.  The
+ * problem layout (seq, n_seq, a_off, a_len, b_off, b_len, P) is ds2_edit_distance_i32's.  Side a is the hypothesis (m symbols), side
+ * b the reference (n symbols).
+ * The DP: D[i][0] = i, D[0][j] = j, D[i][j] = min(D[i-1][j-1] + (a[i-1] != b[j-1]), D[i][j-1] + 1, D[i-1][j] + 1).
+ * The path is traced from (m, n) to (0, 0); at (i, j) the FIRST option that holds is taken:
+ *   1. i > 0 && j > 0 && D[i-1][j-1] + (a[i-1] != b[j-1]) == D[i][j]: a[i-1] pairs with b[j-1], a hit if equal, else a substitution;
+ *   2. j > 0 && D[i][j-1] + 1 == D[i][j]: b[j-1] is a deletion;
+ *   3. otherwise a[i-1] is an insertion.
+ * Optimal alignments are not unique; this rule picks one, whichever side the kernel puts on its rows.
+ * Outputs: counts (P,4) int32 = (hits, substitutions, deletions, insertions), so S + D + I is ds2_edit_distance_i32's distance;
+ *  a_map (P,max_len): a_map[p][i] = the index in b paired with a[i], -1 for an insertion; b_map (P,max_len): b_map[p][j] = the index
+ *  in a paired with b[j], -1 for a deletion; entries at or beyond a side's length are -1, so every row is fully written.  A problem
+ *  whose range leaves [0, n_seq) or with a side above max_len gets counts (-1,-1,-1,-1) and rows of -1.  An empty side gives all
+ *  insertions or all deletions.
+ * Workspace: ds2_edit_align_workspace_bytes(P, max_len) = P * ceil(max_len / 64) * max_len * 16 bytes (every column's bit-vector pair,
+ *  2 bits per DP cell) + ds2_edit_distance_workspace_bytes(P, max_len), or 0 for P <= 0 or max_len <= 0; ws 16-byte aligned.  It grows
+ *  with the SQUARE of max_len: about 3 MB for 128 problems of 300 symbols, 625 MB for one pair of 50 000; there is no linear-memory
+ *  traceback.  max_len >= every problem's longer side (host-known lengths: the call never synchronises); it must fit int32.
+ * One launch, one wave per problem: ceil(min/64) * max column steps, then at most m + n traceback steps. */
+size_t ds2_edit_align_workspace_bytes(int P, long long max_len);
+int ds2_edit_align_i32(const int* seq, long long n_seq, const long long* a_off, const int* a_len, const long long* b_off,
+                       const int* b_len, int P, long long max_len, int* counts, int* a_map, int* b_map, void* ws, size_t ws_bytes,
+                       void* stream);
+
 /* Pause segmentation of CTC posteriors (csrc/ctc_segment.h): where to cut a long recording so that its pieces can be decoded as one
  * batch.  Integer work on the blank column; every output is pinned to the integer by tests/ctc_segment_oracle.py, which restates this
  * text.  The reference has nothing like it.
