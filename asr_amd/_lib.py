@@ -52,7 +52,7 @@ SIGNATURES = {
     "ds2_cast_bf16": (i32, [vp, i32, vp, i32, i32, i32, vp]),
     "ds2_gemm_bf16_nt_obf16": (i32, [i32, i32, i32, vp, i32, vp, i32, vp, i32, vp, vp]),
     "ds2_cast_f32_from_bf16": (i32, [vp, vp, i64, vp]),
-    "ds2_rnn_fwd_x": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
+    "ds2_rnn_fwd_x": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, sz, vp, i32]),
     "ds2_split_bf16": (i32, [vp, i32, vp, i32, i32, i32, i32, vp]),
     "ds2_cast_transpose_bf16": (i32, [vp, i32, vp, i32, i32, i32, vp]),
     "ds2_cast_bf16_both_workspace_bytes": (sz, [i32, i32]),
@@ -102,12 +102,12 @@ SIGNATURES = {
     "ds2_rnn_pack_whh": (i32, [i32, vp, vp, vp, i32, i32, vp]),
     "ds2_weight_prep_bf16": (i32, [vp, i32, vp]),
     "ds2_rnn_fwd_workspace_bytes": (sz, [i32, i32, i32]),
-    "ds2_rnn_fwd_ex": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
+    "ds2_rnn_fwd_ex": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp, i32]),
     "ds2_rnn_fwd": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, sz, vp]),
     "ds2_rnn_bwd_workspace_bytes": (sz, [i32, i32, i32, i32]),
-    "ds2_rnn_bwd_ex": (i32, [vp, i32, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
-    "ds2_rnn_bwd_bn": (i32, [vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
-    "ds2_rnn_bwd_bn_xbf16": (i32, [vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
+    "ds2_rnn_bwd_ex": (i32, [vp, i32, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp, i32]),
+    "ds2_rnn_bwd_bn": (i32, [vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp, i32]),
+    "ds2_rnn_bwd_bn_xbf16": (i32, [vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp, i32]),
     "ds2_rnn_bias_grads": (i32, [i32, vp, i32, i32, vp, vp, vp]),
     "ds2_rnn_bwd": (i32, [vp, i32, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
     "ds2_ctc_workspace_bytes": (sz, [i32, i32, i32]),

@@ -4,6 +4,7 @@
 #include "common.h"
 #include <string.h>
 #include <stdlib.h>
+#include <atomic>
 
 static thread_local char g_ds2_err[1024] = "";
 
@@ -27,6 +28,24 @@ extern "C" int ds2_device_info(int* cu_count, int* wave_size, char* arch, int ar
   if (wave_size) *wave_size = p.warpSize;
   if (arch && arch_len > 0) snprintf(arch, arch_len, "%s", p.gcnArchName);
   return 0;
+}
+
+// common.h: CU count and architecture of the current device.  One packed word per device id (0 = not queried yet), so two threads making
+// their first calls on two devices at worst both query and store the same value.
+ds2_dev_facts_t ds2_dev_facts() {
+  static std::atomic<unsigned> cache[64];
+  constexpr unsigned KNOWN = 1u << 31, GFX950 = 1u << 30;
+  int dev = -1;
+  const bool have = hipGetDevice(&dev) == hipSuccess;
+  const int slot = (have && dev >= 0 && dev < 64) ? dev : -1;
+  unsigned v = slot >= 0 ? cache[slot].load(std::memory_order_relaxed) : 0;
+  if (!v) {
+    hipDeviceProp_t p;
+    const bool ok = have && hipGetDeviceProperties(&p, dev) == hipSuccess;
+    v = KNOWN | ((ok && strncmp(p.gcnArchName, "gfx950", 6) == 0) ? GFX950 : 0) | (unsigned)((ok && p.multiProcessorCount > 0) ? p.multiProcessorCount : 1);
+    if (slot >= 0) cache[slot].store(v, std::memory_order_relaxed);
+  }
+  return {slot, (int)(v & (GFX950 - 1)), (v & GFX950) != 0};
 }
 
 // Kernel-family / tile-shape SELECTORS of the recurrence (every selection computes the full result): 8 / 16 = alternative tile shapes of the

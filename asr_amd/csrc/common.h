@@ -39,6 +39,16 @@ static inline const char* ds2_exp_getenv(const char* name) {
 }
 static inline size_t align_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
 
+// Facts about the CURRENT device, cached per device id in ONE place (api.cpp; atomic slots: a process may drive two GPUs from two threads).
+// slot = the device id where it has a cache slot, else -1: an id outside [0, 64) or a failed hipGetDevice is queried on every call and
+// never answered with another device's facts.  A failed property query gives cus = 1, gfx950 = false.
+struct ds2_dev_facts_t {
+  int slot;
+  int cus;
+  bool gfx950;
+};
+ds2_dev_facts_t ds2_dev_facts();
+
 // wave64 reductions (all 64 lanes participate)
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

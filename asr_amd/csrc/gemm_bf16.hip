@@ -21,6 +21,7 @@
 #include <cstdint>
 #include <stdlib.h>
 #include <string.h>
+#include <atomic>
 
 namespace {
 
@@ -932,38 +933,19 @@ __global__ __launch_bounds__(256) void split_bf16_kernel(const float* __restrict
 
 }  // namespace
 
-// CU count of the CURRENT device, and "set this function's dynamic-LDS attribute once per DEVICE": per device id, so that a process that
-// drives two GPUs (device_test != device, two threads on two devices) never launches with the other device's grid size or without the
-// attribute.  The four-wave kernels (gemm_nt_w4.h / gemm_tn_w4.h: v_mfma_f32_16x16x32_bf16, 128 KB of LDS, one in-order
-// vmcnt shared by loads and stores) are gfx950 code: ds2_is_gfx950() gates them in the launchers.
-static int ds2_dev_index() {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  return dev;
-}
-static int ds2_cus_current() {
-  static int cus[64] = {0};
-  const int dev = ds2_dev_index();
-  if (!cus[dev]) {
-    hipDeviceProp_t prop;
-    cus[dev] = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 1;
-  }
-  return cus[dev];
-}
-static bool ds2_is_gfx950() {
-  static int known[64] = {0};                            // 0 unknown, 1 yes, 2 no
-  const int dev = ds2_dev_index();
-  if (!known[dev]) {
-    hipDeviceProp_t prop;
-    known[dev] = (hipGetDeviceProperties(&prop, dev) == hipSuccess && strncmp(prop.gcnArchName, "gfx950", 6) == 0) ? 1 : 2;
-  }
-  return known[dev] == 1;
-}
+// CU count of the CURRENT device (ds2_dev_facts, common.h), and "set this function's dynamic-LDS attribute once per DEVICE": per device id,
+// so that a process that drives two GPUs (device_test != device, two threads on two devices) never launches with the other device's grid
+// size or without the attribute; a device id without a cache slot sets the attribute on every call.  The four-wave kernels
+// (gemm_nt_w4.h / gemm_tn_w4.h: v_mfma_f32_16x16x32_bf16, 128 KB of LDS, one in-order vmcnt shared by loads and stores) are gfx950 code:
+// ds2_dev_facts().gfx950 gates them in the launchers.
 #define DS2_ATTR_ONCE(func, bytes)                                                                                          \
   do {                                                                                                                      \
-    static bool done_[64] = {false};                                                                                        \
-    const int d_ = ds2_dev_index();                                                                                         \
-    if (!done_[d_]) { DS2_HIP(hipFuncSetAttribute((const void*)func, hipFuncAttributeMaxDynamicSharedMemorySize, bytes)); done_[d_] = true; } \
+    static std::atomic<bool> done_[64];                                                                                     \
+    const int d_ = ds2_dev_facts().slot;                                                                                    \
+    if (d_ < 0 || !done_[d_].load(std::memory_order_acquire)) {                                                             \
+      DS2_HIP(hipFuncSetAttribute((const void*)func, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));                   \
+      if (d_ >= 0) done_[d_].store(true, std::memory_order_release);                                                        \
+    }                                                                                                                       \
   } while (0)
 
 extern "C" size_t ds2_gemm_bf16_workspace_bytes(int M, int N, int batch, int splitk) {
@@ -997,12 +979,12 @@ extern "C" int ds2_gemm_bf16_nt(int M, int N, int K, const void* A, int lda, lon
   const long long tiles256 = (long long)ceil_div(N, 256) * ceil_div(M, 256) * batch * splitk;
   if (M >= 256 && N >= 256 && tiles256 >= 128) {
     const int ntx = ceil_div(N, 256), nty = ceil_div(M, 256);
-    const int cus = ds2_cus_current();
+    const int cus = ds2_dev_facts().cus;
     const bool wide = (N % 4) == 0 && (ldc % 4) == 0 && ((uintptr_t)C % 16) == 0 && (!bias || ((uintptr_t)bias % 16) == 0);
     // four waves x 128 x 128, one workgroup per CU walking the tiles (gemm_nt_w4.h): wherever it applies — K a multiple of the 64-deep
     // k-tile, more tiles than CUs, plain write-out, 32-bit lane offsets inside a tile.  Otherwise 8 waves (128 x 64 per wave), one
     // workgroup per tile: the same products in the same order.
-    const bool w4 = ds2_is_gfx950() && batch == 1 && splitk == 1 && !accumulate && (K % 64) == 0 && K >= 128 && wide && ntx * nty > cus &&
+    const bool w4 = ds2_dev_facts().gfx950 && batch == 1 && splitk == 1 && !accumulate && (K % 64) == 0 && K >= 128 && wide && ntx * nty > cus &&
                     (long long)lda * 512 < (1ll << 31) && (long long)ldb * 512 < (1ll << 31);
     if (w4) {
       DS2_ATTR_ONCE((gemm_bf16_nt_w4_kernel<false>), W4_LDS);
@@ -1033,9 +1015,9 @@ extern "C" int ds2_gemm_bf16_nt_obf16(int M, int N, int K, const void* A, int ld
   DS2_REQUIRE(M > 0 && N > 0 && K > 0 && A && B && C, "ds2_gemm_bf16_nt_obf16: bad arguments M=%d N=%d K=%d", M, N, K);
   DS2_REQUIRE((K % 8) == 0 && (lda % 8) == 0 && (ldb % 8) == 0 && ((uintptr_t)A % 16) == 0 && ((uintptr_t)B % 16) == 0,
               "ds2_gemm_bf16_nt_obf16: K, lda, ldb must be multiples of 8 and the operands 16-byte aligned");
-  const int cus = ds2_cus_current();
+  const int cus = ds2_dev_facts().cus;
   const int ntx = ceil_div(N, 256), nty = ceil_div(M, 256);
-  const bool ok = ds2_is_gfx950() && (K % 64) == 0 && K >= 128 && (N % 8) == 0 && (ldc % 8) == 0 && ((uintptr_t)C % 16) == 0 && (!bias || ((uintptr_t)bias % 16) == 0) &&
+  const bool ok = ds2_dev_facts().gfx950 && (K % 64) == 0 && K >= 128 && (N % 8) == 0 && (ldc % 8) == 0 && ((uintptr_t)C % 16) == 0 && (!bias || ((uintptr_t)bias % 16) == 0) &&
                   ntx * nty > cus && (long long)lda * 512 < (1ll << 31) && (long long)ldb * 512 < (1ll << 31);
   if (!ok) return 1;
   BArgs g;
@@ -1160,7 +1142,7 @@ static int tn_splitk_group_impl(int nprob, const ds2_tn_problem* probs, int spli
   if (any_slab) DS2_REQUIRE(workspace && workspace_bytes >= off, "ds2_gemm_bf16_tn_splitk_group: workspace too small");
   DS2_ATTR_ONCE((gemm_bf16_tn_glds_kernel<true>), G_LDS);
   // four waves x 128 x 128 (gemm_tn_w4.h) when every k-tile of every slice is full
-  bool w4 = ds2_is_gfx950();
+  bool w4 = ds2_dev_facts().gfx950;
   for (int i = 0; i < nprob; ++i) {
     const ds2_tn_problem& q = probs[i];
     const int kc = g.p[i].kchunk, klast = q.K - (splitk - 1) * kc;
@@ -1206,7 +1188,7 @@ extern "C" int ds2_gemm_bf16_tn_group(int nprob, const ds2_tn_problem* probs, in
   }
   for (int i = nprob; i < TNG_MAX_PROBLEMS; ++i) g.p[i] = g.p[0];
   g.nprob = nprob; g.ntiles = tiles;
-  const int cus = ds2_cus_current() < 8 ? 8 : ds2_cus_current();
+  const int cus = ds2_dev_facts().cus < 8 ? 8 : ds2_dev_facts().cus;
   int grid = max_workgroups > 0 ? (max_workgroups < cus ? max_workgroups : cus) : cus;
   if (grid > tiles) grid = tiles;
   grid = grid < 8 ? 8 : grid / 8 * 8;                  // the tile walk deals whole runs to the 8 XCDs

@@ -31,6 +31,7 @@
 // what makes the reverse direction start at each sample's own last frame.
 #include "common.h"
 #include "permlane.h"
+#include "rnn_sizes.h"
 #include <type_traits>
 #include <algorithm>
 
@@ -1549,6 +1550,8 @@ __global__ __launch_bounds__(256) void rnn_pack_split_bwd_kernel(const float* __
   }
 }
 
+using namespace rnn_sizes;   // host-side size arithmetic, shared with the workspace queries
+
 inline int pick_mb(int B, int H) {
   const int nsl = ceil_div(H, 16);
   if (B <= 16) return 1;
@@ -1564,13 +1567,8 @@ inline int pick_mb(int B, int H) {
 // transient (another process or stream holding CUs for a moment) costs a few slow steps, not the rest of the run.  The backward kernel must
 // be switched off (ds2_rnn_persistent_enable) by a caller that runs collectives on another stream during backward, because a persistent
 // launch needs every one of its workgroups resident at once.  No context: no persistent launch.
-// ds2_rnn_ctx.ws_prearmed is a one-shot promise about the workspace of the NEXT recurrence call through the context: read and cleared at entry
-int take_prearmed(ds2_rnn_ctx* c) {
-  if (!c) return 0;
-  const int v = c->ws_prearmed;
-  c->ws_prearmed = 0;
-  return v;
-}
+// persist_allowed COUNTS a cooldown call, so where each launcher calls it among its other tests is observable through
+// ds2_rnn_persistent_counters (a cooling-down entry counts once); persist_idle only looks.
 bool persist_allowed(ds2_rnn_ctx* c, bool bwd) {
   if (!c || !c->status_dev) return false;
   if (c->cooldown != 0) {
@@ -1581,40 +1579,72 @@ bool persist_allowed(ds2_rnn_ctx* c, bool bwd) {
 }
 bool persist_idle(const ds2_rnn_ctx* c, bool bwd) { return c && c->status_dev && c->cooldown == 0 && (bwd ? c->persist_bwd : c->persist_fwd) != 0; }
 
-// bytes of ONE packed h buffer of the forward recurrence ([2 dirs][tiles][chunks][1 KiB]); the persistent kernel uses four
-size_t fwd_xbuf_bytes(int B, int H, int bf16) { return (size_t)2 * (ceil_div(B, 32) * 2) * ceil_div(H, bf16 ? 32 : 16) * 1024; }
-
-int cu_count() {                                          // of the CURRENT device (cached per device id: a process may drive two GPUs)
-  static int n[64] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  if (!n[dev]) {
-    hipDeviceProp_t p;
-    if (hipGetDeviceProperties(&p, dev) == hipSuccess) n[dev] = p.multiProcessorCount;
-    if (n[dev] <= 0) n[dev] = 1;
-  }
-  return n[dev];
-}
+// The environment switches of the recurrence, each read once per process at first use (the list: INTEGRATION.md §1)
+bool env_persistent_off() { static const char* e = getenv("DS2_RNN_PERSISTENT"); return e && e[0] == '0'; }   // "0" = always the step kernels (A/B runs, debugging)
+bool env_xcd_local_off() { static const char* e = getenv("DS2_RNN_XCD_LOCAL"); return e && e[0] == '0'; }     // "0" = the placement-independent sc1 protocol (A/B runs)
+bool env_f32_rnn() { static const char* e = getenv("DS2_F32_RNN"); return e && e[0] == 'f'; }                 // "f32": fp32 mode never takes a split kernel (A/B runs)
+bool env_ksplit_off() { static const char* e = ds2_exp_getenv("DS2_RNN_KSPLIT"); return e && e[0] == '0'; }   // "0": keep the all-gather backward kernel (A/B runs)
+// polls before a wave gives up (~1 s): a missing workgroup is reported instead of hanging the queue
+int env_spin_limit() { static const char* e = getenv("DS2_RNN_SPIN_LIMIT"); return e ? atoi(e) : (1 << 20); }
 
 // XCD-local exchange (persist_role's census mode): possible when every exchange group (gs workgroups) fits one XCD and the groups fit the
-// chip, on the 8 x 32-CU part this library is written for.  DS2_RNN_XCD_LOCAL=0 keeps the placement-independent sc1 protocol (A/B runs).
+// chip, on the 8 x 32-CU part this library is written for.
 constexpr int XCDS = 8, CUS_PER_XCD = 32;
 bool xcd_local_fits(int gs, int ngroups) {
-  static const char* env = getenv("DS2_RNN_XCD_LOCAL");
-  if (env && env[0] == '0') return false;
-  return cu_count() == XCDS * CUS_PER_XCD && gs >= 1 && gs <= CUS_PER_XCD && ngroups <= XCDS * (CUS_PER_XCD / gs);
+  if (env_xcd_local_off()) return false;
+  return ds2_dev_facts().cus == XCDS * CUS_PER_XCD && gs >= 1 && gs <= CUS_PER_XCD && ngroups <= XCDS * (CUS_PER_XCD / gs);
 }
-constexpr size_t CENSUS_BYTES = 64;                       // 8 per-XCD slot counters, the arrival counter, one "unexpected XCC id" flag
+
+// ---- the tail every persistent launcher ends in.  A launcher keeps its eligibility rules and its instance switch; once a shape has passed,
+// it states what it decided as a plan, and persist_arm turns the plan into the protocol arguments, the armed buffers and the grid.
+struct PersistPlan {
+  int gs, nbt;          // workgroups of one exchange group, batch tiles (the launch has gs * nbt * 2 roles)
+  bool census_ok;       // may use the census protocol (XCD-local exchange) where the groups fit
+  size_t xbytes;        // exchange bytes of the kernel family (rnn_sizes.h); the census words sit behind them
+};
+struct PersistLaunch {
+  char* xbuf;
+  unsigned* census;
+  dim3 grid, block;
+  int spin_limit;
+};
+// pk_bytes: what the entry's workspace holds from a.pk on.  0 = ready to launch, < 0 = error.
+int persist_arm(RnnArgs& a, const PersistPlan& p, size_t pk_bytes, hipStream_t st, PersistLaunch& l) {
+  if (p.xbytes + CENSUS_BYTES > pk_bytes)
+    return ds2_set_error("rnn: a persistent launch needs %zu bytes of exchange workspace, the call gave %zu", p.xbytes + CENSUS_BYTES, pk_bytes);
+  a.p_nbt = p.nbt; a.p_gs = p.gs; a.p_cux = CUS_PER_XCD;
+  a.p_census = (p.census_ok && xcd_local_fits(p.gs, 2 * p.nbt)) ? 1 : 0;
+  l.xbuf = reinterpret_cast<char*>(a.pk);
+  // every 16-byte chunk = the "not yet published" sentinel; census words = -1.  Skipped when the caller armed the whole workspace (ws_armed)
+  if (!a.prearmed) DS2_HIP(hipMemsetAsync(l.xbuf, 0xff, p.xbytes + CENSUS_BYTES, st));
+  l.census = reinterpret_cast<unsigned*>(l.xbuf + p.xbytes);
+  // 1-D grid.  Census mode: one workgroup per CU of the whole chip, roles by real XCD id (surplus workgroups exit); else exactly the workgroups needed
+  l.grid = dim3(a.p_census ? ds2_dev_facts().cus : p.gs * p.nbt * 2);
+  l.block = dim3(NW * 64);
+  l.spin_limit = env_spin_limit();
+  return 0;
+}
+// behind a launcher's instance switch / a loop of step launches: ok = what the launcher returns when the launches were accepted
+int launch_result(const char* what, int ok) {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? ok : ds2_set_error("%s launch failed: %s", what, hipGetErrorString(e));
+}
+
+// the runtime `gates` as a template argument: f(std::integral_constant<int, G>), use g() in the lambda.  by_gates_34: the families that
+// exist for G = 3 / 4 only (ksplit_avail, u10_avail) — 0 = not eligible for the tanh cell, and no G = 1 instance of them is ever built
+template <typename F>
+int by_gates_34(int gates, F&& f) { return gates == 1 ? 0 : gates == 3 ? f(std::integral_constant<int, 3>{}) : f(std::integral_constant<int, 4>{}); }
+template <typename F>
+int by_gates(int gates, F&& f) { return gates == 1 ? f(std::integral_constant<int, 1>{}) : by_gates_34(gates, f); }
 
 // Forward recurrence in one persistent launch (bf16 operands).  Returns 1 if launched, 0 if the shape / device does not qualify
 // (the caller then runs the step kernels), < 0 on error.
 template <int G, bool BF, bool SP = false>
-int try_launch_persistent_fwd(RnnArgs a, hipStream_t st) {
+int try_launch_persistent_fwd(RnnArgs a, size_t pk_bytes, hipStream_t st) {
   constexpr int NPL = SP ? 2 : 1;
   constexpr int RLIM = SP ? 200 : 180;                            // lane-vector budget (x 4 registers) of W_hh fragments + gathered operand
-  static const char* env = getenv("DS2_RNN_PERSISTENT");          // "0" = always the step kernels (A/B runs, debugging)
-  if (env && env[0] == '0') return 0;
-  if (a.dbg & ~128) return 0;                                     // any selector but 128 (= no K-split backward) selects the step kernels
+  if (env_persistent_off()) return 0;
+  if (a.dbg & ~128) return 0;                                    // any selector but 128 (= no K-split backward) selects the step kernels
   if ((a.H % 16) != 0 || a.T < 2 || !persist_allowed(a.hctx, false)) return 0;
   const int nsl = a.H / 16;
   const int nch = ceil_div(a.H, kchunk<BF>());
@@ -1632,7 +1662,7 @@ int try_launch_persistent_fwd(RnnArgs a, hipStream_t st) {
   // tile is H wide either way; 16 x 32 halves the producers and is what lets a group fit one XCD), so G = 1 takes the same rule below:
   // at c3's shape (H = 1024, B = 64) that is 16 x 32, 8 groups of 32 workgroups on 256 CUs.
   int mb = 1, ns = 2;
-  const bool ns2_ok = (nsl % 2) == 0 && ncw * NPL * (2 * G + 1) * 4 <= RLIM && (long long)(nsl / 2) * ceil_div(a.B, 16) * 2 <= cu_count();
+  const bool ns2_ok = (nsl % 2) == 0 && ncw * NPL * (2 * G + 1) * 4 <= RLIM && (long long)(nsl / 2) * ceil_div(a.B, 16) * 2 <= ds2_dev_facts().cus;
   // ... and 16 x 32 also where 16 x 16 would be chosen but only the wider slice lets an exchange group fit one XCD (L2-local exchange;
   // bf16 only: in fp32 the doubled MFMA instruction count per workgroup costs more than the exchange saves, c2 5.4 -> 6.1 us per step)
   const bool ns2_for_local = BF && ns2_ok && !xcd_local_fits(nsl, ceil_div(a.B, 16 * pick_mb(a.B, a.H)) * 2) && xcd_local_fits(nsl / 2, ceil_div(a.B, 16) * 2);
@@ -1643,23 +1673,15 @@ int try_launch_persistent_fwd(RnnArgs a, hipStream_t st) {
   }
   const int nbt = ceil_div(a.B, 16 * mb);
   // every workgroup must be resident at once: one per CU (up to 160 KB of registers + up to 129 KB of LDS each)
-  if ((long long)(nsl / ns) * nbt * 2 > cu_count()) return 0;
+  if ((long long)(nsl / ns) * nbt * 2 > ds2_dev_facts().cus) return 0;
   a.nsl = nsl;
   a.nbt16 = ceil_div(a.B, 32) * 2;
-  a.p_nbt = nbt; a.p_gs = nsl / ns; a.p_cux = CUS_PER_XCD;
-  a.p_census = xcd_local_fits(a.p_gs, 2 * nbt) ? 1 : 0;
-  char* xbuf = reinterpret_cast<char*>(a.pk);
-  const size_t xbytes = 4 * NPL * fwd_xbuf_bytes(a.B, a.H, BF ? 1 : 0);
-  if (!a.prearmed) DS2_HIP(hipMemsetAsync(xbuf, 0xff, xbytes + CENSUS_BYTES, st));      // every 16-byte chunk = the "not yet published" sentinel; census words = -1
-  unsigned* census = reinterpret_cast<unsigned*>(xbuf + xbytes);
-  // 1-D grid.  Census mode: one workgroup per CU of the whole chip, roles by real XCD id (surplus workgroups exit); else exactly the workgroups needed
-  dim3 grid(a.p_census ? cu_count() : a.p_gs * nbt * 2), block(NW * 64);
-  static const char* sl = getenv("DS2_RNN_SPIN_LIMIT");
-  const int spin_limit = sl ? atoi(sl) : (1 << 20);              // ~1 s of polling: a missing workgroup is reported instead of hanging the queue
+  PersistLaunch l;
+  if (int e = persist_arm(a, {nsl / ns, nbt, true, fwd_allgather_xbytes(a.B, a.H, SP ? OP_SPLIT : BF ? OP_BF16 : OP_F32)}, pk_bytes, st, l)) return e;
 #define DS2_PLAUNCH(MB_, NS_, NCW_)                                                                                                   \
   do {                                                                                                                                \
     if constexpr (NCW_ * NPL * (NS_ * G + MB_) * 4 <= RLIM)                                                                           \
-      hipLaunchKernelGGL((rnn_fwd_persistent_kernel<G, MB_, NS_, NCW_, BF, SP>), grid, block, 0, st, a, xbuf, census, spin_limit);             \
+      hipLaunchKernelGGL((rnn_fwd_persistent_kernel<G, MB_, NS_, NCW_, BF, SP>), l.grid, l.block, 0, st, a, l.xbuf, l.census, l.spin_limit); \
     else                                                                                                                              \
       return 0;                                                                                                                       \
   } while (0)
@@ -1677,19 +1699,14 @@ int try_launch_persistent_fwd(RnnArgs a, hipStream_t st) {
   }
 #undef DS2_PCASE
 #undef DS2_PLAUNCH
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return ds2_set_error("rnn persistent launch failed: %s", hipGetErrorString(e));
-  return 1;
+  return launch_result("rnn persistent", 1);
 }
-
-size_t bwd_xbuf_bytes(int gates, int B, int H, int bf16) { return (size_t)2 * (ceil_div(B, 32) * 2) * ceil_div(gates * H, bf16 ? 32 : 16) * 1024; }
 
 // Backward recurrence in one persistent launch (bf16 training path).  1 = launched, 0 = not eligible, < 0 = error.
 template <int G, bool BF, bool SP = false>
-int try_launch_persistent_bwd(RnnArgs a, hipStream_t st) {
+int try_launch_persistent_bwd(RnnArgs a, size_t pk_bytes, hipStream_t st) {
   constexpr int NPL = SP ? 2 : 1;
-  static const char* env = getenv("DS2_RNN_PERSISTENT");
-  if ((env && env[0] == '0') || (a.dbg & ~128)) return 0;
+  if (env_persistent_off() || (a.dbg & ~128)) return 0;
   // buffers: either the bf16 training path's (packed gate records in, bf16 dGx out) or the plain ones (gates in gx, dGx in place)
   // (tanh cell: no gate record either way — h comes from hbuf; dGx goes to the bf16 buffer if given, else into gx)
   if (G == 1 ? !(a.dgx_bf || a.gx) : !((a.gates_bf && a.dgx_bf) || (!a.gates_bf && !a.dgx_bf && a.gx))) return 0;
@@ -1709,22 +1726,15 @@ int try_launch_persistent_bwd(RnnArgs a, hipStream_t st) {
   if (ns == 2) mb = 1;
   const int nbt = ceil_div(a.B, 16 * mb);
   if (ncw > (BF ? 12 : 18) || ncw * NPL * (ns + mb) * 4 > (SP ? 160 : 192) || NPL * ncw * mb > 32) return 0;   // W_hh^T fragments + operand lane vectors must fit the registers
-  if ((long long)(nsl / ns) * nbt * 2 > cu_count()) return 0;
+  if ((long long)(nsl / ns) * nbt * 2 > ds2_dev_facts().cus) return 0;
   a.nsl = nsl;
   a.nbt16 = ceil_div(a.B, 32) * 2;
-  a.p_nbt = nbt; a.p_gs = nsl / ns; a.p_cux = CUS_PER_XCD;
-  a.p_census = xcd_local_fits(a.p_gs, 2 * nbt) ? 1 : 0;
-  char* xbuf = reinterpret_cast<char*>(a.pk);
-  const size_t xbytes = 4 * NPL * bwd_xbuf_bytes(G, a.B, a.H, BF ? 1 : 0);
-  if (!a.prearmed) DS2_HIP(hipMemsetAsync(xbuf, 0xff, xbytes + CENSUS_BYTES, st));
-  unsigned* census = reinterpret_cast<unsigned*>(xbuf + xbytes);
-  dim3 grid(a.p_census ? cu_count() : a.p_gs * nbt * 2), block(NW * 64);   // see the forward launcher
-  static const char* sl = getenv("DS2_RNN_SPIN_LIMIT");
-  const int spin_limit = sl ? atoi(sl) : (1 << 20);
+  PersistLaunch l;
+  if (int e = persist_arm(a, {nsl / ns, nbt, true, bwd_allgather_xbytes(G, a.B, a.H, SP ? OP_SPLIT : BF ? OP_BF16 : OP_F32)}, pk_bytes, st, l)) return e;
 #define DS2_PB(MB_, NS_, NCW_)                                                                                                      \
   do {                                                                                                                              \
     if constexpr (NCW_ * NPL * (NS_ + MB_) * 4 <= (SP ? 160 : 192) && NPL * NCW_ * MB_ <= 32)                                                   \
-      hipLaunchKernelGGL((rnn_bwd_persistent_kernel<G, MB_, NS_, NCW_, BF, SP>), grid, block, 0, st, a, xbuf, census, spin_limit);           \
+      hipLaunchKernelGGL((rnn_bwd_persistent_kernel<G, MB_, NS_, NCW_, BF, SP>), l.grid, l.block, 0, st, a, l.xbuf, l.census, l.spin_limit); \
     else                                                                                                                            \
       return 0;                                                                                                                     \
   } while (0)
@@ -1754,9 +1764,7 @@ int try_launch_persistent_bwd(RnnArgs a, hipStream_t st) {
   }
 #undef DS2_PBCASE
 #undef DS2_PB
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return ds2_set_error("rnn persistent backward launch failed: %s", hipGetErrorString(e));
-  return 1;
+  return launch_result("rnn persistent backward", 1);
 }
 
 // 16-byte exchange store with a wave-uniform 64-bit base (SGPR pair) + a per-lane 32-bit offset: no 64-bit vector address arithmetic per store
@@ -1789,7 +1797,7 @@ int launch_steps(bool bwd, RnnArgs a, hipStream_t st) {
   const int ns = (mb == 2 && (a.nsl % 2) == 0 && ((bwd && !(a.dbg & 8)) || (!bwd && (a.dbg & 16)))) ? 2 : 1;
   if (ns == 2) mb = 1;
   const int nbt = ceil_div(a.B, 16 * mb);
-  a.nbt16 = ceil_div(a.B, 32) * 2;                                   // tile rows of the packed exchange buffers (pk_floats)
+  a.nbt16 = ceil_div(a.B, 32) * 2;                                   // tile rows of the packed exchange buffers (step_bytes, rnn_sizes.h)
   dim3 grid(a.nsl / ns, nbt, 2), block(NW * 64);
   if (a.nbt16 > 0xffff || a.T > 0xffff || a.B > 0xffff || a.H > 0xffff)
     return ds2_set_error("rnn: T, B, H and the tile count must fit 16 bits (T=%d B=%d H=%d)", a.T, a.B, a.H);
@@ -1812,19 +1820,72 @@ int launch_steps(bool bwd, RnnArgs a, hipStream_t st) {
       else hipLaunchKernelGGL((rnn_bwd_step_kernel<G, 1, 1, BF, SP>), grid, block, 0, st, pk, wp, gx_or_rec, auxb, a.dy, s_H, T_B, packed, a.lddy, a);
     }
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return ds2_set_error("rnn step launch failed: %s", hipGetErrorString(e));
-  return 0;
-}
-
-size_t pk_floats(int B, int H, int kdim, int bf16) {   // size in 4-byte units (1 chunk = 1 KiB = 256 units in both precisions)
-  const int nbt16 = ceil_div(B, 32) * 2;
-  return (size_t)2 * 2 * nbt16 * ceil_div(kdim, bf16 ? 32 : 16) * 256;
+  return launch_result("rnn step", 0);
 }
 
 template <bool BF>
 int dispatch(int gates, bool bwd, const RnnArgs& a, hipStream_t st) {
-  return gates == 1 ? launch_steps<1, BF>(bwd, a, st) : gates == 3 ? launch_steps<3, BF>(bwd, a, st) : launch_steps<4, BF>(bwd, a, st);
+  return by_gates(gates, [&](auto g) { return launch_steps<g(), BF>(bwd, a, st); });
+}
+
+// ---- what the entries share: argument checks, the common part of RnnArgs, the record of what ran
+
+// (who: the entry's name in the message; ptrs_ok / gx_ok: the entry's own pointer conditions)
+int check_entry(const char* who, int gates, bool ptrs_ok, bool gx_ok, int T, int B, int H, const void* ws, size_t ws_bytes, size_t ws_need) {
+  DS2_REQUIRE(gates == 1 || gates == 3 || gates == 4, "%s: gates must be 1 (tanh RNN), 3 (GRU) or 4 (LSTM)", who);
+  DS2_REQUIRE(ptrs_ok, "%s: null pointer", who);
+  DS2_REQUIRE(gx_ok, "%s: gx may only be NULL with both gates_bf16 (not for gates = 1) and dgx_bf16 given", who);
+  DS2_REQUIRE(T > 0 && B > 0 && H > 0 && (H % 4) == 0, "%s: need H %% 4 == 0 (H=%d)", who, H);
+  DS2_REQUIRE(ws && ws_bytes >= ws_need, "%s: workspace too small", who);
+  return 0;
+}
+
+// ws_armed: the caller has filled the call's whole workspace with 0xff bytes earlier in the stream (RnnArgs.prearmed: persist_arm skips its fill)
+RnnArgs common_args(ds2_rnn_ctx* ctx, int gates, float* gx, float* aux, const float* hbuf, const void* wp, const int* lens_dev, int T, int B, int H,
+                    const void* gates_bf16, int ws_armed) {
+  RnnArgs a{};
+  a.gx = gx; a.aux = aux; a.hbuf = const_cast<float*>(hbuf); a.wp = (const float*)wp; a.lens = lens_dev;
+  a.T = T; a.B = B; a.H = H;
+  a.gates_bf = gates == 1 ? nullptr : (__bf16*)const_cast<void*>(gates_bf16);       // (tanh cell: no gate record, h comes from hbuf)
+  a.hctx = ctx; a.status = ctx ? ctx->status_dev : nullptr;
+  a.prearmed = ws_armed;
+  a.dbg = ctx ? ctx->debug_flags : 0;
+  return a;
+}
+// backward: the carry (4, B, H) in front of the exchange buffers
+RnnArgs bwd_args(ds2_rnn_ctx* ctx, int gates, const float* dy, int lddy, float* gx, float* aux, const float* hbuf, const void* wp_bwd, const int* lens_dev,
+                 int T, int B, int H, void* dgx_bf16, const void* gates_bf16, void* dhn_bf16, float* bias_part, void* ws, int ws_armed) {
+  RnnArgs a = common_args(ctx, gates, gx, aux, hbuf, wp_bwd, lens_dev, T, B, H, gates_bf16, ws_armed);
+  a.dy = dy; a.lddy = lddy;
+  a.dcar = (float*)ws; a.pk = (float*)((char*)ws + bwd_carry_bytes(B, H));
+  a.dgx_bf = (__bf16*)dgx_bf16; a.dhn_bf = (__bf16*)dhn_bf16; a.bsum = bias_part;
+  return a;
+}
+const float* bytes_behind(const void* p, size_t n) { return reinterpret_cast<const float*>(reinterpret_cast<const char*>(p) + n); }
+
+// The kernel family that took a call = the DS2_RNN_PATH_* bits (include/ds2hip.h) it leaves in the context: stated here, once
+enum FwdRan {
+  FWD_STEPS = 0, FWD_PERSISTENT = DS2_RNN_PATH_FWD_PERSISTENT, FWD_SPLIT = FWD_PERSISTENT | DS2_RNN_PATH_FWD_SPLIT, FWD_U10 = FWD_SPLIT | DS2_RNN_PATH_FWD_U10,
+  FWD_BITS = FWD_U10
+};
+enum BwdRan {
+  BWD_STEPS = 0, BWD_SPLIT_STEPS = DS2_RNN_PATH_BWD_SPLIT, BWD_ALLGATHER = DS2_RNN_PATH_BWD_PERSISTENT, BWD_SPLIT_ALLGATHER = BWD_ALLGATHER | BWD_SPLIT_STEPS,
+  BWD_KSPLIT = BWD_ALLGATHER | DS2_RNN_PATH_BWD_KSPLIT, BWD_SPLIT_KSPLIT = BWD_KSPLIT | BWD_SPLIT_STEPS, BWD_KSPLIT_BN = BWD_KSPLIT | DS2_RNN_PATH_BWD_BN_FUSED,
+  BWD_BITS = BWD_SPLIT_KSPLIT | BWD_KSPLIT_BN
+};
+void record(ds2_rnn_ctx* ctx, FwdRan f) {
+  if (ctx) ctx->last_path = (ctx->last_path & ~FWD_BITS) | f;
+}
+void record(ds2_rnn_ctx* ctx, BwdRan f) {
+  if (!ctx) return;
+  ctx->last_path = (ctx->last_path & ~BWD_BITS) | f;
+  ctx->last_bwd_kind = (f & DS2_RNN_PATH_BWD_KSPLIT) ? 2 : (f & DS2_RNN_PATH_BWD_PERSISTENT) ? 1 : 0;
+}
+
+// forward on the step kernels: zero padding rows / columns of the ping-pong buffers (a persistent launch has filled its own with the sentinel)
+int fwd_steps(int gates, int bf16, const RnnArgs& a, void* ws, hipStream_t st) {
+  DS2_HIP(hipMemsetAsync(ws, 0, fwd_workspace_bytes(a.B, a.H, bf16), st));
+  return bf16 == 1 ? dispatch<true>(gates, false, a, st) : dispatch<false>(gates, false, a, st);
 }
 
 }  // namespace
@@ -1886,12 +1947,8 @@ extern "C" int ds2_rnn_persistent_status(ds2_rnn_ctx* ctx, int* out8) {
 }
 
 // bf16: 0 fp32, 1 bf16 operands, 2 fp32 mode with the split (hi + lo bf16) persistent forward kernel and the fp32 kernels as fallback
-extern "C" size_t ds2_rnn_fwd_workspace_bytes(int B, int H, int bf16) {
-  const size_t step = pk_floats(B, H, H, bf16 == 1) * sizeof(float);            // two ping-pong buffers of the step kernels
-  size_t pers = 4 * fwd_xbuf_bytes(B, H, bf16 == 1) + 64;                        // four round-robin buffers of the persistent kernel + its census words
-  if (bf16 == 2) { const size_t sp = 8 * fwd_xbuf_bytes(B, H, 1) + 64; pers = sp > pers ? sp : pers; }
-  return step > pers ? step : pers;
-}
+// (the larger of the step kernels' ping-pong buffers and the exchange buffers + census words of every persistent family the mode can reach: rnn_sizes.h)
+extern "C" size_t ds2_rnn_fwd_workspace_bytes(int B, int H, int bf16) { return fwd_workspace_bytes(B, H, bf16); }
 
 // gates: 3 = GRU (r,z,n), 4 = LSTM (i,f,g,o).  bf16 = 1: the h W_hh^T product uses bf16 MFMA operands (fp32 accumulate;
 // h, c, gates stay fp32) and wp_fwd must have been packed with bf16 = 1.
@@ -1901,54 +1958,45 @@ extern "C" size_t ds2_rnn_fwd_workspace_bytes(int B, int H, int bf16) {
 //   aux    (T,B,2,H) out: GRU W_hn h + b_hn ; LSTM cell state
 //   h_bf16 optional (T,B,2,H) bf16: a bf16 copy of hbuf, written by a PERSISTENT launch only (ds2_rnn_last_path() & 1 after the call)
 extern "C" int ds2_rnn_fwd_ex(ds2_rnn_ctx* ctx, int gates, float* gx, const void* wp_fwd, const float* bhh, float* hbuf, float* aux, const int* lens_dev, int T,
-                              int B, int H, int bf16, void* gates_bf16, void* h_bf16, void* ws, size_t ws_bytes, void* stream) {
-  DS2_REQUIRE(gates == 1 || gates == 3 || gates == 4, "ds2_rnn_fwd: gates must be 1 (tanh RNN), 3 (GRU) or 4 (LSTM)");
-  DS2_REQUIRE(gx && wp_fwd && bhh && hbuf && (aux || gates == 1) && lens_dev, "ds2_rnn_fwd: null pointer");
-  DS2_REQUIRE(T > 0 && B > 0 && H > 0 && (H % 4) == 0, "ds2_rnn_fwd: need H %% 4 == 0 (H=%d)", H);
-  DS2_REQUIRE(ws && ws_bytes >= ds2_rnn_fwd_workspace_bytes(B, H, bf16), "ds2_rnn_fwd: workspace too small");
-  RnnArgs a{};
-  a.gx = gx; a.aux = aux; a.hbuf = hbuf; a.wp = (const float*)wp_fwd; a.bhh = bhh; a.pk = (float*)ws; a.lens = lens_dev;
-  a.T = T; a.B = B; a.H = H; a.gates_bf = gates == 1 ? nullptr : (__bf16*)gates_bf16; a.h_bf = (__bf16*)h_bf16;
-  a.hctx = ctx; a.status = ctx ? ctx->status_dev : nullptr;
-  a.prearmed = take_prearmed(ctx);
-  int scratch_path = 0;
-  int& last_path = ctx ? ctx->last_path : scratch_path;
-  {
-    a.dbg = ctx ? ctx->debug_flags : 0;
-    hipStream_t st = (hipStream_t)stream;
-    int rc = 0;
-    if (bf16 == 2) {
-      // fp32 mode, split forward recurrence: operands behind the fp32 fragments of wp_fwd (ds2_rnn_packed_bytes(.., 0, 2)); where its shape
-      // does not qualify (or during a cooldown, which the fp32 attempt below counts) the fp32 kernels take the call with the fp32 fragments
-      static const char* env = getenv("DS2_F32_RNN");              // "f32": never the split kernel (A/B runs)
-      if (persist_idle(ctx, false) && !(env && env[0] == 'f') && !a.gates_bf) {
-        RnnArgs b = a;
-        b.wp = reinterpret_cast<const float*>(reinterpret_cast<const char*>(wp_fwd) + ds2_rnn_packed_bytes(gates, H, 0, 0));
-        b.dbg &= ~256;
-        last_path &= ~256;
-        if (!(a.dbg & 256))                                         // (debug flag 256: prefer the 10-unit kernel where its shape qualifies)
-          rc = gates == 1 ? try_launch_persistent_fwd<1, true, true>(b, st) : gates == 3 ? try_launch_persistent_fwd<3, true, true>(b, st) : try_launch_persistent_fwd<4, true, true>(b, st);
-        if (rc == 0 && u10_avail(gates, H)) {
-          // the 16-unit split kernel does not fit (LSTM H = 1280 at B = 32: BASELINE C4): ten-unit slices, rnn_fwd_u10.h
-          b.wp = reinterpret_cast<const float*>(reinterpret_cast<const char*>(wp_fwd) + ds2_rnn_packed_bytes(gates, H, 0, 0) +
-                                                2 * ds2_rnn_packed_bytes(gates, H, 0, 1));
-          rc = gates == 3 ? try_launch_fwd_u10<3>(b, st) : try_launch_fwd_u10<4>(b, st);
-          if (rc == 1) last_path |= 256;                          // bit 8: the 10-unit kernel
-        }
-        if (rc == 1) last_path |= 32;                             // bit 5: a split kernel took the call
+                              int B, int H, int bf16, void* gates_bf16, void* h_bf16, void* ws, size_t ws_bytes, void* stream, int ws_armed) {
+  if (int e = check_entry("ds2_rnn_fwd", gates, gx && wp_fwd && bhh && hbuf && (aux || gates == 1) && lens_dev, true, T, B, H, ws, ws_bytes,
+                          fwd_workspace_bytes(B, H, bf16)))
+    return e;
+  hipStream_t st = (hipStream_t)stream;
+  RnnArgs a = common_args(ctx, gates, gx, aux, hbuf, wp_fwd, lens_dev, T, B, H, gates_bf16, ws_armed);
+  a.bhh = bhh; a.pk = (float*)ws; a.h_bf = (__bf16*)h_bf16;
+  int rc = 0;
+  FwdRan ran = FWD_PERSISTENT;
+  if (bf16 == 2) {
+    // fp32 mode, split forward recurrence: operands behind the fp32 fragments of wp_fwd (ds2_rnn_packed_bytes(.., 0, 2)); where its shape
+    // does not qualify (or during a cooldown, which the fp32 attempt below counts) the fp32 kernels take the call with the fp32 fragments
+    if (persist_idle(ctx, false) && !env_f32_rnn() && !a.gates_bf) {
+      RnnArgs b = a;
+      b.wp = bytes_behind(wp_fwd, ds2_rnn_packed_bytes(gates, H, 0, 0));
+      b.dbg &= ~256;
+      ran = FWD_SPLIT;
+      // (debug flag 256: prefer the 10-unit kernel where its shape qualifies)
+      if (!(a.dbg & 256)) rc = by_gates(gates, [&](auto g) { return try_launch_persistent_fwd<g(), true, true>(b, ws_bytes, st); });
+      if (rc == 0 && u10_avail(gates, H)) {
+        // the 16-unit split kernel does not fit (LSTM H = 1280 at B = 32: BASELINE C4): ten-unit slices, rnn_fwd_u10.h
+        b.wp = bytes_behind(wp_fwd, ds2_rnn_packed_bytes(gates, H, 0, 0) + 2 * ds2_rnn_packed_bytes(gates, H, 0, 1));
+        ran = FWD_U10;
+        rc = by_gates_34(gates, [&](auto g) { return try_launch_fwd_u10<g()>(b, ws_bytes, st); });
       }
-      if (rc == 0) { last_path &= ~32; a.dbg &= ~256; rc = gates == 1 ? try_launch_persistent_fwd<1, false>(a, st) : gates == 3 ? try_launch_persistent_fwd<3, false>(a, st) : try_launch_persistent_fwd<4, false>(a, st); }
-    } else {
-      last_path &= ~(32 | 256);
-      rc = bf16 ? (gates == 1 ? try_launch_persistent_fwd<1, true>(a, st) : gates == 3 ? try_launch_persistent_fwd<3, true>(a, st) : try_launch_persistent_fwd<4, true>(a, st))
-                : (gates == 1 ? try_launch_persistent_fwd<1, false>(a, st) : gates == 3 ? try_launch_persistent_fwd<3, false>(a, st) : try_launch_persistent_fwd<4, false>(a, st));
     }
-    last_path = (last_path & ~1) | (rc == 1 ? 1 : 0);
-    if (rc != 0) return rc < 0 ? rc : 0;
+    if (rc == 0) {
+      a.dbg &= ~256;
+      ran = FWD_PERSISTENT;
+      rc = by_gates(gates, [&](auto g) { return try_launch_persistent_fwd<g(), false>(a, ws_bytes, st); });
+    }
+  } else {
+    rc = by_gates(gates, [&](auto g) {
+      return bf16 ? try_launch_persistent_fwd<g(), true>(a, ws_bytes, st) : try_launch_persistent_fwd<g(), false>(a, ws_bytes, st);
+    });
   }
-  // step kernels: zero padding rows / columns of the ping-pong buffers (the persistent path has filled its own with the sentinel)
-  DS2_HIP(hipMemsetAsync(ws, 0, ds2_rnn_fwd_workspace_bytes(B, H, bf16), (hipStream_t)stream));
-  return bf16 == 1 ? dispatch<true>(gates, false, a, (hipStream_t)stream) : dispatch<false>(gates, false, a, (hipStream_t)stream);
+  if (rc < 0) return rc;
+  record(ctx, rc == 1 ? ran : FWD_STEPS);
+  return rc == 1 ? 0 : fwd_steps(gates, bf16, a, ws, st);
 }
 
 // ds2_rnn_fwd_ex for the bf16 TRAINING mode (bf16 == 1, packed gate records), with two more optional operands:
@@ -1959,34 +2007,27 @@ extern "C" int ds2_rnn_fwd_ex(ds2_rnn_ctx* ctx, int gates, float* gx, const void
 //            (ds2_rnn_last_path() & 1), the input of ds2_center_colstats.
 // Returns 0 = done, 1 = see gx_bf16, < 0 error.
 extern "C" int ds2_rnn_fwd_x(ds2_rnn_ctx* ctx, int gates, float* gx, const void* gx_bf16, const void* wp_fwd, const float* bhh, float* hbuf, float* aux,
-                             const int* lens_dev, int T, int B, int H, void* gates_bf16, void* h_bf16, float* hsum, void* ws, size_t ws_bytes, void* stream) {
-  DS2_REQUIRE(gates == 1 || gates == 3 || gates == 4, "ds2_rnn_fwd_x: gates must be 1 (tanh RNN), 3 (GRU) or 4 (LSTM)");
-  DS2_REQUIRE((gx || gx_bf16) && wp_fwd && bhh && hbuf && ((aux && gates_bf16) || gates == 1) && lens_dev, "ds2_rnn_fwd_x: null pointer");
-  DS2_REQUIRE(T > 0 && B > 0 && H > 0 && (H % 4) == 0, "ds2_rnn_fwd_x: need H %% 4 == 0 (H=%d)", H);
-  DS2_REQUIRE(ws && ws_bytes >= ds2_rnn_fwd_workspace_bytes(B, H, 1), "ds2_rnn_fwd_x: workspace too small");
+                             const int* lens_dev, int T, int B, int H, void* gates_bf16, void* h_bf16, float* hsum, void* ws, size_t ws_bytes, void* stream,
+                             int ws_armed) {
+  if (int e = check_entry("ds2_rnn_fwd_x", gates, (gx || gx_bf16) && wp_fwd && bhh && hbuf && ((aux && gates_bf16) || gates == 1) && lens_dev, true, T, B, H,
+                          ws, ws_bytes, fwd_workspace_bytes(B, H, 1)))
+    return e;
   if (!gx && !persist_idle(ctx, false)) return 1;
-  RnnArgs a{};
-  a.gx = gx_bf16 ? nullptr : gx; a.gxb = (const __bf16*)gx_bf16; a.aux = aux; a.hbuf = hbuf; a.wp = (const float*)wp_fwd; a.bhh = bhh; a.pk = (float*)ws;
-  a.lens = lens_dev; a.T = T; a.B = B; a.H = H; a.gates_bf = gates == 1 ? nullptr : (__bf16*)gates_bf16; a.h_bf = (__bf16*)h_bf16; a.hsum = hsum;
-  a.hctx = ctx; a.status = ctx ? ctx->status_dev : nullptr;
-  a.prearmed = take_prearmed(ctx);
-  a.dbg = ctx ? ctx->debug_flags : 0;
-  int scratch_path = 0;
-  int& last_path = ctx ? ctx->last_path : scratch_path;
-  const int rc = gates == 1 ? try_launch_persistent_fwd<1, true>(a, (hipStream_t)stream)
-                 : gates == 3 ? try_launch_persistent_fwd<3, true>(a, (hipStream_t)stream) : try_launch_persistent_fwd<4, true>(a, (hipStream_t)stream);
+  hipStream_t st = (hipStream_t)stream;
+  RnnArgs a = common_args(ctx, gates, gx_bf16 ? nullptr : gx, aux, hbuf, wp_fwd, lens_dev, T, B, H, gates_bf16, ws_armed);
+  a.gxb = (const __bf16*)gx_bf16; a.bhh = bhh; a.pk = (float*)ws; a.h_bf = (__bf16*)h_bf16; a.hsum = hsum;
+  const int rc = by_gates(gates, [&](auto g) { return try_launch_persistent_fwd<g(), true>(a, ws_bytes, st); });
   if (rc < 0) return rc;
-  last_path = (last_path & ~(1 | 32 | 256)) | (rc == 1 ? 1 : 0);
+  record(ctx, rc == 1 ? FWD_PERSISTENT : FWD_STEPS);
   if (rc == 1) return 0;
   if (!gx) return 1;
   a.gx = gx; a.gxb = nullptr; a.hsum = nullptr;
-  DS2_HIP(hipMemsetAsync(ws, 0, ds2_rnn_fwd_workspace_bytes(B, H, 1), (hipStream_t)stream));
-  return dispatch<true>(gates, false, a, (hipStream_t)stream);
+  return fwd_steps(gates, 1, a, ws, st);
 }
 
 extern "C" int ds2_rnn_fwd(ds2_rnn_ctx* ctx, int gates, float* gx, const void* wp_fwd, const float* bhh, float* hbuf, float* aux, const int* lens_dev, int T,
                            int B, int H, int bf16, void* gates_bf16, void* ws, size_t ws_bytes, void* stream) {
-  return ds2_rnn_fwd_ex(ctx, gates, gx, wp_fwd, bhh, hbuf, aux, lens_dev, T, B, H, bf16, gates_bf16, nullptr, ws, ws_bytes, stream);
+  return ds2_rnn_fwd_ex(ctx, gates, gx, wp_fwd, bhh, hbuf, aux, lens_dev, T, B, H, bf16, gates_bf16, nullptr, ws, ws_bytes, stream, 0);
 }
 
 // bias gradients from the per-batch-row sums of the persistent backward kernel: part (B,2,4,H) -> db_ih (2,G*H), db_hh (2,G*H).
@@ -2021,19 +2062,11 @@ extern "C" int ds2_rnn_bias_grads(int gates, const float* bias_part, int B, int 
   return 0;
 }
 
-extern "C" size_t ds2_rnn_bwd_workspace_bytes(int gates, int B, int H, int bf16) {
-  const size_t step = pk_floats(B, H, gates * H, bf16 == 1) * sizeof(float);     // two ping-pong buffers of the step kernels
-  size_t pers = 4 * bwd_xbuf_bytes(gates, B, H, bf16 == 1) + 64;                  // four round-robin buffers of the persistent kernel + its census words
-  if (bf16 == 2) pers = std::max(pers, 8 * bwd_xbuf_bytes(gates, B, H, 1) + 64);  // the split form: hi and lo plane per buffer
-  if (bf16 == 2 && ksplit_avail(gates, H)) pers = std::max(pers, 2 * ksplit_xbuf_bytes(B, H) + 64);   // ... of the K-split kernel: two planes of two slots
-  if (bf16 == 1 && ksplit_avail(gates, H)) pers = std::max(pers, ksplit_xbuf_bytes(B, H) + 64);   // two slots of the K-split kernel + census
-  return (size_t)4 * B * H * sizeof(float) + (step > pers ? step : pers);
-}
+// (the carry + the larger of the step kernels' ping-pong buffers and the exchange buffers + census words of every reachable family: rnn_sizes.h)
+extern "C" size_t ds2_rnn_bwd_workspace_bytes(int gates, int B, int H, int bf16) { return bwd_workspace_bytes(gates, B, H, bf16); }
 
-// Which recurrences may run as ONE persistent launch (bf16 mode; default: both).  A persistent launch needs all of its workgroups resident
-// at once, so a caller that runs other kernels concurrently on the device during backward (collectives on a communication stream)
-// must switch the backward one off.  DS2_RNN_PERSISTENT=0 in the environment switches both off.
-// which kernel family the last recurrence calls used: bit 0 = ds2_rnn_fwd, bit 1 = ds2_rnn_bwd took the persistent kernel (reporting only)
+// which kernel family the last forward and the last backward call through the context took (reporting only): the DS2_RNN_PATH_* bits of
+// include/ds2hip.h, written by record() above
 extern "C" int ds2_rnn_last_path(const ds2_rnn_ctx* ctx) { return ctx ? ctx->last_path : 0; }
 
 namespace {
@@ -2104,6 +2137,9 @@ extern "C" int ds2_rnn_bwd_ksplit_footprint(int gates, int H, int* out3) {
   return 1;
 }
 
+// Which recurrences may run as ONE persistent launch (bf16 mode; default: both).  A persistent launch needs all of its workgroups resident
+// at once, so a caller that runs other kernels concurrently on the device during backward (collectives on a communication stream)
+// must switch the backward one off.  DS2_RNN_PERSISTENT=0 in the environment switches both off.
 extern "C" int ds2_rnn_persistent_enable(ds2_rnn_ctx* ctx, int forward, int backward) {
   DS2_REQUIRE(ctx, "ds2_rnn_persistent_enable: null context");
   ctx->persist_fwd = forward != 0;
@@ -2130,68 +2166,45 @@ extern "C" int ds2_rnn_persistent_counters(const ds2_rnn_ctx* ctx, int* out2) {
 //             / [d i, d f, d g, d o] (LSTM); their column sums over B are db_ih / db_hh             } call); untouched otherwise
 extern "C" int ds2_rnn_bwd_ex(ds2_rnn_ctx* ctx, int gates, const float* dy, int lddy, float* gx, float* aux, const float* hbuf, const void* wp_bwd,
                               const int* lens_dev, int T, int B, int H, int bf16, void* dgx_bf16, const void* gates_bf16, void* dhn_bf16,
-                              float* bias_part, void* ws, size_t ws_bytes, void* stream) {
-  DS2_REQUIRE(gates == 1 || gates == 3 || gates == 4, "ds2_rnn_bwd: gates must be 1 (tanh RNN), 3 (GRU) or 4 (LSTM)");
-  DS2_REQUIRE(dy && (aux || gates == 1) && hbuf && wp_bwd && lens_dev, "ds2_rnn_bwd: null pointer");
-  DS2_REQUIRE(gx || ((gates_bf16 || gates == 1) && dgx_bf16), "ds2_rnn_bwd: gx may only be NULL with both gates_bf16 (not for gates = 1) and dgx_bf16 given");
-  DS2_REQUIRE(T > 0 && B > 0 && H > 0 && (H % 4) == 0, "ds2_rnn_bwd: need H %% 4 == 0 (H=%d)", H);
-  DS2_REQUIRE(ws && ws_bytes >= ds2_rnn_bwd_workspace_bytes(gates, B, H, bf16), "ds2_rnn_bwd: workspace too small");
-  RnnArgs a{};
-  a.gx = gx; a.aux = aux; a.hbuf = const_cast<float*>(hbuf); a.wp = (const float*)wp_bwd; a.dy = dy; a.lddy = lddy;
-  a.dcar = (float*)ws; a.pk = (float*)ws + (size_t)4 * B * H;
-  a.dgx_bf = (__bf16*)dgx_bf16;
-  a.gates_bf = gates == 1 ? nullptr : (__bf16*)const_cast<void*>(gates_bf16);
-  a.dhn_bf = (__bf16*)dhn_bf16; a.bsum = bias_part;
-  a.lens = lens_dev; a.T = T; a.B = B; a.H = H;
-  a.hctx = ctx; a.status = ctx ? ctx->status_dev : nullptr;
-  a.prearmed = take_prearmed(ctx);
-  int scratch_path = 0, scratch_kind = 0;
-  int& last_path = ctx ? ctx->last_path : scratch_path;
-  int& last_bwd_kind = ctx ? ctx->last_bwd_kind : scratch_kind;
-  {
-    a.dbg = ctx ? ctx->debug_flags : 0;
-    hipStream_t st = (hipStream_t)stream;
-    // bf16: the K-split kernel where the shape qualifies (2 = it does, but a starved launch's cooldown is running: step kernels)
-    int rc = (bf16 == 1 && gates != 1) ? (gates == 3 ? try_launch_ksplit_bwd<3>(a, st) : try_launch_ksplit_bwd<4>(a, st)) : 0;
-    last_bwd_kind = rc == 1 ? 2 : 0;
-    bool split = false;
-    if (rc == 0 && bf16 == 2) {
-      // fp32 mode, split backward recurrence (operands behind the fp32 fragments of wp_bwd); else / during a cooldown the fp32 kernels
-      static const char* env = getenv("DS2_F32_RNN");
-      if (persist_idle(ctx, true) && !(env && env[0] == 'f') && !a.gates_bf && !a.dgx_bf) {
-        RnnArgs b = a;
-        b.wp = reinterpret_cast<const float*>(reinterpret_cast<const char*>(wp_bwd) + ds2_rnn_packed_bytes(gates, H, 1, 0));
-        static const char* envk = ds2_exp_getenv("DS2_RNN_KSPLIT");
-        const int rk = ((envk && envk[0] == '0') || gates == 1) ? 0 : (gates == 3 ? try_launch_ksplit_bwd<3, true>(b, st) : try_launch_ksplit_bwd<4, true>(b, st));
-        if (rk < 0) return rk;
-        if (rk == 1) { rc = 1; split = true; last_bwd_kind = 2; }
-        else {
-          rc = gates == 1 ? try_launch_persistent_bwd<1, true, true>(b, st) : gates == 3 ? try_launch_persistent_bwd<3, true, true>(b, st) : try_launch_persistent_bwd<4, true, true>(b, st);
-          split = rc == 1;
-          if (split) last_bwd_kind = 1;
-        }
-      }
-    }
-    if (rc == 0) {
-      rc = bf16 == 1 ? (gates == 1 ? try_launch_persistent_bwd<1, true>(a, st) : gates == 3 ? try_launch_persistent_bwd<3, true>(a, st) : try_launch_persistent_bwd<4, true>(a, st))
-                     : (gates == 1 ? try_launch_persistent_bwd<1, false>(a, st) : gates == 3 ? try_launch_persistent_bwd<3, false>(a, st) : try_launch_persistent_bwd<4, false>(a, st));
-      last_bwd_kind = rc == 1 ? 1 : 0;
-    }
-    last_path = (last_path & ~(6 | 16 | 64)) | (rc == 1 ? 2 : 0) | (last_bwd_kind == 2 ? 4 : 0) | (split ? 64 : 0);   // bit 6: the split kernel
-    if (rc != 0 && rc != 2) return rc < 0 ? rc : 0;
-  }
-  DS2_HIP(hipMemsetAsync(ws, 0, ds2_rnn_bwd_workspace_bytes(gates, B, H, bf16), (hipStream_t)stream));   // step kernels: zero carry + padding
-  if (bf16 == 2 && (H % 32) == 0 && !a.gates_bf && !a.dgx_bf) {
-    // fp32 mode, no persistent kernel took the call (shape, cooldown): the step kernels in split form — unless DS2_F32_RNN=f32 / debug selectors
-    static const char* env = getenv("DS2_F32_RNN");
-    if (!(env && env[0] == 'f') && !(a.dbg & ~128)) {
-      a.wp = reinterpret_cast<const float*>(reinterpret_cast<const char*>(wp_bwd) + ds2_rnn_packed_bytes(gates, H, 1, 0));
-      last_path |= 64;                                            // bit 6 without bit 1: split step kernels
-      return gates == 1 ? launch_steps<1, true, true>(true, a, (hipStream_t)stream)
-                         : gates == 3 ? launch_steps<3, true, true>(true, a, (hipStream_t)stream) : launch_steps<4, true, true>(true, a, (hipStream_t)stream);
+                              float* bias_part, void* ws, size_t ws_bytes, void* stream, int ws_armed) {
+  if (int e = check_entry("ds2_rnn_bwd", gates, dy && (aux || gates == 1) && hbuf && wp_bwd && lens_dev, gx || ((gates_bf16 || gates == 1) && dgx_bf16), T, B, H,
+                          ws, ws_bytes, bwd_workspace_bytes(gates, B, H, bf16)))
+    return e;
+  hipStream_t st = (hipStream_t)stream;
+  RnnArgs a = bwd_args(ctx, gates, dy, lddy, gx, aux, hbuf, wp_bwd, lens_dev, T, B, H, dgx_bf16, gates_bf16, dhn_bf16, bias_part, ws, ws_armed);
+  const size_t pk_bytes = ws_bytes - bwd_carry_bytes(B, H);
+  // bf16: the K-split kernel where the shape qualifies (2 = it does, but a starved launch's cooldown is running: step kernels)
+  BwdRan ran = BWD_KSPLIT;
+  int rc = bf16 == 1 ? by_gates_34(gates, [&](auto g) { return try_launch_ksplit_bwd<g()>(a, pk_bytes, st); }) : 0;
+  // fp32 mode, split backward recurrence (operands behind the fp32 fragments of wp_bwd); else / during a cooldown the fp32 kernels
+  if (rc == 0 && bf16 == 2 && persist_idle(ctx, true) && !env_f32_rnn() && !a.gates_bf && !a.dgx_bf) {
+    RnnArgs b = a;
+    b.wp = bytes_behind(wp_bwd, ds2_rnn_packed_bytes(gates, H, 1, 0));
+    ran = BWD_SPLIT_KSPLIT;
+    rc = env_ksplit_off() ? 0 : by_gates_34(gates, [&](auto g) { return try_launch_ksplit_bwd<g(), true>(b, pk_bytes, st); });
+    if (rc < 0) return rc;
+    if (rc != 1) {
+      ran = BWD_SPLIT_ALLGATHER;
+      rc = by_gates(gates, [&](auto g) { return try_launch_persistent_bwd<g(), true, true>(b, pk_bytes, st); });
     }
   }
-  return bf16 == 1 ? dispatch<true>(gates, true, a, (hipStream_t)stream) : dispatch<false>(gates, true, a, (hipStream_t)stream);
+  if (rc == 0) {
+    ran = BWD_ALLGATHER;
+    rc = by_gates(gates, [&](auto g) {
+      return bf16 == 1 ? try_launch_persistent_bwd<g(), true>(a, pk_bytes, st) : try_launch_persistent_bwd<g(), false>(a, pk_bytes, st);
+    });
+  }
+  if (rc < 0) return rc;
+  record(ctx, rc == 1 ? ran : BWD_STEPS);
+  if (rc == 1) return 0;
+  DS2_HIP(hipMemsetAsync(ws, 0, bwd_workspace_bytes(gates, B, H, bf16), st));   // step kernels: zero carry + padding
+  // fp32 mode, no persistent kernel took the call (shape, cooldown): the step kernels in split form — unless DS2_F32_RNN=f32 / debug selectors
+  if (bf16 == 2 && (H % 32) == 0 && !a.gates_bf && !a.dgx_bf && !env_f32_rnn() && !(a.dbg & ~128)) {
+    a.wp = bytes_behind(wp_bwd, ds2_rnn_packed_bytes(gates, H, 1, 0));
+    record(ctx, BWD_SPLIT_STEPS);
+    return by_gates(gates, [&](auto g) { return launch_steps<g(), true, true>(true, a, st); });
+  }
+  return bf16 == 1 ? dispatch<true>(gates, true, a, st) : dispatch<false>(gates, true, a, st);
 }
 
 // ds2_rnn_bwd_ex for a layer whose output feeds a BatchNorm1d (every recurrent layer of the model: SequenceWise(BatchNorm1d) of the next
@@ -2205,53 +2218,41 @@ static int rnn_bwd_bn_impl(ds2_rnn_ctx* ctx, int gates, const float* dyn, int ld
                               const float* bn_gamma, const float* bn_s0, const float* bn_s1, float bn_eps, float* dy_scratch, float* gx,
                               float* aux, const float* hbuf, const void* wp_bwd, const int* lens_dev, int T, int B, int H, int bf16,
                               void* dgx_bf16, const void* gates_bf16, void* dhn_bf16, float* bias_part, void* ws, size_t ws_bytes,
-                              void* stream) {
-  DS2_REQUIRE(gates == 1 || gates == 3 || gates == 4, "ds2_rnn_bwd_bn: gates must be 1 (tanh RNN), 3 (GRU) or 4 (LSTM)");
-  DS2_REQUIRE(dyn && bn_x && bn_mean && bn_var && bn_gamma && bn_s0 && bn_s1 && (aux || gates == 1) && hbuf && wp_bwd && lens_dev,
-              "ds2_rnn_bwd_bn: null pointer");
-  DS2_REQUIRE(gx || ((gates_bf16 || gates == 1) && dgx_bf16), "ds2_rnn_bwd_bn: gx may only be NULL with both gates_bf16 (not for gates = 1) and dgx_bf16 given");
-  DS2_REQUIRE(T > 0 && B > 0 && H > 0 && (H % 4) == 0, "ds2_rnn_bwd_bn: need H %% 4 == 0 (H=%d)", H);
-  DS2_REQUIRE(ws && ws_bytes >= ds2_rnn_bwd_workspace_bytes(gates, B, H, bf16), "ds2_rnn_bwd_bn: workspace too small");
+                              void* stream, int ws_armed) {
+  if (int e = check_entry("ds2_rnn_bwd_bn", gates, dyn && bn_x && bn_mean && bn_var && bn_gamma && bn_s0 && bn_s1 && (aux || gates == 1) && hbuf && wp_bwd && lens_dev,
+                          gx || ((gates_bf16 || gates == 1) && dgx_bf16), T, B, H, ws, ws_bytes, bwd_workspace_bytes(gates, B, H, bf16)))
+    return e;
   hipStream_t st = (hipStream_t)stream;
-  if (bf16 == 1) {
-    RnnArgs a{};
-    a.gx = gx; a.aux = aux; a.hbuf = const_cast<float*>(hbuf); a.wp = (const float*)wp_bwd; a.dy = dyn; a.lddy = lddyn;
-    a.dcar = (float*)ws; a.pk = (float*)ws + (size_t)4 * B * H;
-    a.dgx_bf = (__bf16*)dgx_bf16; a.gates_bf = (__bf16*)const_cast<void*>(gates_bf16);
-    a.dhn_bf = (__bf16*)dhn_bf16; a.bsum = bias_part;
-    a.lens = lens_dev; a.T = T; a.B = B; a.H = H;
+  // (only when the persistent backward is armed: a cool-down call is counted once, by the un-fused call below)
+  if (bf16 == 1 && persist_idle(ctx, true)) {
+    RnnArgs a = bwd_args(ctx, gates, dyn, lddyn, gx, aux, hbuf, wp_bwd, lens_dev, T, B, H, dgx_bf16, gates_bf16, dhn_bf16, bias_part, ws, ws_armed);
     a.bn_x = bn_x; a.bn_x_bf16 = bn_x_bf16; a.ldbnx = ldx; a.bn_mean = bn_mean; a.bn_var = bn_var; a.bn_gamma = bn_gamma; a.bn_s0 = bn_s0; a.bn_s1 = bn_s1; a.bn_eps = bn_eps;
-    a.hctx = ctx; a.status = ctx ? ctx->status_dev : nullptr;
-    a.prearmed = take_prearmed(ctx);
-    a.dbg = ctx ? ctx->debug_flags : 0;
-    // (only when the persistent backward is armed: a cool-down call is counted once, by the un-fused call below)
-    const int rc = (persist_idle(ctx, true) && gates != 1) ? (gates == 3 ? try_launch_ksplit_bwd<3>(a, st) : try_launch_ksplit_bwd<4>(a, st)) : 0;
+    const size_t pk_bytes = ws_bytes - bwd_carry_bytes(B, H);
+    const int rc = by_gates_34(gates, [&](auto g) { return try_launch_ksplit_bwd<g()>(a, pk_bytes, st); });
     if (rc < 0) return rc;
     if (rc == 1) {
-      ctx->last_bwd_kind = 2;
-      ctx->last_path = (ctx->last_path & ~(2 | 4 | 16)) | 2 | 4 | 16;
+      record(ctx, BWD_KSPLIT_BN);
       return 0;
     }
   }
   // not taken by the K-split kernel: materialise dy, then the ordinary path.  dy_scratch == NULL: nothing has been launched or counted
   // yet — return 1 so that the caller allocates the (T*B, H) buffer only when it is really needed, and calls again
   if (!dy_scratch) return 1;
-  int rc = bn_x_bf16 ? ds2i_bn1d_bwd_apply_xbf(dyn, lddyn, bn_x, ldx, dy_scratch, H, T * B, H, bn_mean, bn_var, bn_gamma, bn_s0, bn_s1, bn_eps, st)
-                     : ds2i_bn1d_bwd_apply(dyn, lddyn, bn_x, ldx, dy_scratch, H, T * B, H, bn_mean, bn_var, bn_gamma, bn_s0, bn_s1, bn_eps, st);
+  const int rc = bn_x_bf16 ? ds2i_bn1d_bwd_apply_xbf(dyn, lddyn, bn_x, ldx, dy_scratch, H, T * B, H, bn_mean, bn_var, bn_gamma, bn_s0, bn_s1, bn_eps, st)
+                           : ds2i_bn1d_bwd_apply(dyn, lddyn, bn_x, ldx, dy_scratch, H, T * B, H, bn_mean, bn_var, bn_gamma, bn_s0, bn_s1, bn_eps, st);
   if (rc) return rc;
-  rc = ds2_rnn_bwd_ex(ctx, gates, dy_scratch, H, gx, aux, hbuf, wp_bwd, lens_dev, T, B, H, bf16, dgx_bf16, gates_bf16, dhn_bf16, bias_part, ws, ws_bytes,
-                      stream);
-  if (ctx) ctx->last_path &= ~16;
-  return rc;
+  // (the fused attempt launched nothing, so a workspace that was armed still is)
+  return ds2_rnn_bwd_ex(ctx, gates, dy_scratch, H, gx, aux, hbuf, wp_bwd, lens_dev, T, B, H, bf16, dgx_bf16, gates_bf16, dhn_bf16, bias_part, ws, ws_bytes,
+                        stream, ws_armed);
 }
 
 extern "C" int ds2_rnn_bwd_bn(ds2_rnn_ctx* ctx, int gates, const float* dyn, int lddyn, const float* bn_x, int ldx, const float* bn_mean, const float* bn_var,
                               const float* bn_gamma, const float* bn_s0, const float* bn_s1, float bn_eps, float* dy_scratch, float* gx,
                               float* aux, const float* hbuf, const void* wp_bwd, const int* lens_dev, int T, int B, int H, int bf16,
                               void* dgx_bf16, const void* gates_bf16, void* dhn_bf16, float* bias_part, void* ws, size_t ws_bytes,
-                              void* stream) {
+                              void* stream, int ws_armed) {
   return rnn_bwd_bn_impl(ctx, gates, dyn, lddyn, bn_x, 0, ldx, bn_mean, bn_var, bn_gamma, bn_s0, bn_s1, bn_eps, dy_scratch, gx, aux, hbuf, wp_bwd, lens_dev,
-                         T, B, H, bf16, dgx_bf16, gates_bf16, dhn_bf16, bias_part, ws, ws_bytes, stream);
+                         T, B, H, bf16, dgx_bf16, gates_bf16, dhn_bf16, bias_part, ws, ws_bytes, stream, ws_armed);
 }
 
 // ds2_rnn_bwd_bn with the BatchNorm's input given as bf16 (pitch ldx, even; H % 4 == 0): the centred operand of ds2_center_colstats, bn_mean its
@@ -2259,15 +2260,16 @@ extern "C" int ds2_rnn_bwd_bn(ds2_rnn_ctx* ctx, int gates, const float* dyn, int
 extern "C" int ds2_rnn_bwd_bn_xbf16(ds2_rnn_ctx* ctx, int gates, const float* dyn, int lddyn, const void* bn_x_bf16, int ldx, const float* bn_mean,
                                     const float* bn_var, const float* bn_gamma, const float* bn_s0, const float* bn_s1, float bn_eps, float* dy_scratch,
                                     float* gx, float* aux, const float* hbuf, const void* wp_bwd, const int* lens_dev, int T, int B, int H, int bf16,
-                                    void* dgx_bf16, const void* gates_bf16, void* dhn_bf16, float* bias_part, void* ws, size_t ws_bytes, void* stream) {
+                                    void* dgx_bf16, const void* gates_bf16, void* dhn_bf16, float* bias_part, void* ws, size_t ws_bytes, void* stream,
+                                    int ws_armed) {
   DS2_REQUIRE((ldx % 2) == 0 && (H % 4) == 0 && ((uintptr_t)bn_x_bf16 % 4) == 0, "ds2_rnn_bwd_bn_xbf16: even pitch, H %% 4 == 0, 4-byte aligned base");
   return rnn_bwd_bn_impl(ctx, gates, dyn, lddyn, (const float*)bn_x_bf16, 1, ldx, bn_mean, bn_var, bn_gamma, bn_s0, bn_s1, bn_eps, dy_scratch, gx, aux, hbuf,
-                         wp_bwd, lens_dev, T, B, H, bf16, dgx_bf16, gates_bf16, dhn_bf16, bias_part, ws, ws_bytes, stream);
+                         wp_bwd, lens_dev, T, B, H, bf16, dgx_bf16, gates_bf16, dhn_bf16, bias_part, ws, ws_bytes, stream, ws_armed);
 }
 
 extern "C" int ds2_rnn_bwd(ds2_rnn_ctx* ctx, int gates, const float* dy, int lddy, float* gx, float* aux, const float* hbuf, const void* wp_bwd,
                            const int* lens_dev, int T, int B, int H, int bf16, void* dgx_bf16, const void* gates_bf16, void* ws, size_t ws_bytes,
                            void* stream) {
   return ds2_rnn_bwd_ex(ctx, gates, dy, lddy, gx, aux, hbuf, wp_bwd, lens_dev, T, B, H, bf16, dgx_bf16, gates_bf16, nullptr, nullptr, ws, ws_bytes,
-                        stream);
+                        stream, 0);
 }

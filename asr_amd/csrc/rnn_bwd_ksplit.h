@@ -508,44 +508,32 @@ __global__ __launch_bounds__(NW * 64) void rnn_bwd_ksplit_kernel(RnnArgs a, char
 #undef DS2_KS_FETCH_WAIT
 }
 
-// bytes of the two exchange slots: [2 slots][2 dirs x batch tiles][gs consumers][8 waves][gs producers][128 B]
-size_t ksplit_xbuf_bytes(int B, int H) { const size_t gs = (size_t)H / 32; return (size_t)2 * 2 * ceil_div(B, 16) * gs * gs * 1024; }
-bool ksplit_shape_ok(int H) { return H >= 256 && (H % 256) == 0 && H <= 1280; }
-
 // 1 = launched, 0 = not eligible (the caller tries the all-gather persistent kernel, then the step kernels), 2 = eligible but cooling
 // down after a starved launch (step kernels), < 0 = error
 template <int G, bool SP = false>
-int try_launch_ksplit_bwd(RnnArgs a, hipStream_t st) {
+int try_launch_ksplit_bwd(RnnArgs a, size_t pk_bytes, hipStream_t st) {
   constexpr int NPL = SP ? 2 : 1;
-  static const char* env = getenv("DS2_RNN_PERSISTENT");
-  static const char* envk = ds2_exp_getenv("DS2_RNN_KSPLIT");               // "0": keep the all-gather backward kernel (A/B runs)
-  if ((env && env[0] == '0') || (envk && envk[0] == '0') || a.dbg) return 0;   // any selector: not this kernel
+  if (env_persistent_off() || env_ksplit_off() || a.dbg) return 0;   // DS2_RNN_KSPLIT=0: keep the all-gather backward kernel (A/B runs); any selector: not this kernel
   if (!((a.gates_bf && a.dgx_bf) || (!a.gates_bf && !a.dgx_bf && a.gx))) return 0;
   if (SP && (a.gates_bf || a.dgx_bf)) return 0;                      // the split form: plain fp32 buffers
   if (!ksplit_shape_ok(a.H) || a.T < 2) return 0;
   const int gs = a.H / 32, nt = a.H / 128, nbt = ceil_div(a.B, 16);
   if (nt * G * 4 * NPL > (SP ? 150 : 176)) return 0;                 // W_hh fragments must leave room for the rest (256 registers per lane)
-  if ((long long)gs * nbt * 2 > cu_count()) return 0;
+  if ((long long)gs * nbt * 2 > ds2_dev_facts().cus) return 0;
   if (!persist_allowed(a.hctx, true)) return 2;                             // eligible, but a starved launch's cooldown is running
-  a.p_nbt = nbt; a.p_gs = gs; a.p_cux = CUS_PER_XCD;
-  a.p_census = xcd_local_fits(gs, 2 * nbt) ? 1 : 0;
-  char* xbuf = reinterpret_cast<char*>(a.pk);
-  const size_t xbytes = NPL * ksplit_xbuf_bytes(a.B, a.H);
-  if (!a.prearmed) DS2_HIP(hipMemsetAsync(xbuf, 0xff, xbytes + CENSUS_BYTES, st));     // both slots: tag 1 = "not the data of steps 0 / 1"; census words = -1
-  unsigned* census = reinterpret_cast<unsigned*>(xbuf + xbytes);
-  dim3 grid(a.p_census ? cu_count() : gs * nbt * 2), block(NW * 64);
-  static const char* sl = getenv("DS2_RNN_SPIN_LIMIT");
-  const int spin_limit = sl ? atoi(sl) : (1 << 20);
+  // the fill arms both slots: tag 1 = "not the data of steps 0 / 1"
+  PersistLaunch l;
+  if (int e = persist_arm(a, {gs, nbt, true, bwd_ksplit_xbytes(a.B, a.H, SP ? OP_SPLIT : OP_BF16)}, pk_bytes, st, l)) return e;
   switch (nt) {
 #define DS2_KS(NT_)                                                                                                       \
   case NT_:                                                                                                               \
     if constexpr (SP && NT_ * G * 4 * 2 <= 150) {                                                                         \
-      hipLaunchKernelGGL((rnn_bwd_ksplit_kernel<G, NT_, false, true>), grid, block, 0, st, a, xbuf, census, spin_limit);  \
+      hipLaunchKernelGGL((rnn_bwd_ksplit_kernel<G, NT_, false, true>), l.grid, l.block, 0, st, a, l.xbuf, l.census, l.spin_limit);  \
     } else if constexpr (!SP && NT_ * G * 4 <= 176) {                                                                     \
       if (G == 3 && a.gates_bf && a.dgx_bf) {                                                                             \
-        if constexpr (G == 3) hipLaunchKernelGGL((rnn_bwd_ksplit_kernel<3, NT_, true>), grid, block, 0, st, a, xbuf, census, spin_limit); \
+        if constexpr (G == 3) hipLaunchKernelGGL((rnn_bwd_ksplit_kernel<3, NT_, true>), l.grid, l.block, 0, st, a, l.xbuf, l.census, l.spin_limit); \
       } else {                                                                                                            \
-        hipLaunchKernelGGL((rnn_bwd_ksplit_kernel<G, NT_, false>), grid, block, 0, st, a, xbuf, census, spin_limit);      \
+        hipLaunchKernelGGL((rnn_bwd_ksplit_kernel<G, NT_, false>), l.grid, l.block, 0, st, a, l.xbuf, l.census, l.spin_limit);      \
       }                                                                                                                   \
     } else {                                                                                                              \
       return 0;                                                                                                           \
@@ -555,7 +543,5 @@ int try_launch_ksplit_bwd(RnnArgs a, hipStream_t st) {
 #undef DS2_KS
     default: return 0;
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return ds2_set_error("rnn k-split backward launch failed: %s", hipGetErrorString(e));
-  return 1;
+  return launch_result("rnn k-split backward", 1);
 }

@@ -19,9 +19,7 @@ __device__ __forceinline__ void store4_sc1(void* p, unsigned v) { asm volatile("
 
 constexpr int U10 = 10;
 __host__ __device__ constexpr int u10_tiles(int G) { return (G * U10 + 15) / 16; }
-// shapes the packed operand is produced for (independent of the batch): whole 32-unit chunks, whole 10-unit slices, at most one workgroup
-// per CU for both directions of one batch tile, at most five chunks per wave
-inline bool u10_shape_ok(int H) { return H >= 160 && (H % 160) == 0 && H <= 1280; }
+// (the shapes the packed operand is produced for, independent of the batch: u10_shape_ok, rnn_sizes.h)
 
 // packed operand: [plane hi | plane lo][dir][slice H/10][tile][chunk H/32][lane 64] x 16 bytes (8 bf16: column (lane & 15) of the tile, k = 8 (lane >> 4) ..)
 __global__ __launch_bounds__(256) void rnn_pack_u10_kernel(const float* __restrict__ whh, void* __restrict__ wp_hi, void* __restrict__ wp_lo, int G, int H) {
@@ -265,34 +263,25 @@ __global__ __launch_bounds__(NW * 64) void rnn_fwd_u10_kernel(RnnArgs a, char* x
 
 // 1 = launched, 0 = not eligible, < 0 = error.  a.wp = the hi plane of the 10-unit packed operand (lo plane behind it).
 template <int G>
-int try_launch_fwd_u10(RnnArgs a, hipStream_t st) {
-  static const char* env = getenv("DS2_RNN_PERSISTENT");
-  if (env && env[0] == '0') return 0;
+int try_launch_fwd_u10(RnnArgs a, size_t pk_bytes, hipStream_t st) {
+  if (env_persistent_off()) return 0;
   if (a.dbg & ~(128 | 256)) return 0;
   if (!u10_shape_ok(a.H) || a.T < 2 || a.gates_bf || a.h_bf) return 0;
   const int mb = a.B > 16 ? 2 : 1, nbt = ceil_div(a.B, 16 * mb), gs = a.H / U10, nch = a.H / 32, ncw = ceil_div(nch, NW);
-  if (ncw > 5 || (long long)gs * nbt * 2 > cu_count()) return 0;             // every workgroup resident at once: one per CU
+  if (ncw > 5 || (long long)gs * nbt * 2 > ds2_dev_facts().cus) return 0;    // every workgroup resident at once: one per CU
   a.nsl = a.H / 16;
   a.nbt16 = ceil_div(a.B, 32) * 2;
-  a.p_nbt = nbt; a.p_gs = gs; a.p_cux = CUS_PER_XCD; a.p_census = 0;         // 128 slices never fit one XCD: placement-independent protocol
-  char* xbuf = reinterpret_cast<char*>(a.pk);
-  const size_t xbytes = 4 * 2 * fwd_xbuf_bytes(a.B, a.H, 1);
-  if (!a.prearmed) DS2_HIP(hipMemsetAsync(xbuf, 0xff, xbytes + CENSUS_BYTES, st));
-  unsigned* census = reinterpret_cast<unsigned*>(xbuf + xbytes);
-  dim3 grid(gs * nbt * 2), block(NW * 64);
-  static const char* sl = getenv("DS2_RNN_SPIN_LIMIT");
-  const int spin_limit = sl ? atoi(sl) : (1 << 20);
+  PersistLaunch l;                                                           // no census: 128 slices never fit one XCD, placement-independent protocol
+  if (int e = persist_arm(a, {gs, nbt, false, fwd_u10_xbytes(a.B, a.H)}, pk_bytes, st, l)) return e;
 #define DS2_U10(NCW_)                                                                                                        \
   case NCW_:                                                                                                                 \
-    if (mb == 2) hipLaunchKernelGGL((rnn_fwd_u10_kernel<G, 2, NCW_>), grid, block, 0, st, a, xbuf, census, spin_limit);       \
-    else hipLaunchKernelGGL((rnn_fwd_u10_kernel<G, 1, NCW_>), grid, block, 0, st, a, xbuf, census, spin_limit);               \
+    if (mb == 2) hipLaunchKernelGGL((rnn_fwd_u10_kernel<G, 2, NCW_>), l.grid, l.block, 0, st, a, l.xbuf, l.census, l.spin_limit);       \
+    else hipLaunchKernelGGL((rnn_fwd_u10_kernel<G, 1, NCW_>), l.grid, l.block, 0, st, a, l.xbuf, l.census, l.spin_limit);               \
     break;
   switch (ncw) {
     DS2_U10(1) DS2_U10(2) DS2_U10(3) DS2_U10(4) DS2_U10(5)
     default: return 0;
   }
 #undef DS2_U10
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return ds2_set_error("rnn 10-unit forward launch failed: %s", hipGetErrorString(e));
-  return 1;
+  return launch_result("rnn 10-unit forward", 1);
 }

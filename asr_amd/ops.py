@@ -49,7 +49,7 @@ class RnnCtx(C.Structure):
     bits, cooldown, enable switches or starvation record."""
     _fields_ = [("size", C.c_int), ("persist_fwd", C.c_int), ("persist_bwd", C.c_int), ("cooldown", C.c_int), ("rearm_calls", C.c_int),
                 ("starved_total", C.c_int), ("last_path", C.c_int), ("last_bwd_kind", C.c_int), ("debug_flags", C.c_int),
-                ("ws_prearmed", C.c_int), ("reserved", C.c_int * 6), ("status_dev", C.c_void_p), ("poison_host", C.c_void_p), ("poison_dev", C.c_void_p)]
+                ("reserved", C.c_int * 7), ("status_dev", C.c_void_p), ("poison_host", C.c_void_p), ("poison_dev", C.c_void_p)]
 
 
 _RNN_TLS = threading.local()
@@ -1005,7 +1005,7 @@ def weight_prep_bf16(layers):
 def rnn_ws(kind: str, gates: int, B: int, H: int, bf16, device) -> Tensor:
     """The workspace of ONE rnn_fwd ("fwd") / rnn_bwd / rnn_bwd_bn ("bwd") call, filled with 0xff bytes NOW, in stream order: pass it as `ws=` to
     the call.  A persistent launch needs its exchange buffers armed with that pattern; armed here — ahead of the GEMM in front of the recurrence —
-    the fill is no longer a launch of its own between that GEMM and the launch that waits for every CU (ds2_rnn_ctx.ws_prearmed)."""
+    the fill is no longer a launch of its own between that GEMM and the launch that waits for every CU (the entries' `ws_armed` argument)."""
     lib = _lib.load()
     n = lib.ds2_rnn_fwd_workspace_bytes(B, H, int(bf16)) if kind == "fwd" else lib.ds2_rnn_bwd_workspace_bytes(gates, B, H, int(bf16))
     ws = _ws(n, device)
@@ -1019,17 +1019,6 @@ def _take_ws(ws: Optional[Tensor], need: int, device):
         return _ws(need, device), False
     assert ws.numel() >= need and ws.device == torch.device(device)
     return ws, True
-
-
-def _rnn_call(device, armed: bool, thunk):
-    """Run one recurrence entry point with the context's one-shot `ws_prearmed` promise set iff the workspace was armed by rnn_ws — and never
-    left standing: the library clears it when it reads it; an argument check that fails before that must not hand it to the NEXT call."""
-    ctx = rnn_ctx(device)
-    ctx.ws_prearmed = 1 if armed else 0
-    try:
-        return thunk()
-    finally:
-        ctx.ws_prearmed = 0
 
 
 def rnn_persistent_enable(forward: bool = True, backward: bool = True, device=None) -> None:
@@ -1104,18 +1093,18 @@ def rnn_fwd(gates: int, gx: Tensor, wp_fwd: Tensor, bhh: Tensor, lens_dev: Tenso
         gxb = gx if gx.dtype == torch.bfloat16 else None
         gxf = None if gxb is not None else gx
         for _attempt in (0, 1):
-            rc = _rnn_call(gx.device, armed and _attempt == 0, lambda: lib.ds2_rnn_fwd_x(
+            rc = lib.ds2_rnn_fwd_x(
                 _ctxp(gx.device), gates, _ptr(gxf), _ptr(gxb), wp_fwd.data_ptr(), bhh.data_ptr(), hbuf.data_ptr(), _ptr(aux),
-                lens_dev.data_ptr(), T, B, H, _ptr(rec), _ptr(h_bf16), _ptr(hsum), ws.data_ptr(), wsb, _stream()))
+                lens_dev.data_ptr(), T, B, H, _ptr(rec), _ptr(h_bf16), _ptr(hsum), ws.data_ptr(), wsb, _stream(), int(armed and _attempt == 0))
             if rc != 1:
                 break
             gxf, gxb = widen_bf16(gxb), None
         _lib.check(rc, "ds2_rnn_fwd_x")
         return hbuf, aux, rec
     _chk_f32(gx)
-    _lib.check(_rnn_call(gx.device, armed, lambda: lib.ds2_rnn_fwd_ex(
+    _lib.check(lib.ds2_rnn_fwd_ex(
         _ctxp(gx.device), gates, gx.data_ptr(), wp_fwd.data_ptr(), bhh.data_ptr(), hbuf.data_ptr(), _ptr(aux),
-        lens_dev.data_ptr(), T, B, H, int(bf16), _ptr(rec), _ptr(h_bf16), ws.data_ptr(), wsb, _stream())), "ds2_rnn_fwd")
+        lens_dev.data_ptr(), T, B, H, int(bf16), _ptr(rec), _ptr(h_bf16), ws.data_ptr(), wsb, _stream(), int(armed)), "ds2_rnn_fwd")
     return (hbuf, aux, rec) if packed_gates else (hbuf, aux)
 
 
@@ -1136,8 +1125,10 @@ def wgrad_fits_beside_bwd_recurrence(gates: int, H: int) -> bool:
 
 
 def rnn_last_path(device=None) -> int:
-    """bit 0 / bit 1: the last rnn_fwd / rnn_bwd call ran as one persistent launch (and produced its optional outputs); bit 2: that
-    backward launch was the K-split kernel (bf16 partial-dh exchange; results within a stated tolerance of the step kernels')"""
+    """The DS2_RNN_PATH_* bits of include/ds2hip.h.  1 / 2: the last rnn_fwd / rnn_bwd call ran as one persistent launch (and produced its
+    optional outputs); 4: that backward launch was the K-split kernel (bf16 partial-dh exchange; results within a stated tolerance of the step
+    kernels'); 16: it applied the BatchNorm1d backward on the fly (rnn_bwd_bn); 32 / 64: a split (fp32-mode) forward / backward kernel took
+    the call; 256: the 10-unit-slice forward kernel."""
     return _lib.load().ds2_rnn_last_path(_ctxp(device))
 
 
@@ -1163,10 +1154,10 @@ def rnn_bwd(gates: int, dy: Tensor, gx: Optional[Tensor], aux: Optional[Tensor],
     lib = _lib.load()
     wsb = lib.ds2_rnn_bwd_workspace_bytes(gates, B, H, int(bf16))
     ws, armed = _take_ws(ws, wsb, dy.device)
-    _lib.check(_rnn_call(dy.device, armed, lambda: lib.ds2_rnn_bwd_ex(
+    _lib.check(lib.ds2_rnn_bwd_ex(
         _ctxp(dy.device), gates, dy.data_ptr(), _row_pitch(dy), _ptr(gx), _ptr(aux), hbuf.data_ptr(), wp_bwd.data_ptr(),
         lens_dev.data_ptr(), T, B, H, int(bf16), _ptr(dgx_bf16), _ptr(gates_bf16), _ptr(dhn_bf16), _ptr(bias_part),
-        ws.data_ptr(), wsb, _stream())), "ds2_rnn_bwd")
+        ws.data_ptr(), wsb, _stream(), int(armed)), "ds2_rnn_bwd")
 
 
 def bn1d_bwd_sums(dY: Tensor, X: Tensor, mean: Tensor, var: Tensor, gamma: Tensor, out: Optional[Tuple[Tensor, Tensor]] = None) -> Tuple[Tensor, Tensor]:
@@ -1202,11 +1193,13 @@ def rnn_bwd_bn(gates: int, dyn: Tensor, bn_x: Tensor, mean: Tensor, var: Tensor,
     lib = _lib.load()
     wsb = lib.ds2_rnn_bwd_workspace_bytes(gates, B, H, int(bf16))
     ws, armed = _take_ws(ws, wsb, dyn.device)
+    entry = lib.ds2_rnn_bwd_bn_xbf16 if xbf else lib.ds2_rnn_bwd_bn
+
     def call(scratch):
-        return _rnn_call(dyn.device, armed and scratch is None, lambda: (lib.ds2_rnn_bwd_bn_xbf16 if xbf else lib.ds2_rnn_bwd_bn)(_ctxp(dyn.device), gates, dyn.data_ptr(), _row_pitch(dyn), bn_x.data_ptr(), bn_x.stride(0), mean.data_ptr(), var.data_ptr(),
-                                  gamma.data_ptr(), s0.data_ptr(), s1.data_ptr(), BN_EPS, _ptr(scratch), _ptr(gx), _ptr(aux),
-                                  hbuf.data_ptr(), wp_bwd.data_ptr(), lens_dev.data_ptr(), T, B, H, int(bf16), _ptr(dgx_bf16), _ptr(gates_bf16),
-                                  _ptr(dhn_bf16), _ptr(bias_part), ws.data_ptr(), wsb, _stream()))
+        return entry(_ctxp(dyn.device), gates, dyn.data_ptr(), _row_pitch(dyn), bn_x.data_ptr(), bn_x.stride(0), mean.data_ptr(), var.data_ptr(),
+                     gamma.data_ptr(), s0.data_ptr(), s1.data_ptr(), BN_EPS, _ptr(scratch), _ptr(gx), _ptr(aux),
+                     hbuf.data_ptr(), wp_bwd.data_ptr(), lens_dev.data_ptr(), T, B, H, int(bf16), _ptr(dgx_bf16), _ptr(gates_bf16),
+                     _ptr(dhn_bf16), _ptr(bias_part), ws.data_ptr(), wsb, _stream(), int(armed and scratch is None))
     rc = call(None)                  # the fused K-split launch needs no scratch: the (T*B, H) fp32 buffer is allocated only on the fallback (rc 1)
     if rc == 1:
         rc = call(torch.empty(T * B, H, dtype=torch.float32, device=dyn.device))

@@ -51,16 +51,16 @@ typedef struct ds2_rnn_ctx {
   int last_path;            /* out: bits describing what the last forward / backward call launched (ds2_rnn_last_path) */
   int last_bwd_kind;        /* out: 0 step kernels, 1 all-gather persistent, 2 K-split persistent */
   int debug_flags;          /* kernel-family selectors (ds2_debug_flags) */
-  int ws_prearmed;          /* in, one-shot (cleared by the next recurrence call through this context): the caller has filled that call's whole
-                             * workspace with 0xff bytes (ds2_memset_async) EARLIER in the stream — a persistent launch then skips its own
-                             * fill of the exchange buffers, which otherwise sits between the projection GEMM and the launch that needs every CU */
-  int reserved[6];
+  int reserved[7];
   int* status_dev;
   int* poison_host;
   int* poison_dev;
 } ds2_rnn_ctx;
 int ds2_rnn_ctx_init(ds2_rnn_ctx* ctx, int* status_dev, int* poison_host, int* poison_dev);
-/* hipMemsetAsync through the C ABI (workspace pre-arming, see ws_prearmed). */
+/* hipMemsetAsync through the C ABI.  Workspace pre-arming: the recurrence entries that take a trailing `ws_armed` skip a persistent launch's
+ * own fill of the exchange buffers — which otherwise sits between the projection GEMM and the launch that needs every CU — when it is 1: the
+ * caller promises that it has filled THIS call's whole workspace with 0xff bytes earlier in the stream.  The promise belongs to the one call
+ * it is passed to (an argument, not state of the context: two threads driving one context cannot hand it to each other's calls). */
 int ds2_memset_async(void* dst, int value, size_t bytes, void* stream);
 /* Kernel-family selectors of the recurrence (every selection computes the full result; used by the parity tests and A/B scripts):
  * 8 / 16 alternative tile shapes of the wide step kernels, 64 one launch per time step instead of the persistent kernels, 128 the
@@ -316,7 +316,17 @@ int ds2_rnn_persistent_enable(ds2_rnn_ctx* ctx, int forward, int backward);
  * whether ds2_gemm_bf16_tn_group (4 waves x 128 registers, 84 KB of LDS) fits on a CU BESIDE the recurrence of the layer below
  * (asr_deepspeech/modules/blocks.py:87-89 backward; the weight gradients of blocks.py:76-78 are off its critical path). */
 int ds2_rnn_bwd_ksplit_footprint(int gates, int H, int* out3);
-/* reporting: bit 0 / bit 1 set if the last ds2_rnn_fwd / ds2_rnn_bwd call through this context ran as a persistent launch (bench.py labels its roofline with it) */
+/* reporting: which kernel family the last forward and the last backward call through this context took (bench.py labels its roofline with
+ * it).  No FWD_* / BWD_* bit: that direction's last call ran on the one-launch-per-step kernels. */
+enum {
+  DS2_RNN_PATH_FWD_PERSISTENT = 1,  /* forward ran as ONE persistent launch (and produced its optional outputs) */
+  DS2_RNN_PATH_BWD_PERSISTENT = 2,  /* backward ran as ONE persistent launch (and produced its optional outputs) */
+  DS2_RNN_PATH_BWD_KSPLIT = 4,      /* ... and that launch was the K-split kernel (asr_amd/csrc/rnn_bwd_ksplit.h) */
+  DS2_RNN_PATH_BWD_BN_FUSED = 16,   /* ... which applied the BatchNorm1d backward of the layer above on the fly (ds2_rnn_bwd_bn) */
+  DS2_RNN_PATH_FWD_SPLIT = 32,      /* fp32 mode (bf16 = 2): a split (hi + lo bf16) persistent forward kernel took the call */
+  DS2_RNN_PATH_BWD_SPLIT = 64,      /* fp32 mode: a split backward kernel took the call (without bit 1: the split step kernels) */
+  DS2_RNN_PATH_FWD_U10 = 256        /* ... the split forward kernel was the 10-unit-slice one (asr_amd/csrc/rnn_fwd_u10.h) */
+};
 int ds2_rnn_last_path(const ds2_rnn_ctx* ctx);
 size_t ds2_rnn_fwd_workspace_bytes(int B, int H, int bf16);
 /* gates_bf16: NULL, or a (T,B,2,H,4) bf16 buffer that receives the saved-for-backward record of every hidden unit as ONE 8-byte
@@ -325,9 +335,10 @@ size_t ds2_rnn_fwd_workspace_bytes(int B, int H, int bf16);
 int ds2_rnn_fwd(ds2_rnn_ctx* ctx, int gates, float* gx, const void* wp_fwd, const float* bhh, float* hbuf, float* aux, const int* lens_dev, int T, int B,
                 int H, int bf16, void* gates_bf16, void* ws, size_t ws_bytes, void* stream);
 /* ds2_rnn_fwd plus h_bf16: NULL, or a (T,B,2,H) bf16 buffer that receives a bf16 copy of hbuf (the K-row-major operand of the TN-form
- * dW_hh GEMM).  Written by a PERSISTENT launch only: check ds2_rnn_last_path() & 1 after the call. */
+ * dW_hh GEMM).  Written by a PERSISTENT launch only: check ds2_rnn_last_path() & 1 after the call.  ws_armed: see ds2_memset_async (the short
+ * forms ds2_rnn_fwd / ds2_rnn_bwd pass 0). */
 int ds2_rnn_fwd_ex(ds2_rnn_ctx* ctx, int gates, float* gx, const void* wp_fwd, const float* bhh, float* hbuf, float* aux, const int* lens_dev, int T, int B,
-                   int H, int bf16, void* gates_bf16, void* h_bf16, void* ws, size_t ws_bytes, void* stream);
+                   int H, int bf16, void* gates_bf16, void* h_bf16, void* ws, size_t ws_bytes, void* stream, int ws_armed);
 /* ds2_rnn_fwd_ex for the bf16 TRAINING mode (bf16 operands, packed gate records required) with two more optional operands.
  * gx_bf16: the x-projections as the **bf16** tensor ds2_gemm_bf16_nt_obf16 wrote (same (T,B,2,G*H) layout; half the bytes written by the
  *   projection and read here: aten::gru / aten::lstm of blocks.py:87-89 take them from aten::addmm at full precision — the rounding is part of
@@ -339,7 +350,8 @@ int ds2_rnn_fwd_ex(ds2_rnn_ctx* ctx, int gates, float* gx, const void* wp_fwd, c
  *   ds2_center_colstats.
  * Returns 0 = done, 1 = see gx_bf16, < 0 = error. */
 int ds2_rnn_fwd_x(ds2_rnn_ctx* ctx, int gates, float* gx, const void* gx_bf16, const void* wp_fwd, const float* bhh, float* hbuf, float* aux,
-                  const int* lens_dev, int T, int B, int H, void* gates_bf16, void* h_bf16, float* hsum, void* ws, size_t ws_bytes, void* stream);
+                  const int* lens_dev, int T, int B, int H, void* gates_bf16, void* h_bf16, float* hsum, void* ws, size_t ws_bytes, void* stream,
+                  int ws_armed);
 size_t ds2_rnn_bwd_workspace_bytes(int gates, int B, int H, int bf16);
 /* dgx_bf16: NULL, or a (T,B,2,G*H) bf16 buffer that receives the gradient wrt the x-projections instead of gx (which then keeps
  * the gates): the bf16-mode GEMMs consume it directly.  gates_bf16: NULL, or the packed records written by ds2_rnn_fwd — read
@@ -347,7 +359,7 @@ size_t ds2_rnn_bwd_workspace_bytes(int gates, int B, int H, int bf16);
 int ds2_rnn_bwd(ds2_rnn_ctx* ctx, int gates, const float* dy, int lddy, float* gx, float* aux, const float* hbuf, const void* wp_bwd, const int* lens_dev,
                 int T, int B, int H, int bf16, void* dgx_bf16, const void* gates_bf16, void* ws, size_t ws_bytes, void* stream);
 
-/* ds2_rnn_last_path() bits after a backward call: 2 = ran as ONE persistent launch; 4 = that launch was the K-split kernel (bf16, H a multiple
+/* The K-split backward kernel (DS2_RNN_PATH_BWD_KSPLIT in ds2_rnn_last_path() after a backward call; bf16 operands or split form, H a multiple
  * of 256: asr_amd/csrc/rnn_bwd_ksplit.h — bf16 partial sums of dh are exchanged instead of dGh; results equal those of the other kernel
  * families within 4e-3 relative L2 and sit at the same distance from an fp64 recurrence, run-to-run bit-identical).  A K-split launch that
  * is given dhn_bf16 writes ONLY that bf16 copy of d(W_hn h + b_hn), not the fp32 one into aux.
@@ -357,7 +369,7 @@ int ds2_rnn_bwd(ds2_rnn_ctx* ctx, int gates, const float* dy, int lddy, float* g
  * over B are the bias gradients, so no pass over dGx. */
 int ds2_rnn_bwd_ex(ds2_rnn_ctx* ctx, int gates, const float* dy, int lddy, float* gx, float* aux, const float* hbuf, const void* wp_bwd, const int* lens_dev,
                    int T, int B, int H, int bf16, void* dgx_bf16, const void* gates_bf16, void* dhn_bf16, float* bias_part, void* ws,
-                   size_t ws_bytes, void* stream);
+                   size_t ws_bytes, void* stream, int ws_armed);
 
 /* ds2_rnn_bwd_ex for a layer whose output y feeds a BatchNorm1d (SequenceWise(BatchNorm1d) of the next layer, modules/blocks.py:75,85-86, or
  * of the fc block, modules/deepspeech.py:104): dyn = gradient wrt that BatchNorm's OUTPUT, bn_x = its input (= y, pitch ldx), bn_mean /
@@ -370,13 +382,13 @@ int ds2_rnn_bwd_ex(ds2_rnn_ctx* ctx, int gates, const float* dy, int lddy, float
 int ds2_rnn_bwd_bn(ds2_rnn_ctx* ctx, int gates, const float* dyn, int lddyn, const float* bn_x, int ldx, const float* bn_mean, const float* bn_var,
                    const float* bn_gamma, const float* bn_s0, const float* bn_s1, float bn_eps, float* dy_scratch, float* gx, float* aux,
                    const float* hbuf, const void* wp_bwd, const int* lens_dev, int T, int B, int H, int bf16, void* dgx_bf16,
-                   const void* gates_bf16, void* dhn_bf16, float* bias_part, void* ws, size_t ws_bytes, void* stream);
+                   const void* gates_bf16, void* dhn_bf16, float* bias_part, void* ws, size_t ws_bytes, void* stream, int ws_armed);
 
 /* ds2_rnn_bwd_bn with the BatchNorm's input given as bf16 (the centred operand of ds2_center_colstats; bn_mean = its delta; even pitch, H % 4 == 0) */
 int ds2_rnn_bwd_bn_xbf16(ds2_rnn_ctx* ctx, int gates, const float* dyn, int lddyn, const void* bn_x_bf16, int ldx, const float* bn_mean,
                          const float* bn_var, const float* bn_gamma, const float* bn_s0, const float* bn_s1, float bn_eps, float* dy_scratch, float* gx,
                          float* aux, const float* hbuf, const void* wp_bwd, const int* lens_dev, int T, int B, int H, int bf16, void* dgx_bf16,
-                         const void* gates_bf16, void* dhn_bf16, float* bias_part, void* ws, size_t ws_bytes, void* stream);
+                         const void* gates_bf16, void* dhn_bf16, float* bias_part, void* ws, size_t ws_bytes, void* stream, int ws_armed);
 
 /* bias gradients of one recurrent layer from ds2_rnn_bwd_ex's bias_part (B,2,4,H): db_ih (2,G*H) [bias_ih_l0 | bias_ih_l0_reverse] and
  * db_hh (2,G*H); GRU: db_ih = [d r, d z, d n], db_hh = [d r, d z, d(hn)]; LSTM: both = [d i, d f, d g, d o]; tanh cell: both = [d pre]. */

@@ -1,6 +1,7 @@
 """CPU: the Elman (tanh) cell, rnn_type="nn.RNN" — the fp64 restatement (tests/tanh_rnn_oracle.py) against golden vectors of the unmodified
 reference (tests/golden/make_golden_rnn.py), the model's cell configuration, and the library's size queries for gates = 1."""
 import ctypes as C
+import os
 
 import numpy as np
 import pytest
@@ -80,6 +81,27 @@ def test_library_sizes_for_one_gate(H):
             # the forward recurrence of the tanh cell has the GRU's workspace (it depends on H only through the h exchange)
             assert lib.ds2_rnn_fwd_workspace_bytes(B, H, bf16) > 0
             assert got <= lib.ds2_rnn_bwd_workspace_bytes(3, B, H, bf16)
+
+
+def test_library_sizes_match_the_recorded_table(golden_dir):
+    """ds2_rnn_fwd_workspace_bytes, ds2_rnn_bwd_workspace_bytes and ds2_rnn_packed_bytes over gates x mode x H x B against
+    tests/golden/rnn_sizes.json, recorded from the library before the sizes moved into csrc/rnn_sizes.h: callers size their buffers with
+    these, and the launchers fill what the same functions state."""
+    import json
+    lib = _lib()
+    with open(os.path.join(golden_dir, "rnn_sizes.json")) as f:
+        tab = json.load(f)
+    G, M, Hs, Bs = tab["gates"], tab["modes"], tab["H"], tab["B"]
+    assert (G, M) == ([1, 3, 4], [0, 1, 2]) and len(Hs) == 11 and len(Bs) == 6
+    for mi, m in enumerate(M):
+        for hi, H in enumerate(Hs):
+            for bi, B in enumerate(Bs):
+                assert lib.ds2_rnn_fwd_workspace_bytes(B, H, m) == tab["fwd_workspace_bytes"][mi][hi][bi], (m, H, B)
+                for gi, g in enumerate(G):
+                    assert lib.ds2_rnn_bwd_workspace_bytes(g, B, H, m) == tab["bwd_workspace_bytes"][gi][mi][hi][bi], (g, m, H, B)
+            for gi, g in enumerate(G):
+                for which in (0, 1):
+                    assert lib.ds2_rnn_packed_bytes(g, H, which, m) == tab["packed_bytes"][gi][mi][hi][which], (g, m, H, which)
 
 
 @pytest.mark.parametrize("H", [256, 512, 1024, 1280])
