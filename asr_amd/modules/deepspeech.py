@@ -59,7 +59,7 @@ class _DS2Function(torch.autograd.Function):
             Gr = flat.tensors(model, grads=True)
             with ops.use_rnn_ctx(ctx.rnn_ctx, ctx.device), torch.cuda.device(ctx.device):
                 engine.backward(W, Gr, model._cfg, ctx.saved, dlogits.contiguous(),
-                                on_bucket=None if accumulating else model._on_bucket)
+                                on_bucket=None if accumulating else model._on_bucket, serial_buckets=model._serial_buckets)
         finally:
             if accumulating:
                 flat.flat_grad = keep
@@ -90,6 +90,7 @@ class DeepSpeech(nn.Module):
         self.decoder = GreedyDecoder(self.labels)
         self._flat: Optional[FlatParams] = None
         self._on_bucket = None          # DP hook: called as each layer's gradients become final
+        self._serial_buckets = False    # ... by a reducer that orders its collectives into the compute stream (engine.backward)
         self._param_names = [n for n, _ in self.named_parameters()]
         kind = {nn.GRU: "gru", nn.LSTM: "lstm", nn.RNN: "rnn"}.get(self.rnn_type)
         self._cfg = engine.ModelCfg(rnn=kind or "unsupported", hidden=rnn_hidden_size, layers=rnn_hidden_layers,

@@ -257,7 +257,7 @@ class DeepSpeechTrainer:
                 pin["loss_done"].record(pin["stream"])
             loss.record_stream(pin["stream"])
             red = self._get_reducer()
-            engine.backward(W, Gr, model._cfg, ctx, dlogits, on_bucket=red.on_bucket if red.active else None)
+            engine.backward(W, Gr, model._cfg, ctx, dlogits, on_bucket=red.on_bucket if red.active else None, serial_buckets=red.mode == "serial")
             red.finish()
             pin["loss_done"].synchronize()                                   # the step's single host wait: CTC done (backward is running)
             loss_value = float(pin["loss"][0])
@@ -303,7 +303,7 @@ class DeepSpeechTrainer:
                 nll, dlogits = self._ctc(logits, tg, off, lens_dev, tl, max_u, fl[0] if fl else None, B)
                 loss = ops.ctc_batch_mean(nll)[0]
                 red = self._get_reducer()
-                engine.backward(W, Gr, model._cfg, ctx, dlogits, on_bucket=red.on_bucket if red.active else None)
+                engine.backward(W, Gr, model._cfg, ctx, dlogits, on_bucket=red.on_bucket if red.active else None, serial_buckets=red.mode == "serial")
                 red.finish()
                 loss_value = loss.item()
                 torch.cuda.synchronize(inputs.device)

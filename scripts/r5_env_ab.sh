@@ -1,5 +1,5 @@
 #!/bin/bash
-# the c3 train step with one experimental switch off / on, same box, interleaved:   bash scripts/r5_env_ab.sh DS2_OVERLAP 1 2      (value - = unset)
+# the c3 train step with one experimental switch off / on, same box, interleaved:   bash scripts/r5_env_ab.sh DS2_BN_FOLD 0 1      (value - = unset)
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp DS2_EXPERIMENTAL=1
 for rep in 1 2 3; do

@@ -559,6 +559,38 @@ def test_fp32_split_gemm_decision_needs_an_aligned_hidden_size():
     assert not engine._f32_split_ok(648, 2 * 3 * 100, 1312, 100)          # dW_hh problems would have N = 100, column offsets 100, 300
 
 
+def test_engine_decides_the_paths_of_a_shape_in_one_record(monkeypatch):
+    """engine._decide: the shape-and-switch decisions forward and backward share, on a 256-CU device, at the shapes the schedules were
+    measured at, and under the switches as they are when it is called (nothing is cached)."""
+    from asr_amd import engine
+    for k, v in dict(WGRAD_TN=True, WGRAD_SIDE="sk", WGRAD_IDLE=True, BN_FOLD=True, F32_RNN="split").items():
+        monkeypatch.setattr(engine, k, v)
+    bf = lambda rnn, H: engine.ModelCfg(rnn, H, 3, 29, precision="bf16")
+    c3 = engine._decide(bf("gru", 1024), 64, 501, 256, 1312)                # 2 x 4 x 32 = 256 workgroups: no CU idle
+    assert (c3.rmode, c3.pack, c3.deferred, c3.may_fold, c3.wants_h_bf, c3.group_ok, c3.side_ok, c3.idle, c3.idle_f32) == \
+        (1, True, True, True, True, True, False, False, False)
+    assert engine._decide(bf("lstm", 1280), 32, 751, 256, 1312).idle        # c4: 160 of 256 CUs in the recurrence
+    assert engine._decide(bf("gru", 1024), 48, 21, 256, 1312).idle          # 192 of 256: 64 idle, the least that counts
+    assert not engine._decide(bf("gru", 1024), 32, 501, 256, 1312).idle     # 128 / 128: the recurrence is not the majority tenant
+    assert not engine._decide(bf("gru", 256), 16, 21, 256, 1312).idle       # 240 idle
+    odd = engine._decide(bf("gru", 256), 12, 21, 256, 1312)                 # B % 8 != 0: fp32 gates and dGx, layer-wise backward
+    assert not (odd.pack or odd.deferred or odd.may_fold or odd.wants_h_bf or odd.idle)
+    one = engine._decide(bf("gru", 256), 16, 1, 256, 1312)                  # T = 1: packed gates, but nothing to defer, fold or shift
+    assert one.pack and not (one.deferred or one.may_fold or one.wants_h_bf)
+    assert not engine._decide(bf("gru", 100), 16, 21, 256, 1312).may_fold   # H % 8 != 0
+    assert not engine._decide(bf("gru", 256), 16, 21, 256, 1312, training=False, save=False).pack
+    f32 = engine._decide(engine.ModelCfg("gru", 768, 2, 29), 32, 81, 256, 1312)
+    assert (f32.rmode, f32.pack, f32.deferred, f32.idle, f32.idle_f32) == (2, False, False, False, True)
+    assert engine._decide(engine.ModelCfg("gru", 36, 2, 29), 3, 21, 256, 1312).rmode == 0
+    monkeypatch.setattr(engine, "WGRAD_IDLE", False)
+    assert not engine._decide(bf("lstm", 1280), 32, 751, 256, 1312).idle and not engine._decide(engine.ModelCfg("gru", 768, 2, 29), 32, 81, 256, 1312).idle_f32
+    monkeypatch.setattr(engine, "BN_FOLD", False)
+    monkeypatch.setattr(engine, "WGRAD_TN", False)
+    monkeypatch.setattr(engine, "WGRAD_SIDE", "0")
+    off = engine._decide(bf("gru", 1024), 64, 501, 256, 1312)
+    assert off.deferred and not (off.may_fold or off.wants_h_bf or off.group_ok)
+
+
 def test_library_exports_no_writable_global_state():
     """SURVEY §8(b) "Threading": no mutable global state besides the thread-local error message.  The dynamic symbol table of the shipped
     library holds functions, kernel descriptors and the HIP fat-binary bookkeeping — no data object of the library's own — and the
