@@ -105,3 +105,7 @@ extern "C" int ds2_greedy_decode_f32(const float* probs, long long ld_b, long lo
 // The pause segmentation of long recordings and the packing of its segments into decode batches (ds2_ctc_segment_*), likewise.
 #define DS2_CTC_SEGMENT_TU
 #include "ctc_segment.h"
+
+// The LM term of finished label sequences and the (alpha, beta) sweep over n-best features (ds2_lm_score_*, ds2_nbest_sweep), likewise.
+#define DS2_LM_SCORE_TU
+#include "lm_score.h"

@@ -10,7 +10,9 @@ pauses and packed into decode batches on the GPU (csrc/ctc_segment.h); its host 
 and `assemble_transcript`.  `CTCConfidence.score` says HOW SURE a text is of each word or character, as a conditional probability
 (csrc/ctc_conf.h); its host half is `confidence_units`.  `Decoder.align_batch` says WHICH words and characters are wrong: the edit
 alignment behind the distances (csrc/edit_align.h); its host half is `assemble_edit_alignments`, `ErrorReport` adds the records up and
-`reliability` bins confidences against their right / wrong flags."""
+`reliability` bins confidences against their right / wrong flags.  `NBestRescorer` re-ranks a beam search's n-best list under any LM
+weights, or a larger LM, from per-hypothesis features (csrc/lm_score.h) and `tune_lm_weights` sweeps an (alpha, beta) grid over
+them after ONE decode; its host half is `tune_summary`."""
 from __future__ import annotations
 
 import math
@@ -426,6 +428,243 @@ class BeamCTCDecoder(Decoder):
         lens_h = host[2 * n:2 * n + B * K].view(B, K)
         self.last_scores = host[2 * n + B * K:].view(torch.float32).view(B, K).clone()
         return self.convert_to_strings(labels_h, lens_h), self.convert_tensor(offs_h, lens_h)
+
+
+def _reference_strings(references):
+    """references as tune_lm_weights takes them: strings, or evaluate()'s output_data form [[str]] -> a list of strings"""
+    out = []
+    for r in references:
+        if not isinstance(r, str):
+            r = list(r)
+            if len(r) != 1 or not isinstance(r[0], str):
+                raise ValueError("references must be strings, or one-element lists of a string as evaluate()'s output_data holds them")
+            r = r[0]
+        out.append(r)
+    return out
+
+
+def _check_grid(who, alphas, betas, metric):
+    alphas, betas = (np.asarray(list(np.ravel(g)), np.float64) for g in (alphas, betas))
+    if alphas.size < 1 or betas.size < 1 or not (np.isfinite(alphas).all() and np.isfinite(betas).all()):
+        raise ValueError(f"{who}: alphas and betas must be non-empty and finite")
+    if metric not in ("wer", "cer"):
+        raise ValueError(f"{who}: metric must be 'wer' or 'cer', got {metric!r}")
+    return alphas, betas
+
+
+def tune_summary(total, ref_words, ref_chars, alphas, betas, metric="wer", first_pass=(0, 0), oracle=(0, 0)):
+    """Pure host half of tune_lm_weights: total (Ga,Gb,2) the summed (word, character) errors of the picks at every grid point,
+    ref_words / ref_chars the references' summed lengths (0 divides as 1, as in evaluate()), first_pass / oracle the summed (word,
+    character) errors of slot 0 and of the best slot per utterance -> the dict tune_lm_weights returns.  Rates are percentages, as
+    evaluate() returns them.  The winner is the lowest error count on `metric`; ties go to the first point in row-major (alpha, beta)
+    order."""
+    alphas, betas = _check_grid("tune_summary", alphas, betas, metric)
+    total = np.asarray(total)
+    if total.shape != (alphas.size, betas.size, 2):
+        raise ValueError(f"tune_summary: totals of {total.shape} for a {alphas.size} x {betas.size} grid")
+    nw, nc = max(int(ref_words), 1), max(int(ref_chars), 1)
+    col = 0 if metric == "wer" else 1
+    a, b = np.unravel_index(int(np.argmin(total[:, :, col])), total.shape[:2])   # argmin: the first of equal minima, row-major
+    rate = lambda pair: (100.0 * int(pair[0]) / nw, 100.0 * int(pair[1]) / nc)   # noqa: E731
+    return {"alpha": float(alphas[a]), "beta": float(betas[b]), "wer": rate(total[a, b])[0], "cer": rate(total[a, b])[1],
+            "grid_wer": 100.0 * total[:, :, 0].astype(np.float64) / nw, "grid_cer": 100.0 * total[:, :, 1].astype(np.float64) / nc,
+            "first_pass": rate(first_pass), "oracle": rate(oracle)}
+
+
+class NBestRescorer:
+    """Second pass over a BeamCTCDecoder's n-best list: every hypothesis gets the feature vector (acoustic log-likelihood, LM log10 sum,
+    token count, OOV count), and a score (ac + alpha * (lm_sum + oov_score * n_oov)) + beta * n_tok under ANY weights, without decoding
+    again (contracts: include/ds2hip.h, ds2_lm_score_seqs and ds2_nbest_sweep).
+      decoder   the first pass, run with its own settings (LM, hotwords, width);
+      lm        the rescoring model: an ARPA path, an NgramLM, or None = the decoder's own.  It may be larger than what the first pass
+                could carry (any order up to 6: the search's candidate limit does not apply here);
+      acoustic  "exact": the CTC likelihood of every hypothesis recomputed from the posteriors (ops.ctc_mwer's lattices), free of the LM
+                and hotword terms that only chose the list; "beam": the first pass's scores, refused when the decoder has an LM or
+                hotwords, whose terms are inside those scores;
+      oov_score the log10 price of an out-of-vocabulary token (the search's is -1000);
+      workspace_bytes  bound on the exact likelihoods' workspace: the batch is cut into chunks of utterances that stay within it (at
+                least one utterance per chunk).
+    Exact: the likelihoods (fp32 lattices of the loss) and the LM sums (the search's own cond_score, added in token order).  NOT part of
+    the score: hotword terms.  NOT pinned: parity with ctcdecode's or KenLM's scoring; OOV is a constant, not an <unk> probability.
+    NOT measured: whether weights tuned this way lower the WER of a real corpus, and how far the optimum on n-best lists lies from
+    the optimum of decoding again at every grid point."""
+
+    def __init__(self, decoder, lm=None, acoustic="exact", oov_score=-1000.0, workspace_bytes=2 << 30):
+        if not isinstance(decoder, BeamCTCDecoder):
+            raise ValueError("NBestRescorer: decoder must be a BeamCTCDecoder")
+        if acoustic not in ("exact", "beam"):
+            raise ValueError(f"NBestRescorer: acoustic must be 'exact' or 'beam', got {acoustic!r}")
+        if acoustic == "beam" and (decoder.lm is not None or decoder.hotwords is not None):
+            raise ValueError("NBestRescorer: acoustic='beam' takes the first pass's scores as the acoustic term, but this decoder's scores "
+                             "hold its language-model or hotword terms; use acoustic='exact'")
+        if acoustic == "exact" and decoder.blank_index != 0:
+            raise ValueError("NBestRescorer: acoustic='exact' needs blank_index 0 (the lattice kernels take class 0 as the blank)")
+        if isinstance(lm, str):
+            from .lm import NgramLM
+            space = decoder.space_index if decoder.int_to_char.get(decoder.space_index) == " " else next(
+                (i for i, c in sorted(decoder.int_to_char.items()) if c == " "), None)
+            lm = NgramLM(lm, decoder.int_to_char, decoder.blank_index, space)
+        lm = decoder.lm if lm is None else lm
+        if lm is None:
+            raise ValueError("NBestRescorer: no language model: pass lm=, or a decoder that has one")
+        if lm.blank != decoder.blank_index:
+            raise ValueError(f"NBestRescorer: the language model was bound to blank {lm.blank}, the decoder has blank {decoder.blank_index}")
+        oov_score = float(oov_score)
+        if math.isnan(oov_score):
+            raise ValueError("NBestRescorer: oov_score is NaN")
+        if isinstance(workspace_bytes, bool) or int(workspace_bytes) != workspace_bytes or int(workspace_bytes) < 1:
+            raise ValueError(f"NBestRescorer: workspace_bytes must be a positive integer, got {workspace_bytes!r}")
+        self.decoder, self.lm, self.acoustic, self.oov_score, self.workspace_bytes = decoder, lm, acoustic, oov_score, int(workspace_bytes)
+        self.last_scores = None
+
+    def _chunks(self, lens_h, T, K):
+        """utterance ranges [b0, b1) whose exact-likelihood workspace, at the range's longest hypothesis, stays within workspace_bytes"""
+        from .. import _lib
+        need = _lib.load().ds2_ctc_mwer_workspace_bytes
+        longest = lens_h.max(axis=1) if lens_h.size else np.zeros(0, np.int64)
+        out, b0, B = [], 0, lens_h.shape[0]
+        while b0 < B:
+            b1, mh = b0 + 1, int(longest[b0])
+            while b1 < B and need(T, b1 + 1 - b0, K, max(mh, int(longest[b1]))) <= self.workspace_bytes:
+                mh = max(mh, int(longest[b1]))
+                b1 += 1
+            out.append((b0, b1, mh))
+            b0 = b1
+        return out
+
+    def exact_likelihoods(self, logp, labels, off, lens, valid, in_lens, lens_host):
+        """log p_ctc of every slot, (B,K) fp32 on the GPU: ops.ctc_mwer's lattices (want_grad=False) on logp (B,T,C), chunk by chunk
+        (_chunks), max_hyp_len the chunk's longest hypothesis.  labels (B,K,T) i32, off (B,K) i64 into it, lens (B,K) i32, valid
+        (B,K) bool, in_lens (B) i32 on the GPU; lens_host: the lengths as a NumPy array.  An invalid slot gets -inf."""
+        from .. import ops
+        B, K, T = labels.shape
+        valid_i = valid.to(torch.int32)
+        risk = torch.zeros((B, K), dtype=torch.float32, device=labels.device)
+        ac = torch.empty((B, K), dtype=torch.float32, device=labels.device)
+        for b0, b1, mh in self._chunks(lens_host, T, K):
+            x = torch.empty((T, b1 - b0, logp.shape[2]), dtype=torch.float32, device=logp.device)   # (fresh: canonical strides at b1 - b0 = 1 too)
+            x.copy_(logp[b0:b1].transpose(0, 1))
+            _, nll, _, _ = ops.ctc_mwer(x, labels, off[b0:b1], lens[b0:b1], valid_i[b0:b1], in_lens[b0:b1], mh, risk[b0:b1], want_grad=False)
+            ac[b0:b1] = -nll
+        return ac
+
+    def features(self, probs, sizes=None, is_log=False):
+        """probs (B,T,C) as decode() takes them (probabilities, or log-probabilities with is_log=True), sizes (B) valid frames or None
+        -> a dict of GPU tensors: "labels" / "offsets" (B,K,T) i32, "lens" (B,K) i32 and "scores" (B,K) fp32 of the first pass,
+        "ac" (B,K) fp32 natural log (-inf for an empty slot), "lm_sum" (B,K) fp32 log10, "n_tok", "n_oov" (B,K) i32; and "lens_host", the
+        lengths as a NumPy array.  The labels make no host round trip; the lengths are copied once."""
+        from .. import ops
+        dec = self.decoder
+        probs = torch.as_tensor(probs)
+        if probs.dim() != 3:
+            raise ValueError(f"NBestRescorer.features: probs must be (B,T,C), got {tuple(probs.shape)}")
+        if not probs.is_cuda:
+            probs = probs.to(_device("NBestRescorer", ".features"))
+        probs = probs.float()
+        if probs.stride(2) != 1:
+            probs = probs.contiguous()
+        B, T, C = probs.shape
+        dev = probs.device
+        sizes = None if sizes is None else torch.as_tensor(sizes)
+        logp = probs if is_log else None
+        if is_log:
+            probs = torch.exp(probs)
+        labels, offs, lens, scores = ops.ctc_beam_decode(probs, sizes, dec.blank_index, dec.beam_width, dec.cutoff_top_n, dec.cutoff_prob,
+                                                         dec.lm, dec.alpha, dec.beta, dec.hotwords)
+        K = labels.shape[1]
+        off = torch.arange(B * K, device=dev, dtype=torch.int64) * T
+        lm_sum, n_tok, n_oov = (t.view(B, K) for t in ops.lm_score(labels, off, lens.view(-1), self.lm, T))
+        lens_h = lens.cpu().numpy()
+        if ops.rnn_poison_seen(dev):
+            # as in GreedyDecoder.decode: a poisoned forward (a starved persistent recurrence launch) raises here
+            ops.rnn_persistent_check(dev)
+        valid = scores > -math.inf
+        if self.acoustic == "beam":
+            ac = scores.clone()
+        else:
+            in_lens = torch.full((B,), T, dtype=torch.int32, device=dev) if sizes is None else ops._sizes_i32(sizes, B, dev)
+            ac = self.exact_likelihoods(torch.log(probs) if logp is None else logp, labels, off.view(B, K), lens, valid, in_lens, lens_h)
+        ac = torch.where(valid, ac, torch.full_like(ac, -math.inf))
+        return {"labels": labels, "offsets": offs, "lens": lens, "scores": scores, "ac": ac, "lm_sum": lm_sum, "n_tok": n_tok,
+                "n_oov": n_oov, "lens_host": lens_h}
+
+    def strings(self, features):
+        """the hypotheses of `features` as strings[b][k] (one device-to-host copy of the labels; kept in features["strings"])"""
+        if "strings" not in features:
+            features["strings"] = self.decoder.convert_to_strings(features["labels"].cpu(), features["lens_host"])
+        return features["strings"]
+
+    def scores(self, features, alpha, beta):
+        """(B,K) fp32 on the GPU: the score of every slot at (alpha, beta), rounded as ds2_nbest_sweep rounds it; NaN counts as -inf"""
+        f = features
+        w = lambda v: torch.full((), float(v), dtype=torch.float32, device=f["ac"].device)   # noqa: E731
+        lm = f["lm_sum"] + w(self.oov_score) * f["n_oov"].float()
+        s = (f["ac"] + w(alpha) * lm) + w(beta) * f["n_tok"].float()
+        return torch.where(torch.isnan(s), torch.full_like(s, -math.inf), s)
+
+    def rescore(self, probs, sizes=None, alpha=0.0, beta=0.0, is_log=False):
+        """What decode() returns, (strings[b][k], offsets[b][k]), K per utterance, reordered by the rescored total at (alpha, beta):
+        highest first, equal totals in first-pass order (the sweep's tie rule).  The totals stay in `last_scores` (B,K) on the host."""
+        f = self.features(probs, sizes, is_log)
+        s, order = torch.sort(self.scores(f, alpha, beta), dim=1, descending=True, stable=True)
+        B, K, T = f["labels"].shape
+        idx = order[:, :, None].expand(B, K, T)
+        lens = torch.gather(f["lens"], 1, order)
+        host = torch.cat((torch.gather(f["labels"], 1, idx).reshape(-1), torch.gather(f["offsets"], 1, idx).reshape(-1), lens.reshape(-1),
+                          s.contiguous().view(torch.int32).reshape(-1))).cpu()
+        n = B * K * T
+        lens_h = host[2 * n:2 * n + B * K].view(B, K)
+        self.last_scores = host[2 * n + B * K:].view(torch.float32).view(B, K).clone()
+        return (self.decoder.convert_to_strings(host[:n].view(B, K, T), lens_h),
+                self.decoder.convert_tensor(host[n:2 * n].view(B, K, T), lens_h))
+
+    def errors(self, features, references):
+        """The word and character distances of every slot against its utterance's reference (pack_scoring, one ops.edit_distance launch)
+        -> (B,K,2) int32 on the GPU; features["ref_len"] receives the (B,2) reference lengths (words, characters) as a NumPy array."""
+        from .. import ops
+        references = _reference_strings(references)
+        strings = self.strings(features)
+        B, K = len(strings), len(strings[0]) if strings else 0
+        if len(references) != B:
+            raise ValueError(f"NBestRescorer.errors: {len(references)} references for a batch of {B}")
+        dev = features["ac"].device
+        seq, a_off, a_len, b_off, b_len, ref_w, ref_c = pack_scoring([h for row in strings for h in row], [r for r in references for _ in range(K)])
+        features["ref_len"] = np.stack((ref_w[::K], ref_c[::K]), axis=1) if B else np.zeros((0, 2), np.int64)
+        if B * K == 0:
+            return torch.zeros((B, K, 2), dtype=torch.int32, device=dev)
+        max_len = int(max(a_len.max(), b_len.max()))
+        dist = ops.edit_distance(*_upload_scoring(dev, seq, a_off, a_len, b_off, b_len), max_len=max_len)
+        return torch.stack((dist[:B * K].view(B, K), dist[B * K:].view(B, K)), dim=2).contiguous()
+
+
+def tune_lm_weights(rescorer, batches, alphas, betas, metric="wer"):
+    """Choose the LM weights of a BeamCTCDecoder on a dev set from ONE decode: `batches` yields (probs, sizes, reference strings), and a
+    list of evaluate()'s output_data triples is accepted as it is.  Every batch gives rescorer.features and rescorer.errors, which
+    stay on the GPU; then one ops.nbest_sweep runs over the whole alphas x betas grid.  Returns {"alpha", "beta", "wer", "cer" at that
+    point, "grid_wer", "grid_cer" (Ga,Gb), "first_pass": (wer, cer) of slot 0, "oracle": (wer, cer) of the best slot per utterance},
+    rates as percentages (tune_summary).  What the chosen weights do to the WER of decoding again is not measured here: rescoring
+    only sees the hypotheses the first pass kept."""
+    from .. import ops
+    alphas, betas = _check_grid("tune_lm_weights", alphas, betas, metric)
+    feats, errs, ref = {k: [] for k in ("ac", "lm_sum", "n_tok", "n_oov")}, [], np.zeros(2, np.int64)
+    for probs, sizes, references in batches:
+        f = rescorer.features(probs, sizes)
+        errs.append(rescorer.errors(f, references))
+        ref += f["ref_len"].sum(axis=0)
+        for k in feats:
+            feats[k].append(f[k])
+    if not errs:
+        raise ValueError("tune_lm_weights: no batch")
+    ac, lm_sum, n_tok, n_oov = (torch.cat(feats[k]).contiguous() for k in ("ac", "lm_sum", "n_tok", "n_oov"))
+    err = torch.cat(errs).contiguous()
+    _, total = ops.nbest_sweep(ac, lm_sum, n_tok, n_oov, err, alphas, betas, rescorer.oov_score, want_pick=False)
+    # the best slot per utterance among the surviving ones (slot 0 where none survived), per error kind
+    big = torch.iinfo(torch.int32).max
+    live = (ac > -math.inf)[:, :, None].expand_as(err)
+    best = torch.where(live, err, torch.full_like(err, big)).min(dim=1).values
+    best = torch.where(best == big, err[:, 0, :], best)
+    host = torch.cat((total.reshape(-1), err[:, 0, :].sum(0, dtype=torch.int64), best.sum(0, dtype=torch.int64))).cpu().numpy()
+    return tune_summary(host[:-4].reshape(alphas.size, betas.size, 2), ref[0], ref[1], alphas, betas, metric, host[-4:-2], host[-2:])
 
 
 def encode_transcripts(transcripts, labels, star=None, unknown="error"):

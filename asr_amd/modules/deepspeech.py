@@ -519,6 +519,51 @@ class DeepSpeech(nn.Module):
                 print(f"saved output to {output_file}")
             return wer * 100, cer * 100, output_data
 
+    def tune_decoder(self, loader=None, manifest=None, batch_size=None, num_workers=32, decoder=None, lm=None,
+                     alphas=tuple(0.25 * i for i in range(21)), betas=tuple(0.2 * i - 2.0 for i in range(21)), metric="wer", confirm=False,
+                     device="auto"):
+        """Choose the LM weights (alpha, beta) of a BeamCTCDecoder on a dev set from ONE decode of it: the eval forward per batch, the
+        decoder's n-best lists rescored at every point of the alphas x betas grid (decoders.NBestRescorer, decoders.tune_lm_weights),
+        instead of one evaluate() per grid point.  decoder: a BeamCTCDecoder (None: self.decoder); lm: the rescoring model, an ARPA
+        path or an NgramLM (None: the decoder's own).  Returns tune_lm_weights' dict.  With confirm=True and a decoder that carries an
+        LM the set is decoded once more with the chosen weights fused into the search, and that evaluate()'s (wer, cer) is reported
+        under "confirmed": the number that rescoring only approximates; the decoder's own weights are restored afterwards.
+        NOT measured: whether the weights chosen this way lower the WER of a real corpus, and how far they lie from the optimum of
+        decoding again at every grid point.  Hotword terms are not part of the rescoring score."""
+        from ..decoders import BeamCTCDecoder, GreedyDecoder, NBestRescorer, tune_lm_weights
+        decoder = self.decoder if decoder is None else decoder
+        if not isinstance(decoder, BeamCTCDecoder):
+            raise ValueError("tune_decoder: the decoder must be a BeamCTCDecoder")
+        rescorer = NBestRescorer(decoder, lm=lm)
+        device = resolve_device(device)
+        if loader is None:
+            loader, _ = self.get_loader(manifest=manifest, batch_size=batch_size, num_workers=num_workers)
+        spell = GreedyDecoder(self.labels)
+
+        def batches():
+            for inputs, targets, input_percentages, target_sizes in loader:
+                input_sizes = input_percentages.mul(int(inputs.size(3))).int()
+                out, output_sizes = self.forward(inputs.to(device), input_sizes)
+                ops.rnn_persistent_check(out.device)
+                split, offset = [], 0
+                for size in target_sizes:
+                    split.append(targets[offset:offset + size])
+                    offset += size
+                yield out, output_sizes, spell.convert_to_strings(split)
+
+        with torch.no_grad():
+            self.eval()
+            self.to(device)
+            result = tune_lm_weights(rescorer, batches(), alphas, betas, metric)
+            if confirm and decoder.lm is not None:
+                kept = (self.decoder, decoder.alpha, decoder.beta)
+                try:
+                    self.decoder, decoder.alpha, decoder.beta = decoder, result["alpha"], result["beta"]
+                    result["confirmed"] = self.evaluate(loader=loader, device=device)[:2]
+                finally:
+                    self.decoder, decoder.alpha, decoder.beta = kept
+        return result
+
     def __call__(self, *args, **kwargs):
         """The reference overrides __call__ with its eval loop (deepspeech.py:161).  Keep that calling
         convention (`model(loader=..., device=...)`) and fall through to nn.Module for tensors."""

@@ -1749,6 +1749,67 @@ def ctc_beam_decode(probs: Tensor, sizes: Tensor | None = None, blank: int = 0, 
     return labels, offs, lens, scores
 
 
+def lm_score(labels: Tensor, off: Tensor, lens: Tensor, lm, max_len: int):
+    """The LM term of P finished label sequences, one launch -> (lm_sum (P) fp32 log10, n_tok (P) i32, n_oov (P) i32) on the GPU
+    (contract: include/ds2hip.h, ds2_lm_score_seqs).  labels: int32 on the GPU, any shape, read flat; sequence p is
+    labels.view(-1)[off[p]:][:lens[p]]; off (P) int64 and lens (P) int32 on the GPU; lm a decoders.lm.NgramLM (its classes, blank and
+    space are the call's); max_len bounds every length.  A sequence longer than max_len, outside the buffer, or holding the blank or a
+    label outside the classes gets NaN, -1, -1.  lm_sum leaves OOV tokens out and n_oov counts them: lm_sum - 1000 * n_oov is the beam
+    search's LM total."""
+    if not torch.is_tensor(labels) or not labels.is_cuda:
+        raise ValueError("lm_score: labels must be a GPU tensor (no CPU fallback exists)")
+    dev = labels.device
+    _chk_on_dev("lm_score", dev, torch.int32, {"labels": labels, "lens": lens})
+    _chk_on_dev("lm_score", dev, torch.int64, {"off": off})
+    if off.dim() != 1 or lens.dim() != 1 or off.numel() != lens.numel():
+        raise ValueError("lm_score: off and lens must be one-dimensional and of one length")
+    if lm is None or not hasattr(lm, "packed"):
+        raise ValueError("lm_score: lm must be an NgramLM")
+    if not _is_int(max_len, 0, 2 ** 31 - 65):
+        raise ValueError(f"lm_score: max_len must be an integer in [0, 2^31 - 65], got {max_len!r}")
+    P = lens.numel()
+    lm_sum = torch.empty((P,), dtype=torch.float32, device=dev)
+    n_tok = torch.empty((P,), dtype=torch.int32, device=dev)
+    n_oov = torch.empty((P,), dtype=torch.int32, device=dev)
+    tab = lm.device_tables(dev)
+    _lib.check(_lib.load().ds2_lm_score_seqs(labels.data_ptr(), labels.numel(), off.data_ptr(), lens.data_ptr(), P, int(max_len), tab.data_ptr(),
+                                             lm.packed.ctypes.data, lm.packed.nbytes, lm.order, lm.mode, lm.space if lm.space is not None else -1,
+                                             lm.C, lm.blank, lm_sum.data_ptr(), n_tok.data_ptr(), n_oov.data_ptr(), _stream()),
+               "ds2_lm_score_seqs")
+    return lm_sum, n_tok, n_oov
+
+
+def nbest_sweep(ac: Tensor, lm_sum: Tensor, n_tok: Tensor, n_oov: Tensor, err: Tensor, alphas, betas, oov_score: float = -1000.0,
+                want_pick: bool = True):
+    """Which slot of every n-best list wins at every point of an (alpha, beta) grid, and the winners' summed errors, one launch ->
+    (pick (Ga,Gb,N) i32 or None, total (Ga,Gb,R) i64) on the GPU (contract: include/ds2hip.h, ds2_nbest_sweep).  ac, lm_sum (N,K) fp32,
+    n_tok, n_oov (N,K) i32, err (N,K,R) i32, all contiguous on the GPU; alphas / betas: sequences or tensors of Ga / Gb weights.
+    Slot k scores (ac + alpha * (lm_sum + oov_score * n_oov)) + beta * n_tok in fp32; NaN counts as -inf, ties go to the lowest k."""
+    if not torch.is_tensor(ac) or not ac.is_cuda:
+        raise ValueError("nbest_sweep: ac must be a GPU tensor (no CPU fallback exists)")
+    dev = ac.device
+    _chk_on_dev("nbest_sweep", dev, torch.float32, {"ac": ac, "lm_sum": lm_sum})
+    _chk_on_dev("nbest_sweep", dev, torch.int32, {"n_tok": n_tok, "n_oov": n_oov, "err": err})
+    if ac.dim() != 2 or ac.shape[1] < 1 or any(t.shape != ac.shape for t in (lm_sum, n_tok, n_oov)):
+        raise ValueError("nbest_sweep: ac, lm_sum, n_tok and n_oov must be (N, K) with K >= 1")
+    N, K = ac.shape
+    if err.dim() != 3 or err.shape[:2] != (N, K) or not 1 <= err.shape[2] <= 64:
+        raise ValueError(f"nbest_sweep: err must be ({N}, {K}, R) with 1 <= R <= 64, got {tuple(err.shape)}")
+    R = err.shape[2]
+    grid = [torch.as_tensor(g, dtype=torch.float32).reshape(-1).to(dev).contiguous() for g in (alphas, betas)]
+    Ga, Gb = grid[0].numel(), grid[1].numel()
+    if Ga < 1 or Gb < 1:
+        raise ValueError("nbest_sweep: alphas and betas must not be empty")
+    if math.isnan(float(oov_score)):
+        raise ValueError("nbest_sweep: oov_score is NaN")
+    pick = torch.empty((Ga, Gb, N), dtype=torch.int32, device=dev) if want_pick else None
+    total = torch.empty((Ga, Gb, R), dtype=torch.int64, device=dev)
+    _lib.check(_lib.load().ds2_nbest_sweep(ac.data_ptr(), lm_sum.data_ptr(), n_tok.data_ptr(), n_oov.data_ptr(), err.data_ptr(), N, K, R,
+                                           float(oov_score), grid[0].data_ptr(), Ga, grid[1].data_ptr(), Gb, _ptr(pick), total.data_ptr(),
+                                           _stream()), "ds2_nbest_sweep")
+    return pick, total
+
+
 _BASIS_CACHE = {}
 
 

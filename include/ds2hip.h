@@ -742,6 +742,46 @@ int ds2_ctc_beam_decode_lm_f32(const float* probs, long long ld_b, long long ld_
                                int lm_mode, int space, float alpha, float beta, int* labels, int* offsets, int* lens, float* scores,
                                void* ws, size_t ws_bytes, void* stream);
 
+/* N-best rescoring, part 1: the LM term of FINISHED label sequences as a number of its own (csrc/lm_score.h; restated by
+ * tests/lm_score_oracle.py).  The search above fuses that term into its totals, where alpha and beta cannot be varied without decoding
+ * again; with it apart, a list decoded once can be re-ranked under any weights, or under a larger model than the first pass could carry.
+ * P sequences: labels flat int32 (n_labels of them), sequence p is labels[off[p] .. off[p] + len[p]); off (P) int64, len (P) int32,
+ * device arrays; max_len bounds every length.  The model is the blob ds2_ctc_lm_pack made, on the device (lm_dev) and as the host copy
+ * (lm_host, lm_bytes) whose magic and sizes are checked before the launch, against lm_order, lm_mode and C as well; space, C, blank as
+ * the LM search takes them.  The kernel's lookups end only because the packer keeps its tables at most half full: pass no other bytes.
+ *  - tokens, character mode: every label is a token, label_tok[label], the space label included;
+ *  - tokens, word mode: the sequence is split at the space label; empty runs (a leading, doubled or trailing space) are skipped and
+ *    score nothing; every non-empty run is one token, the word id of the trie node its labels spell, -1 when the walk leaves the trie
+ *    or the node spells no word.  The last run is scored whether or not a space follows it (the search's end-of-utterance term), so
+ *    "a b" and "a b " score alike.  </s> is never scored;
+ *  - score of token i: s_i = lm(w_i | h_i) as above (cond_score of csrc/ctc_lm.h), h_i the previous order-1 tokens of the sequence,
+ *    out-of-vocabulary ids included, left-padded with <s>.  If s_i is the OOV constant -1000 (w_i or a context token is outside the
+ *    vocabulary) n_oov is incremented and nothing is added; otherwise lm_sum += s_i in fp32, IN TOKEN ORDER.  n_tok counts every
+ *    token, OOV ones included.  So lm_sum + n_oov * (-1000) is the search's LM total of an admissible labeling at alpha = 1, beta = 0,
+ *    and a caller may price OOV differently;
+ *  - outputs per sequence: lm_sum fp32 (log10), n_tok int32, n_oov int32.  They are a function of the sequence and the blob alone:
+ *    not of P, of the position in the batch or of max_len;
+ *  - a sequence with len outside [0, max_len], a range outside [0, n_labels), or a label outside [0, C) or equal to the blank is
+ *    refused: NaN, -1, -1, found by a ballot before anything is read through the label; its neighbours are not disturbed.
+ * One launch, one wavefront per sequence, no workspace, any length.  ds2_lm_score_seq_host scores ONE sequence on the host, serially,
+ * through the same token and score routines and the same order of additions (order and mode are the packed header's). */
+int ds2_lm_score_seqs(const int* labels, long long n_labels, const long long* off, const int* len, int P, int max_len,
+                      const void* lm_dev, const void* lm_host, size_t lm_bytes, int lm_order, int lm_mode, int space, int C, int blank,
+                      float* lm_sum, int* n_tok, int* n_oov, void* stream);
+int ds2_lm_score_seq_host(const void* packed, size_t packed_bytes, const int* labels, int len, int max_len, int space, int C, int blank,
+                          float* lm_sum, int* n_tok, int* n_oov);
+
+/* N-best rescoring, part 2: which slot of every utterance's list wins at every point of an (alpha, beta) grid, and what the winners'
+ * errors add up to (csrc/lm_score.h).  Per (utterance n < N, slot k < K), device arrays: ac fp32 (natural log), lm_sum fp32, n_tok and
+ * n_oov int32 (the outputs above), err (N,K,R) int32 for 1 <= R <= 64 error kinds; oov_score (log10, not NaN); alphas (Ga), betas (Gb)
+ * fp32 on the device.  Score of slot k at (a, b), fp32, every operation rounded on its own (no contraction into an fma, so a float32
+ * restatement matches the bits):  lm = lm_sum + oov_score * n_oov;  s = (ac + alpha * lm) + beta * n_tok.
+ * A NaN score counts as -inf; the pick is the highest s, ties to the lowest k; if every slot is -inf the pick is slot 0.
+ * Outputs: pick (Ga,Gb,N) int32 or NULL; total (Ga,Gb,R) int64 = sum over n of err[n, pick, r], integer atomics: exact, order-free.
+ * One launch (and one memset of total); nothing of size N * K * Ga * Gb is stored.  N may be 0 (totals of 0). */
+int ds2_nbest_sweep(const float* ac, const float* lm_sum, const int* n_tok, const int* n_oov, const int* err, int N, int K, int R,
+                    float oov_score, const float* alphas, int Ga, const float* betas, int Gb, int* pick, long long* total, void* stream);
+
 /* The same search with hotword boosting: the caller names a few phrases and the search prefers prefixes that spell them, with or
  * without the LM above (asr_amd/decoders/hotwords.py builds the automaton; restated by tests/ctc_beam_hot_oracle.py).  Parity with
  * pyctcdecode, WeNet or icefall biasing is not pinned.
