@@ -12,6 +12,8 @@
 // ctc_beam_kernel<PROF, true, HotArgs> is the hotword arm (ds2_ctc_beam_decode_hot_f32) on the same full grid: one more int of
 // state per beam (the node of the automaton of ctc_hot.h), the term phi(n') - phi(n) added to the LM term of every extension, and
 // the end-of-utterance re-score (-phi(state)) and re-sort always run.  Its LM blob may be null (hot-only): no LM table is read.
+// ctc_beam_kernel<PROF, LM, Streamed<arm>> are the streaming instances of the three (ds2_ctc_beam_stream_feed_f32, ctc_beam_stream.h):
+// the beams come from and go back to a state blob in global memory, and the frames of one call continue those of the calls before.
 //
 // Per frame, inside the workgroup (256 threads, all state in LDS):
 //  1. class keys (prob bits, index) of the frame's row, block bitonic sort, running-sum cutoff by wave 0, the threshold key
@@ -347,15 +349,65 @@ struct is_hot<HotArgs> {
   static constexpr bool value = true;
 };
 
-// LM = false takes no LmArgs (an empty pack): its kernel arguments, and its code, are those of the kernel without the LM arm
+// Streaming instances (ctc_beam_stream.h): the arm's arguments wrapped with the stream's.  The search resumes from a state blob in
+// global memory, consumes this call's frames, writes the state back and, when asked, reads the beams out.  Every difference from the
+// one-call kernel sits under `if constexpr (STREAM)`: an instance without Streamed<> in its pack compiles to the code it was.
+struct NoArm {};
+struct StreamArgs {
+  char* state;        // B blobs of `stride` bytes: StreamHeader | beam buffer | LmBeams (LM, hotwords) | hotword states
+  size_t stride;
+  int cap, n_out, W;  // node storage for `cap` frames per utterance; read-out of n_out slots in rows of W (n_out == 0: none)
+  int* stable_len;    // (B)
+  int* frames;        // (B)
+};
+template <class Arm>
+struct Streamed {
+  Arm arm;
+  StreamArgs st;
+};
+struct StreamHeader {   // 64 bytes; all zero = a freshly opened stream
+  int opened, t0, nb, stable_len, stable_node, pad[11];
+};
+__device__ inline LmArgs lm_args(const NoArm&) { return LmArgs{}; }
+__device__ inline const void* hot_blob(const NoArm&) { return nullptr; }
+template <class Arm>
+__device__ inline LmArgs lm_args(const Streamed<Arm>& a) { return lm_args(a.arm); }
+template <class Arm>
+__device__ inline const void* hot_blob(const Streamed<Arm>& a) { return hot_blob(a.arm); }
+template <>
+struct is_hot<Streamed<HotArgs>> {
+  static constexpr bool value = true;
+};
+template <class... Lm>
+struct is_stream {
+  static constexpr bool value = false;
+};
+template <class Arm>
+struct is_stream<Streamed<Arm>> {
+  static constexpr bool value = true;
+};
+__device__ inline StreamArgs stream_args() { return StreamArgs{}; }
+__device__ inline StreamArgs stream_args(const LmArgs&) { return StreamArgs{}; }
+__device__ inline StreamArgs stream_args(const HotArgs&) { return StreamArgs{}; }
+template <class Arm>
+__device__ inline StreamArgs stream_args(const Streamed<Arm>& a) { return a.st; }
+// defined in ctc_beam_stream.h
+__device__ inline void stream_load(const StreamArgs& st, int b, const Layout& L, char* smem, Header* hd, bool lm, const LmBeams& l0, int* h0);
+__device__ inline void stream_save(const StreamArgs& st, int b, const Layout& L, char* smem, const Header* hd, int cur, int frames, bool lm,
+                                   const LmBeams& l0, const LmBeams& l1, const int* hf);
+__device__ inline void stream_stable(const StreamArgs& st, int b, Header* hd, const Beams& f, int nb, const int* n_parent);
+
+// LM = false takes no LmArgs (an empty pack, or Streamed<NoArm>): its kernel arguments, and its code, are those of the kernel without
+// the LM arm
 template <bool PROF, bool LM, class... Lm>
 __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __restrict__ probs, long long ld_b, long long ld_t, int T,
                                                                int C, const int* __restrict__ sizes, int blank, int K, int top_n,
                                                                float cutoff_prob, int PC, int PK, int HT, int* __restrict__ labels,
                                                                int* __restrict__ offsets, int* __restrict__ lens, float* __restrict__ scores,
                                                                int* __restrict__ nodes, u64* __restrict__ prof, Lm... lm_arg) {
-  static_assert(sizeof...(Lm) == (LM ? 1 : 0), "the LM arm takes one LmArgs or HotArgs");
-  constexpr bool HOT = is_hot<Lm...>::value;
+  constexpr bool HOT = is_hot<Lm...>::value, STREAM = is_stream<Lm...>::value;
+  static_assert(sizeof...(Lm) == (LM || STREAM ? 1 : 0), "the LM arm takes one LmArgs or HotArgs, a streaming instance one Streamed<>");
+  [[maybe_unused]] const StreamArgs st = stream_args(lm_arg...);
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const LmArgs lm = lm_args(lm_arg...);
   const Layout L(K, PC, PK, HT);
@@ -372,11 +424,20 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
   int* c_cls = c_src + PK;
   float* c_pb = (float*)(c_cls + PK);
   float* c_pnb = c_pb + PK;
-  const long long TK = (long long)T * K;
+  long long TK = (long long)T * K;
+  if constexpr (STREAM) TK = (long long)st.cap * K;   // node ids t * K + slot count the stream's frames: they do not depend on the capacity
   int* n_parent = nodes + (long long)b * 3 * TK;
   int* n_label = n_parent + TK;
   int* n_frame = n_label + TK;
-  const int n = sizes ? min(max(sizes[b], 0), T) : T;
+  int n = sizes ? min(max(sizes[b], 0), T) : T;
+  [[maybe_unused]] int t0 = 0;        // frames consumed by earlier calls
+  [[maybe_unused]] bool fresh = true;  // no earlier call: the beams start from the empty prefix
+  if constexpr (STREAM) {
+    const StreamHeader* sh = (const StreamHeader*)(st.state + (size_t)b * st.stride);
+    fresh = sh->opened == 0;
+    t0 = fresh ? 0 : sh->t0;
+    n = max(min(n, st.cap - t0), 0);   // (the entry has checked the host's bound; a wrong bound must not write past the nodes)
+  }
   const int R = min(top_n, C);
   ds2lm::LmView lv;
   LmBeams l0, l1;
@@ -388,7 +449,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
     hv = ds2hot::hot_view(hot_blob(lm_arg...));
     h0 = (int*)(smem + Layout::align_up(lm_layout_total(L, lm.nbl), 16));
     h1 = (int*)((char*)h0 + hot_state_bytes(K));
-    if (tid == 0) h0[0] = 0;
+    if (tid == 0 && fresh) h0[0] = 0;
   }
   if constexpr (LM) {
     if (!HOT || lm.blob) lv = ds2lm::lm_view(lm.blob);
@@ -396,7 +457,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
     l1 = lm_beams_at(smem, L, 1);
     lnb_lp = (float*)(smem + Layout::align_up(L.total, 16) + 2 * lm_beams_bytes(K));
     lnb_cls = (int*)(lnb_lp + lm.nbl);
-    if (tid == 0) {
+    if (tid == 0 && fresh) {
       for (int i = 0; i < lm.m; ++i) l0.ctx[i] = lv.h->bos;
       ds2lm::context_backoffs(lv, l0.ctx, lm.m, l0.bow);
       l0.node[0] = 0;
@@ -404,7 +465,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
     }
   }
 
-  if (tid == 0) {
+  if (tid == 0 && fresh) {
     const Beams& s = b0;
     s.pb[0] = 0.f;
     s.pnb[0] = -INFINITY;
@@ -416,6 +477,9 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
     s.ph[0] = 0;
     hd->nb = 1;
     hd->pad0 = hd->pad1 = 0;
+  }
+  if constexpr (STREAM) {
+    if (!fresh) stream_load(st, b, L, smem, hd, LM, l0, h0);
   }
   u64 ticks[4] = {0, 0, 0, 0}, stamp = PROF ? wall_clock64() : 0;
   auto lap = [&](int phase) {
@@ -612,10 +676,12 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
         if constexpr (LM) lm_copy(lm, mo, src, mw, j);
         if constexpr (HOT) hw[j] = ho[src];
       } else {
-        const int nd = t * K + j;
+        int tg = t;   // the frame's index in the stream
+        if constexpr (STREAM) tg += t0;
+        const int nd = tg * K + j;
         n_parent[nd] = o.node[src];
         n_label[nd] = cls;
-        n_frame[nd] = t;
+        n_frame[nd] = tg;
         w.pb[j] = -INFINITY;
         w.pnb[j] = c_pnb[idx];
         w.tot[j] = c_pnb[idx];
@@ -646,9 +712,18 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
     prof[b * 8 + 6] = n;
   }
 
+  [[maybe_unused]] bool readout = true;
+  if constexpr (STREAM) {
+    // the state the next call resumes from, before the end-of-utterance stage below: that stage works on the LDS copy alone
+    const int* hf = nullptr;
+    if constexpr (HOT) hf = cur ? h1 : h0;
+    stream_save(st, b, L, smem, hd, cur, t0 + n, LM, l0, l1, hf);
+    readout = st.n_out > 0;
+  }
+
   if constexpr (LM) {
     // end of utterance: score the partial word (word mode), give back the lead of a partial hotword match, re-sort the survivors
-    if ((HOT || lm.mode == ds2lm::MODE_WORD) && hd->nb > 0) {
+    if ((HOT || lm.mode == ds2lm::MODE_WORD) && hd->nb > 0 && readout) {
       const int nbf = hd->nb, P = pow2_ceil(nbf);
       const Beams f = cur ? b1 : b0, w = cur ? b0 : b1;
       const LmBeams lf = cur ? l1 : l0, lw = cur ? l0 : l1;
@@ -695,30 +770,38 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
   // results: K slots per utterance, best first; label / offset rows zero past each length
   const int nb = hd->nb;
   const Beams f = cur ? b1 : b0;
-  int* lab = labels + (long long)b * K * T;
-  int* off = offsets + (long long)b * K * T;
-  for (int j = 0; j < K; ++j) {
+  int KO = K, TO = T;   // slots per utterance and row width of the outputs
+  if constexpr (STREAM) {
+    KO = st.n_out;
+    TO = st.W;
+  }
+  int* lab = labels + (long long)b * KO * TO;
+  int* off = offsets + (long long)b * KO * TO;
+  for (int j = 0; j < KO; ++j) {
     const int len = j < nb ? f.len[j] : 0;
-    for (int s = len + tid; s < T; s += BEAM_THREADS) {
-      lab[(long long)j * T + s] = 0;
-      off[(long long)j * T + s] = 0;
+    for (int s = len + tid; s < TO; s += BEAM_THREADS) {
+      lab[(long long)j * TO + s] = 0;
+      off[(long long)j * TO + s] = 0;
     }
   }
-  for (int j = tid; j < K; j += BEAM_THREADS) {
+  for (int j = tid; j < KO; j += BEAM_THREADS) {
     if (j < nb) {
       int x = f.node[j];
       for (int s = f.len[j] - 1; s >= 0; --s) {
-        lab[(long long)j * T + s] = n_label[x];
-        off[(long long)j * T + s] = n_frame[x];
+        if (!STREAM || s < TO) {   // (a stream's rows are the caller's width; the entry has checked that it holds every frame)
+          lab[(long long)j * TO + s] = n_label[x];
+          off[(long long)j * TO + s] = n_frame[x];
+        }
         x = n_parent[x];
       }
-      lens[b * K + j] = f.len[j];
-      scores[b * K + j] = f.tot[j];
+      lens[b * KO + j] = f.len[j];
+      scores[b * KO + j] = f.tot[j];
     } else {
-      lens[b * K + j] = 0;
-      scores[b * K + j] = -INFINITY;
+      lens[b * KO + j] = 0;
+      scores[b * KO + j] = -INFINITY;
     }
   }
+  if constexpr (STREAM) stream_stable(st, b, hd, f, nb, n_parent);
 }
 
 }  // namespace

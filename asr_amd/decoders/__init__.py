@@ -429,6 +429,150 @@ class BeamCTCDecoder(Decoder):
         self.last_scores = host[2 * n + B * K:].view(torch.float32).view(B, K).clone()
         return self.convert_to_strings(labels_h, lens_h), self.convert_tensor(offs_h, lens_h)
 
+    def open_stream(self, batch=1, nbest=1, capacity=256):
+        """A BeamStream over `batch` utterances that are fed chunk by chunk (see there).  The stream keeps the settings the decoder has
+        now: width, cut-offs, language model, alpha / beta, hotwords; changing them on the decoder later leaves an open stream as it
+        is.  nbest: how many hypotheses a partial result lists (at most beam_width).  capacity: the frames the back-pointer storage
+        holds at first; it doubles when a feed needs more."""
+        return BeamStream(self, batch, nbest, capacity)
+
+
+def stream_capacity(capacity, need):
+    """The growth plan of BeamStream's node storage: the capacity (>= 1 frame) doubled until it holds `need` frames."""
+    capacity = max(int(capacity), 1)
+    while capacity < int(need):
+        capacity *= 2
+    return capacity
+
+
+class BeamStream:
+    """A running beam search over `batch` utterances (BeamCTCDecoder.open_stream): feed() consumes posteriors chunk by chunk and
+    returns the best text so far and how much of it is final; finish() returns what BeamCTCDecoder.decode() returns for the
+    concatenated frames, with the same bits, whatever the cuts.  The search's state (the beams of the kernel, with the language model's
+    and the hotwords' per-beam state) lives on the device between calls (`ds2_ctc_beam_stream_feed_f32`, contract in
+    include/ds2hip.h), and so do the back-pointers: 12 * beam_width bytes per frame and utterance, never compacted (216 MB for an
+    hour at width 100), in storage that doubles when a feed needs more.  A partial result copies nbest rows of the stream's length to
+    the host, so the partials of a long stream cost more as it grows; feed(..., partial=False) copies nothing.
+    `frames`: the frames consumed per utterance; `closed`: finish() has run.
+    NOT MEASURED: how far the stable prefix lags the best hypothesis on real recordings."""
+
+    def __init__(self, decoder, batch=1, nbest=1, capacity=256):
+        from ..ops import _is_int
+        if not _is_int(batch, 1):
+            raise ValueError(f"BeamStream: batch must be a positive integer, got {batch!r}")
+        if not _is_int(nbest, 1, decoder.beam_width):
+            raise ValueError(f"BeamStream: nbest must be an integer in 1..beam_width ({decoder.beam_width}), got {nbest!r}")
+        if not _is_int(capacity, 1):
+            raise ValueError(f"BeamStream: capacity must be a positive number of frames, got {capacity!r}")
+        self.decoder, self.batch, self.nbest = decoder, int(batch), int(nbest)
+        self.search = dict(blank=decoder.blank_index, beam_width=decoder.beam_width, cutoff_top_n=decoder.cutoff_top_n,
+                           cutoff_prob=decoder.cutoff_prob, lm=decoder.lm, alpha=decoder.alpha, beta=decoder.beta, hotwords=decoder.hotwords)
+        self.C, self.frames, self.closed = None, [0] * self.batch, False
+        self.capacity, self._first_capacity = 0, int(capacity)
+        self._state = self._nodes = None
+
+    def check_feed(self, probs, sizes=None):
+        """The host half of feed(), before any device call: refuses a closed stream, a shape that is not (batch, T, C) (or (T, C) with
+        batch 1), a C other than the first feed's, and sizes outside [0, T] -> (probs (B, T, C), the chunk's frames per utterance as a
+        list).  The first call fixes C."""
+        if self.closed:
+            raise ValueError("BeamStream.feed: the stream is closed (finish() has run)")
+        probs = torch.as_tensor(probs)
+        if probs.dim() == 2 and self.batch == 1:
+            probs = probs[None]
+        if probs.dim() != 3 or probs.size(0) != self.batch:
+            raise ValueError(f"BeamStream.feed: probs must be ({self.batch}, T, C){' or (T, C)' if self.batch == 1 else ''}, "
+                             f"got {tuple(probs.shape)}")
+        T, C = probs.size(1), probs.size(2)
+        if T < 1:
+            raise ValueError("BeamStream.feed: a chunk needs at least one frame (sizes may be 0)")
+        if self.C is not None and C != self.C:
+            raise ValueError(f"BeamStream.feed: the stream was opened with {self.C} classes, this chunk has {C}")
+        if sizes is None:
+            n = [T] * self.batch
+        else:
+            sizes = torch.as_tensor(sizes).reshape(-1)
+            if sizes.numel() != self.batch or sizes.dtype.is_floating_point:
+                raise ValueError(f"BeamStream.feed: sizes must hold {self.batch} integers")
+            n = [int(v) for v in sizes.tolist()]
+            if any(v < 0 or v > T for v in n):
+                raise ValueError(f"BeamStream.feed: sizes {n} outside [0, {T}], the chunk's frames")
+        self.C = C
+        return probs, n
+
+    def _device_state(self, dev, need):
+        """the state (zeros: a fresh stream) and node storage for `need` frames, grown by doubling with the nodes copied over"""
+        from .. import ops
+        K = self.search["beam_width"]
+        if self._state is None:
+            self._state = ops.ctc_beam_stream_state(self.batch, K, self.search["lm"], self.search["hotwords"], dev)
+        cap = stream_capacity(self.capacity or self._first_capacity, need)
+        if cap != self.capacity:
+            self._nodes = ops.ctc_beam_stream_nodes(self.batch, cap, K, dev, self._nodes, self.capacity)
+            self.capacity = cap
+
+    def _call(self, probs, sizes, n_out, dev):
+        from .. import ops
+        bound = max(self.frames)
+        self._device_state(dev, bound + (0 if probs is None else probs.size(1)))
+        return ops.ctc_beam_stream_feed(probs, sizes, self._state, self._nodes, self.capacity, bound, n_out,
+                                        classes=self.C if self.C is not None else len(self.decoder.labels), **self.search)
+
+    def _download(self, out, dev):
+        """one device-to-host copy of a read-out -> labels, offsets (B, n_out, W), lens (B, n_out), scores (B, n_out) fp32, stable (B)"""
+        from .. import ops
+        labels, offs, lens, scores, stable, _ = out
+        B, n_out, W = labels.shape
+        host = torch.cat((labels.reshape(-1), offs.reshape(-1), lens.reshape(-1), scores.view(torch.int32).reshape(-1), stable)).cpu()
+        if ops.rnn_poison_seen(dev):
+            ops.rnn_persistent_check(dev)    # as in BeamCTCDecoder.decode: a poisoned forward raises here
+        n, m = B * n_out * W, B * n_out
+        return (host[:n].view(B, n_out, W), host[n:2 * n].view(B, n_out, W), host[2 * n:2 * n + m].view(B, n_out),
+                host[2 * n + m:2 * n + 2 * m].view(torch.float32).view(B, n_out).clone(), host[2 * n + 2 * m:].tolist())
+
+    def feed(self, probs, sizes=None, partial=True):
+        """probs (B, T, C) or, with batch 1, (T, C) probabilities, on the host or the device, as decode() takes them; sizes: the chunk's
+        valid frames per utterance (0: the utterance has nothing in this chunk).  One launch.  partial=True: one device-to-host copy and
+        one record per utterance: {"text", "offsets", "score": the best hypothesis so far, as decode() of the frames so far gives it;
+        "stable": how many of its characters are final, in every later result and in finish(), with their offsets; "stable_text": those
+        characters; "frames": the frames consumed; with nbest > 1 "nbest": [(text, offsets, score)]}.  partial=False: nothing is copied,
+        None is returned."""
+        probs, n = self.check_feed(probs, sizes)
+        if not probs.is_cuda:
+            probs = probs.to(_device("BeamStream", ".feed"))
+        probs = probs.float()
+        if probs.stride(2) != 1:
+            probs = probs.contiguous()
+        dev = probs.device
+        out = self._call(probs, None if sizes is None else torch.tensor(n, dtype=torch.int32), self.nbest if partial else 0, dev)
+        self.frames = [f + v for f, v in zip(self.frames, n)]
+        if not partial:
+            return None
+        labels, offs, lens, scores, stable = self._download(out, dev)
+        strings, offsets = self.decoder.convert_to_strings(labels, lens), self.decoder.convert_tensor(offs, lens)
+        records = []
+        for b in range(self.batch):
+            rec = {"text": strings[b][0], "offsets": offsets[b][0], "score": float(scores[b, 0]), "stable": stable[b],
+                   "stable_text": strings[b][0][:stable[b]], "frames": self.frames[b]}
+            if self.nbest > 1:
+                rec["nbest"] = [(strings[b][k], offsets[b][k], float(scores[b, k])) for k in range(self.nbest)]
+            records.append(rec)
+        return records
+
+    def finish(self):
+        """Ends the stream -> (strings[b][k], offsets[b][k]) with beam_width entries per utterance, as BeamCTCDecoder.decode() returns
+        them for the concatenated frames; the decoder's `last_scores` are set as decode() sets them.  A stream that was never fed
+        gives decode()'s result for utterances of 0 frames.  A later feed() raises ValueError."""
+        if self.closed:
+            raise ValueError("BeamStream.finish: the stream is closed already")
+        dev = self._state.device if self._state is not None else _device("BeamStream", ".finish")
+        out = self._call(None, None, self.search["beam_width"], dev)
+        labels, offs, lens, scores, _ = self._download(out, dev)
+        self.closed = True
+        self._state = self._nodes = None
+        self.decoder.last_scores = scores
+        return self.decoder.convert_to_strings(labels, lens), self.decoder.convert_tensor(offs, lens)
+
 
 def _reference_strings(references):
     """references as tune_lm_weights takes them: strings, or evaluate()'s output_data form [[str]] -> a list of strings"""

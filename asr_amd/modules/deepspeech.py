@@ -277,31 +277,71 @@ class DeepSpeech(nn.Module):
         unmeasured; the frames next to an inner edge were computed with `overlap` input frames of context on that side, and the overlap
         is the caller's knob.  The defaults (20 s windows, 2 s overlap at a 10 ms stride) keep the model near its training lengths.
         The model is left in eval mode."""
+        probs = None
+        for chunk, out, t_out in self._long_batches("posteriors_long", spect, window, overlap, batch_size):
+            if probs is None:
+                probs = torch.empty((t_out, out.size(2)), dtype=torch.float32, device=out.device)
+            for n, (_, _, out_start, keep_from, keep_to) in enumerate(chunk):
+                probs[out_start:out_start + keep_to - keep_from] = out[n, keep_from:keep_to]
+        ops.rnn_persistent_check(probs.device)          # raise if a persistent recurrence of any batch starved (its rows are NaN then)
+        return probs
+
+    def _long_batches(self, who, spect, window, overlap, batch_size):
+        """The window loop of posteriors_long and stream_long: yields (windows, out, t_out) per batch: the batch's windows as
+        functional.long_windows lists them (start, length, out_start, keep_from, keep_to), the eval-mode forward's output for them
+        (computed without gradients) and the recording's output frames.  The argument checks run when the first batch is asked for."""
         from ..functional import long_windows
         spect = torch.as_tensor(spect)
         if spect.dim() == 4 and spect.size(0) == 1 and spect.size(1) == 1:
             spect = spect[0, 0]
         if spect.dim() != 2:
-            raise ValueError(f"posteriors_long: spect must be (F,T) or (1,1,F,T), got {tuple(spect.shape)}")
+            raise ValueError(f"{who}: spect must be (F,T) or (1,1,F,T), got {tuple(spect.shape)}")
         if int(batch_size) < 1:
-            raise ValueError("posteriors_long: batch_size must be positive")
+            raise ValueError(f"{who}: batch_size must be positive")
         wins = long_windows(spect.size(1), window, overlap)
         self.eval()
         dev = spect.device if spect.is_cuda else next(self.parameters()).device
-        probs = None
-        with torch.no_grad():
-            for i in range(0, len(wins), int(batch_size)):
-                chunk = wins[i:i + int(batch_size)]
+        for i in range(0, len(wins), int(batch_size)):
+            chunk = wins[i:i + int(batch_size)]
+            with torch.no_grad():
                 x = torch.zeros((len(chunk), 1, spect.size(0), max(w[1] for w in chunk)), dtype=torch.float32, device=dev)
                 for n, (start, length, _, _, _) in enumerate(chunk):
                     x[n, 0, :, :length] = spect[:, start:start + length]
                 out, _ = self.forward(x, torch.tensor([w[1] for w in chunk], dtype=torch.int32))
-                if probs is None:
-                    probs = torch.empty(((spect.size(1) - 1) // 2 + 1, out.size(2)), dtype=torch.float32, device=out.device)
-                for n, (_, _, out_start, keep_from, keep_to) in enumerate(chunk):
-                    probs[out_start:out_start + keep_to - keep_from] = out[n, keep_from:keep_to]
-            ops.rnn_persistent_check(probs.device)          # raise if a persistent recurrence of any batch starved (its rows are NaN then)
-        return probs
+            yield chunk, out, (spect.size(1) - 1) // 2 + 1
+
+    def stream_long(self, spect, window=2000, overlap=200, batch_size=32, decoder=None):
+        """The text of ONE recording of any length while it is being computed: a generator.  The forward of posteriors_long runs batch
+        by batch (see there for the windows and for what is not claimed about their edges); each window's kept frames go, in time
+        order, into one decoders.BeamStream of `decoder or self.decoder`, which must be a BeamCTCDecoder (TypeError otherwise; there is
+        no streaming GreedyDecoder): ONE beam search over the whole recording, so a language model's context is never reset.  After
+        each batch it yields {"text": the best text so far, "stable_text": the part of it no later item changes, "frames", "seconds":
+        the output frames consumed and their time, "final": False}; the last item has "final": True, the text BeamCTCDecoder.decode()
+        gives for posteriors_long's result, and "words": [(word, start, end, start_s, end_s)] as transcribe() gives them.  The
+        starvation check of evaluate() runs with every item.  NOT MEASURED: whether this lowers WER against the segmented
+        transcribe_long with a language model, and how far "stable_text" lags "text" on real recordings.  The model is left in eval
+        mode."""
+        from ..decoders import BeamCTCDecoder
+        dec = decoder or self.decoder
+        if not isinstance(dec, BeamCTCDecoder):
+            raise TypeError(f"stream_long: needs a BeamCTCDecoder (given or self.decoder), got {type(dec).__name__}")
+        return self._stream_long(dec.open_stream(), spect, window, overlap, batch_size)
+
+    def _stream_long(self, stream, spect, window, overlap, batch_size):
+        from ..decoders import words_from_offsets
+        fs = 2.0 * float(self.audio_conf.window_stride)
+        for chunk, out, _ in self._long_batches("stream_long", spect, window, overlap, batch_size):
+            kept = [n for n, w in enumerate(chunk) if w[4] > w[3]]      # (a short last window may keep no frame)
+            for n in kept:
+                rec = stream.feed(out[n, chunk[n][3]:chunk[n][4]], partial=n == kept[-1])
+            if kept:
+                yield {"text": rec[0]["text"], "stable_text": rec[0]["stable_text"], "frames": rec[0]["frames"],
+                       "seconds": rec[0]["frames"] * fs, "final": False}
+        frames = stream.frames[0]
+        strings, offsets = stream.finish()
+        text = strings[0][0]
+        yield {"text": text, "stable_text": text, "frames": frames, "seconds": frames * fs, "final": True,
+               "words": [w + (w[1] * fs, w[2] * fs) for w in words_from_offsets(text, offsets[0][0])]}
 
     def align_long(self, spect, transcript, window=2000, overlap=200, batch_size=32, star=None, star_penalty=math.log(0.5),
                    unknown="error", free_start=False, free_end=False):

@@ -1698,6 +1698,36 @@ def ctc_segment_gather(probs: Tensor, seg_b: Tensor, seg_start: Tensor, seg_len:
     return out, out_sizes
 
 
+def _beam_search_args(who, lib, C, blank, beam_width, cutoff_top_n, lm, hotwords) -> int:
+    """What ctc_beam_decode and ctc_beam_stream_feed check of the search's arguments before anything is allocated -> the beam width"""
+    K = int(beam_width)
+    if not 1 <= K <= lib.ds2_ctc_beam_max_width():
+        raise ValueError(f"{who}: beam_width {K} outside the supported 1..{lib.ds2_ctc_beam_max_width()}")
+    if hotwords is not None and hotwords.C != C:
+        raise ValueError(f"{who}: the hotwords were bound to {hotwords.C} classes, probs have {C}")
+    if hotwords is not None and hotwords.blank != int(blank):
+        raise ValueError(f"{who}: the hotwords were bound to blank {hotwords.blank}, the decode has blank {int(blank)}")
+    if lm is not None and lm.C != C:
+        raise ValueError(f"{who}: the language model was bound to {lm.C} classes, probs have {C}")
+    grid, cap = K * (min(int(cutoff_top_n), C - 1) + 2), lib.ds2_ctc_beam_lm_max_candidates()
+    if (lm is not None or hotwords is not None) and grid > cap:          # (the plain search has its staircase: no full grid, no limit)
+        why = "with a language model " if hotwords is None else \
+            "with hotwords every beam is extended by every kept class, with or without a language model: "
+        raise ValueError(f"{who}: {why}beam_width * (min(cutoff_top_n, C - 1) + 2) = {grid} exceeds the {cap} candidate slots")
+    return K
+
+
+def _beam_arm_args(lm, alpha, beta, hotwords, dev):
+    """The language-model and hotword arguments of the beam entries: (lm_dev, lm_bytes, order, mode, space, alpha, beta), (hot_dev,
+    hot_host, hot_bytes) and the device tensors that must outlive the call"""
+    tab = lm.device_tables(dev) if lm is not None else None
+    lm_args = (None, 0, 0, 0, -1) if lm is None else (tab.data_ptr(), tab.numel(), lm.order, lm.mode, lm.space if lm.space is not None else -1)
+    lm_args += (float(alpha), float(beta))
+    hot = hotwords.device_tables(dev) if hotwords is not None else None
+    hot_args = (None, None, 0) if hotwords is None else (hot.data_ptr(), hotwords.packed.ctypes.data, hotwords.packed.nbytes)
+    return lm_args, hot_args, (tab, hot)
+
+
 def ctc_beam_decode(probs: Tensor, sizes: Tensor | None = None, blank: int = 0, beam_width: int = 100, cutoff_top_n: int = 40,
                     cutoff_prob: float = 1.0, lm=None, alpha: float = 0.0, beta: float = 0.0, hotwords=None, labels_out: Tensor | None = None):
     """CTC prefix beam search of probs (B,T,C) fp32 on the GPU -> (labels (B,K,T) i32, offsets (B,K,T) i32, lengths (B,K) i32,
@@ -1709,20 +1739,7 @@ def ctc_beam_decode(probs: Tensor, sizes: Tensor | None = None, blank: int = 0, 
     buffer that also holds the references, so that one edit-distance launch sees both)."""
     B, T, C, dev, ld_b, ld_t = _posteriors("ctc_beam_decode", probs, off_gpu=_lib.DS2LibraryError)
     lib = _lib.load()
-    K = int(beam_width)
-    if not 1 <= K <= lib.ds2_ctc_beam_max_width():
-        raise ValueError(f"ctc_beam_decode: beam_width {K} outside the supported 1..{lib.ds2_ctc_beam_max_width()}")
-    if hotwords is not None and hotwords.C != C:
-        raise ValueError(f"ctc_beam_decode: the hotwords were bound to {hotwords.C} classes, probs have {C}")
-    if hotwords is not None and hotwords.blank != int(blank):
-        raise ValueError(f"ctc_beam_decode: the hotwords were bound to blank {hotwords.blank}, the decode has blank {int(blank)}")
-    if lm is not None and lm.C != C:
-        raise ValueError(f"ctc_beam_decode: the language model was bound to {lm.C} classes, probs have {C}")
-    grid, cap = K * (min(int(cutoff_top_n), C - 1) + 2), lib.ds2_ctc_beam_lm_max_candidates()
-    if (lm is not None or hotwords is not None) and grid > cap:          # (the plain search has its staircase: no full grid, no limit)
-        why = "with a language model " if hotwords is None else \
-            "with hotwords every beam is extended by every kept class, with or without a language model: "
-        raise ValueError(f"ctc_beam_decode: {why}beam_width * (min(cutoff_top_n, C - 1) + 2) = {grid} exceeds the {cap} candidate slots")
+    K = _beam_search_args("ctc_beam_decode", lib, C, blank, beam_width, cutoff_top_n, lm, hotwords)
     sizes = _sizes_i32(sizes, B, dev)
     if labels_out is not None and (labels_out.shape != (B, K, T) or labels_out.dtype != torch.int32 or labels_out.device != dev
                                    or not labels_out.is_contiguous()):
@@ -1735,18 +1752,76 @@ def ctc_beam_decode(probs: Tensor, sizes: Tensor | None = None, blank: int = 0, 
     ws = _ws(n, dev)
     search = (probs.data_ptr(), ld_b, ld_t, B, T, C, _ptr(sizes), int(blank), K, int(cutoff_top_n), float(cutoff_prob))
     out = (labels.data_ptr(), offs.data_ptr(), lens.data_ptr(), scores.data_ptr(), ws.data_ptr(), n, _stream())
-    tab = lm.device_tables(dev) if lm is not None else None
-    lm_args = (None, 0, 0, 0, -1) if lm is None else (tab.data_ptr(), tab.numel(), lm.order, lm.mode, lm.space if lm.space is not None else -1)
-    lm_args += (float(alpha), float(beta))
+    lm_args, hot_args, _keep = _beam_arm_args(lm, alpha, beta, hotwords, dev)
     if hotwords is not None:
-        hot = hotwords.device_tables(dev)
-        _lib.check(lib.ds2_ctc_beam_decode_hot_f32(*search, *lm_args, hot.data_ptr(), hotwords.packed.ctypes.data, hotwords.packed.nbytes, *out),
-                   "ds2_ctc_beam_decode_hot_f32")
+        _lib.check(lib.ds2_ctc_beam_decode_hot_f32(*search, *lm_args, *hot_args, *out), "ds2_ctc_beam_decode_hot_f32")
     elif lm is not None:
         _lib.check(lib.ds2_ctc_beam_decode_lm_f32(*search, *lm_args, *out), "ds2_ctc_beam_decode_lm_f32")
     else:
         _lib.check(lib.ds2_ctc_beam_decode_f32(*search, *out), "ds2_ctc_beam_decode_f32")
     return labels, offs, lens, scores
+
+
+def ctc_beam_stream_state(B: int, beam_width: int, lm, hotwords, dev) -> Tensor:
+    """The state of B freshly opened streams for ctc_beam_stream_feed: zero bytes on dev (ds2_ctc_beam_stream_state_bytes)."""
+    n = _lib.load().ds2_ctc_beam_stream_state_bytes(int(B), int(beam_width), int(lm is not None), int(hotwords is not None))
+    if n == 0:
+        raise ValueError(f"ctc_beam_stream_state: batch {B} or beam_width {beam_width} outside the supported sizes")
+    return torch.zeros(n, dtype=torch.uint8, device=dev)
+
+
+def ctc_beam_stream_nodes(B: int, cap_frames: int, beam_width: int, dev, old: Tensor | None = None, old_cap: int = 0) -> Tensor:
+    """Node storage for ctc_beam_stream_feed with room for cap_frames frames per utterance: (B, 3, cap_frames * beam_width) int32 on dev.
+    With `old` (the storage of capacity old_cap <= cap_frames) every utterance's three arrays are copied to the front of their new
+    places: node ids do not depend on the capacity."""
+    nodes = torch.empty((int(B), 3, int(cap_frames) * int(beam_width)), dtype=torch.int32, device=dev)
+    if old is not None:
+        nodes[:, :, :int(old_cap) * int(beam_width)] = old.view(int(B), 3, -1)
+    return nodes
+
+
+def ctc_beam_stream_feed(probs: Tensor | None, sizes: Tensor | None, state: Tensor, nodes: Tensor, cap_frames: int, frames_bound: int,
+                         n_out: int, blank: int = 0, beam_width: int = 100, cutoff_top_n: int = 40, cutoff_prob: float = 1.0, lm=None,
+                         alpha: float = 0.0, beta: float = 0.0, hotwords=None, classes: int | None = None):
+    """One chunk of frames into B running beam searches (contract: include/ds2hip.h, ds2_ctc_beam_stream_feed_f32): probs (B,T,C) fp32 on
+    the GPU, or None for a pure read-out (`classes` then gives C); sizes (B) the chunk's valid frames per utterance or None; state and
+    nodes as ctc_beam_stream_state / ctc_beam_stream_nodes make them (the batch is nodes.shape[0]), nodes with room for cap_frames >=
+    frames_bound + T frames; frames_bound an upper bound of the frames consumed so far.  The search's arguments are ctc_beam_decode's
+    and must not change within a stream.  n_out in 0..beam_width slots are read out -> (labels (B,n_out,W) i32, offsets (B,n_out,W) i32,
+    lengths (B,n_out) i32, scores (B,n_out) fp32, stable_len (B) i32, frames (B) i32), all on the GPU, W = max(frames_bound + T, 1); the
+    first four are None when n_out == 0.  A read-out has the bits of ctc_beam_decode on the frames so far; stable_len labels and offsets
+    of every beam are final.  One launch on the current stream, nothing is copied back."""
+    who = "ctc_beam_stream_feed"
+    lib = _lib.load()
+    dev = state.device
+    if probs is None:
+        if classes is None:
+            raise ValueError(f"{who}: a call without probs needs the number of classes")
+        B, T, C, ld_b, ld_t = nodes.shape[0], 0, int(classes), 1, 1
+    else:
+        B, T, C, pdev, ld_b, ld_t = _posteriors(who, probs, off_gpu=_lib.DS2LibraryError)
+        if pdev != dev:
+            raise ValueError(f"{who}: probs on {pdev}, the state on {dev}")
+    K = _beam_search_args(who, lib, C, blank, beam_width, cutoff_top_n, lm, hotwords)
+    if not _is_int(n_out, 0, K):
+        raise ValueError(f"{who}: n_out must be an integer in 0..beam_width ({K}), got {n_out!r}")
+    _chk_on_dev(who, dev, torch.uint8, {"state": state})
+    _chk_on_dev(who, dev, torch.int32, {"nodes": nodes})
+    sizes = _sizes_i32(sizes, B, dev)
+    n_out, W = int(n_out), max(int(frames_bound) + T, 1)
+    labels = offs = lens = scores = None
+    if n_out:
+        labels = torch.empty((B, n_out, W), dtype=torch.int32, device=dev)
+        offs = torch.empty((B, n_out, W), dtype=torch.int32, device=dev)
+        lens = torch.empty((B, n_out), dtype=torch.int32, device=dev)
+        scores = torch.empty((B, n_out), dtype=torch.float32, device=dev)
+    tail = torch.empty((2, B), dtype=torch.int32, device=dev)
+    lm_args, hot_args, _keep = _beam_arm_args(lm, alpha, beta, hotwords, dev)
+    _lib.check(lib.ds2_ctc_beam_stream_feed_f32(_ptr(probs), ld_b, ld_t, B, T, C, _ptr(sizes), int(blank), K, int(cutoff_top_n), float(cutoff_prob),
+                                                *lm_args, *hot_args, state.data_ptr(), state.numel(), nodes.data_ptr(), nodes.numel() * 4,
+                                                int(cap_frames), int(frames_bound), n_out, W, _ptr(labels), _ptr(offs), _ptr(lens), _ptr(scores),
+                                                tail[0].data_ptr(), tail[1].data_ptr(), _stream()), "ds2_ctc_beam_stream_feed_f32")
+    return labels, offs, lens, scores, tail[0], tail[1]
 
 
 def lm_score(labels: Tensor, off: Tensor, lens: Tensor, lm, max_len: int):

@@ -823,6 +823,42 @@ int ds2_ctc_beam_decode_hot_f32(const float* probs, long long ld_b, long long ld
                                 size_t hot_bytes, int* labels, int* offsets, int* lens, float* scores, void* ws, size_t ws_bytes,
                                 void* stream);
 
+/* Streaming beam search: the three searches above, fed a chunk of frames at a time (csrc/ctc_beam_stream.h).  The same kernel in
+ * streaming instances: a call loads every utterance's beams from `state`, runs the unchanged frame loop over this call's frames,
+ * writes the beams back, optionally reads them out, and reports how much of the text is final.  After any cuts of an utterance's
+ * frames into calls, a read-out gives the BITS of one decode call on the frames consumed so far (labels, offsets, lengths, scores).
+ *  - search arguments: those of ds2_ctc_beam_decode_hot_f32.  lm_dev and hot_dev are both nullable: both NULL is the plain search
+ *    with its staircase, lm_dev alone the LM arm, hot_dev the hotword arm (with or without lm_dev); the limits and refusals of the
+ *    arm apply.  T >= 0 frames in this call (probs may be NULL at T == 0); sizes_dev (B) valid frames of THIS call per utterance
+ *    (clamped to [0, T]; NULL: T each), so an utterance with 0 simply does not advance.  Every call of one stream passes the same B,
+ *    C, blank, beam_width, cut-offs, model and hotwords: the state does not record them.
+ *  - state: ds2_ctc_beam_stream_state_bytes(B, beam_width, lm, hot) bytes of device memory (lm / hot: non-zero when lm_dev / hot_dev
+ *    will be given; 0 for B or beam_width outside the limits), opaque, written by every call.  All zero bytes is a freshly opened
+ *    stream: opening is one ds2_memset_async.
+ *  - nodes: the back-pointers (parent | label | frame per utterance, cap_frames * beam_width int32 each), caller-owned,
+ *    ds2_ctc_beam_stream_nodes_bytes(B, cap_frames, beam_width) = 12 * B * cap_frames * beam_width bytes.  Node ids do not depend on
+ *    cap_frames: to grow, allocate for a larger capacity and copy each utterance's three arrays to the front of their new places.
+ *    frames_bound: an upper bound of the frames any utterance has consumed so far (the sum of the earlier calls' T will do);
+ *    frames_bound + T <= cap_frames < 2^20 or the call is refused.  Nothing compacts the nodes: 12 * beam_width bytes per frame.
+ *  - read-out, when n_out > 0 (n_out <= beam_width): the end-of-utterance stage (word mode's partial-word term, the hotwords'
+ *    -phi(state), the re-sort) on a copy the next call does not see, then labels / offsets (B, n_out, W) int32, zero past each length,
+ *    lens (B, n_out), scores (B, n_out): the first n_out slots of the decode call's outputs; a slot past the surviving beams has
+ *    length 0 and score -inf.  W >= frames_bound + T.  With n_out == 0 the four pointers may be NULL.  T == 0 with n_out > 0 is a pure
+ *    read-out (the final result: n_out = beam_width); T == 0 with n_out == 0 is refused.
+ *  - stable_len (B) int32: the length of the longest prefix of (label, offset) pairs common to ALL live beams.  Every beam of every
+ *    later call descends from a live beam, so the first stable_len labels and offsets of any later read-out, of any slot, are these:
+ *    the value never decreases, and with no live beam it is kept.  frames (B) int32: frames consumed so far, this call included.
+ * One launch on `stream`, nothing is copied back.  A state of another arm, width or stream, or one not written by this entry, is
+ * not detected. */
+size_t ds2_ctc_beam_stream_state_bytes(int B, int beam_width, int lm, int hot);
+size_t ds2_ctc_beam_stream_nodes_bytes(int B, int cap_frames, int beam_width);
+int ds2_ctc_beam_stream_feed_f32(const float* probs, long long ld_b, long long ld_t, int B, int T, int C, const int* sizes_dev, int blank,
+                                 int beam_width, int cutoff_top_n, float cutoff_prob, const void* lm_dev, size_t lm_bytes, int lm_order,
+                                 int lm_mode, int space, float alpha, float beta, const void* hot_dev, const void* hot_host,
+                                 size_t hot_bytes, void* state, size_t state_bytes, void* nodes, size_t nodes_bytes, int cap_frames,
+                                 int frames_bound, int n_out, int W, int* labels, int* offsets, int* lens, float* scores,
+                                 int* stable_len, int* frames, void* stream);
+
 /* Batched Levenshtein distance (unit costs: insert, delete, substitute) of P independent pairs of int32 symbol sequences, one launch;
  * the WER / CER scoring of DeepSpeech.evaluate() (replaces Decoder.wer / Decoder.cer's per-utterance DP, decoders/decoder.py:26-58,
  * whose reference uses the `Levenshtein` C package).  The host maps words / characters to ids (asr_amd/decoders), symbols compare
