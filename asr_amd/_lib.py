@@ -133,6 +133,10 @@ SIGNATURES = {
                                            sz, vp]),
     "ds2_ctc_kws_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "ds2_ctc_kws_f32": (i32, [vp, i64, i64, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "ds2_ctc_kws_stream_state_bytes": (sz, [i32, i32, i32]),
+    "ds2_ctc_kws_stream_workspace_bytes": (sz, [i32, i32, i32, i32]),
+    "ds2_ctc_kws_stream_feed_f32": (i32, [vp, i64, i64, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp, i32, i32, i32, i32, i64, vp, sz,
+                                          vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     "ds2_add_i64": (i32, [vp, i32, i64, vp]),
     "ds2_softmax_rows_f32": (i32, [vp, i32, vp, i32, i32, i32, vp]),
     "ds2_greedy_decode_workspace_bytes": (sz, [i32, i32]),

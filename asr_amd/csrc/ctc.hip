@@ -681,6 +681,9 @@ extern "C" int ds2_ctc_loss_f32(const float* logits, int ld, int T, int B, int C
 // Keyword search (ds2_ctc_kws_*): the one-wavefront lattice entered at any frame, a start frame per state instead of back-pointers,
 // behind the same pre-pass with penalty 0, and a pick of non-overlapping detections
 #include "ctc_kws.h"
+// ... and its streaming form (ds2_ctc_kws_stream_*): the same lattice kernel resumed from a state blob, and a pick that reports a
+// detection as final once no later frame can change it
+#include "ctc_kws_stream.h"
 // Minimum-error-rate training on an n-best list (ds2_ctc_mwer_*): the MW = true instances of the two lattice kernels above, a weights
 // launch and a gradient kernel that folds the K occupancies of an utterance into one row
 #include "ctc_mwer.h"

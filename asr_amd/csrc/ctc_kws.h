@@ -20,6 +20,7 @@
 #ifndef DS2_CTC_ALIGN_TU
 #error "ctc_kws.h is a part of ctc.hip"
 #endif
+#include <type_traits>
 
 namespace {
 
@@ -45,14 +46,26 @@ struct KwsArgs {
 // lane l <- lane l - 1; lane 0 keeps `first`
 __device__ __forceinline__ int kws_shift1(int first, int v) { return __builtin_amdgcn_update_dpp(first, v, 0x138, 0xf, 0xf, false); }
 
-template <int IS_LOG>
-__global__ __launch_bounds__(64) void ctc_kws_wave_kernel(KwsArgs a) {
+// A = KwsArgs: the one-call search.  A = KwsStreamArgs (ctc_kws_stream.h): the streaming instance, which loads the four registers of
+// every lane and the frames consumed so far (n0) from the state, counts the start frames from n0, and stores them after the last frame;
+// every difference is under `if constexpr (STREAM)`.  Frame indices stay relative to the chunk (loads, the staging by l == (t & 63),
+// the stores of the per-frame arrays): only the start that the entering move writes is absolute.
+template <int IS_LOG, class A = KwsArgs>
+__global__ __launch_bounds__(64) void ctc_kws_wave_kernel(A a) {
+  constexpr bool STREAM = !std::is_same<A, KwsArgs>::value;
   const int l = threadIdx.x;
   const int b = blockIdx.x / a.K, k = blockIdx.x - b * a.K;
   const long long row = (long long)blockIdx.x * a.T;
   float* fs = a.fscore + row;
   int* fst = a.fstart + row;
   int Tb = a.in_lens ? min(a.in_lens[b], a.T) : a.T;
+  float E = NEG_INF, O = NEG_INF;
+  int sE = -1, sO = -1;
+  int n0 = 0, Tadv = 0;                                          // STREAM: frames before this chunk, frames this chunk advances by
+  if constexpr (STREAM) {
+    n0 = a.stream_load(l, E, O, sE, sO);
+    Tb = Tadv = max(min(Tb, 0x7fffffff - n0), 0);
+  }
   const int U = __builtin_amdgcn_readfirstlane(a.kw_lens[k]);
   const int* lab = a.kw_labels + a.kw_off[k];
   bool ok = U >= 1 && U <= a.maxU && U <= KWS_MAX_LEN && Tb > 0;
@@ -77,8 +90,8 @@ __global__ __launch_bounds__(64) void ctc_kws_wave_kernel(KwsArgs a) {
       xO = xb[(long long)ii * a.ld_t + cls];
       gg = gb[ii];
     };
-    float E = NEG_INF, O = NEG_INF, sv = NEG_INF;
-    int sE = -1, sO = -1, ss = -1;
+    float sv = NEG_INF;
+    int ss = -1;
     auto frame = [&](float xE, float xO, float gg, int t) {
       float dE, dO;
       {
@@ -89,7 +102,7 @@ __global__ __launch_bounds__(64) void ctc_kws_wave_kernel(KwsArgs a) {
       dE = actE ? dE : NEG_INF;
       dO = actO ? dO : NEG_INF;
       const float Om = __int_as_float(kws_shift1(__float_as_int(0.f), __float_as_int(O)));
-      const int sOm = kws_shift1(t, sO), sE0 = sE;
+      const int sOm = kws_shift1(STREAM ? t + n0 : t, sO), sE0 = sE;
       const unsigned nib = align_cell(E, O, Om, skip, dE, dO);
       sE = (nib & 1u) ? sOm : sE0;
       sO = (nib & 8u) ? sOm : ((nib & 4u) ? sE0 : sO);
@@ -129,6 +142,7 @@ __global__ __launch_bounds__(64) void ctc_kws_wave_kernel(KwsArgs a) {
     fs[t] = NEG_INF;
     fst[t] = -1;
   }
+  if constexpr (STREAM) a.stream_save(l, k, n0, Tadv, E, O, sE, sO);
 }
 
 __global__ __launch_bounds__(64) void ctc_kws_pick_kernel(KwsArgs a) {

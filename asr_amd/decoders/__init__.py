@@ -1149,6 +1149,167 @@ class KeywordSpotter(Decoder):
                           f"pair(s), the first: utterance {b}, keyword {kw!r}; the rest were dropped", RuntimeWarning, stacklevel=2)
         return records if frame_seconds is None else add_seconds(records, float(frame_seconds))
 
+    def open_stream(self, batch=1, max_lag=None, pending=1024):
+        """A running search over `batch` utterances that reports detections while the frames arrive: a KeywordStream (see there).
+        max_lag: the most frames the settled part of the stream (the tail) may end behind the frames consumed after a feed, kept by
+        forced cuts, which can lose a detection instead of releasing it (None: no cut, and the stream's detections are exactly
+        search()'s); pending: the candidates kept per utterance and keyword between feeds.  The stream keeps its own copy of the
+        keywords and thresholds: a later set_keywords does not touch it."""
+        return KeywordStream(self, batch, max_lag, pending)
+
+
+def assemble_stream_detections(hit_start, hit_end, hit_score, hit_final, n_hits, keywords, kw_lens, max_hits):
+    """Pure host half of KeywordStream.feed: assemble_detections' records and order, every record with "final": True (reported now,
+    once, and never changed) or False (tentative: the search's detection on the frames so far, which a later frame may still replace)."""
+    hit_start, hit_end, hit_final = np.asarray(hit_start), np.asarray(hit_end), np.asarray(hit_final)
+    hit_score, n_hits = np.asarray(hit_score, np.float32), np.asarray(n_hits)
+    records, overflowed = [], []
+    for b in range(n_hits.shape[0]):
+        found = []
+        for k, kw in enumerate(keywords):
+            n = int(n_hits[b, k])
+            if n > max_hits:
+                overflowed.append((b, kw))
+            for h in range(min(n, max_hits)):
+                found.append((int(hit_start[b, k, h]), int(hit_end[b, k, h]), k, float(hit_score[b, k, h]), bool(hit_final[b, k, h])))
+        records.append([{"keyword": keywords[k], "start": s, "end": e, "score": sc, "confidence": math.exp(sc / kw_lens[k]), "final": f}
+                        for s, e, k, sc, f in sorted(found)])
+    return records, overflowed
+
+
+class KeywordStream:
+    """A running keyword search over `batch` utterances (KeywordSpotter.open_stream): feed() consumes posteriors chunk by chunk and
+    returns the detections that became FINAL with this chunk, each exactly once, and the TENTATIVE ones, which are the search's
+    detections on the frames so far that a later frame may still replace; finish() flushes.  Without max_lag the final detections of
+    the whole stream are exactly those of KeywordSpotter.search() on the concatenated frames, whatever the cuts
+    (`ds2_ctc_kws_stream_feed_f32`, contract in include/ds2hip.h; restated by tests/ctc_kws_stream_oracle.py).  The state on the device
+    is 4 * (264 + 3 * pending) bytes per utterance and keyword; memory and time per feed depend on the chunk, not on the stream's length.
+    A detection is withheld while a path above the threshold that began before it is still alive (the keyword spoken up to its last
+    label but one, then silence, keeps such a path for as long as the silence lasts).  max_lag bounds how far the settled part of the stream
+    may end behind the frames consumed, by forced cuts, the only place where a stream may differ from search(): a cut that falls into a
+    pending candidate's span loses that detection, so max_lag is no bound on how long a detection is withheld.  `detections`: the final records per utterance so far; `forced`, `dropped`:
+    (batch, K) counts of forced cuts and of candidates lost to one or to a full pending list; `frames`; `closed`.
+    NOT MEASURED: which max_lag serves real recordings, and how long detections are withheld on them without one."""
+
+    def __init__(self, spotter, batch=1, max_lag=None, pending=1024):
+        from ..ops import KWS_MAX_PENDING, _is_int
+        if not _is_int(batch, 1):
+            raise ValueError(f"KeywordStream: batch must be a positive integer, got {batch!r}")
+        if max_lag is not None and not _is_int(max_lag, 0, 0x7fffffff):
+            raise ValueError(f"KeywordStream: max_lag must be None or a number of frames >= 0, got {max_lag!r}")
+        if not _is_int(pending, 1, KWS_MAX_PENDING):
+            raise ValueError(f"KeywordStream: pending must be an integer in [1, {KWS_MAX_PENDING}], got {pending!r}")
+        self.batch, self.max_lag, self.pending = int(batch), None if max_lag is None else int(max_lag), int(pending)
+        self.keywords, self.kw_ids, self.kw_lens = list(spotter.keywords), [list(i) for i in spotter.kw_ids], list(spotter.kw_lens)
+        self.max_hits, self.n_labels = spotter.max_hits, len(spotter.labels)
+        K = len(self.keywords)
+        # the constant part of the int32 image: kw_off, kw_lens, thr (its bits), labels; the chunk's sizes follow per feed
+        self._image = np.concatenate([np.cumsum([0] + self.kw_lens[:-1]), self.kw_lens, spotter.thr.view(np.int32),
+                                      [i for ids in self.kw_ids for i in ids]]).astype(np.int32)
+        self.C, self.frames, self.closed = None, [0] * self.batch, False
+        self.detections = [[] for _ in range(self.batch)]
+        self.forced, self.dropped = np.zeros((self.batch, K), np.int64), np.zeros((self.batch, K), np.int64)
+        self._state = None
+
+    def check_feed(self, probs, sizes=None):
+        """The host half of feed(), before any device call: refuses a closed stream, a shape that is not (batch, T, C) (or (T, C) with
+        batch 1), a C other than the first feed's, and sizes outside [0, T] -> (probs (B, T, C), the chunk's frames per utterance as a
+        list).  The first call fixes C."""
+        if self.closed:
+            raise ValueError("KeywordStream.feed: the stream is closed (finish() has run)")
+        probs = torch.as_tensor(probs)
+        if probs.dim() == 2 and self.batch == 1:
+            probs = probs[None]
+        if probs.dim() != 3 or probs.size(0) != self.batch:
+            raise ValueError(f"KeywordStream.feed: probs must be ({self.batch}, T, C){' or (T, C)' if self.batch == 1 else ''}, "
+                             f"got {tuple(probs.shape)}")
+        T, C = probs.size(1), probs.size(2)
+        if T < 1:
+            raise ValueError("KeywordStream.feed: a chunk needs at least one frame (sizes may be 0)")
+        if self.C is not None and C != self.C:
+            raise ValueError(f"KeywordStream.feed: the stream was opened with {self.C} classes, this chunk has {C}")
+        if sizes is None:
+            n = [T] * self.batch
+        else:
+            sizes = torch.as_tensor(sizes).reshape(-1)
+            if sizes.numel() != self.batch or sizes.dtype.is_floating_point:
+                raise ValueError(f"KeywordStream.feed: sizes must hold {self.batch} integers")
+            n = [int(v) for v in sizes.tolist()]
+            if any(v < 0 or v > T for v in n):
+                raise ValueError(f"KeywordStream.feed: sizes {n} outside [0, {T}], the chunk's frames")
+        if max(self.frames) + T > 0x7fffffff:
+            raise ValueError(f"KeywordStream.feed: {max(self.frames)} frames so far + {T} now pass 2^31 - 1")
+        self.C = C
+        return probs, n
+
+    def _call(self, who, probs, n, is_log, finish, dev, frame_seconds):
+        """one pinned upload (the packed keywords and the chunk's sizes), one library call, one device-to-host copy of the hits"""
+        import warnings
+
+        from .. import ops
+        K, B = len(self.keywords), self.batch
+        if self._state is None:
+            self._state = ops.ctc_kws_stream_state(B, K, self.pending, dev)
+        host = torch.empty(self._image.size + B, dtype=torch.int32, pin_memory=True)
+        h = host.numpy()
+        h[:self._image.size], h[self._image.size:] = self._image, n
+        d = host.to(dev, non_blocking=True)
+        hs, he, hsc, hf, nh, _, _, forced, dropped, _, _ = ops.ctc_kws_stream_feed(
+            probs, d[self._image.size:], self._state, d[3 * K:self._image.size], d[:K], d[K:2 * K], max(self.kw_lens),
+            d[2 * K:3 * K].view(torch.float32), self.pending, max(self.frames), is_log, self.max_hits, self.max_lag, finish,
+            classes=self.C if self.C is not None else self.n_labels, batch=B)
+        out = torch.cat((hs.reshape(-1), he.reshape(-1), hsc.view(torch.int32).reshape(-1), hf.reshape(-1), nh.reshape(-1), forced.reshape(-1),
+                         dropped.reshape(-1))).cpu()
+        if ops.rnn_poison_seen(dev):
+            ops.rnn_persistent_check(dev)    # as in KeywordSpotter.search: a poisoned forward raises here
+        self.frames = [f + v for f, v in zip(self.frames, n)]
+        o, m = out.numpy(), B * K * self.max_hits
+        shape = (B, K, self.max_hits)
+        records, overflowed = assemble_stream_detections(o[:m].reshape(shape), o[m:2 * m].reshape(shape), o[2 * m:3 * m].view(np.float32).reshape(shape),
+                                                         o[3 * m:4 * m].reshape(shape), o[4 * m:4 * m + B * K].reshape(B, K), self.keywords,
+                                                         self.kw_lens, self.max_hits)
+        forced, dropped = (o[4 * m + (i + 1) * B * K:4 * m + (i + 2) * B * K].reshape(B, K).astype(np.int64) for i in (0, 1))
+        lost = np.argwhere(dropped > self.dropped)
+        self.forced, self.dropped = forced, dropped
+        if overflowed:
+            b, kw = overflowed[0]
+            warnings.warn(f"{who}: more than max_hits={self.max_hits} detections for {len(overflowed)} (utterance, keyword) "
+                          f"pair(s), the first: utterance {b}, keyword {kw!r}; the rest were dropped", RuntimeWarning, stacklevel=3)
+        if len(lost):
+            b, k = (int(v) for v in lost[0])
+            why = f"more than pending={self.pending} candidates" if self.max_lag is None else \
+                f"more than pending={self.pending} candidates, or candidates cut by max_lag={self.max_lag}"
+            warnings.warn(f"{who}: {why} for {len(lost)} (utterance, keyword) pair(s), the first: utterance {b}, keyword "
+                          f"{self.keywords[k]!r}; the rest were dropped", RuntimeWarning, stacklevel=3)
+        for b, utt in enumerate(records):
+            self.detections[b] += [r for r in utt if r["final"]]
+        return records if frame_seconds is None else add_seconds(records, float(frame_seconds))
+
+    def feed(self, probs, sizes=None, is_log=False, frame_seconds=None):
+        """probs (B, T, C) or, with batch 1, (T, C), on the host or the device, as KeywordSpotter.search takes them (probabilities, or
+        log-probabilities with is_log=True); sizes: the chunk's valid frames per utterance (0: the utterance has nothing in this chunk).
+        Returns, per utterance, the records of search() (frames counted from the stream's first frame) with "final": True for a
+        detection that is reported now and never again or changed, False for a tentative one, which every feed reports anew while it
+        stands; sorted by (start, end, keyword).  Warns when a keyword had more than max_hits detections to report (final ones take the
+        slots first) and when candidates were dropped (a full pending list, a forced cut)."""
+        probs, n = self.check_feed(probs, sizes)
+        if not probs.is_cuda:
+            probs = probs.to(_device("KeywordStream", ".feed"))
+        probs = probs.float()
+        if probs.stride(2) != 1:
+            probs = probs.contiguous()
+        return self._call("KeywordStream.feed", probs, n, is_log, False, probs.device, frame_seconds)
+
+    def finish(self, frame_seconds=None):
+        """Ends the stream: everything still pending is picked as search() would on the frames consumed, and returned as final records
+        per utterance.  A later feed() raises ValueError."""
+        if self.closed:
+            raise ValueError("KeywordStream.finish: the stream is closed already")
+        dev = self._state.device if self._state is not None else _device("KeywordStream", ".finish")
+        records = self._call("KeywordStream.finish", None, [0] * self.batch, False, True, dev, frame_seconds)
+        self.closed, self._state = True, None
+        return records
+
 
 CONF_MAX_UNIT_LABELS = 63
 

@@ -379,6 +379,34 @@ class DeepSpeech(nn.Module):
         probs = self.posteriors_long(spect, window, overlap, batch_size)
         return spotter.search(probs[None], None, frame_seconds=2.0 * float(self.audio_conf.window_stride))[0]
 
+    def spot_stream(self, spect, keywords, window=2000, overlap=200, batch_size=32, threshold=0.5, max_hits=32, max_lag=None):
+        """Where the keywords were said in ONE recording of any length, while it is being computed: a generator shaped like stream_long.
+        The forward of posteriors_long runs batch by batch (see there for the windows and for what is not claimed about their edges);
+        each window's kept frames go, in time order, into one decoders.KeywordStream (see there for max_lag and for what is not
+        measured about it).  After each batch it yields {"detections": the records, as spot_long gives them, that became final in this
+        step, each in exactly one item, "tentative": the detections on the frames so far that a later frame may still replace,
+        "frames", "seconds": the output frames consumed and their time, "final": False}; the last item, after the stream's finish(),
+        has "final": True and no tentative record.  Without max_lag the "detections" of all items together are spot_long's records.
+        The model is left in eval mode."""
+        from ..decoders import KeywordSpotter
+        stream = KeywordSpotter(self.labels, keywords, threshold=threshold, max_hits=max_hits).open_stream(max_lag=max_lag)
+        return self._spot_stream(stream, spect, window, overlap, batch_size)
+
+    def _spot_stream(self, stream, spect, window, overlap, batch_size):
+        fs = 2.0 * float(self.audio_conf.window_stride)
+        plain = lambda recs, final: [{k: v for k, v in r.items() if k != "final"} for r in recs if r["final"] == final]
+        for chunk, out, _ in self._long_batches("spot_stream", spect, window, overlap, batch_size):
+            kept = [n for n, w in enumerate(chunk) if w[4] > w[3]]      # (a short last window may keep no frame)
+            done = []
+            for n in kept:
+                recs = stream.feed(out[n, chunk[n][3]:chunk[n][4]], frame_seconds=fs)[0]
+                done += plain(recs, True)
+            if kept:
+                yield {"detections": done, "tentative": plain(recs, False), "frames": stream.frames[0], "seconds": stream.frames[0] * fs,
+                       "final": False}
+        recs = stream.finish(frame_seconds=fs)[0]
+        yield {"detections": plain(recs, True), "tentative": [], "frames": stream.frames[0], "seconds": stream.frames[0] * fs, "final": True}
+
     # -- transcription with times (no counterpart in the reference) -------------------------------
     def transcribe(self, inputs, input_sizes, decoder=None):
         """The text of each utterance with word times: the eval-mode forward, then `decoder or self.decoder or GreedyDecoder(labels)`

@@ -1628,6 +1628,83 @@ def ctc_keyword_search(x: Tensor, kw_labels: Tensor, kw_off: Tensor, kw_lens: Te
     return fscore, fstart, hstart, hend, hscore, nhits
 
 
+KWS_MAX_PENDING = 65536
+
+
+def ctc_kws_stream_state(B: int, K: int, pending: int, dev) -> Tensor:
+    """The state of B freshly opened keyword streams of K keywords for ctc_kws_stream_feed: zero bytes on dev
+    (ds2_ctc_kws_stream_state_bytes: 4 * (264 + 3 * pending) per utterance and keyword)."""
+    if not (_is_int(B, 1) and _is_int(K, 1) and _is_int(pending, 1, KWS_MAX_PENDING)):
+        raise ValueError(f"ctc_kws_stream_state: B and K must be positive integers and pending one in [1, {KWS_MAX_PENDING}], "
+                         f"got {B!r}, {K!r}, {pending!r}")
+    n = _lib.load().ds2_ctc_kws_stream_state_bytes(int(B), int(K), int(pending))
+    if n == 0:
+        raise ValueError(f"ctc_kws_stream_state: {B} utterances x {K} keywords outside the supported sizes")
+    return torch.zeros(n, dtype=torch.uint8, device=dev)
+
+
+def ctc_kws_stream_feed(probs: Tensor | None, sizes: Tensor | None, state: Tensor, kw_labels: Tensor, kw_off: Tensor, kw_lens: Tensor,
+                        max_kw_len: int, thr: Tensor, pending: int, frames_bound: int, is_log: bool = False, max_hits: int = 32,
+                        max_lag: int | None = None, finish: bool = False, return_frames: bool = False, classes: int | None = None,
+                        batch: int | None = None):
+    """One chunk of frames into B running keyword searches (contract: include/ds2hip.h, ds2_ctc_kws_stream_feed_f32): probs (B,T,C) fp32
+    on the GPU (any batch / frame strides, classes contiguous), or None for a call without frames (`classes` and `batch` then give C and
+    B): a flush with finish=True, a second look at the tentative detections without.  sizes (B) the chunk's valid frames per utterance,
+    any integer dtype and device, or None; state as ctc_kws_stream_state made it for (B, K, pending); the packed keywords and thr as
+    ctc_keyword_search takes them.  The keywords, thr, pending and max_lag must not change within a stream.  frames_bound: an upper bound
+    of the frames consumed so far.  max_lag: the most frames the tail may lie behind the frames consumed after a feed (None: no limit, and the stream's detections
+    are exactly the one-call search's).  -> (hit_start, hit_end (B,K,max_hits) i32, hit_score (B,K,max_hits) f32, hit_final
+    (B,K,max_hits) i32, n_hits, tail, frames, forced, dropped (B,K) i32, frame_score (B,K,T) f32 and frame_start (B,K,T) i32 or None,
+    None without return_frames), all on the GPU, frames absolute.  Two launches for the lattice, one for the pick, on the current
+    stream; nothing is copied back."""
+    who = "ctc_kws_stream_feed"
+    if not all(torch.is_tensor(t) for t in (state, kw_labels, kw_off, kw_lens, thr)):
+        raise ValueError(f"{who}: state, kw_labels, kw_off, kw_lens and thr must be tensors")
+    if not 0 <= int(max_kw_len) <= KWS_MAX_LEN:
+        raise ValueError(f"{who}: max_kw_len must lie in [0, {KWS_MAX_LEN}] (one wavefront holds a keyword), got {max_kw_len}")
+    if not _is_int(max_hits, 1, KWS_MAX_HITS):
+        raise ValueError(f"{who}: max_hits must lie in [1, {KWS_MAX_HITS}], got {max_hits}")
+    if not _is_int(pending, 1, KWS_MAX_PENDING):
+        raise ValueError(f"{who}: pending must lie in [1, {KWS_MAX_PENDING}], got {pending}")
+    if max_lag is not None and not _is_int(max_lag, 0, 0x7fffffff):
+        raise ValueError(f"{who}: max_lag must be None or an integer >= 0, got {max_lag!r}")
+    dev = state.device
+    if probs is None:
+        if classes is None or batch is None:
+            raise ValueError(f"{who}: a call without probs needs the number of classes and the batch")
+        B, T, Cc, ld_b, ld_t = int(batch), 0, int(classes), 1, 1
+    else:
+        B, T, Cc, pdev, ld_b, ld_t = _posteriors(who, probs)
+        if pdev != dev:
+            raise ValueError(f"{who}: probs on {pdev}, the state on {dev}")
+    K = kw_lens.numel()
+    if K < 1 or kw_off.numel() != K or thr.numel() != K:
+        raise ValueError(f"{who}: {kw_off.numel()} offsets / {K} lengths / {thr.numel()} thresholds (one each per keyword, at least one)")
+    _chk_on_dev(who, dev, torch.uint8, dict(state=state))
+    _chk_on_dev(who, dev, torch.int32, dict(kw_labels=kw_labels, kw_off=kw_off, kw_lens=kw_lens))
+    _chk_on_dev(who, dev, torch.float32, dict(thr=thr))
+    if int(frames_bound) < 0 or int(frames_bound) + T > 0x7fffffff:
+        raise ValueError(f"{who}: {frames_bound} frames so far + {T} now pass 2^31 - 1")
+    sizes = _sizes_i32(sizes, B, dev)
+    max_hits = int(max_hits)
+    hits = torch.empty((4, B, K, max_hits), dtype=torch.int32, device=dev)
+    tail = torch.empty((5, B, K), dtype=torch.int32, device=dev)
+    fscore = torch.empty((B, K, T), dtype=torch.float32, device=dev) if return_frames else None
+    fstart = torch.empty((B, K, T), dtype=torch.int32, device=dev) if return_frames else None
+    lib = _lib.load()
+    wsb = lib.ds2_ctc_kws_stream_workspace_bytes(B, T, K, 1 if return_frames else 0)
+    ws = _ws(wsb, dev)
+    _lib.check(lib.ds2_ctc_kws_stream_feed_f32(_ptr(probs), ld_b, ld_t, B, T, Cc, 1 if is_log else 0, _ptr(sizes),
+                                               _ptr(kw_labels) if kw_labels.numel() else None, kw_off.data_ptr(), kw_lens.data_ptr(), K,
+                                               int(max_kw_len), thr.data_ptr(), max_hits, -1 if max_lag is None else int(max_lag),
+                                               1 if finish else 0, int(pending), int(frames_bound), state.data_ptr(), state.numel(),
+                                               _ptr(fscore), _ptr(fstart), hits[0].data_ptr(), hits[1].data_ptr(), hits[2].data_ptr(),
+                                               hits[3].data_ptr(), tail[0].data_ptr(), tail[1].data_ptr(), tail[2].data_ptr(),
+                                               tail[3].data_ptr(), tail[4].data_ptr(), ws.data_ptr(), wsb, _stream()),
+               "ds2_ctc_kws_stream_feed_f32")
+    return hits[0], hits[1], hits[2].view(torch.float32), hits[3], tail[0], tail[1], tail[2], tail[3], tail[4], fscore, fstart
+
+
 def segment_max_segs(T: int, min_gap: int, max_len: int) -> int:
     """The most segments ctc_segment can give an utterance of T frames: at most (T + min_gap) // (min_gap + 1) regions (two regions are
     min_gap silent frames and a frame apart, an end's pause may be shorter) and at most T // ((max_len + 1) // 2) forced cuts (a piece

@@ -670,6 +670,72 @@ int ds2_ctc_kws_f32(const float* x, long long ld_b, long long ld_t, int B, int T
                     float* frame_score, int* frame_start, int* hit_start, int* hit_end, float* hit_score, int* n_hits,
                     void* ws, size_t ws_bytes, void* stream);
 
+/* Streaming keyword search: ds2_ctc_kws_f32 fed a chunk of frames at a time, with every detection reported as final as soon as no later
+ * frame can change it (csrc/ctc_kws_stream.h; restated in NumPy by tests/ctc_kws_stream_oracle.py).  The lattice is the same kernel in a
+ * streaming instance; what is new is the rule for when the greedy pick, which is not causal (a later, better candidate kills an earlier
+ * one), has settled.  Memory and time per feed depend on the chunk and on `pending`, not on how long the stream has run; step 4 scans the
+ * list once per lowering of c, so it is quadratic in the candidates pending in the worst case (a chain of candidates that overlap
+ * pairwise: at pending = 65536 about 6.7e7 loads by one wavefront), linear when c cuts no candidate.
+ * State, per (utterance b, keyword k), caller-owned device memory, opaque, written by every feed: the frames consumed n_b; the value and
+ *  start frame of the keyword's states as the lanes of the lattice kernel hold them (E, O, sE, sO per lane), start frames ABSOLUTE,
+ *  counted from the stream's first frame; the tail c (every frame below it is settled); a pending list of at most `pending` candidates
+ *  (t, start, score), ascending in t; the counters `forced` and `dropped`.  The per-frame arrays are not kept across feeds.  All zero
+ *  bytes is a freshly opened stream (opening is one ds2_memset_async): a frame count of 0 means "initialise, do not load".
+ *  ds2_ctc_kws_stream_state_bytes(B, K, pending) = 4 * B * K * (264 + 3 * pending), or 0 for B, K <= 0, B * K >= 2^31 or pending outside
+ *  [1, 65536].  The keywords, the thresholds, B, C, `pending` and max_lag must not change within a stream: the state does not record
+ *  them, and a state of another stream or one not written by this entry is not detected.
+ * Arguments: x (B,T,C), ld_b, ld_t, is_log as ds2_ctc_kws_f32 takes them, T >= 0 frames in this call (x may be NULL at T == 0);
+ *  in_lens_dev (B) the valid frames of THIS call per utterance (clamped to [0, T]; NULL: T each), 0 leaves the utterance's lattice and
+ *  frame count untouched; the packed keywords and thr_dev exactly as ds2_ctc_kws_f32 takes them; max_hits in [1, 1024]; max_lag: the
+ *  most frames the tail may lie behind n_b after a feed (negative: no limit); finish 0 or 1 (T == 0 with finish == 1 is a pure flush;
+ *  T == 0 with finish == 0 reads the tentative detections out again).  frames_bound: an upper bound of the frames any utterance has
+ *  consumed so far (the sum of the earlier calls' T will do); frames_bound + T > 2^31 - 1 is refused, and the kernel itself never takes
+ *  n_b past 2^31 - 1 (it consumes fewer frames instead).
+ * A feed does, per (b, k):
+ *  1. Lattice.  Frames n_b .. n_b + T_b - 1 run the recurrence of ds2_ctc_kws_f32 (the same cell, tie order, single subtract and single
+ *     add) with t absolute, g being the best-class row of the chunk.  frame_score / frame_start (B,K,T), optional (both NULL or both
+ *     given): chunk-relative in position, absolute in the start values, (-inf, -1) beyond T_b.  Concatenated over the feeds they have
+ *     the BITS of ds2_ctc_kws_f32 on the concatenated frames, for any cuts.
+ *  2. Intake.  Every frame of the chunk whose end-state score is finite and >= thr[k] becomes a candidate (t, start, score).  One whose
+ *     start lies below the tail is dropped and counted in `dropped` (possible only after a forced cut, step 4); one that does not fit
+ *     into the list is dropped and counted.
+ *  3. Horizon.  h = min(n, min over the states q whose value is finite and >= thr[k] of start[q]), after the chunk's last frame.  Every
+ *     emission term d is <= 0 and an fp32 add of a non-positive number never increases a value, so a state below the threshold can
+ *     never again produce a candidate: every candidate of a later feed starts at or after h.
+ *  4. Settle.  c = the largest value in [tail, max(tail, h)] for which no pending candidate has start < c <= t; with finish, c = n.  If
+ *     max_lag >= 0 and n - c > max_lag: c = n - max_lag, `forced` is incremented, and the pending candidates with start < c <= t are
+ *     dropped and counted (a forced cut).
+ *  5. Pick.  The greedy rule of ds2_ctc_kws_f32 (largest score first, a tie to the smaller t, a winner kills every candidate whose
+ *     closed span intersects its own) on the pending candidates with t < c, which are FINAL, then on the rest, which are TENTATIVE,
+ *     into the same max_hits slots.  Candidates on the two sides of c cannot overlap, so the two passes select what one pass would;
+ *     final first means an overflow costs tentative detections before final ones.  hit_start / hit_end (exclusive) / hit_score /
+ *     hit_final (B,K,max_hits) in order of acceptance, absolute frames, unused slots (-1, -1, -inf, 0); n_hits (B,K) the slots
+ *     written, or max_hits + 1 if a live candidate remained; tail = c, frames = n, forced, dropped (B,K), the last two totals of the
+ *     stream.
+ *  6. The candidates with t < c leave the list, and tail = c.
+ * Consequences.  Without max_lag and without an overflow (of the list or of the slots), for ANY cuts of the frames into feeds: the
+ *  detections reported final so far together with the current tentative ones are exactly the detections of ds2_ctc_kws_f32 on the
+ *  frames consumed so far, as a set of (start, end, score bits); a final detection is reported in exactly one feed and never changes.
+ *  Final detections of one keyword never overlap, with or without max_lag.  A forced cut is the only place where a stream may differ
+ *  from the one-call search.  A final detection can be withheld for as long as a path at or above the threshold that began before it
+ *  stays alive; the typical case is the keyword spoken up to its last label but one, then silence, which keeps that path's value.  That
+ *  is what max_lag is for; which max_lag serves real recordings is unmeasured.  A forced cut that falls into the span of a pending
+ *  candidate loses that candidate: it lies at n - max_lag after the feed that forces it, so with feeds of one frame and a path that
+ *  stays alive it moves through every frame, and a withheld detection of more than one frame is dropped, not released.
+ * Workspace: the row g (B * T floats) and, when frame_score is NULL, the two per-frame arrays of the chunk:
+ *  ds2_ctc_kws_stream_workspace_bytes(B, T, K, frames_out) = 4 * B * T * (frames_out ? 1 : 1 + 2 * K); 0 at T == 0 (ws may be NULL).
+ * Launches on `stream`: the g row and the lattice (T > 0 only), then intake / settle / pick as one kernel, one wavefront per (b, k).
+ * Nothing is copied back.  Nonzero return on bad arguments, a short state or a short workspace, before any launch: the state is then
+ * unchanged. */
+size_t ds2_ctc_kws_stream_state_bytes(int B, int K, int pending);
+size_t ds2_ctc_kws_stream_workspace_bytes(int B, int T, int K, int frames_out);
+int ds2_ctc_kws_stream_feed_f32(const float* x, long long ld_b, long long ld_t, int B, int T, int C, int is_log, const int* in_lens_dev,
+                                const int* kw_labels_dev, const int* kw_off_dev, const int* kw_lens_dev, int K, int max_kw_len,
+                                const float* thr_dev, int max_hits, int max_lag, int finish, int pending, long long frames_bound,
+                                void* state, size_t state_bytes, float* frame_score, int* frame_start,
+                                int* hit_start, int* hit_end, float* hit_score, int* hit_final, int* n_hits,
+                                int* tail, int* frames, int* forced, int* dropped, void* ws, size_t ws_bytes, void* stream);
+
 /* softmax over the last dim (eval-mode InferenceBatchSoftmax, modules/blocks.py:59-64) */
 int ds2_softmax_rows_f32(const float* x, int ldx, float* y, int ldy, int rows, int C, void* stream);
 
