@@ -165,6 +165,10 @@ SIGNATURES = {
     "ds2_ctc_beam_stream_nodes_bytes": (sz, [i32, i32, i32]),
     "ds2_ctc_beam_stream_feed_f32": (i32, [vp, i64, i64, i32, i32, i32, vp, i32, i32, i32, f32, vp, sz, i32, i32, i32, f32, f32, vp, vp, sz,
                                            vp, sz, vp, sz, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "ds2_ctc_beam_stream_feed_committed_f32": (i32, [vp, i64, i64, i32, i32, i32, vp, i32, i32, i32, f32, vp, sz, i32, i32, i32, f32, f32, vp,
+                                                     vp, sz, vp, sz, vp, sz, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "ds2_ctc_beam_stream_commit_workspace_bytes": (sz, [i32, i32, i32]),
+    "ds2_ctc_beam_stream_commit": (i32, [vp, sz, i32, i32, i32, i32, vp, sz, i32, vp, sz, i32, vp, i32, vp, vp, vp, vp, vp, sz, vp]),
     "ds2_edit_distance_workspace_bytes": (sz, [i32, i64]),
     "ds2_edit_distance_i32": (i32, [vp, i64, vp, vp, vp, vp, i32, i64, vp, vp, sz, vp]),
     "ds2_edit_align_workspace_bytes": (sz, [i32, i64]),

@@ -356,7 +356,8 @@ struct NoArm {};
 struct StreamArgs {
   char* state;        // B blobs of `stride` bytes: StreamHeader | beam buffer | LmBeams (LM, hotwords) | hotword states
   size_t stride;
-  int cap, n_out, W;  // node storage for `cap` frames per utterance; read-out of n_out slots in rows of W (n_out == 0: none)
+  int cap, n_out, W;  // node storage for `cap` rows of K nodes per utterance (a row per frame until a commit compacts them,
+                      // ctc_beam_commit.h); read-out of n_out slots in rows of W (n_out == 0: none)
   int* stable_len;    // (B)
   int* frames;        // (B)
 };
@@ -365,9 +366,14 @@ struct Streamed {
   Arm arm;
   StreamArgs st;
 };
-struct StreamHeader {   // 64 bytes; all zero = a freshly opened stream
-  int opened, t0, nb, stable_len, stable_node, pad[11];
+// 64 bytes; all zero = a freshly opened stream.  The last four fields belong to the commit kernel (ctc_beam_commit.h) and stay zero in a
+// stream that never commits: the frame t0 + t writes row row_base + t0 + t - frame_base of the node storage (rows below row_base hold
+// the compacted live tree), and the first committed_len (label, offset) pairs of every beam have left the storage for the host
+// (the last of them at frame commit_frame), so a read-out starts at pair committed_len.
+struct StreamHeader {
+  int opened, t0, nb, stable_len, stable_node, row_base, frame_base, committed_len, commit_frame, pad[7];
 };
+static_assert(sizeof(StreamHeader) == 64, "the state blob's header is 64 bytes");
 __device__ inline LmArgs lm_args(const NoArm&) { return LmArgs{}; }
 __device__ inline const void* hot_blob(const NoArm&) { return nullptr; }
 template <class Arm>
@@ -425,18 +431,20 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
   float* c_pb = (float*)(c_cls + PK);
   float* c_pnb = c_pb + PK;
   long long TK = (long long)T * K;
-  if constexpr (STREAM) TK = (long long)st.cap * K;   // node ids t * K + slot count the stream's frames: they do not depend on the capacity
+  if constexpr (STREAM) TK = (long long)st.cap * K;   // node ids row * K + slot do not depend on the capacity
   int* n_parent = nodes + (long long)b * 3 * TK;
   int* n_label = n_parent + TK;
   int* n_frame = n_label + TK;
   int n = sizes ? min(max(sizes[b], 0), T) : T;
   [[maybe_unused]] int t0 = 0;        // frames consumed by earlier calls
   [[maybe_unused]] bool fresh = true;  // no earlier call: the beams start from the empty prefix
+  [[maybe_unused]] int row_shift = 0;  // frame t0 + t writes node row t0 + t + row_shift: 0 in a stream that never committed
   if constexpr (STREAM) {
     const StreamHeader* sh = (const StreamHeader*)(st.state + (size_t)b * st.stride);
     fresh = sh->opened == 0;
     t0 = fresh ? 0 : sh->t0;
-    n = max(min(n, st.cap - t0), 0);   // (the entry has checked the host's bound; a wrong bound must not write past the nodes)
+    row_shift = fresh ? 0 : sh->row_base - sh->frame_base;
+    n = max(min(n, st.cap - (t0 + row_shift)), 0);   // (the entry has checked the host's bound; a wrong bound must not write past the nodes)
   }
   const int R = min(top_n, C);
   ds2lm::LmView lv;
@@ -480,6 +488,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
   }
   if constexpr (STREAM) {
     if (!fresh) stream_load(st, b, L, smem, hd, LM, l0, h0);
+    if (tid == 0) hd->pad1 = row_shift * K;   // kept in LDS, not in a register across the frame loop (pad1 is the profiling build's)
   }
   u64 ticks[4] = {0, 0, 0, 0}, stamp = PROF ? wall_clock64() : 0;
   auto lap = [&](int phase) {
@@ -676,9 +685,11 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
         if constexpr (LM) lm_copy(lm, mo, src, mw, j);
         if constexpr (HOT) hw[j] = ho[src];
       } else {
-        int tg = t;   // the frame's index in the stream
-        if constexpr (STREAM) tg += t0;
-        const int nd = tg * K + j;
+        int tg = t, nd = t * K + j;   // the frame's index in the stream, the node's id
+        if constexpr (STREAM) {
+          tg += t0;
+          nd = tg * K + j + hd->pad1;
+        }
         n_parent[nd] = o.node[src];
         n_label[nd] = cls;
         n_frame[nd] = tg;
@@ -771,14 +782,17 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
   const int nb = hd->nb;
   const Beams f = cur ? b1 : b0;
   int KO = K, TO = T;   // slots per utterance and row width of the outputs
+  [[maybe_unused]] int done = 0;   // (label, offset) pairs the host holds already: a stream's read-out starts there
   if constexpr (STREAM) {
     KO = st.n_out;
     TO = st.W;
+    done = ((const StreamHeader*)(st.state + (size_t)b * st.stride))->committed_len;   // (stream_save has left it as it was)
   }
   int* lab = labels + (long long)b * KO * TO;
   int* off = offsets + (long long)b * KO * TO;
   for (int j = 0; j < KO; ++j) {
-    const int len = j < nb ? f.len[j] : 0;
+    int len = j < nb ? f.len[j] : 0;
+    if constexpr (STREAM) len = max(len - done, 0);   // (a row holds the pairs from the committed length on)
     for (int s = len + tid; s < TO; s += BEAM_THREADS) {
       lab[(long long)j * TO + s] = 0;
       off[(long long)j * TO + s] = 0;
@@ -787,12 +801,20 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
   for (int j = tid; j < KO; j += BEAM_THREADS) {
     if (j < nb) {
       int x = f.node[j];
-      for (int s = f.len[j] - 1; s >= 0; --s) {
-        if (!STREAM || s < TO) {   // (a stream's rows are the caller's width; the entry has checked that it holds every frame)
+      if constexpr (STREAM) {   // (a stream's rows are the caller's width; the entry has checked that it holds every uncommitted pair)
+        for (int s = f.len[j] - 1 - done; s >= 0; --s) {
+          if (s < TO) {
+            lab[(long long)j * TO + s] = n_label[x];
+            off[(long long)j * TO + s] = n_frame[x];
+          }
+          x = n_parent[x];
+        }
+      } else {
+        for (int s = f.len[j] - 1; s >= 0; --s) {
           lab[(long long)j * TO + s] = n_label[x];
           off[(long long)j * TO + s] = n_frame[x];
+          x = n_parent[x];
         }
-        x = n_parent[x];
       }
       lens[b * KO + j] = f.len[j];
       scores[b * KO + j] = f.tot[j];

@@ -16,8 +16,10 @@
 // parent together until every thread holds the same node.  The previous length stays in the state; it is a floor (every live beam
 // descends from beams that shared it), so a call walks the unstable suffix, not the stream.  With no live beam the value is kept.
 //
-// Node storage is the caller's, laid out for `cap` frames per utterance (parent | label | frame, cap * K each); node ids do not depend
-// on cap, so the host grows it between calls by copying each utterance's three arrays into a larger buffer.
+// Node storage is the caller's, laid out for `cap` rows of K nodes per utterance (parent | label | frame, cap * K each); node ids do not
+// depend on cap, so the host grows it between calls by copying each utterance's three arrays into a larger buffer.  A frame writes the
+// row of its index until a commit (ctc_beam_commit.h) compacts the rows to the live tree: then frame t0 + t writes row row_base + t0 + t
+// - frame_base, and a read-out starts at the pair committed_len (all zero in a stream that never commits).
 #pragma once
 #ifndef DS2_CTC_BEAM_TU
 #error "ctc_beam_stream.h defines the ds2_ctc_beam_stream_* entry points: it is compiled once, as part of decode.hip, after ctc_beam.h"
@@ -113,18 +115,19 @@ extern "C" size_t ds2_ctc_beam_stream_nodes_bytes(int B, int cap_frames, int bea
   return ds2_ctc_beam_workspace_bytes(B, cap_frames, beam_width);
 }
 
-extern "C" int ds2_ctc_beam_stream_feed_f32(const float* probs, long long ld_b, long long ld_t, int B, int T, int C, const int* sizes_dev,
-                                            int blank, int beam_width, int cutoff_top_n, float cutoff_prob, const void* lm_dev,
-                                            size_t lm_bytes, int lm_order, int lm_mode, int space, float alpha, float beta,
-                                            const void* hot_dev, const void* hot_host, size_t hot_bytes, void* state, size_t state_bytes,
-                                            void* nodes, size_t nodes_bytes, int cap_frames, int frames_bound, int n_out, int W,
-                                            int* labels, int* offsets, int* lens, float* scores, int* stable_len, int* frames,
-                                            void* stream) {
-  const char* who = "ds2_ctc_beam_stream_feed_f32";
+// The two feed entries.  A stream that never committed counts its node rows in frames (cap_frames, frames_bound) and a read-out row holds
+// every frame; a committed stream (ctc_beam_commit.h) counts rows (cap_frames and frames_bound are then cap_rows and rows_bound) and a
+// read-out row holds the uncommitted labels, of which the host knows the bound labels_bound (< 0: the uncommitted entry).
+static int stream_feed(const char* who, const float* probs, long long ld_b, long long ld_t, int B, int T, int C, const int* sizes_dev, int blank,
+                       int beam_width, int cutoff_top_n, float cutoff_prob, const void* lm_dev, size_t lm_bytes, int lm_order, int lm_mode,
+                       int space, float alpha, float beta, const void* hot_dev, const void* hot_host, size_t hot_bytes, void* state,
+                       size_t state_bytes, void* nodes, size_t nodes_bytes, int cap_frames, int frames_bound, int labels_bound, int n_out, int W,
+                       int* labels, int* offsets, int* lens, float* scores, int* stable_len, int* frames, void* stream) {
+  const bool committed = labels_bound >= 0;
   DS2_REQUIRE(state && nodes && stable_len && frames && (T == 0 || probs) && (n_out <= 0 || (labels && offsets && lens && scores)),
               "%s: null pointer", who);
-  DS2_REQUIRE(T >= 0 && frames_bound >= 0 && cap_frames >= 1, "%s: bad dims (T=%d, %d frames so far, node capacity %d frames)", who, T,
-              frames_bound, cap_frames);
+  DS2_REQUIRE(T >= 0 && frames_bound >= 0 && cap_frames >= 1, "%s: bad dims (T=%d, %d %s so far, node capacity %d %s)", who, T,
+              frames_bound, committed ? "rows" : "frames", cap_frames, committed ? "rows" : "frames");
   DS2_REQUIRE(T > 0 || n_out > 0, "%s: no frames and no read-out (T = 0 and n_out = 0): nothing to do", who);
   DS2_REQUIRE((long long)frames_bound + T <= cap_frames, "%s: node buffer too small: capacity %d frames, %d so far + %d now", who, cap_frames,
               frames_bound, T);
@@ -138,7 +141,11 @@ extern "C" int ds2_ctc_beam_stream_feed_f32(const float* probs, long long ld_b, 
                           n_out > 0 ? lens : out_or, n_out > 0 ? scores : (float*)state, nodes, nodes_bytes)) return rc;
   const int K = beam_width;
   DS2_REQUIRE(n_out >= 0 && n_out <= K, "%s: n_out %d outside 0..beam_width (%d)", who, n_out, K);
-  DS2_REQUIRE(n_out == 0 || W >= frames_bound + T, "%s: rows of W = %d labels cannot hold %d frames so far + %d now", who, W, frames_bound, T);
+  if (committed)
+    DS2_REQUIRE(n_out == 0 || (long long)W >= (long long)labels_bound + T, "%s: rows of W = %d labels cannot hold %d uncommitted labels + %d frames now",
+                who, W, labels_bound, T);
+  else
+    DS2_REQUIRE(n_out == 0 || W >= frames_bound + T, "%s: rows of W = %d labels cannot hold %d frames so far + %d now", who, W, frames_bound, T);
   const bool hot = hot_dev != nullptr, lm = lm_dev != nullptr;
   DS2_REQUIRE(state_bytes >= ds2_ctc_beam_stream_state_bytes(B, K, lm, hot), "%s: state too small: %zu bytes, %zu needed", who, state_bytes,
               ds2_ctc_beam_stream_state_bytes(B, K, lm, hot));
@@ -183,4 +190,30 @@ extern "C" int ds2_ctc_beam_stream_feed_f32(const float* probs, long long ld_b, 
                                                                        sizes_dev, blank, K, cutoff_top_n, cutoff_prob, PC, PK, HT, labels,
                                                                        offsets, lens, scores, (int*)nodes, nullptr,
                                                                        Streamed<HotArgs>{HotArgs{la, hot_dev}, sa});
+}
+
+extern "C" int ds2_ctc_beam_stream_feed_f32(const float* probs, long long ld_b, long long ld_t, int B, int T, int C, const int* sizes_dev,
+                                            int blank, int beam_width, int cutoff_top_n, float cutoff_prob, const void* lm_dev,
+                                            size_t lm_bytes, int lm_order, int lm_mode, int space, float alpha, float beta,
+                                            const void* hot_dev, const void* hot_host, size_t hot_bytes, void* state, size_t state_bytes,
+                                            void* nodes, size_t nodes_bytes, int cap_frames, int frames_bound, int n_out, int W,
+                                            int* labels, int* offsets, int* lens, float* scores, int* stable_len, int* frames,
+                                            void* stream) {
+  return stream_feed("ds2_ctc_beam_stream_feed_f32", probs, ld_b, ld_t, B, T, C, sizes_dev, blank, beam_width, cutoff_top_n, cutoff_prob, lm_dev,
+                     lm_bytes, lm_order, lm_mode, space, alpha, beta, hot_dev, hot_host, hot_bytes, state, state_bytes, nodes, nodes_bytes,
+                     cap_frames, frames_bound, -1, n_out, W, labels, offsets, lens, scores, stable_len, frames, stream);
+}
+
+extern "C" int ds2_ctc_beam_stream_feed_committed_f32(const float* probs, long long ld_b, long long ld_t, int B, int T, int C,
+                                                      const int* sizes_dev, int blank, int beam_width, int cutoff_top_n, float cutoff_prob,
+                                                      const void* lm_dev, size_t lm_bytes, int lm_order, int lm_mode, int space, float alpha,
+                                                      float beta, const void* hot_dev, const void* hot_host, size_t hot_bytes, void* state,
+                                                      size_t state_bytes, void* nodes, size_t nodes_bytes, int cap_rows, int rows_bound,
+                                                      int labels_bound, int n_out, int W, int* labels, int* offsets, int* lens, float* scores,
+                                                      int* stable_len, int* frames, void* stream) {
+  const char* who = "ds2_ctc_beam_stream_feed_committed_f32";
+  DS2_REQUIRE(labels_bound >= 0, "%s: labels_bound %d is negative", who, labels_bound);
+  return stream_feed(who, probs, ld_b, ld_t, B, T, C, sizes_dev, blank, beam_width, cutoff_top_n, cutoff_prob, lm_dev, lm_bytes, lm_order, lm_mode,
+                     space, alpha, beta, hot_dev, hot_host, hot_bytes, state, state_bytes, nodes, nodes_bytes, cap_rows, rows_bound, labels_bound,
+                     n_out, W, labels, offsets, lens, scores, stable_len, frames, stream);
 }

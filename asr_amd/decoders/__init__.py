@@ -429,12 +429,15 @@ class BeamCTCDecoder(Decoder):
         self.last_scores = host[2 * n + B * K:].view(torch.float32).view(B, K).clone()
         return self.convert_to_strings(labels_h, lens_h), self.convert_tensor(offs_h, lens_h)
 
-    def open_stream(self, batch=1, nbest=1, capacity=256):
+    def open_stream(self, batch=1, nbest=1, capacity=256, commit=False, commit_every=None, max_lag=None):
         """A BeamStream over `batch` utterances that are fed chunk by chunk (see there).  The stream keeps the settings the decoder has
         now: width, cut-offs, language model, alpha / beta, hotwords; changing them on the decoder later leaves an open stream as it
-        is.  nbest: how many hypotheses a partial result lists (at most beam_width).  capacity: the frames the back-pointer storage
-        holds at first; it doubles when a feed needs more."""
-        return BeamStream(self, batch, nbest, capacity)
+        is.  nbest: how many hypotheses a partial result lists (at most beam_width).  capacity: the frames (with commit: the rows of
+        beam_width nodes) the back-pointer storage holds at first; it doubles when a feed needs more.  commit=True: the stream commits
+        its stable prefix to the host and compacts its back-pointers to the live tree, before a feed that does not fit and every
+        commit_every frames (default: capacity); results keep decode()'s bits.  max_lag (frames; needs commit=True): at a commit, the
+        best hypothesis decides the text older than max_lag frames (a forced cut: the one place a stream may differ from decode())."""
+        return BeamStream(self, batch, nbest, capacity, commit, commit_every, max_lag)
 
 
 def stream_capacity(capacity, need):
@@ -445,19 +448,63 @@ def stream_capacity(capacity, need):
     return capacity
 
 
+def commit_due(capacity, rows, chunk, since, commit_every):
+    """BeamStream's commit plan, first half: a committing stream whose storage holds `capacity` rows, of which at most `rows` are in
+    use, commits before a feed of `chunk` frames when the chunk does not fit, or when `since` >= commit_every frames were fed since the
+    last commit."""
+    return int(rows) + int(chunk) > int(capacity) or int(since) >= int(commit_every)
+
+
+def commit_capacity(capacity, live_nodes, beam_width, chunk):
+    """BeamStream's commit plan, second half: after a commit that left live_nodes[b] nodes per utterance -> (rows in use: the fullest
+    utterance's ceil(M / beam_width), the capacity in rows that holds them and the next `chunk` frames, by stream_capacity's doubling)."""
+    K = int(beam_width)
+    rows = max((int(m) + K - 1) // K for m in live_nodes)
+    return rows, stream_capacity(capacity, rows + int(chunk))
+
+
 class BeamStream:
     """A running beam search over `batch` utterances (BeamCTCDecoder.open_stream): feed() consumes posteriors chunk by chunk and
     returns the best text so far and how much of it is final; finish() returns what BeamCTCDecoder.decode() returns for the
     concatenated frames, with the same bits, whatever the cuts.  The search's state (the beams of the kernel, with the language model's
     and the hotwords' per-beam state) lives on the device between calls (`ds2_ctc_beam_stream_feed_f32`, contract in
-    include/ds2hip.h), and so do the back-pointers: 12 * beam_width bytes per frame and utterance, never compacted (216 MB for an
-    hour at width 100), in storage that doubles when a feed needs more.  A partial result copies nbest rows of the stream's length to
-    the host, so the partials of a long stream cost more as it grows; feed(..., partial=False) copies nothing.
-    `frames`: the frames consumed per utterance; `closed`: finish() has run.
-    NOT MEASURED: how far the stable prefix lags the best hypothesis on real recordings."""
+    include/ds2hip.h), and so do the back-pointers: 12 * beam_width bytes per frame and utterance (216 MB for an hour at width 100), in
+    storage that doubles when a feed needs more.  Without commit=True nothing compacts them, and a partial result copies nbest rows
+    of the stream's length to the host, so the partials of a long stream cost more as it grows; feed(..., partial=False) copies nothing.
 
-    def __init__(self, decoder, batch=1, nbest=1, capacity=256):
+    commit=True bounds both by what is still undecided.  Before a feed whose chunk does not fit the storage, and at the latest
+    every commit_every frames (default: capacity), one launch (`ds2_ctc_beam_stream_commit`, csrc/ctc_beam_commit.h) writes the stable
+    (label, offset) pairs that have not left yet to the host (`committed[b]`: (labels, offsets), the text every later result starts
+    with) and renumbers the LIVE TREE, the chains from the live beams down to the last committed pair, into the front of a fresh
+    buffer; one device-to-host copy brings the pairs and the tree's size (`live_nodes[b]`).  The storage (`capacity`, in rows of
+    beam_width nodes) doubles only when live tree + chunk still do not fit; read-outs are sized by the uncommitted labels, not by the
+    stream.  Records and finish() are those of an uncommitted stream, bit for bit: node ids never enter the search's arithmetic.
+    That is exact, and it bounds memory whenever the tree is small: over silence it is a handful of nodes, but a full beam of peaked
+    frames can keep an early low-margin alternative alive for as long as the stream runs, and then the tree grows with it.
+    max_lag (frames) is the stated bound for that case: at a commit, the first slot of the search decides the text older than max_lag
+    frames, beams that disagree are dropped (`forced[b]` counts the commits at which one was), and every node older than the cut
+    leaves.  With max_lag a result may differ from decode(); without it, it never does.  `commits`: commit launches so far.
+
+    finish(index) ends ONE utterance of the batch: decode()'s result for its frames so far, and its slot reopened for the next call.
+    `frames`: the frames consumed per utterance; `closed`: finish() has run.
+    Limits that remain: 2^20 - 1 labels per utterance between two finish(index) (the length field of the candidate key); fp32
+    totals are absolute, not rebased, so their resolution falls as a stream's total grows.
+    NOT MEASURED: how far the stable prefix lags the best hypothesis on real recordings; what max_lag costs in WER; how large the live
+    tree gets on real recordings at width 100."""
+
+    def __init__(self, decoder, batch=1, nbest=1, capacity=256, commit=False, commit_every=None, max_lag=None):
         from ..ops import _is_int
+        for name, v in (("commit_every", commit_every), ("max_lag", max_lag)):
+            if v is None:
+                continue
+            try:
+                ok = _is_int(v, 1)
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError(f"BeamStream: {name} must be a positive integer number of frames, got {v!r}")
+            if not commit:
+                raise ValueError(f"BeamStream: {name} needs commit=True")
         if not _is_int(batch, 1):
             raise ValueError(f"BeamStream: batch must be a positive integer, got {batch!r}")
         if not _is_int(nbest, 1, decoder.beam_width):
@@ -470,6 +517,13 @@ class BeamStream:
         self.C, self.frames, self.closed = None, [0] * self.batch, False
         self.capacity, self._first_capacity = 0, int(capacity)
         self._state = self._nodes = None
+        self.commit = bool(commit)
+        self.commit_every = None if not commit else int(commit_every) if commit_every is not None else int(capacity)
+        self.max_lag = None if max_lag is None else int(max_lag)
+        self.commits, self.live_nodes, self.forced = 0, [0] * self.batch, [0] * self.batch
+        self.committed = [([], []) for _ in range(self.batch)]      # per utterance: the labels and offsets that left the device
+        self._commit_frame = [0] * self.batch                       # the frame of each utterance's last committed pair
+        self._rows, self._lab, self._since = [0] * self.batch, [0] * self.batch, 0   # bounds: rows in use, uncommitted labels; frames since
 
     def check_feed(self, probs, sizes=None):
         """The host half of feed(), before any device call: refuses a closed stream, a shape that is not (batch, T, C) (or (T, C) with
@@ -511,12 +565,77 @@ class BeamStream:
             self._nodes = ops.ctc_beam_stream_nodes(self.batch, cap, K, dev, self._nodes, self.capacity)
             self.capacity = cap
 
-    def _call(self, probs, sizes, n_out, dev):
+    def _commit(self, dev, chunk):
+        """one commit launch and one device-to-host copy; then the storage grows if the live tree and `chunk` frames do not fit"""
         from .. import ops
-        bound = max(self.frames)
-        self._device_state(dev, bound + (0 if probs is None else probs.size(1)))
-        return ops.ctc_beam_stream_feed(probs, sizes, self._state, self._nodes, self.capacity, bound, n_out,
-                                        classes=self.C if self.C is not None else len(self.decoder.labels), **self.search)
+        K, B = self.search["beam_width"], self.batch
+        cut = None
+        if self.max_lag is not None:
+            cut = torch.tensor([f - self.max_lag for f in self.frames], dtype=torch.int32).to(dev)   # (< 0: no cut yet)
+        width = max(self._lab)
+        fresh = ops.ctc_beam_stream_nodes(B, self.capacity, K, dev)
+        packed = ops.ctc_beam_stream_commit(self._state, self._nodes, self.capacity, fresh, self.capacity, K, self.search["lm"],
+                                            self.search["hotwords"], width, cut)[4]
+        info, dropped, labels, offs = ops.commit_unpack(packed.cpu(), B, width)
+        self._nodes = fresh
+        for b in range(B):
+            n = int(info[b, 0])
+            self.committed[b][0].extend(labels[b, :n].tolist())
+            self.committed[b][1].extend(offs[b, :n].tolist())
+            self.live_nodes[b], self._lab[b], self._commit_frame[b] = int(info[b, 1]), int(info[b, 2]), int(info[b, 3])
+            self.forced[b] += int(dropped[b]) > 0
+        self.commits += 1
+        self._since = 0
+        rows, cap = commit_capacity(self.capacity, self.live_nodes, K, chunk)
+        self._rows = [(m + K - 1) // K for m in self.live_nodes]
+        if cap != self.capacity:
+            self._nodes = ops.ctc_beam_stream_nodes(B, cap, K, dev, self._nodes, self.capacity)
+            self.capacity = cap
+
+    def _call(self, probs, sizes, n_out, dev, index=None):
+        """one feed launch (probs None: a pure read-out; index: of that utterance alone, through views of its state and nodes)"""
+        from .. import ops
+        T = 0 if probs is None else probs.size(1)
+        classes = self.C if self.C is not None else len(self.decoder.labels)
+        if not self.commit:
+            bound = max(self.frames) if index is None else self.frames[index]
+            self._device_state(dev, max(self.frames) + T)
+            state, nodes = self._slot(index)
+            return ops.ctc_beam_stream_feed(probs, sizes, state, nodes, self.capacity, bound, n_out, classes=classes, **self.search)
+        if self._nodes is not None and T and commit_due(self.capacity, max(self._rows), T, self._since, self.commit_every):
+            self._commit(dev, T)
+        self._device_state(dev, max(self._rows) + T)      # (the first feed, or a chunk the doubling has yet to make room for)
+        state, nodes = self._slot(index)
+        rows, lab = (max(self._rows), max(self._lab)) if index is None else (self._rows[index], self._lab[index])
+        out = ops.ctc_beam_stream_feed_committed(probs, sizes, state, nodes, self.capacity, rows, lab, n_out, classes=classes, **self.search)
+        self._rows, self._lab, self._since = [r + T for r in self._rows], [n + T for n in self._lab], self._since + T
+        return out
+
+    def _slot(self, index):
+        """the state and the nodes of the whole batch, or contiguous views of one utterance's"""
+        if index is None:
+            return self._state, self._nodes
+        stride = self._state.numel() // self.batch
+        return self._state[index * stride:(index + 1) * stride], self._nodes[index:index + 1]
+
+    def _join(self, b, labels, offs, lens, scores):
+        """utterance b's read-out rows (n_out, W) of a committing stream -> full rows: the committed pairs, then the read-out's.  A slot
+        past the surviving beams stays empty, as decode() leaves it."""
+        head_l, head_o = self.committed[b]
+        n = len(head_l)
+        if n == 0:
+            return labels, offs
+        alive = ((lens >= n) & (scores > -math.inf)).to(labels.dtype)[:, None]      # (n_out, 1)
+        return (torch.cat((torch.tensor(head_l, dtype=labels.dtype)[None] * alive, labels * alive), 1),
+                torch.cat((torch.tensor(head_o, dtype=offs.dtype)[None] * alive, offs * alive), 1))
+
+    def _joined(self, labels, offs, lens, scores, only=None):
+        """the download of a read-out -> per utterance rows that start at the utterance's first label (lists over the batch)"""
+        ids = range(self.batch) if only is None else [only]
+        if not self.commit:
+            return [labels[i] for i in range(len(ids))], [offs[i] for i in range(len(ids))]
+        pairs = [self._join(b, labels[i], offs[i], lens[i], scores[i]) for i, b in enumerate(ids)]
+        return [p[0] for p in pairs], [p[1] for p in pairs]
 
     def _download(self, out, dev):
         """one device-to-host copy of a read-out -> labels, offsets (B, n_out, W), lens (B, n_out), scores (B, n_out) fp32, stable (B)"""
@@ -549,6 +668,7 @@ class BeamStream:
         if not partial:
             return None
         labels, offs, lens, scores, stable = self._download(out, dev)
+        labels, offs = self._joined(labels, offs, lens, scores)
         strings, offsets = self.decoder.convert_to_strings(labels, lens), self.decoder.convert_tensor(offs, lens)
         records = []
         for b in range(self.batch):
@@ -559,19 +679,39 @@ class BeamStream:
             records.append(rec)
         return records
 
-    def finish(self):
+    def finish(self, index=None):
         """Ends the stream -> (strings[b][k], offsets[b][k]) with beam_width entries per utterance, as BeamCTCDecoder.decode() returns
         them for the concatenated frames; the decoder's `last_scores` are set as decode() sets them.  A stream that was never fed
-        gives decode()'s result for utterances of 0 frames.  A later feed() raises ValueError."""
+        gives decode()'s result for utterances of 0 frames.  A later feed() raises ValueError.
+        finish(index) ends utterance `index` alone -> (strings[k], offsets[k], scores (beam_width) fp32): decode()'s result for its
+        frames so far, read out and copied to the host for that utterance only.  Its slot is reopened (its state zeroed, frames[index]
+        = 0, its committed text cleared): the next frames fed to it start a new utterance.  The other utterances are untouched, the
+        stream stays open and the decoder's last_scores are left alone."""
         if self.closed:
             raise ValueError("BeamStream.finish: the stream is closed already")
+        if index is not None:
+            from ..ops import _is_int
+            try:
+                ok = _is_int(index, 0, self.batch - 1)
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError(f"BeamStream.finish: index must be an integer in 0..{self.batch - 1}, got {index!r}")
+            index = int(index)
         dev = self._state.device if self._state is not None else _device("BeamStream", ".finish")
-        out = self._call(None, None, self.search["beam_width"], dev)
+        out = self._call(None, None, self.search["beam_width"], dev, index)
         labels, offs, lens, scores, _ = self._download(out, dev)
+        labels, offs = self._joined(labels, offs, lens, scores, index)
+        strings, offsets = self.decoder.convert_to_strings(labels, lens), self.decoder.convert_tensor(offs, lens)
+        if index is not None:
+            self._slot(index)[0].zero_()
+            self.frames[index] = self.live_nodes[index] = self._rows[index] = self._lab[index] = self._commit_frame[index] = 0
+            self.committed[index] = ([], [])
+            return strings[0], offsets[0], scores[0]
         self.closed = True
         self._state = self._nodes = None
         self.decoder.last_scores = scores
-        return self.decoder.convert_to_strings(labels, lens), self.decoder.convert_tensor(offs, lens)
+        return strings, offsets
 
 
 def _reference_strings(references):

@@ -310,7 +310,7 @@ class DeepSpeech(nn.Module):
                 out, _ = self.forward(x, torch.tensor([w[1] for w in chunk], dtype=torch.int32))
             yield chunk, out, (spect.size(1) - 1) // 2 + 1
 
-    def stream_long(self, spect, window=2000, overlap=200, batch_size=32, decoder=None):
+    def stream_long(self, spect, window=2000, overlap=200, batch_size=32, decoder=None, commit=False, max_lag=None):
         """The text of ONE recording of any length while it is being computed: a generator.  The forward of posteriors_long runs batch
         by batch (see there for the windows and for what is not claimed about their edges); each window's kept frames go, in time
         order, into one decoders.BeamStream of `decoder or self.decoder`, which must be a BeamCTCDecoder (TypeError otherwise; there is
@@ -319,13 +319,14 @@ class DeepSpeech(nn.Module):
         the output frames consumed and their time, "final": False}; the last item has "final": True, the text BeamCTCDecoder.decode()
         gives for posteriors_long's result, and "words": [(word, start, end, start_s, end_s)] as transcribe() gives them.  The
         starvation check of evaluate() runs with every item.  NOT MEASURED: whether this lowers WER against the segmented
-        transcribe_long with a language model, and how far "stable_text" lags "text" on real recordings.  The model is left in eval
-        mode."""
+        transcribe_long with a language model, and how far "stable_text" lags "text" on real recordings.  commit / max_lag go to
+        BeamCTCDecoder.open_stream (see BeamStream): commit=True keeps the search's memory to its live tree and yields the same
+        items; max_lag (frames) forces the text older than that, and then items may differ.  The model is left in eval mode."""
         from ..decoders import BeamCTCDecoder
         dec = decoder or self.decoder
         if not isinstance(dec, BeamCTCDecoder):
             raise TypeError(f"stream_long: needs a BeamCTCDecoder (given or self.decoder), got {type(dec).__name__}")
-        return self._stream_long(dec.open_stream(), spect, window, overlap, batch_size)
+        return self._stream_long(dec.open_stream(commit=commit, max_lag=max_lag), spect, window, overlap, batch_size)
 
     def _stream_long(self, stream, spect, window, overlap, batch_size):
         from ..decoders import words_from_offsets

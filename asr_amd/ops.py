@@ -1868,7 +1868,28 @@ def ctc_beam_stream_feed(probs: Tensor | None, sizes: Tensor | None, state: Tens
     lengths (B,n_out) i32, scores (B,n_out) fp32, stable_len (B) i32, frames (B) i32), all on the GPU, W = max(frames_bound + T, 1); the
     first four are None when n_out == 0.  A read-out has the bits of ctc_beam_decode on the frames so far; stable_len labels and offsets
     of every beam are final.  One launch on the current stream, nothing is copied back."""
-    who = "ctc_beam_stream_feed"
+    return _beam_stream_feed("ctc_beam_stream_feed", probs, sizes, state, nodes, cap_frames, frames_bound, None, n_out, blank, beam_width,
+                             cutoff_top_n, cutoff_prob, lm, alpha, beta, hotwords, classes)
+
+
+def ctc_beam_stream_feed_committed(probs: Tensor | None, sizes: Tensor | None, state: Tensor, nodes: Tensor, cap_rows: int, rows_bound: int,
+                                   labels_bound: int, n_out: int, blank: int = 0, beam_width: int = 100, cutoff_top_n: int = 40,
+                                   cutoff_prob: float = 1.0, lm=None, alpha: float = 0.0, beta: float = 0.0, hotwords=None,
+                                   classes: int | None = None):
+    """ctc_beam_stream_feed for a state that ctc_beam_stream_commit has compacted (contract: include/ds2hip.h,
+    ds2_ctc_beam_stream_feed_committed_f32): the node capacity and rows_bound count rows of beam_width nodes (rows_bound: at least
+    ceil(M / beam_width) of the last commit plus the frames fed since, for every utterance), and the read-out rows hold the pairs from
+    each utterance's committed length on, in rows of W = max(labels_bound + T, 1) (labels_bound: at least the last commit's info[b][2]
+    plus the frames fed since); lengths, scores and stable_len stay absolute.  Same outputs as ctc_beam_stream_feed."""
+    if not _is_int(labels_bound, 0, 0x7fffffff):
+        raise ValueError(f"ctc_beam_stream_feed_committed: labels_bound must be a non-negative integer, got {labels_bound!r}")
+    return _beam_stream_feed("ctc_beam_stream_feed_committed", probs, sizes, state, nodes, cap_rows, rows_bound, int(labels_bound), n_out,
+                             blank, beam_width, cutoff_top_n, cutoff_prob, lm, alpha, beta, hotwords, classes)
+
+
+def _beam_stream_feed(who, probs, sizes, state, nodes, cap, bound, labels_bound, n_out, blank, beam_width, cutoff_top_n, cutoff_prob, lm, alpha,
+                      beta, hotwords, classes):
+    """The host path of the two feed entries: labels_bound None is the uncommitted one, whose read-out rows hold every frame"""
     lib = _lib.load()
     dev = state.device
     if probs is None:
@@ -1885,7 +1906,7 @@ def ctc_beam_stream_feed(probs: Tensor | None, sizes: Tensor | None, state: Tens
     _chk_on_dev(who, dev, torch.uint8, {"state": state})
     _chk_on_dev(who, dev, torch.int32, {"nodes": nodes})
     sizes = _sizes_i32(sizes, B, dev)
-    n_out, W = int(n_out), max(int(frames_bound) + T, 1)
+    n_out, W = int(n_out), max((int(bound) if labels_bound is None else labels_bound) + T, 1)
     labels = offs = lens = scores = None
     if n_out:
         labels = torch.empty((B, n_out, W), dtype=torch.int32, device=dev)
@@ -1894,11 +1915,58 @@ def ctc_beam_stream_feed(probs: Tensor | None, sizes: Tensor | None, state: Tens
         scores = torch.empty((B, n_out), dtype=torch.float32, device=dev)
     tail = torch.empty((2, B), dtype=torch.int32, device=dev)
     lm_args, hot_args, _keep = _beam_arm_args(lm, alpha, beta, hotwords, dev)
-    _lib.check(lib.ds2_ctc_beam_stream_feed_f32(_ptr(probs), ld_b, ld_t, B, T, C, _ptr(sizes), int(blank), K, int(cutoff_top_n), float(cutoff_prob),
-                                                *lm_args, *hot_args, state.data_ptr(), state.numel(), nodes.data_ptr(), nodes.numel() * 4,
-                                                int(cap_frames), int(frames_bound), n_out, W, _ptr(labels), _ptr(offs), _ptr(lens), _ptr(scores),
-                                                tail[0].data_ptr(), tail[1].data_ptr(), _stream()), "ds2_ctc_beam_stream_feed_f32")
+    head = (_ptr(probs), ld_b, ld_t, B, T, C, _ptr(sizes), int(blank), K, int(cutoff_top_n), float(cutoff_prob), *lm_args, *hot_args,
+            state.data_ptr(), state.numel(), nodes.data_ptr(), nodes.numel() * 4, int(cap), int(bound))
+    outs = (n_out, W, _ptr(labels), _ptr(offs), _ptr(lens), _ptr(scores), tail[0].data_ptr(), tail[1].data_ptr(), _stream())
+    if labels_bound is None:
+        _lib.check(lib.ds2_ctc_beam_stream_feed_f32(*head, *outs), "ds2_ctc_beam_stream_feed_f32")
+    else:
+        _lib.check(lib.ds2_ctc_beam_stream_feed_committed_f32(*head, labels_bound, *outs), "ds2_ctc_beam_stream_feed_committed_f32")
     return labels, offs, lens, scores, tail[0], tail[1]
+
+
+def ctc_beam_stream_commit(state: Tensor, nodes: Tensor, cap_rows: int, nodes_out: Tensor, cap_rows_out: int, beam_width: int, lm, hotwords,
+                           width: int, cut_frame: Tensor | None = None):
+    """Commit and compaction of B running beam searches' back-pointers, one launch (contract: include/ds2hip.h,
+    ds2_ctc_beam_stream_commit): the stable (label, offset) pairs that have not left yet go to rows of `width` cells, the live tree of
+    `nodes` (capacity cap_rows rows of beam_width nodes) is renumbered into nodes_out, a distinct buffer of cap_rows_out >= cap_rows rows
+    as ctc_beam_stream_nodes makes them, and the state is rewritten to match; feed it through ctc_beam_stream_feed_committed from then
+    on.  cut_frame: (B) int32 on the GPU or None; where >= 0 the forced cut of the contract runs first.  lm / hotwords: what the stream
+    was opened with.  -> (info (B, 4): pairs committed now, M live nodes, longest live beam - committed length, frame of the last
+    committed pair; dropped (B): the beams the cut dropped; labels, offsets (B, width): the committed pairs, zero past info[b][0];
+    packed), all int32 on the GPU: the first four are views of `packed`, in that order, so one copy of it brings everything to the host
+    (commit_unpack splits the copy)."""
+    who = "ctc_beam_stream_commit"
+    lib = _lib.load()
+    dev = state.device
+    _chk_on_dev(who, dev, torch.uint8, {"state": state})
+    _chk_on_dev(who, dev, torch.int32, {"nodes": nodes, "nodes_out": nodes_out})
+    if cut_frame is not None:
+        _chk_on_dev(who, dev, torch.int32, {"cut_frame": cut_frame})
+    B, K = nodes.shape[0], int(beam_width)
+    if not _is_int(width, 0, 0x7fffffff):
+        raise ValueError(f"{who}: width must be a non-negative integer, got {width!r}")
+    if nodes_out.shape[0] != B or (cut_frame is not None and cut_frame.numel() != B):
+        raise ValueError(f"{who}: nodes of {B} utterances, nodes_out of {nodes_out.shape[0]}"
+                         + (f", cut_frame of {cut_frame.numel()}" if cut_frame is not None else ""))
+    Wc = int(width)
+    packed = torch.zeros((B * (5 + 2 * Wc),), dtype=torch.int32, device=dev)
+    info, dropped, lab, off = commit_unpack(packed, B, Wc)
+    wsb = lib.ds2_ctc_beam_stream_commit_workspace_bytes(B, int(cap_rows), K)
+    ws = _ws(wsb, dev) if wsb else None
+    _lib.check(lib.ds2_ctc_beam_stream_commit(state.data_ptr(), state.numel(), B, K, int(lm is not None), int(hotwords is not None),
+                                              nodes.data_ptr(), nodes.numel() * 4, int(cap_rows), nodes_out.data_ptr(), nodes_out.numel() * 4,
+                                              int(cap_rows_out), _ptr(cut_frame), Wc, _ptr(lab) if Wc else None, _ptr(off) if Wc else None,
+                                              info.data_ptr(), dropped.data_ptr(), _ptr(ws), wsb, _stream()), "ds2_ctc_beam_stream_commit")
+    return info, dropped, lab, off, packed
+
+
+def commit_unpack(packed: Tensor, B: int, width: int):
+    """ctc_beam_stream_commit's packed result, on any device -> views (info (B, 4), dropped (B), labels (B, width), offsets (B, width))"""
+    B, Wc = int(B), int(width)
+    if packed.numel() != B * (5 + 2 * Wc):
+        raise ValueError(f"commit_unpack: {packed.numel()} values for {B} utterances and rows of {Wc}")
+    return (packed[:4 * B].view(B, 4), packed[4 * B:5 * B], packed[5 * B:5 * B + B * Wc].view(B, Wc), packed[5 * B + B * Wc:].view(B, Wc))
 
 
 def lm_score(labels: Tensor, off: Tensor, lens: Tensor, lm, max_len: int):

@@ -905,7 +905,8 @@ int ds2_ctc_beam_decode_hot_f32(const float* probs, long long ld_b, long long ld
  *    ds2_ctc_beam_stream_nodes_bytes(B, cap_frames, beam_width) = 12 * B * cap_frames * beam_width bytes.  Node ids do not depend on
  *    cap_frames: to grow, allocate for a larger capacity and copy each utterance's three arrays to the front of their new places.
  *    frames_bound: an upper bound of the frames any utterance has consumed so far (the sum of the earlier calls' T will do);
- *    frames_bound + T <= cap_frames < 2^20 or the call is refused.  Nothing compacts the nodes: 12 * beam_width bytes per frame.
+ *    frames_bound + T <= cap_frames < 2^20 or the call is refused.  This entry compacts nothing: 12 * beam_width bytes per frame
+ *    (ds2_ctc_beam_stream_commit below does; a state that went through it must be fed through the committed entry, not this one).
  *  - read-out, when n_out > 0 (n_out <= beam_width): the end-of-utterance stage (word mode's partial-word term, the hotwords'
  *    -phi(state), the re-sort) on a copy the next call does not see, then labels / offsets (B, n_out, W) int32, zero past each length,
  *    lens (B, n_out), scores (B, n_out): the first n_out slots of the decode call's outputs; a slot past the surviving beams has
@@ -924,6 +925,46 @@ int ds2_ctc_beam_stream_feed_f32(const float* probs, long long ld_b, long long l
                                  size_t hot_bytes, void* state, size_t state_bytes, void* nodes, size_t nodes_bytes, int cap_frames,
                                  int frames_bound, int n_out, int W, int* labels, int* offsets, int* lens, float* scores,
                                  int* stable_len, int* frames, void* stream);
+
+/* Bounding an open stream: commit and compaction of its back-pointers (csrc/ctc_beam_commit.h).  Every later beam descends from a
+ * live beam, so the stable prefix can leave the device, and of the nodes only the LIVE TREE is still needed: the chains from the live
+ * beams down to the node of the last committed pair.  ds2_ctc_beam_stream_commit, one launch, per opened utterance with live beams:
+ *  - forced cut, only where cut_frame[b] >= 0 (cut_frame (B) int32 on the device, or NULL: no cut anywhere).  The first slot of the
+ *    saved state (the search's own order, before any end-of-utterance term) has m pairs with an offset < cut_frame[b]; if m exceeds the
+ *    stable length, every live beam that is shorter than m or does not share those m pairs is dropped, the survivors keep their order
+ *    and every per-beam field, and the stable prefix becomes those m pairs.  This is the ONLY step after which a stream may differ from
+ *    one decode call.  dropped (B) int32, nullable: the beams dropped.
+ *  - commit: the pairs from the committed length up to min(stable length, committed length + Wc) are written in text order to
+ *    labels / offsets (B, Wc) int32 (cells past them are not written); Wc >= 0, the rows may be NULL at Wc == 0.
+ *  - compaction: the live tree is renumbered in the order of its ids (a parent stays below its children) and written to nodes_out, a
+ *    DISTINCT buffer of cap_rows_out >= cap_rows rows (an overlap with `nodes` is refused), so growth and compaction are one copy; the
+ *    node of the last committed pair becomes the root (parent -1).  The next frame writes row ceil(M / beam_width) of nodes_out.
+ *  - info (B, 4) int32: pairs committed by this call, M = nodes of the live tree, the longest live beam's length less the committed
+ *    length (a bound on the row width a read-out needs, grows by at most one per frame), the frame of the last committed pair.
+ * An utterance never fed, or one with no live beam, has nothing to move: M = 0.  lm / hot as ds2_ctc_beam_stream_state_bytes takes them.
+ * ws: ds2_ctc_beam_stream_commit_workspace_bytes(B, cap_rows, beam_width) bytes of device memory, 0 (ws may be NULL) where the
+ * bitmap of cap_rows * beam_width nodes fits LDS; the query gives 0 for sizes outside the limits as well, which the entry refuses.
+ * The search's results do not depend on node ids, so without a forced cut a read-out keeps the bits of one decode call.
+ * A COMMITTED state (one that went through this entry) is fed through ds2_ctc_beam_stream_feed_committed_f32 and must NOT go through
+ * ds2_ctc_beam_stream_feed_f32, whose bounds count frames: here the node capacity and the bound count ROWS of beam_width nodes
+ * (rows_bound >= ceil(M / beam_width) + the frames fed since the commit, for every utterance; rows_bound + T <= cap_rows), the read-out
+ * rows hold only the pairs from the committed length on (at position s - committed length; lens, scores and stable_len stay absolute,
+ * offsets stay absolute frames), and W >= labels_bound + T with labels_bound >= info[b][2] + the frames fed since, for every
+ * utterance.  Everything else is ds2_ctc_beam_stream_feed_f32's contract; a state that never committed may be fed through either.
+ * Limits that remain: 2^20 - 1 labels per utterance between resets (the candidate key's length field), and fp32 totals that are
+ * absolute, not rebased. */
+size_t ds2_ctc_beam_stream_commit_workspace_bytes(int B, int cap_rows, int beam_width);
+int ds2_ctc_beam_stream_commit(void* state, size_t state_bytes, int B, int beam_width, int lm, int hot, const void* nodes,
+                               size_t nodes_bytes, int cap_rows, void* nodes_out, size_t nodes_out_bytes, int cap_rows_out,
+                               const int* cut_frame, int Wc, int* labels, int* offsets, int* info, int* dropped, void* ws,
+                               size_t ws_bytes, void* stream);
+int ds2_ctc_beam_stream_feed_committed_f32(const float* probs, long long ld_b, long long ld_t, int B, int T, int C, const int* sizes_dev,
+                                           int blank, int beam_width, int cutoff_top_n, float cutoff_prob, const void* lm_dev,
+                                           size_t lm_bytes, int lm_order, int lm_mode, int space, float alpha, float beta,
+                                           const void* hot_dev, const void* hot_host, size_t hot_bytes, void* state, size_t state_bytes,
+                                           void* nodes, size_t nodes_bytes, int cap_rows, int rows_bound, int labels_bound, int n_out,
+                                           int W, int* labels, int* offsets, int* lens, float* scores, int* stable_len, int* frames,
+                                           void* stream);
 
 /* Batched Levenshtein distance (unit costs: insert, delete, substitute) of P independent pairs of int32 symbol sequences, one launch;
  * the WER / CER scoring of DeepSpeech.evaluate() (replaces Decoder.wer / Decoder.cer's per-utterance DP, decoders/decoder.py:26-58,
