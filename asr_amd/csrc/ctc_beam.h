@@ -6,14 +6,18 @@
 //   c == blank: pb'(l) += total(l) + lp;   c == e: pnb'(l) += pnb(l) + lp, pnb'(l+c) += pb(l) + lp;
 //   otherwise:  pnb'(l+c) += total(l) + lp
 // and the K prefixes with the highest total = logaddexp(pb, pnb) survive (ties: shorter first, then smaller label sequence).
-// ctc_beam_kernel<PROF, true> is the language-model arm (ds2_ctc_beam_decode_lm_f32): the LM terms of ctc_lm.h ride in pnb of
+// The kernel is ctc_beam_kernel<PROF, Arm>; its last argument, the arm, says which search it is.  ctc_beam_kernel<PROF, NoArm> is the
+// search above (ds2_ctc_beam_decode_f32): the arm is empty and the kernel compiles without the code of the others.
+// ctc_beam_kernel<PROF, LmArgs> is the language-model arm (ds2_ctc_beam_decode_lm_f32): the LM terms of ctc_lm.h ride in pnb of
 // each extension, every beam is extended by every kept class (no staircase) and, in word mode, the survivors are re-scored and
-// re-sorted after the last frame.  LM = false takes no extra kernel argument and compiles to the kernel without that arm.
-// ctc_beam_kernel<PROF, true, HotArgs> is the hotword arm (ds2_ctc_beam_decode_hot_f32) on the same full grid: one more int of
+// re-sorted after the last frame.
+// ctc_beam_kernel<PROF, HotArgs> is the hotword arm (ds2_ctc_beam_decode_hot_f32) on the same full grid: one more int of
 // state per beam (the node of the automaton of ctc_hot.h), the term phi(n') - phi(n) added to the LM term of every extension, and
 // the end-of-utterance re-score (-phi(state)) and re-sort always run.  Its LM blob may be null (hot-only): no LM table is read.
-// ctc_beam_kernel<PROF, LM, Streamed<arm>> are the streaming instances of the three (ds2_ctc_beam_stream_feed_f32, ctc_beam_stream.h):
+// ctc_beam_kernel<PROF, Streamed<Arm>> are the streaming instances of the three (ds2_ctc_beam_stream_feed_f32, ctc_beam_stream.h):
 // the beams come from and go back to a state blob in global memory, and the frames of one call continue those of the calls before.
+// Host side, every entry is beam_check -> beam_plan (sizes, LDS carve, the arm's arguments: BeamPlan) -> beam_dispatch, which picks the
+// instance and launches it through the one launch site, beam_launch.
 //
 // Per frame, inside the workgroup (256 threads, all state in LDS):
 //  1. class keys (prob bits, index) of the frame's row, block bitonic sort, running-sum cutoff by wave 0, the threshold key
@@ -83,7 +87,9 @@ struct Layout {
   int K, PC, PK, HT;
   size_t beams, nb, rows, tab, uni, total;
   __host__ __device__ Layout(int K_, int PC_, int PK_, int HT_) : K(K_), PC(PC_), PK(PK_), HT(HT_) {
-    const size_t bb = align_up(6 * 4 * (size_t)K, 16) + 2 * 8 * (size_t)K;  // one buffer: pb pnb tot node len last | h ph
+    // buffer_bytes(K), written out: calling it here reorders the address arithmetic at the head of every kernel instance, and with it
+    // their register allocation (profiles/beam_plan_resources.txt)
+    const size_t bb = align_up(6 * 4 * (size_t)K, 16) + 2 * 8 * (size_t)K;
     beams = 64;
     nb = beams + 2 * bb;
     rows = nb + 2 * align_up(4 * (size_t)(K + 1), 16);
@@ -93,6 +99,8 @@ struct Layout {
     total = uni + (cls > cand ? cls : cand);
   }
   __host__ __device__ static size_t align_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
+  // one beam buffer, in LDS and in a stream's state blob: pb pnb tot node len last | h ph
+  __host__ __device__ static size_t buffer_bytes(int K) { return align_up(6 * 4 * (size_t)K, 16) + 2 * 8 * (size_t)K; }
 };
 
 struct Beams {
@@ -102,8 +110,7 @@ struct Beams {
 };
 
 __device__ inline Beams beams_at(char* smem, const Layout& L, int which) {
-  const size_t bb = Layout::align_up(6 * 4 * (size_t)L.K, 16) + 2 * 8 * (size_t)L.K;
-  char* p = smem + L.beams + which * bb;
+  char* p = smem + L.beams + which * Layout::buffer_bytes(L.K);
   Beams s;
   s.pb = (float*)p;
   s.pnb = s.pb + L.K;
@@ -239,12 +246,38 @@ struct CandLess {
 
 // PROF: thread 0 stamps the 100 MHz wall clock after each step's closing barrier and writes, per utterance, the ticks of
 // [prune classes, generate candidates, sort candidates, select], the chain walks and their steps, and the frame count.
+//
+// Arms: the kernel's one trailing argument says which instance it is.  An arm type (NoArm, LmArgs, HotArgs, Streamed<> of one of them)
+// states LM, HOT and STREAM and hands out the LmArgs, the hotword blob and the StreamArgs the kernel reads; what an arm does not have is
+// empty and, under the kernel's `if constexpr`, never read.
+// A streaming instance (ctc_beam_stream.h) resumes the search from a state blob in global memory, consumes this call's frames, writes the
+// state back and, when asked, reads the beams out.  Every difference from the one-call kernel sits under `if constexpr (STREAM)`: an
+// instance whose arm is not Streamed<> compiles to the code it was.
+struct StreamArgs {
+  char* state;        // B blobs of `stride` bytes: StreamHeader | beam buffer | LmBeams (LM, hotwords) | hotword states
+  size_t stride;
+  int cap, n_out, W;  // node storage for `cap` rows of K nodes per utterance (a row per frame until a commit compacts them,
+                      // ctc_beam_commit.h); read-out of n_out slots in rows of W (n_out == 0: none)
+  int* stable_len;    // (B)
+  int* frames;        // (B)
+};
 // LM arm (LM = true): shallow fusion with the packed n-gram model of ctc_lm.h.  Per-beam LM state sits in LDS after the no-LM
 // layout (LmBeams, one per beam buffer) and the kept non-blank class list is sized for every kept class (the full grid).
 struct LmArgs {
+  static constexpr bool LM = true, HOT = false, STREAM = false;
   const void* blob;
   float alpha, beta;
   int m, mode, space, nbl;   // context length (order - 1), ds2lm::MODE_*, space label (word mode), non-blank list capacity
+  __device__ LmArgs lm_args() const { return *this; }
+  __device__ const void* hot_blob() const { return nullptr; }
+  __device__ StreamArgs stream_args() const { return StreamArgs{}; }
+};
+// the plain kernel: no extra argument is read, and its code is that of the kernel without the LM arm
+struct NoArm {
+  static constexpr bool LM = false, HOT = false, STREAM = false;
+  __device__ LmArgs lm_args() const { return LmArgs{}; }
+  __device__ const void* hot_blob() const { return nullptr; }
+  __device__ StreamArgs stream_args() const { return StreamArgs{}; }
 };
 
 constexpr int LM_CTX = ds2lm::MAX_ORDER - 1;
@@ -315,8 +348,19 @@ __device__ inline void lm_copy(const LmArgs& a, const LmBeams& o, int src, const
 // Hotword arm: the LM arm's arguments (lm.blob null: hot-only, the LM term is 0 and no LM table is read) and the packed automaton.
 // Per-beam state: the automaton node of the prefix, one int per beam and beam buffer, after the LM arm's LDS.
 struct HotArgs {
+  static constexpr bool LM = true, HOT = true, STREAM = false;
   LmArgs lm;
   const void* hot;
+  __device__ LmArgs lm_args() const { return lm; }
+  __device__ const void* hot_blob() const { return hot; }
+  __device__ StreamArgs stream_args() const { return StreamArgs{}; }
+};
+// the streaming instance of an arm: the arm's own arguments and constants, and the stream's
+template <class Arm>
+struct Streamed : Arm {
+  static constexpr bool STREAM = true;
+  StreamArgs st;
+  __device__ StreamArgs stream_args() const { return st; }
 };
 
 __host__ __device__ inline size_t hot_state_bytes(int K) { return Layout::align_up(4 * (size_t)K, 16); }
@@ -334,38 +378,6 @@ __device__ inline float hot_bonus(const ds2lm::LmView& v, const LmArgs& a, const
   return b + term;
 }
 
-__device__ inline LmArgs lm_args() { return LmArgs{}; }
-__device__ inline LmArgs lm_args(const LmArgs& a) { return a; }
-__device__ inline LmArgs lm_args(const HotArgs& a) { return a.lm; }
-__device__ inline const void* hot_blob() { return nullptr; }
-__device__ inline const void* hot_blob(const LmArgs&) { return nullptr; }
-__device__ inline const void* hot_blob(const HotArgs& a) { return a.hot; }
-template <class... Lm>
-struct is_hot {
-  static constexpr bool value = false;
-};
-template <>
-struct is_hot<HotArgs> {
-  static constexpr bool value = true;
-};
-
-// Streaming instances (ctc_beam_stream.h): the arm's arguments wrapped with the stream's.  The search resumes from a state blob in
-// global memory, consumes this call's frames, writes the state back and, when asked, reads the beams out.  Every difference from the
-// one-call kernel sits under `if constexpr (STREAM)`: an instance without Streamed<> in its pack compiles to the code it was.
-struct NoArm {};
-struct StreamArgs {
-  char* state;        // B blobs of `stride` bytes: StreamHeader | beam buffer | LmBeams (LM, hotwords) | hotword states
-  size_t stride;
-  int cap, n_out, W;  // node storage for `cap` rows of K nodes per utterance (a row per frame until a commit compacts them,
-                      // ctc_beam_commit.h); read-out of n_out slots in rows of W (n_out == 0: none)
-  int* stable_len;    // (B)
-  int* frames;        // (B)
-};
-template <class Arm>
-struct Streamed {
-  Arm arm;
-  StreamArgs st;
-};
 // 64 bytes; all zero = a freshly opened stream.  The last four fields belong to the commit kernel (ctc_beam_commit.h) and stay zero in a
 // stream that never commits: the frame t0 + t writes row row_base + t0 + t - frame_base of the node storage (rows below row_base hold
 // the compacted live tree), and the first committed_len (label, offset) pairs of every beam have left the storage for the host
@@ -374,48 +386,22 @@ struct StreamHeader {
   int opened, t0, nb, stable_len, stable_node, row_base, frame_base, committed_len, commit_frame, pad[7];
 };
 static_assert(sizeof(StreamHeader) == 64, "the state blob's header is 64 bytes");
-__device__ inline LmArgs lm_args(const NoArm&) { return LmArgs{}; }
-__device__ inline const void* hot_blob(const NoArm&) { return nullptr; }
-template <class Arm>
-__device__ inline LmArgs lm_args(const Streamed<Arm>& a) { return lm_args(a.arm); }
-template <class Arm>
-__device__ inline const void* hot_blob(const Streamed<Arm>& a) { return hot_blob(a.arm); }
-template <>
-struct is_hot<Streamed<HotArgs>> {
-  static constexpr bool value = true;
-};
-template <class... Lm>
-struct is_stream {
-  static constexpr bool value = false;
-};
-template <class Arm>
-struct is_stream<Streamed<Arm>> {
-  static constexpr bool value = true;
-};
-__device__ inline StreamArgs stream_args() { return StreamArgs{}; }
-__device__ inline StreamArgs stream_args(const LmArgs&) { return StreamArgs{}; }
-__device__ inline StreamArgs stream_args(const HotArgs&) { return StreamArgs{}; }
-template <class Arm>
-__device__ inline StreamArgs stream_args(const Streamed<Arm>& a) { return a.st; }
 // defined in ctc_beam_stream.h
 __device__ inline void stream_load(const StreamArgs& st, int b, const Layout& L, char* smem, Header* hd, bool lm, const LmBeams& l0, int* h0);
 __device__ inline void stream_save(const StreamArgs& st, int b, const Layout& L, char* smem, const Header* hd, int cur, int frames, bool lm,
                                    const LmBeams& l0, const LmBeams& l1, const int* hf);
 __device__ inline void stream_stable(const StreamArgs& st, int b, Header* hd, const Beams& f, int nb, const int* n_parent);
 
-// LM = false takes no LmArgs (an empty pack, or Streamed<NoArm>): its kernel arguments, and its code, are those of the kernel without
-// the LM arm
-template <bool PROF, bool LM, class... Lm>
+template <bool PROF, class Arm>
 __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __restrict__ probs, long long ld_b, long long ld_t, int T,
                                                                int C, const int* __restrict__ sizes, int blank, int K, int top_n,
                                                                float cutoff_prob, int PC, int PK, int HT, int* __restrict__ labels,
                                                                int* __restrict__ offsets, int* __restrict__ lens, float* __restrict__ scores,
-                                                               int* __restrict__ nodes, u64* __restrict__ prof, Lm... lm_arg) {
-  constexpr bool HOT = is_hot<Lm...>::value, STREAM = is_stream<Lm...>::value;
-  static_assert(sizeof...(Lm) == (LM || STREAM ? 1 : 0), "the LM arm takes one LmArgs or HotArgs, a streaming instance one Streamed<>");
-  [[maybe_unused]] const StreamArgs st = stream_args(lm_arg...);
+                                                               int* __restrict__ nodes, u64* __restrict__ prof, Arm arm) {
+  constexpr bool LM = Arm::LM, HOT = Arm::HOT, STREAM = Arm::STREAM;
+  [[maybe_unused]] const StreamArgs st = arm.stream_args();
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const LmArgs lm = lm_args(lm_arg...);
+  const LmArgs lm = arm.lm_args();
   const Layout L(K, PC, PK, HT);
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   Header* hd = (Header*)smem;
@@ -454,7 +440,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const float* __r
   [[maybe_unused]] ds2hot::HotView hv;
   [[maybe_unused]] int *h0 = nullptr, *h1 = nullptr;
   if constexpr (HOT) {
-    hv = ds2hot::hot_view(hot_blob(lm_arg...));
+    hv = ds2hot::hot_view(arm.hot_blob());
     h0 = (int*)(smem + Layout::align_up(lm_layout_total(L, lm.nbl), 16));
     h1 = (int*)((char*)h0 + hot_state_bytes(K));
     if (tid == 0 && fresh) h0[0] = 0;
@@ -850,33 +836,122 @@ static int beam_check(const char* who, const float* probs, const void* arm, int 
   return 0;
 }
 
-// The dynamic-LDS limit above 64 KiB, the launch of one workgroup per utterance and its check, for every instance of the kernel
-template <auto KERNEL, class... Args>
-static int beam_launch(const char* label, int B, size_t lds, void* stream, Args... args) {
-  if (lds > 64 * 1024) DS2_HIP(hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(KERNEL, dim3(B), dim3(BEAM_THREADS), lds, (hipStream_t)stream, args...);
+// The language-model arguments of the LM and hotword entries (`who` names the entry in an error)
+static int beam_lm_check(const char* who, size_t lm_bytes, int lm_order, int lm_mode, int space, int C, int blank, float alpha, float beta) {
+  DS2_REQUIRE(lm_order >= 1 && lm_order <= ds2lm::MAX_ORDER && (lm_mode == ds2lm::MODE_CHAR || lm_mode == ds2lm::MODE_WORD) &&
+                  lm_bytes >= sizeof(ds2lm::LmHeader),
+              "%s: bad language model (order %d, mode %d, %zu bytes)", who, lm_order, lm_mode, lm_bytes);
+  DS2_REQUIRE(lm_mode == ds2lm::MODE_CHAR || (space >= 0 && space < C && space != blank),
+              "%s: word mode needs a space label other than the blank (got %d)", who, space);
+  DS2_REQUIRE(alpha == alpha && beta == beta && fabsf(alpha) < INFINITY && fabsf(beta) < INFINITY, "%s: alpha and beta must be finite", who);
+  return 0;
+}
+
+// the sizes a packed automaton claims, against the bytes it was given
+static int hot_header_check(const char* who, const void* packed, size_t bytes) {
+  using namespace ds2hot;
+  DS2_REQUIRE(packed && bytes >= sizeof(HotHeader), "%s: no packed hotword automaton (%zu bytes)", who, bytes);
+  const HotHeader* h = (const HotHeader*)packed;
+  DS2_REQUIRE(h->magic == MAGIC, "%s: not a packed hotword automaton", who);
+  DS2_REQUIRE(h->nnodes >= 2 && h->nnodes <= MAX_NODES && h->tcap == pow2_ceil(2 * (h->nnodes - 1) + 1) && h->depth >= 1 &&
+                  h->depth <= MAX_DEPTH && bytes >= hot_bytes(h->tcap, h->nnodes),
+              "%s: bad hotword automaton (%d nodes, table of %d, depth %d, %zu bytes)", who, h->nnodes, h->tcap, h->depth, bytes);
+  return 0;
+}
+
+// The launch plan, the same for every entry: the sizes the kernel takes, the arm's LDS total and the arm's arguments.  lm_dev / hot_dev
+// null: the entry has no such arm.  Both arms search the full grid of K * (nbl + 2) candidates.
+struct BeamPlan {
+  int K, nbl, PC, PK, HT;
+  size_t lds;
+  bool lm;
+  const void* hot;   // the packed automaton on the device, or null
+  LmArgs la;
+};
+
+static int beam_plan(BeamPlan& p, const char* who, int C, int blank, int beam_width, int cutoff_top_n, const void* lm_dev, size_t lm_bytes,
+                     int lm_order, int lm_mode, int space, float alpha, float beta, const void* hot_dev, const void* hot_host,
+                     size_t hot_bytes) {
+  const bool lm = lm_dev != nullptr, hot = hot_dev != nullptr;
+  if (hot) {
+    if (hot_header_check(who, hot_host, hot_bytes)) return 1;
+    DS2_REQUIRE(((const ds2hot::HotHeader*)hot_host)->C == C, "%s: the hotwords were packed for %d classes, probs have %d", who,
+                ((const ds2hot::HotHeader*)hot_host)->C, C);
+  }
+  if (lm)
+    if (int rc = beam_lm_check(who, lm_bytes, lm_order, lm_mode, space, C, blank, alpha, beta)) return rc;
+  const int K = beam_width, nbl = min(cutoff_top_n, C - 1);
+  DS2_REQUIRE(!(lm || hot) || (long long)K * (nbl + 2) <= ds2_ctc_beam_lm_max_candidates(),
+              "%s: beam_width * (min(cutoff_top_n, C - 1) + 2) = %lld exceeds the %d candidate slots%s", who, (long long)K * (nbl + 2),
+              ds2_ctc_beam_lm_max_candidates(), hot ? " (hotwords search the full grid, with or without a language model)" : "");
+  const int PC = pow2_ceil(C), PK = pow2_ceil(lm || hot ? K * (nbl + 2) : max_candidates(K)), HT = 2 * pow2_ceil(K);
+  const Layout lay(K, PC, PK, HT);
+  // the hotword arm: the LM arm's layout and one int of hotword state per beam and buffer
+  const size_t lds = hot ? hot_layout_total(lay, nbl) : lm ? lm_layout_total(lay, nbl) : lay.total;
+  if (hot)
+    DS2_REQUIRE(lds <= 160 * 1024, "%s: LDS layout of %zu bytes (%zu of them hotword state) does not fit the 160 KiB at beam_width %d, %d classes",
+                who, lds, 2 * hot_state_bytes(K), K, C);
+  else
+    DS2_REQUIRE(PK <= 4096 && lds <= 160 * 1024, "%s: LDS layout of %zu bytes does not fit", who, lds);
+  p = BeamPlan{K, nbl, PC, PK, HT, lds, lm, hot_dev,
+               lm ? LmArgs{lm_dev, alpha, beta, lm_order - 1, lm_mode, lm_mode == ds2lm::MODE_WORD ? space : -1, nbl}
+                  : LmArgs{nullptr, 0.f, 0.f, 0, 0, -1, nbl}};
+  return 0;
+}
+
+// What a launch takes from its entry beside the plan
+struct BeamCall {
+  const float* probs;
+  long long ld_b, ld_t;
+  int B, T, C;
+  const int* sizes;
+  int blank, top_n;
+  float cutoff_prob;
+  int *labels, *offsets, *lens;
+  float* scores;
+  int* nodes;
+  void* stream;
+};
+
+// The one launch site of ctc_beam_kernel<PROF, Arm>: the dynamic-LDS limit above 64 KiB, one workgroup per utterance, the launch check
+template <bool PROF, class Arm>
+static int beam_launch(const char* label, const BeamPlan& p, const BeamCall& c, u64* prof, const Arm& arm) {
+  const auto kernel = ctc_beam_kernel<PROF, Arm>;
+  if (p.lds > 64 * 1024) DS2_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
+  hipLaunchKernelGGL(kernel, dim3(c.B), dim3(BEAM_THREADS), p.lds, (hipStream_t)c.stream, c.probs, c.ld_b, c.ld_t, c.T, c.C, c.sizes, c.blank,
+                     p.K, c.top_n, c.cutoff_prob, p.PC, p.PK, p.HT, c.labels, c.offsets, c.lens, c.scores, c.nodes, prof, arm);
   DS2_LAUNCH_CHECK(label);
   return 0;
+}
+
+// the instance for (hot, lm, streamed); st null: a one-call decode
+static int beam_dispatch(const BeamPlan& p, const BeamCall& c, const StreamArgs* st) {
+  const HotArgs ha{p.la, p.hot};
+  if (st) {
+    if (p.hot) return beam_launch<false>("ctc_beam_kernel<HOT, STREAM>", p, c, nullptr, Streamed<HotArgs>{ha, *st});
+    if (p.lm) return beam_launch<false>("ctc_beam_kernel<LM, STREAM>", p, c, nullptr, Streamed<LmArgs>{p.la, *st});
+    return beam_launch<false>("ctc_beam_kernel<STREAM>", p, c, nullptr, Streamed<NoArm>{NoArm{}, *st});
+  }
+  if (p.hot) return beam_launch<false>("ctc_beam_kernel<HOT>", p, c, nullptr, ha);
+  if (p.lm) return beam_launch<false>("ctc_beam_kernel<LM>", p, c, nullptr, p.la);
+  return beam_launch<false>("ctc_beam_kernel", p, c, nullptr, NoArm{});
 }
 
 extern "C" int ds2_ctc_beam_decode_f32(const float* probs, long long ld_b, long long ld_t, int B, int T, int C, const int* sizes_dev,
                                        int blank, int beam_width, int cutoff_top_n, float cutoff_prob, int* labels, int* offsets,
                                        int* lens, float* scores, void* ws, size_t ws_bytes, void* stream) {
-  if (int rc = beam_check("ds2_ctc_beam_decode_f32", probs, probs, B, T, C, blank, beam_width, cutoff_top_n, cutoff_prob, labels, offsets, lens,
-                          scores, ws, ws_bytes)) return rc;
-  const int K = beam_width, PC = pow2_ceil(C), PK = pow2_ceil(max_candidates(K)), HT = 2 * pow2_ceil(K);
-  const Layout lay(K, PC, PK, HT);
-  DS2_REQUIRE(PK <= 4096 && lay.total <= 160 * 1024, "ds2_ctc_beam_decode_f32: LDS layout of %zu bytes does not fit", lay.total);
+  const char* who = "ds2_ctc_beam_decode_f32";
+  if (int rc = beam_check(who, probs, probs, B, T, C, blank, beam_width, cutoff_top_n, cutoff_prob, labels, offsets, lens, scores, ws, ws_bytes))
+    return rc;
+  BeamPlan p;
+  if (int rc = beam_plan(p, who, C, blank, beam_width, cutoff_top_n, nullptr, 0, 0, 0, 0, 0.f, 0.f, nullptr, nullptr, 0)) return rc;
+  const BeamCall c{probs, ld_b, ld_t, B, T, C, sizes_dev, blank, cutoff_top_n, cutoff_prob, labels, offsets, lens, scores, (int*)ws, stream};
   const char* pe = ds2_exp_getenv("DS2_BEAM_PROFILE");
-  if (!(pe && pe[0] == '1'))
-    return beam_launch<ctc_beam_kernel<false, false>>("ctc_beam_kernel", B, lay.total, stream, probs, ld_b, ld_t, T, C, sizes_dev, blank, K,
-                                                      cutoff_top_n, cutoff_prob, PC, PK, HT, labels, offsets, lens, scores, (int*)ws, nullptr);
+  if (!(pe && pe[0] == '1')) return beam_dispatch(p, c, nullptr);
   // profiling build of the same kernel (experiments only): per-step times averaged over the utterances' frames
   u64* prof = nullptr;
   DS2_HIP(hipMalloc(&prof, (size_t)B * 8 * sizeof(u64)));
-  if (int rc = beam_launch<ctc_beam_kernel<true, false>>("ctc_beam_kernel (profiling)", B, lay.total, stream, probs, ld_b, ld_t, T, C, sizes_dev,
-                                                         blank, K, cutoff_top_n, cutoff_prob, PC, PK, HT, labels, offsets, lens, scores,
-                                                         (int*)ws, prof)) {
+  if (int rc = beam_launch<true>("ctc_beam_kernel (profiling)", p, c, prof, NoArm{})) {
     hipFree(prof);
     return rc;
   }
@@ -896,7 +971,7 @@ extern "C" int ds2_ctc_beam_decode_f32(const float* probs, long long ld_b, long 
   fprintf(stderr,
           "ds2_ctc_beam profile (K=%d C=%d, %.0f frames): us/frame prune %.2f, candidates %.2f, sort %.2f, select %.2f; "
           "chain walks/frame %.1f, steps/walk %.1f\n",
-          K, C, sum[6], sum[0] / fr / 100, sum[1] / fr / 100, sum[2] / fr / 100, sum[3] / fr / 100, sum[4] / fr,
+          p.K, C, sum[6], sum[0] / fr / 100, sum[1] / fr / 100, sum[2] / fr / 100, sum[3] / fr / 100, sum[4] / fr,
           sum[4] > 0 ? sum[5] / sum[4] : 0.0);
   return 0;
 }
@@ -978,36 +1053,18 @@ extern "C" int ds2_ctc_lm_score(const void* packed, const int* hist, int n_hist,
   return 0;
 }
 
-// The language-model arguments of the LM and hotword entries (`who` names the entry in an error)
-static int beam_lm_check(const char* who, size_t lm_bytes, int lm_order, int lm_mode, int space, int C, int blank, float alpha, float beta) {
-  DS2_REQUIRE(lm_order >= 1 && lm_order <= ds2lm::MAX_ORDER && (lm_mode == ds2lm::MODE_CHAR || lm_mode == ds2lm::MODE_WORD) &&
-                  lm_bytes >= sizeof(ds2lm::LmHeader),
-              "%s: bad language model (order %d, mode %d, %zu bytes)", who, lm_order, lm_mode, lm_bytes);
-  DS2_REQUIRE(lm_mode == ds2lm::MODE_CHAR || (space >= 0 && space < C && space != blank),
-              "%s: word mode needs a space label other than the blank (got %d)", who, space);
-  DS2_REQUIRE(alpha == alpha && beta == beta && fabsf(alpha) < INFINITY && fabsf(beta) < INFINITY, "%s: alpha and beta must be finite", who);
-  return 0;
-}
-
 extern "C" int ds2_ctc_beam_decode_lm_f32(const float* probs, long long ld_b, long long ld_t, int B, int T, int C, const int* sizes_dev,
                                           int blank, int beam_width, int cutoff_top_n, float cutoff_prob, const void* lm_dev,
                                           size_t lm_bytes, int lm_order, int lm_mode, int space, float alpha, float beta, int* labels,
                                           int* offsets, int* lens, float* scores, void* ws, size_t ws_bytes, void* stream) {
-  if (int rc = beam_check("ds2_ctc_beam_decode_lm_f32", probs, lm_dev, B, T, C, blank, beam_width, cutoff_top_n, cutoff_prob, labels, offsets,
-                          lens, scores, ws, ws_bytes)) return rc;
-  if (int rc = beam_lm_check("ds2_ctc_beam_decode_lm_f32", lm_bytes, lm_order, lm_mode, space, C, blank, alpha, beta)) return rc;
-  const int K = beam_width, nbl = min(cutoff_top_n, C - 1);
-  DS2_REQUIRE((long long)K * (nbl + 2) <= ds2_ctc_beam_lm_max_candidates(),
-              "ds2_ctc_beam_decode_lm_f32: beam_width * (min(cutoff_top_n, C - 1) + 2) = %lld exceeds the %d candidate slots",
-              (long long)K * (nbl + 2), ds2_ctc_beam_lm_max_candidates());
-  const int PC = pow2_ceil(C), PK = pow2_ceil(K * (nbl + 2)), HT = 2 * pow2_ceil(K);
-  const Layout lay(K, PC, PK, HT);
-  const size_t total = lm_layout_total(lay, nbl);
-  DS2_REQUIRE(total <= 160 * 1024, "ds2_ctc_beam_decode_lm_f32: LDS layout of %zu bytes does not fit", total);
-  const LmArgs la{lm_dev, alpha, beta, lm_order - 1, lm_mode, lm_mode == ds2lm::MODE_WORD ? space : -1, nbl};
-  return beam_launch<ctc_beam_kernel<false, true, LmArgs>>("ctc_beam_kernel<LM>", B, total, stream, probs, ld_b, ld_t, T, C, sizes_dev, blank, K,
-                                                           cutoff_top_n, cutoff_prob, PC, PK, HT, labels, offsets, lens, scores, (int*)ws,
-                                                           nullptr, la);
+  const char* who = "ds2_ctc_beam_decode_lm_f32";
+  if (int rc = beam_check(who, probs, lm_dev, B, T, C, blank, beam_width, cutoff_top_n, cutoff_prob, labels, offsets, lens, scores, ws, ws_bytes))
+    return rc;
+  BeamPlan p;
+  if (int rc = beam_plan(p, who, C, blank, beam_width, cutoff_top_n, lm_dev, lm_bytes, lm_order, lm_mode, space, alpha, beta, nullptr, nullptr, 0))
+    return rc;
+  return beam_dispatch(p, BeamCall{probs, ld_b, ld_t, B, T, C, sizes_dev, blank, cutoff_top_n, cutoff_prob, labels, offsets, lens, scores, (int*)ws,
+                                   stream}, nullptr);
 }
 
 // ---- hotword arm (ds2_ctc_hot_*, ds2_ctc_beam_decode_hot_f32) ----
@@ -1079,18 +1136,6 @@ extern "C" int ds2_ctc_hot_pack(int n_nodes, int n_edges, const int* edge_node, 
   return 0;
 }
 
-// the sizes a packed automaton claims, against the bytes it was given
-static int hot_header_check(const char* who, const void* packed, size_t bytes) {
-  using namespace ds2hot;
-  DS2_REQUIRE(packed && bytes >= sizeof(HotHeader), "%s: no packed hotword automaton (%zu bytes)", who, bytes);
-  const HotHeader* h = (const HotHeader*)packed;
-  DS2_REQUIRE(h->magic == MAGIC, "%s: not a packed hotword automaton", who);
-  DS2_REQUIRE(h->nnodes >= 2 && h->nnodes <= MAX_NODES && h->tcap == pow2_ceil(2 * (h->nnodes - 1) + 1) && h->depth >= 1 &&
-                  h->depth <= MAX_DEPTH && bytes >= hot_bytes(h->tcap, h->nnodes),
-              "%s: bad hotword automaton (%d nodes, table of %d, depth %d, %zu bytes)", who, h->nnodes, h->tcap, h->depth, bytes);
-  return 0;
-}
-
 extern "C" int ds2_ctc_hot_step(const void* packed, int node, int label, int* next, float* term) {
   using namespace ds2hot;
   DS2_REQUIRE(packed && next && term, "ds2_ctc_hot_step: null pointer");
@@ -1106,30 +1151,12 @@ extern "C" int ds2_ctc_beam_decode_hot_f32(const float* probs, long long ld_b, l
                                            size_t lm_bytes, int lm_order, int lm_mode, int space, float alpha, float beta,
                                            const void* hot_dev, const void* hot_host, size_t hot_bytes, int* labels, int* offsets,
                                            int* lens, float* scores, void* ws, size_t ws_bytes, void* stream) {
-  if (int rc = beam_check("ds2_ctc_beam_decode_hot_f32", probs, hot_dev, B, T, C, blank, beam_width, cutoff_top_n, cutoff_prob, labels, offsets,
-                          lens, scores, ws, ws_bytes)) return rc;
-  if (hot_header_check("ds2_ctc_beam_decode_hot_f32", hot_host, hot_bytes)) return 1;
-  DS2_REQUIRE(((const ds2hot::HotHeader*)hot_host)->C == C, "ds2_ctc_beam_decode_hot_f32: the hotwords were packed for %d classes, probs have %d",
-              ((const ds2hot::HotHeader*)hot_host)->C, C);
-  if (lm_dev)
-    if (int rc = beam_lm_check("ds2_ctc_beam_decode_hot_f32", lm_bytes, lm_order, lm_mode, space, C, blank, alpha, beta)) return rc;
-  const int K = beam_width, nbl = min(cutoff_top_n, C - 1);
-  DS2_REQUIRE((long long)K * (nbl + 2) <= ds2_ctc_beam_lm_max_candidates(),
-              "ds2_ctc_beam_decode_hot_f32: beam_width * (min(cutoff_top_n, C - 1) + 2) = %lld exceeds the %d candidate slots (hotwords "
-              "search the full grid, with or without a language model)",
-              (long long)K * (nbl + 2), ds2_ctc_beam_lm_max_candidates());
-  const int PC = pow2_ceil(C), PK = pow2_ceil(K * (nbl + 2)), HT = 2 * pow2_ceil(K);
-  const Layout lay(K, PC, PK, HT);
-  const size_t total = hot_layout_total(lay, nbl);   // the LM arm's layout and one int of hotword state per beam and buffer
-  DS2_REQUIRE(total <= 160 * 1024,
-              "ds2_ctc_beam_decode_hot_f32: LDS layout of %zu bytes (%zu of them hotword state) does not fit the 160 KiB at beam_width %d, "
-              "%d classes",
-              total, 2 * hot_state_bytes(K), K, C);
-  HotArgs ha;
-  ha.lm = lm_dev ? LmArgs{lm_dev, alpha, beta, lm_order - 1, lm_mode, lm_mode == ds2lm::MODE_WORD ? space : -1, nbl}
-                 : LmArgs{nullptr, 0.f, 0.f, 0, 0, -1, nbl};
-  ha.hot = hot_dev;
-  return beam_launch<ctc_beam_kernel<false, true, HotArgs>>("ctc_beam_kernel<HOT>", B, total, stream, probs, ld_b, ld_t, T, C, sizes_dev, blank, K,
-                                                            cutoff_top_n, cutoff_prob, PC, PK, HT, labels, offsets, lens, scores, (int*)ws,
-                                                            nullptr, ha);
+  const char* who = "ds2_ctc_beam_decode_hot_f32";
+  if (int rc = beam_check(who, probs, hot_dev, B, T, C, blank, beam_width, cutoff_top_n, cutoff_prob, labels, offsets, lens, scores, ws, ws_bytes))
+    return rc;
+  BeamPlan p;
+  if (int rc = beam_plan(p, who, C, blank, beam_width, cutoff_top_n, lm_dev, lm_bytes, lm_order, lm_mode, space, alpha, beta, hot_dev, hot_host,
+                         hot_bytes)) return rc;
+  return beam_dispatch(p, BeamCall{probs, ld_b, ld_t, B, T, C, sizes_dev, blank, cutoff_top_n, cutoff_prob, labels, offsets, lens, scores, (int*)ws,
+                                   stream}, nullptr);
 }

@@ -64,7 +64,7 @@ __device__ inline BlobBeams blob_beams(char* p, int K) {
   s.last = s.len + K;
   s.h = (u64*)(q + Layout::align_up(6 * 4 * (size_t)K, 16));
   s.ph = s.h + K;
-  char* l = q + stream_beams_bytes(K);
+  char* l = q + Layout::buffer_bytes(K);
   s.lm_ctx = (int*)l;
   s.lm_bow = (float*)(s.lm_ctx + LM_CTX * K);
   s.lm_node = (int*)(s.lm_bow + LM_CTX * K);
@@ -300,7 +300,7 @@ extern "C" int ds2_ctc_beam_stream_commit(void* state, size_t state_bytes, int B
               ds2_ctc_beam_stream_state_bytes(B, beam_width, lm, hot));
   const size_t need = ds2_ctc_beam_stream_commit_workspace_bytes(B, cap_rows, beam_width), words = commit_words(cap_rows, beam_width);
   DS2_REQUIRE(need == 0 || (ws && ws_bytes >= need), "%s: workspace too small: %zu bytes, %zu needed", who, ws_bytes, need);
-  CommitArgs a{(char*)state, stream_stride(beam_width, lm != 0 || hot != 0, hot != 0), (const int*)nodes, (int*)nodes_out, cap_rows, cap_rows_out,
+  CommitArgs a{(char*)state, stream_stride(beam_width, lm != 0, hot != 0), (const int*)nodes, (int*)nodes_out, cap_rows, cap_rows_out,
                beam_width, Wc, lm != 0 || hot != 0, hot != 0, cut_frame, labels, offsets, info, dropped, need ? (u64*)ws : nullptr, words};
   hipLaunchKernelGGL(ctc_beam_commit_kernel, dim3(B), dim3(BEAM_THREADS), need ? 0 : 12 * words, (hipStream_t)stream, a);
   DS2_LAUNCH_CHECK("ctc_beam_commit_kernel");

@@ -27,11 +27,10 @@
 
 namespace {
 
-__host__ __device__ inline size_t stream_beams_bytes(int K) { return Layout::align_up(6 * 4 * (size_t)K, 16) + 2 * 8 * (size_t)K; }
 __host__ __device__ inline size_t stream_lm_bytes(int K) { return Layout::align_up(lm_beams_bytes(K), 16); }
-// bytes of one utterance's blob; `lm`: the instance keeps LmBeams (the LM arm and the hotword arm, whose lmb rides there without an LM)
+// bytes of one utterance's blob; LmBeams are kept by the LM arm and by the hotword arm, whose lmb rides there without an LM
 __host__ __device__ inline size_t stream_stride(int K, bool lm, bool hot) {
-  return sizeof(StreamHeader) + stream_beams_bytes(K) + (lm ? stream_lm_bytes(K) : 0) + (hot ? hot_state_bytes(K) : 0);
+  return sizeof(StreamHeader) + Layout::buffer_bytes(K) + (lm || hot ? stream_lm_bytes(K) : 0) + (hot ? hot_state_bytes(K) : 0);
 }
 
 // nbytes (a multiple of 4) from src to dst, one of them LDS, by the whole workgroup: 16-byte vectors where both sides allow, else dwords
@@ -49,7 +48,7 @@ __device__ inline void stream_copy(void* dst, const void* src, size_t nbytes) {
 
 __device__ inline void stream_load(const StreamArgs& st, int b, const Layout& L, char* smem, Header* hd, bool lm, const LmBeams& l0, int* h0) {
   const char* p = st.state + (size_t)b * st.stride;
-  const size_t bb = stream_beams_bytes(L.K);
+  const size_t bb = Layout::buffer_bytes(L.K);
   stream_copy(smem + L.beams, p + sizeof(StreamHeader), bb);
   if (lm) stream_copy(l0.ctx, p + sizeof(StreamHeader) + bb, lm_beams_bytes(L.K));
   if (h0) stream_copy(h0, p + sizeof(StreamHeader) + bb + stream_lm_bytes(L.K), hot_state_bytes(L.K));
@@ -59,7 +58,7 @@ __device__ inline void stream_load(const StreamArgs& st, int b, const Layout& L,
 __device__ inline void stream_save(const StreamArgs& st, int b, const Layout& L, char* smem, const Header* hd, int cur, int frames, bool lm,
                                    const LmBeams& l0, const LmBeams& l1, const int* hf) {
   char* p = st.state + (size_t)b * st.stride;
-  const size_t bb = stream_beams_bytes(L.K);
+  const size_t bb = Layout::buffer_bytes(L.K);
   stream_copy(p + sizeof(StreamHeader), smem + L.beams + cur * bb, bb);
   if (lm) stream_copy(p + sizeof(StreamHeader) + bb, (cur ? l1 : l0).ctx, lm_beams_bytes(L.K));
   if (hf) stream_copy(p + sizeof(StreamHeader) + bb + stream_lm_bytes(L.K), hf, hot_state_bytes(L.K));
@@ -108,7 +107,7 @@ __device__ inline void stream_stable(const StreamArgs& st, int b, Header* hd, co
 
 extern "C" size_t ds2_ctc_beam_stream_state_bytes(int B, int beam_width, int lm, int hot) {
   if (B <= 0 || beam_width <= 0 || beam_width > BEAM_MAX_K) return 0;
-  return (size_t)B * stream_stride(beam_width, lm != 0 || hot != 0, hot != 0);
+  return (size_t)B * stream_stride(beam_width, lm != 0, hot != 0);
 }
 
 extern "C" size_t ds2_ctc_beam_stream_nodes_bytes(int B, int cap_frames, int beam_width) {
@@ -149,47 +148,12 @@ static int stream_feed(const char* who, const float* probs, long long ld_b, long
   const bool hot = hot_dev != nullptr, lm = lm_dev != nullptr;
   DS2_REQUIRE(state_bytes >= ds2_ctc_beam_stream_state_bytes(B, K, lm, hot), "%s: state too small: %zu bytes, %zu needed", who, state_bytes,
               ds2_ctc_beam_stream_state_bytes(B, K, lm, hot));
-  if (hot) {
-    if (hot_header_check(who, hot_host, hot_bytes)) return 1;
-    DS2_REQUIRE(((const ds2hot::HotHeader*)hot_host)->C == C, "%s: the hotwords were packed for %d classes, probs have %d", who,
-                ((const ds2hot::HotHeader*)hot_host)->C, C);
-  }
-  if (lm)
-    if (int rc = beam_lm_check(who, lm_bytes, lm_order, lm_mode, space, C, blank, alpha, beta)) return rc;
-  StreamArgs sa{(char*)state, stream_stride(K, lm || hot, hot), cap_frames, n_out, n_out > 0 ? W : 0, stable_len, frames};
-  const int PC = pow2_ceil(C), HT = 2 * pow2_ceil(K);
-  if (!lm && !hot) {
-    const int PK = pow2_ceil(max_candidates(K));
-    const Layout lay(K, PC, PK, HT);
-    DS2_REQUIRE(PK <= 4096 && lay.total <= 160 * 1024, "%s: LDS layout of %zu bytes does not fit", who, lay.total);
-    return beam_launch<ctc_beam_kernel<false, false, Streamed<NoArm>>>("ctc_beam_kernel<STREAM>", B, lay.total, stream, probs, ld_b, ld_t, T, C,
-                                                                        sizes_dev, blank, K, cutoff_top_n, cutoff_prob, PC, PK, HT, labels,
-                                                                        offsets, lens, scores, (int*)nodes, nullptr,
-                                                                        Streamed<NoArm>{NoArm{}, sa});
-  }
-  const int nbl = min(cutoff_top_n, C - 1);
-  DS2_REQUIRE((long long)K * (nbl + 2) <= ds2_ctc_beam_lm_max_candidates(),
-              "%s: beam_width * (min(cutoff_top_n, C - 1) + 2) = %lld exceeds the %d candidate slots%s", who, (long long)K * (nbl + 2),
-              ds2_ctc_beam_lm_max_candidates(), hot ? " (hotwords search the full grid, with or without a language model)" : "");
-  const int PK = pow2_ceil(K * (nbl + 2));
-  const Layout lay(K, PC, PK, HT);
-  const LmArgs la = lm ? LmArgs{lm_dev, alpha, beta, lm_order - 1, lm_mode, lm_mode == ds2lm::MODE_WORD ? space : -1, nbl}
-                       : LmArgs{nullptr, 0.f, 0.f, 0, 0, -1, nbl};
-  if (!hot) {
-    const size_t total = lm_layout_total(lay, nbl);
-    DS2_REQUIRE(total <= 160 * 1024, "%s: LDS layout of %zu bytes does not fit", who, total);
-    return beam_launch<ctc_beam_kernel<false, true, Streamed<LmArgs>>>("ctc_beam_kernel<LM, STREAM>", B, total, stream, probs, ld_b, ld_t, T, C,
-                                                                        sizes_dev, blank, K, cutoff_top_n, cutoff_prob, PC, PK, HT, labels,
-                                                                        offsets, lens, scores, (int*)nodes, nullptr,
-                                                                        Streamed<LmArgs>{la, sa});
-  }
-  const size_t total = hot_layout_total(lay, nbl);
-  DS2_REQUIRE(total <= 160 * 1024, "%s: LDS layout of %zu bytes (%zu of them hotword state) does not fit the 160 KiB at beam_width %d, %d classes",
-              who, total, 2 * hot_state_bytes(K), K, C);
-  return beam_launch<ctc_beam_kernel<false, true, Streamed<HotArgs>>>("ctc_beam_kernel<HOT, STREAM>", B, total, stream, probs, ld_b, ld_t, T, C,
-                                                                       sizes_dev, blank, K, cutoff_top_n, cutoff_prob, PC, PK, HT, labels,
-                                                                       offsets, lens, scores, (int*)nodes, nullptr,
-                                                                       Streamed<HotArgs>{HotArgs{la, hot_dev}, sa});
+  BeamPlan p;
+  if (int rc = beam_plan(p, who, C, blank, K, cutoff_top_n, lm_dev, lm_bytes, lm_order, lm_mode, space, alpha, beta, hot_dev, hot_host, hot_bytes))
+    return rc;
+  const StreamArgs sa{(char*)state, stream_stride(K, lm, hot), cap_frames, n_out, n_out > 0 ? W : 0, stable_len, frames};
+  return beam_dispatch(p, BeamCall{probs, ld_b, ld_t, B, T, C, sizes_dev, blank, cutoff_top_n, cutoff_prob, labels, offsets, lens, scores,
+                                   (int*)nodes, stream}, &sa);
 }
 
 extern "C" int ds2_ctc_beam_stream_feed_f32(const float* probs, long long ld_b, long long ld_t, int B, int T, int C, const int* sizes_dev,

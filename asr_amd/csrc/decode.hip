@@ -93,7 +93,7 @@ extern "C" int ds2_greedy_decode_f32(const float* probs, long long ld_b, long lo
 // list is left as it is because bench.py's recurrence-source hash covers the Makefile.
 #define DS2_CTC_BEAM_TU
 #include "ctc_beam.h"
-#include "ctc_beam_stream.h"   // the streaming instances of the same kernel (ds2_ctc_beam_stream_*)
+#include "ctc_beam_stream.h"   // the streaming instances of the same kernel, ctc_beam_kernel<PROF, Streamed<Arm>> (ds2_ctc_beam_stream_*)
 #include "ctc_beam_commit.h"   // commit and compaction of a stream's back-pointers (ds2_ctc_beam_stream_commit)
 
 // The batched edit distance of the WER / CER scoring (ds2_edit_distance_*) is compiled here as well, for the same reason.
