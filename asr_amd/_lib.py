@@ -156,6 +156,13 @@ SIGNATURES = {
     "ds2_lm_score_seqs": (i32, [vp, i64, vp, vp, i32, i32, vp, vp, sz, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
     "ds2_lm_score_seq_host": (i32, [vp, sz, vp, i32, i32, i32, i32, i32, C.POINTER(f32), C.POINTER(i32), C.POINTER(i32)]),
     "ds2_nbest_sweep": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, f32, vp, i32, vp, i32, vp, vp, vp]),
+    "ds2_ngram_max_order": (i32, [i32]),
+    "ds2_ngram_glob_words": (i32, []),
+    "ds2_ngram_count": (i32, [vp, i64, vp, i64, i32, i32, vp, vp, vp, vp, vp]),
+    "ds2_ngram_adjust": (i32, [i32, i32, vp, vp, vp, vp, vp]),
+    "ds2_ngram_discounts": (i32, [i32, vp, vp, vp, vp, vp, C.POINTER(f64)]),
+    "ds2_ngram_probs": (i32, [i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "ds2_ngram_estimate_host": (i32, [vp, i64, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(f64)]),
     "ds2_ctc_hot_packed_bytes": (sz, [i32, i32]),
     "ds2_ctc_hot_pack": (i32, [i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, sz]),
     "ds2_ctc_hot_step": (i32, [vp, i32, i32, C.POINTER(i32), C.POINTER(f32)]),

@@ -111,3 +111,7 @@ extern "C" int ds2_greedy_decode_f32(const float* probs, long long ld_b, long lo
 // The LM term of finished label sequences and the (alpha, beta) sweep over n-best features (ds2_lm_score_*, ds2_nbest_sweep), likewise.
 #define DS2_LM_SCORE_TU
 #include "lm_score.h"
+
+// The estimation of the n-gram models those read (ds2_ngram_*): counting tables, adjusted counts, Kneser-Ney probabilities, likewise.
+#define DS2_NGRAM_TRAIN_TU
+#include "ngram_train.h"

@@ -369,11 +369,42 @@ class BeamCTCDecoder(Decoder):
         self.lm = None
         if lm_path is not None:
             from .lm import NgramLM
-            space = self.space_index if self.int_to_char.get(self.space_index) == " " else next(
-                (i for i, c in sorted(self.int_to_char.items()) if c == " "), None)
-            self.lm = NgramLM(lm_path, self.int_to_char, self.blank_index, space)
+            self.lm = NgramLM(lm_path, self.int_to_char, self.blank_index, self._space_label())
         self.hotwords, self.hotword_weight = None, hotword_weight
         self.set_hotwords(hotwords)
+
+    def _space_label(self):
+        """the id of the space label, None when the labels have none"""
+        return self.space_index if self.int_to_char.get(self.space_index) == " " else next(
+            (i for i, c in sorted(self.int_to_char.items()) if c == " "), None)
+
+    def fit_lm(self, sentences, order=3, mode=None, path=None, alpha=None, beta=None, device=None):
+        """Estimate an n-gram model from `sentences` (strings spelt with this decoder's labels), write it as an ARPA file and load it as
+        this decoder's language model, as `lm_path=` would: -> the lm_train.NgramEstimate.  mode: "word" or "char"; by default "word"
+        when the labels have a space and "char" when they have none.  A character model covers the labels only (other characters are
+        dropped) and spells the space as U+2581.  path: where the file is kept (.gz compresses); by default a temporary file that is
+        removed once loaded.  alpha / beta, when given, replace the decoder's weights; device as estimate_ngram takes it.  Which order
+        and weights serve real recordings is unmeasured: tune_decoder / tune_lm_weights find the weights."""
+        import os
+        import tempfile
+        from .lm import NgramLM
+        from .lm_train import estimate_ngram
+        space = self._space_label()
+        mode = ("word" if space is not None else "char") if mode is None else mode
+        labels = [c for i, c in sorted(self.int_to_char.items()) if i != self.blank_index]
+        est = estimate_ngram(sentences, order=order, mode=mode, labels=labels if mode == "char" else None, device=device)
+        if path is None:
+            with tempfile.TemporaryDirectory() as d:
+                lm = NgramLM(est.write_arpa(os.path.join(d, "fit_lm.arpa")), self.int_to_char, self.blank_index, space)
+            lm.path = None
+        else:
+            lm = NgramLM(est.write_arpa(path), self.int_to_char, self.blank_index, space)
+        self.lm, self.lm_path = lm, path
+        if alpha is not None:
+            self.alpha = alpha
+        if beta is not None:
+            self.beta = beta
+        return est
 
     def set_hotwords(self, hotwords, hotword_weight=None):
         """Replace the hotword list (None or an empty list: no hotwords); hotword_weight, when given, becomes the default weight."""

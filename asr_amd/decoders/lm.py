@@ -131,7 +131,8 @@ class NgramLM:
                 self.label_tok[i] = self.vocab.get(ch, -1)
             char_label.setdefault(ch, i)
         if self.mode == MODE_CHAR and space is not None and 0 <= space < C:
-            self.label_tok[space] = self.vocab.get(" ", -1)
+            # no file can list " " (lines are split on whitespace): a character model spells the space as U+2581 (lm_train.SPACE_TOKEN)
+            self.label_tok[space] = self.vocab.get(" ", self.vocab.get("▁", -1))
         edges, node_word = {}, [-1]
         self.dictionary = set()
         if self.mode == MODE_WORD:

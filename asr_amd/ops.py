@@ -2030,6 +2030,164 @@ def nbest_sweep(ac: Tensor, lm_sum: Tensor, n_tok: Tensor, n_oov: Tensor, err: T
     return pick, total
 
 
+NGRAM_FALLBACK = (0.5, 1.0, 1.5)
+
+
+def ngram_max_order(n_vocab: int) -> int:
+    """the largest order whose n-grams over n_vocab ids (the three specials included) fit the 64-bit key, at most 6"""
+    return int(_lib.load().ds2_ngram_max_order(int(n_vocab)))
+
+
+def ngram_positions(lengths, order: int):
+    """how many n-grams of each order 1..order the framed sentences hold: a sentence of L > 0 tokens has L + 3 - n of order n"""
+    L = np.asarray(lengths, dtype=np.int64)
+    L = L[L > 0]
+    return [int(np.maximum(L + 3 - n, 0).sum()) for n in range(1, order + 1)]
+
+
+def ngram_slots(positions, n_vocab: int, order: int):
+    """the slots of each order's counting table: a power of two of at least twice min(positions, n_vocab^n), so never more than half full"""
+    return [max(2, 1 << (2 * min(int(positions[n - 1]), int(n_vocab) ** n) - 1).bit_length()) for n in range(1, order + 1)]
+
+
+def _ngram_args(who, n_tokens, lengths, n_vocab, order, discount_fallback):
+    """The host path of both estimators: the checks every entry shares -> (order, n_vocab, fallback (3) float64).  lengths: the sentence
+    lengths on the host (offsets' differences)."""
+    if not _is_int(order, 1, 6):
+        raise ValueError(f"{who}: order must be an integer in [1, 6], got {order!r}")
+    if not _is_int(n_vocab, 4, 2 ** 31 - 1):
+        raise ValueError(f"{who}: n_vocab must be an integer of at least 4 (<unk>, <s>, </s> and one token), got {n_vocab!r}")
+    order, n_vocab = int(order), int(n_vocab)
+    top = ngram_max_order(n_vocab)
+    if order > top:
+        raise ValueError(f"{who}: order {order} over {n_vocab} ids does not fit the 64-bit n-gram key: "
+                         f"this vocabulary admits order {top} at most")
+    fb = np.asarray(discount_fallback, dtype=np.float64).reshape(-1)
+    if fb.shape != (3,) or not all(0.0 <= fb[k] <= k + 1 for k in range(3)):
+        raise ValueError(f"{who}: discount_fallback must be three discounts with D_k in [0, k], got {discount_fallback!r}")
+    lengths = np.asarray(lengths)
+    if lengths.size < 1 or lengths.min() < 0 or int(lengths.sum()) != n_tokens or n_tokens < 1:
+        raise ValueError(f"{who}: offsets must ascend from 0 to the number of tokens, and there must be at least one token")
+    if n_tokens + 2 * lengths.size >= 2 ** 31 - 1:
+        raise ValueError(f"{who}: {n_tokens} tokens in {lengths.size} sentences exceed the 2^31 framed positions of one call")
+    return order, n_vocab, np.ascontiguousarray(fb)
+
+
+def _ngram_discounts(order, glob_host, fb):
+    """ds2_ngram_discounts on a host copy of glob -> (D (order,4), fell_back (order), coc (order,4), log10 p(<unk>))"""
+    D, fell, coc = np.zeros((order, 4), np.float64), np.zeros(order, np.int32), np.zeros((order, 4), np.int64)
+    unk = C.c_double()
+    _lib.check(_lib.load().ds2_ngram_discounts(order, glob_host.ctypes.data, fb.ctypes.data, D.ctypes.data, fell.ctypes.data, coc.ctypes.data,
+                                               C.byref(unk)), "ds2_ngram_discounts")
+    return D, fell, coc, unk.value
+
+
+def _ngram_result(order, n_vocab, per_order, D, fell, coc, unk):
+    return {"order": order, "n_vocab": n_vocab, "bits": (n_vocab - 1).bit_length(), "orders": per_order, "discounts": D[:, 1:].copy(),
+            "count_of_counts": coc, "fallback_orders": [n + 1 for n in range(order) if fell[n]], "unk_log10": float(unk)}
+
+
+def _ptr_array(ptrs):
+    return (C.c_void_p * len(ptrs))(*ptrs)
+
+
+def ngram_count(tokens: Tensor, offsets: Tensor, n_vocab: int, order: int = 3, discount_fallback=NGRAM_FALLBACK, slots=None):
+    """The counting launch of ngram_estimate (contract: include/ds2hip.h, ds2_ngram_count): tokens flat int32 and offsets int64 on the
+    GPU -> the state ngram_solve and ngram_collect take: per-order tables keys (slots) i64, vals (slots, 8) i32, prob (slots, 2) f64, and
+    glob.  slots: per-order table sizes (powers of two) instead of ngram_slots', for the tests."""
+    if not torch.is_tensor(tokens) or not tokens.is_cuda:
+        raise ValueError("ngram_count: tokens must be a GPU tensor (ngram_estimate_host is the estimator without one)")
+    dev = tokens.device
+    _chk_on_dev("ngram_count", dev, torch.int32, {"tokens": tokens})
+    _chk_on_dev("ngram_count", dev, torch.int64, {"offsets": offsets})
+    if tokens.dim() != 1 or offsets.dim() != 1 or offsets.numel() < 2:
+        raise ValueError("ngram_count: tokens and offsets must be one-dimensional, offsets with one entry per sentence and one more")
+    lengths = offsets.diff().cpu().numpy()
+    if int(offsets[0]) != 0:
+        raise ValueError("ngram_count: offsets must start at 0")
+    order, n_vocab, fb = _ngram_args("ngram_count", tokens.numel(), lengths, n_vocab, order, discount_fallback)
+    slots = ngram_slots(ngram_positions(lengths, order), n_vocab, order) if slots is None else [int(s) for s in slots]
+    if len(slots) != order or any(s < 2 or s > 2 ** 30 or s & (s - 1) for s in slots):
+        raise ValueError(f"ngram_count: slots must be {order} powers of two in [2, 2^30], got {slots}")
+    lib = _lib.load()
+    st = {"order": order, "n_vocab": n_vocab, "fallback": fb, "slots": slots, "device": dev,
+          "keys": [torch.empty(s, dtype=torch.int64, device=dev) for s in slots],
+          "vals": [torch.empty((s, 8), dtype=torch.int32, device=dev) for s in slots],
+          "prob": [torch.empty((s, 2), dtype=torch.float64, device=dev) for s in slots],
+          "glob": torch.empty(lib.ds2_ngram_glob_words(), dtype=torch.int64, device=dev)}
+    st["c_slots"] = np.array(slots, dtype=np.int64)
+    st["c_keys"], st["c_vals"], st["c_prob"] = (_ptr_array([t.data_ptr() for t in st[k]]) for k in ("keys", "vals", "prob"))
+    _lib.check(lib.ds2_ngram_count(tokens.data_ptr(), tokens.numel(), offsets.data_ptr(), offsets.numel() - 1, n_vocab, order,
+                                   st["c_slots"].ctypes.data, st["c_keys"], st["c_vals"], st["glob"].data_ptr(), _stream()), "ds2_ngram_count")
+    return st
+
+
+def ngram_solve(st):
+    """The adjusted-count launches, the discounts (on the host, from the 4 x order count-of-counts: one small download) and the
+    probability launches on ngram_count's state; a flag the kernels set (a full table, a bad token id) raises here."""
+    lib = _lib.load()
+    order, n_vocab = st["order"], st["n_vocab"]
+    _lib.check(lib.ds2_ngram_adjust(n_vocab, order, st["c_slots"].ctypes.data, st["c_keys"], st["c_vals"], st["glob"].data_ptr(), _stream()),
+               "ds2_ngram_adjust")
+    glob_host = np.ascontiguousarray(st["glob"].cpu().numpy().view(np.uint64))
+    st["D"], st["fell"], st["coc"], st["unk"] = _ngram_discounts(order, glob_host, st["fallback"])
+    _lib.check(lib.ds2_ngram_probs(n_vocab, order, st["c_slots"].ctypes.data, st["c_keys"], st["c_vals"], st["c_prob"], st["glob"].data_ptr(),
+                                   st["D"].ctypes.data, _stream()), "ds2_ngram_probs")
+    glob_host = st["glob"].cpu().numpy().view(np.uint64)
+    if glob_host[6]:
+        raise _lib.DS2LibraryError("ngram_solve: internal error: a context or suffix of a counted n-gram is in no table")
+    return st
+
+
+def ngram_collect(st):
+    """The distinct entries of every order of a solved state, sorted by key on the device (which slot a key took varies from run to run;
+    the sorted arrays do not), on the host: the dictionary ngram_estimate returns."""
+    per_order = []
+    for keys, vals, prob in zip(st["keys"], st["vals"], st["prob"]):
+        idx = torch.nonzero(keys).view(-1)
+        k = keys[idx]
+        srt = torch.sort(k ^ torch.iinfo(torch.int64).min)          # unsigned order of the 64-bit keys
+        idx = idx[srt.indices]
+        v, p = vals[idx][:, :3].cpu().numpy(), prob[idx].cpu().numpy()
+        per_order.append((k[srt.indices].cpu().numpy().view(np.uint64), v[:, 0].astype(np.int64), v[:, 2].astype(np.int64),
+                          np.ascontiguousarray(p[:, 0]), np.ascontiguousarray(p[:, 1])))
+    return _ngram_result(st["order"], st["n_vocab"], per_order, st["D"], st["fell"], st["coc"], st["unk"])
+
+
+def ngram_estimate(tokens: Tensor, offsets: Tensor, n_vocab: int, order: int = 3, discount_fallback=NGRAM_FALLBACK, slots=None):
+    """An interpolated modified-Kneser-Ney model from sentences of token ids, on the GPU (contract: include/ds2hip.h, ds2_ngram_*):
+    tokens flat int32 with ids in [3, n_vocab) (0 <unk>, 1 <s>, 2 </s> are the kernel's), sentence s is tokens[offsets[s]:offsets[s+1]].
+    -> {"orders": per order n, sorted by key: (keys u64, count, adjusted, log10_prob, log10_backoff (NaN: none)), "discounts" (order, 3),
+    "count_of_counts" (order, 4), "fallback_orders", "unk_log10", "bits": the bits of one token in a key (the oldest token highest)}."""
+    return ngram_collect(ngram_solve(ngram_count(tokens, offsets, n_vocab, order, discount_fallback, slots)))
+
+
+def ngram_estimate_host(tokens, offsets, n_vocab: int, order: int = 3, discount_fallback=NGRAM_FALLBACK):
+    """ngram_estimate's host twin (ds2_ngram_estimate_host: std::unordered_map and the same formula routines): tokens int32 and offsets
+    int64 NumPy arrays -> the same dictionary.  No GPU is needed."""
+    tokens = np.ascontiguousarray(np.asarray(tokens, dtype=np.int32).reshape(-1))
+    offsets = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1))
+    if offsets.size < 2 or offsets[0] != 0:
+        raise ValueError("ngram_estimate_host: offsets must start at 0 and have one entry per sentence and one more")
+    lengths = np.diff(offsets)
+    order, n_vocab, fb = _ngram_args("ngram_estimate_host", tokens.size, lengths, n_vocab, order, discount_fallback)
+    cap = np.array([max(1, min(p, n_vocab ** n)) for n, p in enumerate(ngram_positions(lengths, order), 1)], dtype=np.int64)
+    keys = [np.zeros(c, np.uint64) for c in cap]
+    count, adj = [np.zeros(c, np.uint32) for c in cap], [np.zeros(c, np.uint32) for c in cap]
+    lp, lb = [np.zeros(c, np.float64) for c in cap], [np.zeros(c, np.float64) for c in cap]
+    n_distinct = np.zeros(order, np.int64)
+    D, fell, coc = np.zeros((order, 4), np.float64), np.zeros(order, np.int32), np.zeros((order, 4), np.int64)
+    unk = C.c_double()
+    arr = lambda xs: _ptr_array([x.ctypes.data for x in xs])   # noqa: E731
+    _lib.check(_lib.load().ds2_ngram_estimate_host(tokens.ctypes.data, tokens.size, offsets.ctypes.data, offsets.size - 1, n_vocab, order,
+                                                   fb.ctypes.data, cap.ctypes.data, arr(keys), arr(count), arr(adj), arr(lp), arr(lb),
+                                                   n_distinct.ctypes.data, coc.ctypes.data, D.ctypes.data, fell.ctypes.data, C.byref(unk)),
+               "ds2_ngram_estimate_host")
+    per_order = [(keys[n][:d].copy(), count[n][:d].astype(np.int64), adj[n][:d].astype(np.int64), lp[n][:d].copy(), lb[n][:d].copy())
+                 for n, d in enumerate(n_distinct.tolist())]
+    return _ngram_result(order, n_vocab, per_order, D, fell, coc, unk.value)
+
+
 _BASIS_CACHE = {}
 
 

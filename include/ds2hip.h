@@ -786,7 +786,9 @@ int ds2_ctc_beam_decode_f32(const float* probs, long long ld_b, long long ld_t, 
  *    word (no leading or double space): any other extension is -inf.  Appending the space adds alpha*lm(word | ctx) + beta to
  *    that extension's contribution.  After the last frame every surviving non-empty beam not ending in a space gets
  *    alpha*lm(partial | ctx) + beta (OOV when partial is no dictionary word) and the survivors are re-sorted by the order above;
- *  - character mode: every non-blank extension l -> l+c adds alpha*lm(char(c) | ctx) + beta; no dictionary, no end term;
+ *  - character mode: every non-blank extension l -> l+c adds alpha*lm(char(c) | ctx) + beta; no dictionary, no end term.  An ARPA
+ *    line is split on whitespace, so no file can hold the token " ": a character model spells the space as U+2581 (LOWER ONE EIGHTH
+ *    BLOCK), and the loader gives the space label that token (models without it price a space as OOV, as before);
  *  - everything else is the contract above: the LM terms ride in pnb of the extension, so pb / pnb / total include every bonus
  *    so far (the bonus depends only on the prefix, so merging stays exact), and scores are the fused totals.  ctcdecode's
  *    min_cutoff heuristic and its "approx_ctc" returned score are deliberately left out.
@@ -847,6 +849,54 @@ int ds2_lm_score_seq_host(const void* packed, size_t packed_bytes, const int* la
  * One launch (and one memset of total); nothing of size N * K * Ga * Gb is stored.  N may be 0 (totals of 0). */
 int ds2_nbest_sweep(const float* ac, const float* lm_sum, const int* n_tok, const int* n_oov, const int* err, int N, int K, int R,
                     float oov_score, const float* alphas, int Ga, const float* betas, int Gb, int* pick, long long* total, void* stream);
+
+/* Estimation of the n-gram models the entries above read: interpolated modified Kneser-Ney from sentences of token ids
+ * (csrc/ngram_train.h; restated in fp64 by tests/ngram_train_oracle.py; asr_amd/decoders/lm_train.py tokenises and writes the ARPA
+ * file).  Byte parity with KenLM's lmplz is not pinned; pruning, count thresholds and model interpolation are not offered.
+ * Input: tokens flat int32, offsets (n_sent + 1) int64 ascending from 0 to n_tokens; ids 0 = <unk> (never in the input), 1 = <s>,
+ * 2 = </s>, tokens in [3, n_vocab).  N the order, 1 <= N <= 6.
+ *  - framing: a sentence is its tokens between one <s> and one </s>; a sentence without tokens is skipped; no n-gram spans two;
+ *  - raw counts c_n(g), n = 1..N, over the framed sentences;
+ *  - adjusted counts: a_N = c_N; for n < N, a_n(g) = c_n(g) if g[0] = <s> and n >= 2, else |{v : c_{n+1}(v g) > 0}|; a_1(<s>) = 0 at
+ *    every N;
+ *  - discounts of order n: t_k = |{g : a_n(g) = k}|, k = 1..4 (the count-of-counts); Y = t_1 / (t_1 + 2 t_2);
+ *    D_{n,k} = k - (k + 1) Y t_{k+1} / t_k, k = 1..3; D_{n,0} = 0, counts >= 3 use D_{n,3}.  When a t_k is 0 or a D_{n,k} is outside
+ *    [0, k] the order FALLS BACK to the caller's three discounts (each within [0, k]);
+ *  - a context h of n - 1 tokens has S_n(h) = sum_w a_n(h w), N_{n,k}(h) = |{w : a_n(h w) = k}| (k = 3: >= 3), and
+ *    gamma_n(h) = ((D_1 N_1 + D_2 N_2) + D_3 N_3) / S_n(h);
+ *  - V = every token seen, </s> and <unk>, without <s>; p_1(w) = (a_1(w) - D) / S_1 + gamma_1 / |V|, a_1(<unk>) = 0;
+ *    p_n(w | h) = (a_n(h w) - D) / S_n(h) + gamma_n(h) * p_{n-1}(w | h[1:]) for every counted h w; all in fp64;
+ *  - listed per counted g: log10 p (-99 for <s>), and log10 gamma_{n+1}(g) as its backoff when n < N, g does not end in </s> and
+ *    S_{n+1}(g) > 0 (a gamma of 0 is -99), else none (NaN in these arrays); <unk> is log10(gamma_1 / |V|).
+ * Keys: an n-gram is n * b bits of one 64-bit word, b the bit width of n_vocab - 1, the oldest token highest, so keys of one order sort
+ * as their token ids do; n * b > 64 is refused (ds2_ngram_max_order(n_vocab) is the largest order admitted).  No key is 0.
+ * Device tables, one per order n, caller-allocated: keys (slots[n-1] x u64), vals (slots x 8 uint32: c, lext, adjusted, S, N_1, N_2,
+ * N_3, unused; the last four describe the entry AS A CONTEXT of order n + 1), prob (slots x 2 fp64: log10 p, log10 backoff); slots a
+ * power of two in [2, 2^30], at least the distinct n-grams of that order (twice min(positions, n_vocab^n) is what ops.py takes);
+ * glob: ds2_ngram_glob_words() u64 words (flags: 0 overflow, 5 bad input, 6 missing entry; 1..4 the empty context's S_1, N_{1,k};
+ * 7 the distinct 1-grams = |V|; 8 + 4 (n - 1) + (k - 1) = t_k of order n).  All accumulation is integer atomics: the values do not
+ * depend on arrival order, the slot of a key does, so callers sort the live slots (key != 0) by key.  Probe loops run at most `slots`
+ * steps and then set a flag.
+ *   ds2_ngram_count      clears the tables and glob, then one launch: a lane per token position inserts the n-grams ending there
+ *                        (64-bit compare-and-swap on the key, integer atomic on c); <s> and </s> come from the offsets;
+ *   ds2_ngram_adjust     N launches, order N down to 1: adjusted counts, left extensions of the suffix, sums of the context, t_k;
+ *   ds2_ngram_discounts  HOST: from a copy of glob, D (order x 4), fell_back (order), coc (order x 4), log10 p(<unk>); refuses a set flag;
+ *   ds2_ngram_probs      N launches, order 1 up to N, then N that take the logarithms; D as ds2_ngram_discounts gave it (host);
+ *   ds2_ngram_estimate_host  the whole estimator on the host (std::unordered_map, the same formula routines): per order, cap[n-1]
+ *                        rows of room, n_distinct[n-1] rows written in key order: keys, count, adjusted, log10 p, log10 backoff. */
+int ds2_ngram_max_order(int n_vocab);
+int ds2_ngram_glob_words(void);
+int ds2_ngram_count(const int* tokens, long long n_tokens, const long long* offsets, long long n_sent, int n_vocab, int order,
+                    const long long* slots, void* const* keys, void* const* vals, void* glob, void* stream);
+int ds2_ngram_adjust(int n_vocab, int order, const long long* slots, void* const* keys, void* const* vals, void* glob, void* stream);
+int ds2_ngram_discounts(int order, const unsigned long long* glob_host, const double* fallback, double* D, int* fell_back, long long* coc,
+                        double* unk_log10);
+int ds2_ngram_probs(int n_vocab, int order, const long long* slots, void* const* keys, void* const* vals, void* const* prob, void* glob,
+                    const double* D, void* stream);
+int ds2_ngram_estimate_host(const int* tokens, long long n_tokens, const long long* offsets, long long n_sent, int n_vocab, int order,
+                            const double* fallback, const long long* cap, unsigned long long* const* keys_out, unsigned* const* count_out,
+                            unsigned* const* adjusted_out, double* const* lp_out, double* const* bow_out, long long* n_distinct,
+                            long long* coc, double* D, int* fell_back, double* unk_log10);
 
 /* The same search with hotword boosting: the caller names a few phrases and the search prefers prefixes that spell them, with or
  * without the LM above (asr_amd/decoders/hotwords.py builds the automaton; restated by tests/ctc_beam_hot_oracle.py).  Parity with
