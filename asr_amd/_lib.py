@@ -163,6 +163,16 @@ SIGNATURES = {
     "ds2_ngram_discounts": (i32, [i32, vp, vp, vp, vp, vp, C.POINTER(f64)]),
     "ds2_ngram_probs": (i32, [i32, i32, vp, vp, vp, vp, vp, vp, vp]),
     "ds2_ngram_estimate_host": (i32, [vp, i64, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(f64)]),
+    "ds2_ngram_eval": (i32, [vp, i64, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "ds2_ngram_eval_host": (i32, [vp, i64, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp]),
+    "ds2_ngram_prune_sums": (i32, [i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, i64, vp]),
+    "ds2_ngram_prune_sums_host": (i32, [i32, i32, vp, vp, vp, vp, i32, vp, vp, vp]),
+    "ds2_ngram_prune_entropy": (i32, [i32, i32, vp, vp, vp, vp, vp, vp, vp, f64, vp, vp, vp]),
+    "ds2_ngram_prune_entropy_host": (i32, [i32, i32, vp, vp, vp, vp, vp, vp, vp, f64, vp, vp]),
+    "ds2_ngram_prune_closure": (i32, [i32, i32, vp, vp, vp, vp, i32, vp, vp, vp]),
+    "ds2_ngram_prune_closure_host": (i32, [i32, i32, vp, vp, vp, vp, i32, vp, vp]),
+    "ds2_ngram_prune_backoff": (i32, [i64, vp, vp, vp, vp]),
+    "ds2_ngram_prune_backoff_host": (i32, [i64, vp, vp, vp]),
     "ds2_ctc_hot_packed_bytes": (sz, [i32, i32]),
     "ds2_ctc_hot_pack": (i32, [i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, sz]),
     "ds2_ctc_hot_step": (i32, [vp, i32, i32, C.POINTER(i32), C.POINTER(f32)]),

@@ -115,3 +115,5 @@ extern "C" int ds2_greedy_decode_f32(const float* probs, long long ld_b, long lo
 // The estimation of the n-gram models those read (ds2_ngram_*): counting tables, adjusted counts, Kneser-Ney probabilities, likewise.
 #define DS2_NGRAM_TRAIN_TU
 #include "ngram_train.h"
+// and their evaluation and pruning on the same sorted-key representation (ds2_ngram_eval, ds2_ngram_prune_*)
+#include "ngram_prune.h"

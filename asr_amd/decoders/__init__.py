@@ -378,13 +378,15 @@ class BeamCTCDecoder(Decoder):
         return self.space_index if self.int_to_char.get(self.space_index) == " " else next(
             (i for i, c in sorted(self.int_to_char.items()) if c == " "), None)
 
-    def fit_lm(self, sentences, order=3, mode=None, path=None, alpha=None, beta=None, device=None):
+    def fit_lm(self, sentences, order=3, mode=None, path=None, alpha=None, beta=None, device=None, prune=None, min_count=None):
         """Estimate an n-gram model from `sentences` (strings spelt with this decoder's labels), write it as an ARPA file and load it as
         this decoder's language model, as `lm_path=` would: -> the lm_train.NgramEstimate.  mode: "word" or "char"; by default "word"
         when the labels have a space and "char" when they have none.  A character model covers the labels only (other characters are
         dropped) and spells the space as U+2581.  path: where the file is kept (.gz compresses); by default a temporary file that is
-        removed once loaded.  alpha / beta, when given, replace the decoder's weights; device as estimate_ngram takes it.  Which order
-        and weights serve real recordings is unmeasured: tune_decoder / tune_lm_weights find the weights."""
+        removed once loaded.  alpha / beta, when given, replace the decoder's weights; device as estimate_ngram takes it.  prune (an
+        entropy threshold) and min_count (count cuts per order) shrink the model before it is written: NgramEstimate.prune, whose
+        perplexity() on held-out text is how to choose them.  Which order, threshold and weights serve real recordings is unmeasured:
+        tune_decoder / tune_lm_weights find the weights."""
         import os
         import tempfile
         from .lm import NgramLM
@@ -392,7 +394,8 @@ class BeamCTCDecoder(Decoder):
         space = self._space_label()
         mode = ("word" if space is not None else "char") if mode is None else mode
         labels = [c for i, c in sorted(self.int_to_char.items()) if i != self.blank_index]
-        est = estimate_ngram(sentences, order=order, mode=mode, labels=labels if mode == "char" else None, device=device)
+        est = estimate_ngram(sentences, order=order, mode=mode, labels=labels if mode == "char" else None, device=device, prune=prune,
+                             min_count=min_count)
         if path is None:
             with tempfile.TemporaryDirectory() as d:
                 lm = NgramLM(est.write_arpa(os.path.join(d, "fit_lm.arpa")), self.int_to_char, self.blank_index, space)

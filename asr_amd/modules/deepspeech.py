@@ -633,7 +633,8 @@ class DeepSpeech(nn.Module):
                     self.decoder, decoder.alpha, decoder.beta = kept
         return result
 
-    def fit_lm(self, manifest, order=3, mode=None, path=None, alpha=None, beta=None, decoder=None, device=None):
+    def fit_lm(self, manifest, order=3, mode=None, path=None, alpha=None, beta=None, decoder=None, device=None, prune=None,
+               min_count=None):
         """Estimate an n-gram language model from the `text` column of a manifest CSV and load it into a BeamCTCDecoder (None:
         self.decoder): BeamCTCDecoder.fit_lm on the transcripts, whose arguments these are.  Returns the NgramEstimate.  The transcripts
         should be spelt as the labels spell them (the manifests the loaders read are).  tune_decoder then finds alpha and beta."""
@@ -642,7 +643,8 @@ class DeepSpeech(nn.Module):
         decoder = self.decoder if decoder is None else decoder
         if not isinstance(decoder, BeamCTCDecoder):
             raise ValueError("fit_lm: the decoder must be a BeamCTCDecoder")
-        return decoder.fit_lm(manifest_sentences(manifest), order=order, mode=mode, path=path, alpha=alpha, beta=beta, device=device)
+        return decoder.fit_lm(manifest_sentences(manifest), order=order, mode=mode, path=path, alpha=alpha, beta=beta, device=device,
+                              prune=prune, min_count=min_count)
 
     def __call__(self, *args, **kwargs):
         """The reference overrides __call__ with its eval loop (deepspeech.py:161).  Keep that calling

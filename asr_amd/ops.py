@@ -2139,19 +2139,223 @@ def ngram_solve(st):
     return st
 
 
-def ngram_collect(st):
-    """The distinct entries of every order of a solved state, sorted by key on the device (which slot a key took varies from run to run;
-    the sorted arrays do not), on the host: the dictionary ngram_estimate returns."""
-    per_order = []
+def _ngram_sorted(st):
+    """the distinct entries of every order of a solved state, sorted by key, still on the device: (keys i64, vals (rows, 3), prob (rows, 2))"""
+    out = []
     for keys, vals, prob in zip(st["keys"], st["vals"], st["prob"]):
         idx = torch.nonzero(keys).view(-1)
         k = keys[idx]
         srt = torch.sort(k ^ torch.iinfo(torch.int64).min)          # unsigned order of the 64-bit keys
         idx = idx[srt.indices]
-        v, p = vals[idx][:, :3].cpu().numpy(), prob[idx].cpu().numpy()
-        per_order.append((k[srt.indices].cpu().numpy().view(np.uint64), v[:, 0].astype(np.int64), v[:, 2].astype(np.int64),
+        out.append((k[srt.indices], vals[idx][:, :3], prob[idx]))
+    return out
+
+
+def ngram_collect(st):
+    """The distinct entries of every order of a solved state, sorted by key on the device (which slot a key took varies from run to run;
+    the sorted arrays do not), on the host: the dictionary ngram_estimate returns."""
+    per_order = []
+    for k, v, p in _ngram_sorted(st):
+        v, p = v.cpu().numpy(), p.cpu().numpy()
+        per_order.append((k.cpu().numpy().view(np.uint64), v[:, 0].astype(np.int64), v[:, 2].astype(np.int64),
                           np.ascontiguousarray(p[:, 0]), np.ascontiguousarray(p[:, 1])))
     return _ngram_result(st["order"], st["n_vocab"], per_order, st["D"], st["fell"], st["coc"], st["unk"])
+
+
+def ngram_collect_model(st):
+    """ngram_collect without the download: the model ngram_eval and ngram_prune take (see ngram_model), its arrays left on the device,
+    with what the estimator's dictionary holds beside its arrays under "meta"."""
+    dev = st["device"]
+    one = lambda v, dt: torch.tensor([v], dtype=dt, device=dev)   # noqa: E731   (the <unk> row: key 0 sorts first)
+    keys, lp, lb, count, adj = [], [], [], [], []
+    for n, (k, v, p) in enumerate(_ngram_sorted(st), 1):
+        c, a, x, y = v[:, 0].to(torch.int64), v[:, 2].to(torch.int64), p[:, 0].contiguous(), p[:, 1].contiguous()
+        if n == 1:
+            k, c, a = torch.cat([one(0, torch.int64), k]), torch.cat([one(0, torch.int64), c]), torch.cat([one(0, torch.int64), a])
+            x, y = torch.cat([one(st["unk"], torch.float64), x]), torch.cat([one(math.nan, torch.float64), y])
+        keys.append(k.contiguous()), lp.append(x), lb.append(y), count.append(c), adj.append(a)
+    meta = _ngram_result(st["order"], st["n_vocab"], [], st["D"], st["fell"], st["coc"], st["unk"])
+    return {"order": st["order"], "n_vocab": st["n_vocab"], "bits": meta["bits"], "keys": keys, "lp": lp, "lb": lb, "count": count,
+            "adjusted": adj, "meta": meta}
+
+
+def ngram_model(raw, device):
+    """The model ngram_eval and ngram_prune take, from the dictionary ngram_estimate returns (or one of the same layout whose counts are
+    None and whose "unk_log10" is None when the model lists no <unk>): per order, torch tensors on `device` (a GPU, or "cpu" for the host
+    twins): keys int64 (the u64 keys' bits, ascending as unsigned), lp, lb float64 (NaN: no backoff), count / adjusted int64 or None.
+    <unk> is row 0 of the 1-grams."""
+    dev = torch.device(device)
+    keys, lp, lb, count, adj = [], [], [], [], []
+    for n, (k, c, a, x, y) in enumerate(raw["orders"], 1):
+        k, x, y = np.asarray(k).view(np.int64), np.asarray(x, np.float64), np.asarray(y, np.float64)
+        if n == 1 and raw["unk_log10"] is not None:
+            k, x, y = np.concatenate([[0], k]), np.concatenate([[raw["unk_log10"]], x]), np.concatenate([[np.nan], y])
+            c, a = (None if v is None else np.concatenate([[0], v]) for v in (c, a))
+        keys.append(torch.from_numpy(np.ascontiguousarray(k, np.int64)).to(dev))
+        lp.append(torch.from_numpy(np.ascontiguousarray(x)).to(dev)), lb.append(torch.from_numpy(np.ascontiguousarray(y)).to(dev))
+        count.append(None if c is None else torch.from_numpy(np.ascontiguousarray(c, np.int64)).to(dev))
+        adj.append(None if a is None else torch.from_numpy(np.ascontiguousarray(a, np.int64)).to(dev))
+    meta = {k: v for k, v in raw.items() if k != "orders"}
+    return {"order": raw["order"], "n_vocab": raw["n_vocab"], "bits": raw["bits"], "keys": keys, "lp": lp, "lb": lb, "count": count,
+            "adjusted": adj, "meta": meta}
+
+
+def ngram_model_download(model):
+    """a model's arrays on the host in the layout of ngram_estimate's dictionary: the <unk> row leaves the 1-grams for "unk_log10" (None
+    when there is none), and "order" is the model's"""
+    per_order, unk = [], None
+    host = lambda t: None if t is None else t.cpu().numpy()   # noqa: E731
+    for n in range(model["order"]):
+        k, x, y, c, a = (host(model[f][n]) for f in ("keys", "lp", "lb", "count", "adjusted"))
+        if n == 0 and len(k) and k[0] == 0:
+            unk = float(x[0])
+            k, x, y, c, a = (None if v is None else v[1:] for v in (k, x, y, c, a))
+        per_order.append((np.ascontiguousarray(k).view(np.uint64), c, a, np.ascontiguousarray(x), np.ascontiguousarray(y)))
+    return {**model["meta"], "order": model["order"], "n_vocab": model["n_vocab"], "bits": model["bits"], "orders": per_order,
+            "unk_log10": unk}
+
+
+def _ngram_model_args(who, model):
+    """The host path of every entry that reads a model: its checks -> (device, the arguments every ds2_ngram_eval / _prune_* entry starts
+    or continues with: n_vocab, order, cnt, keys, lp, lb; keep `hold` alive across the call)"""
+    order, n_vocab = model["order"], model["n_vocab"]
+    if not _is_int(order, 1, 6) or len(model["keys"]) != order or len(model["lp"]) != order or len(model["lb"]) != order:
+        raise ValueError(f"{who}: the model must list keys, lp and lb for each of its {order!r} orders (1..6)")
+    if order * model["bits"] > 64 or model["bits"] != (n_vocab - 1).bit_length():
+        raise ValueError(f"{who}: order {order} over {n_vocab} ids does not fit the 64-bit n-gram key")
+    dev = model["keys"][0].device
+    for n in range(order):
+        k, x, y = model["keys"][n], model["lp"][n], model["lb"][n]
+        if not (k.dtype == torch.int64 and x.dtype == y.dtype == torch.float64 and k.dim() == 1 and k.shape == x.shape == y.shape):
+            raise ValueError(f"{who}: order {n + 1}: keys int64, lp and lb float64, one-dimensional and of one length")
+        if not (k.device == x.device == y.device == dev and k.is_contiguous() and x.is_contiguous() and y.is_contiguous()):
+            raise ValueError(f"{who}: order {n + 1}: the arrays must be contiguous and on one device")
+    hold = np.array([k.numel() for k in model["keys"]], dtype=np.int64)
+    args = (n_vocab, order, hold.ctypes.data, *(_ptr_array([t.data_ptr() for t in model[f]]) for f in ("keys", "lp", "lb")))
+    return dev, args, hold
+
+
+def _ngram_call(name, dev, *args):
+    """one ds2_ngram_eval / _prune_* entry: the kernels on a GPU (the stream is the last argument), the host twin for CPU tensors"""
+    lib = _lib.load()
+    if dev.type == "cpu":
+        _lib.check(getattr(lib, name + "_host")(*args), name + "_host")
+    else:
+        _lib.check(getattr(lib, name)(*args, _stream()), name)
+
+
+def ngram_eval(model, tokens: Tensor, offsets: Tensor):
+    """log10 p of every position of sentences of token ids under a model (contract: include/ds2hip.h, ds2_ngram_eval; ngram_model makes
+    the model): tokens flat int32 (0 = <unk>), offsets int64, both on the model's device.  -> (log10_prob float64, order int32), each of
+    tokens.numel() + n_sent positions: sentence s owns offsets[s] + s .. offsets[s+1] + s, its tokens and then </s>.  order is that of
+    the n-gram that was listed; 0, with NaN, where the token is no 1-gram of the model."""
+    dev, args, hold = _ngram_model_args("ngram_eval", model)
+    if not torch.is_tensor(tokens) or not torch.is_tensor(offsets) or tokens.device != dev or offsets.device != dev:
+        raise ValueError(f"ngram_eval: tokens and offsets must be tensors on the model's device ({dev})")
+    if tokens.dtype != torch.int32 or offsets.dtype != torch.int64 or tokens.dim() != 1 or offsets.dim() != 1 or offsets.numel() < 2:
+        raise ValueError("ngram_eval: tokens must be one-dimensional int32, offsets int64 with one entry per sentence and one more")
+    tokens, offsets = tokens.contiguous(), offsets.contiguous()
+    if int(offsets[0]) != 0 or int(offsets[-1]) != tokens.numel() or bool((offsets.diff() < 0).any()):
+        raise ValueError("ngram_eval: offsets must ascend from 0 to the number of tokens")
+    if tokens.numel() and (int(tokens.min()) < 0 or int(tokens.max()) >= model["n_vocab"]):
+        raise ValueError(f"ngram_eval: a token id outside [0, {model['n_vocab']})")
+    P = tokens.numel() + offsets.numel() - 1
+    if P >= 2 ** 31 - 1:
+        raise ValueError(f"ngram_eval: {P} positions exceed the 2^31 of one call")
+    lp = torch.empty(P, dtype=torch.float64, device=dev)
+    order = torch.empty(P, dtype=torch.int32, device=dev)
+    _ngram_call("ds2_ngram_eval", dev, tokens.data_ptr(), tokens.numel(), offsets.data_ptr(), offsets.numel() - 1, *args, lp.data_ptr(),
+                order.data_ptr())
+    return lp, order
+
+
+def _ngram_sums(model, n, want_q=False):
+    """ds2_ngram_prune_sums for the children of order n -> (sp, sq per row of order n - 1, q per row of order n or None)"""
+    dev, args, hold = _ngram_model_args("ngram_prune", model)
+    rows, ctx = model["keys"][n - 1].numel(), model["keys"][n - 2].numel()
+    sp, sq = torch.empty(ctx, dtype=torch.float64, device=dev), torch.empty(ctx, dtype=torch.float64, device=dev)
+    q = torch.empty(rows, dtype=torch.float64, device=dev) if want_q else None
+    tail = ()
+    if dev.type != "cpu":
+        scratch = torch.empty(4 * ((rows + 63) // 64), dtype=torch.float64, device=dev)
+        tail = (scratch.data_ptr(), scratch.numel())
+    _ngram_call("ds2_ngram_prune_sums", dev, *args, n, _ptr(q), sp.data_ptr(), sq.data_ptr(), *tail)
+    return sp, sq, q
+
+
+def ngram_prune_values(model, threshold: float):
+    """The entropy launch on a model (contract: include/ds2hip.h, ds2_ngram_prune_sums / _entropy) -> (val, mark): per order n (entry
+    n - 1; entry 0 is None) exp(dH) - 1 of removing each n-gram alone, float64, and whether it is below the threshold, bool."""
+    dev, args, hold = _ngram_model_args("ngram_prune", model)
+    try:                                                                 # (any real number: a NumPy scalar or a 0-d tensor as well)
+        theta = math.nan if isinstance(threshold, (bool, str, bytes)) else float(threshold)
+    except (TypeError, ValueError):
+        theta = math.nan
+    if not 0.0 < theta < math.inf:
+        raise ValueError(f"ngram_prune: threshold must be a positive number, got {threshold!r}")
+    threshold = theta
+    N = model["order"]
+    q, sp, sq, val, mark = ([None] * N for _ in range(5))
+    for n in range(2, N + 1):
+        sp[n - 1], sq[n - 1], q[n - 1] = _ngram_sums(model, n, want_q=True)
+        val[n - 1] = torch.empty_like(q[n - 1])
+        mark[n - 1] = torch.empty(q[n - 1].numel(), dtype=torch.uint8, device=dev)
+    arr = lambda ts: _ptr_array([0 if t is None else t.data_ptr() for t in ts])   # noqa: E731
+    _ngram_call("ds2_ngram_prune_entropy", dev, *args, arr(q), arr(sp), arr(sq), float(threshold), arr(val), arr(mark))
+    return val, [None if m is None else m.bool() for m in mark]
+
+
+def ngram_prune(model, threshold=None, min_count=None):
+    """Prune a model (contract: include/ds2hip.h, ds2_ngram_prune_*) -> a model of the same layout, or `model` itself when nothing is
+    marked.  min_count: `order` integers >= 1, non-decreasing, the first ignored: an n-gram of order n >= 2 whose raw count is below
+    min_count[n-1] is marked (the model must have counts).  threshold > 0: an n-gram of order >= 2 is marked when removing it alone
+    raises the model's perplexity by less than that fraction (on the model after the count cut, when both are given).  Then marked
+    n-grams that are the context of a kept one are kept, the kept rows are gathered (their lp bit for bit), and the backoffs of every
+    context that still has a child are recomputed bottom up; an order left empty is dropped."""
+    dev, _, _ = _ngram_model_args("ngram_prune", model)
+    N = model["order"]
+    if min_count is not None:
+        try:
+            mc = [int(c) for c in min_count]
+            ok = len(mc) == N and all(int(c) == c and not isinstance(c, bool) for c in min_count)
+        except (TypeError, ValueError):
+            mc, ok = [], False
+        if not ok or any(c < 1 for c in mc) or any(a > b for a, b in zip(mc[1:], mc[2:])):
+            raise ValueError(f"ngram_prune: min_count must be {N} integers >= 1 that do not decrease (the first is ignored), got {min_count!r}")
+        if any(c is None for c in model["count"]):
+            raise ValueError("ngram_prune: min_count needs a model that has counts (one estimated here, not one read from a file)")
+        marks = [None] + [model["count"][n - 1] < mc[n - 1] for n in range(2, N + 1)]
+        model = _ngram_cut(model, marks)
+    if threshold is None:
+        return model
+    _, marks = ngram_prune_values(model, threshold)
+    return _ngram_cut(model, marks[:model["order"]])
+
+
+def _ngram_cut(model, marks):
+    """closure, gathering of the kept rows and the new backoffs for the marks of one pruning mode (entry n - 1 for order n, bool)"""
+    dev, args, hold = _ngram_model_args("ngram_prune", model)
+    N = model["order"]
+    marks = [None if m is None else m.to(torch.uint8).contiguous() for m in marks]
+    for n in range(N, 2, -1):
+        _ngram_call("ds2_ngram_prune_closure", dev, *args, n, marks[n - 1].data_ptr(), marks[n - 2].data_ptr())
+    if not any(m is not None and bool(m.any()) for m in marks):
+        return model
+    keep = [None] + [m == 0 for m in marks[1:]]
+    take = lambda ts: [t if k is None or t is None else t[k].contiguous() for t, k in zip(ts, keep)]   # noqa: E731
+    new = {**model, **{f: take(model[f]) for f in ("keys", "lp", "lb", "count", "adjusted")}}
+    top = max(n for n in range(1, N + 1) if new["keys"][n - 1].numel() or n == 1)
+    new["order"] = top
+    for f in ("keys", "lp", "lb", "count", "adjusted"):
+        new[f] = new[f][:top]
+    new["lb"][top - 1] = torch.full_like(new["lb"][top - 1], math.nan)      # the highest order lists no backoff
+    for n in range(1, top):
+        # the contexts of order n from their kept children of order n + 1; q reads the orders up to n, whose backoffs below n are done
+        sp, sq, _ = _ngram_sums(new, n + 1)
+        lb = torch.empty_like(sp)
+        _ngram_call("ds2_ngram_prune_backoff", dev, sp.numel(), sp.data_ptr(), sq.data_ptr(), lb.data_ptr())
+        new["lb"][n - 1] = lb
+    return new
 
 
 def ngram_estimate(tokens: Tensor, offsets: Tensor, n_vocab: int, order: int = 3, discount_fallback=NGRAM_FALLBACK, slots=None):

@@ -852,7 +852,8 @@ int ds2_nbest_sweep(const float* ac, const float* lm_sum, const int* n_tok, cons
 
 /* Estimation of the n-gram models the entries above read: interpolated modified Kneser-Ney from sentences of token ids
  * (csrc/ngram_train.h; restated in fp64 by tests/ngram_train_oracle.py; asr_amd/decoders/lm_train.py tokenises and writes the ARPA
- * file).  Byte parity with KenLM's lmplz is not pinned; pruning, count thresholds and model interpolation are not offered.
+ * file).  Byte parity with KenLM's lmplz is not pinned; model interpolation is not offered; pruning (a count cut and an entropy
+ * threshold) and perplexity are the entries after these.
  * Input: tokens flat int32, offsets (n_sent + 1) int64 ascending from 0 to n_tokens; ids 0 = <unk> (never in the input), 1 = <s>,
  * 2 = </s>, tokens in [3, n_vocab).  N the order, 1 <= N <= 6.
  *  - framing: a sentence is its tokens between one <s> and one </s>; a sentence without tokens is skipped; no n-gram spans two;
@@ -897,6 +898,55 @@ int ds2_ngram_estimate_host(const int* tokens, long long n_tokens, const long lo
                             const double* fallback, const long long* cap, unsigned long long* const* keys_out, unsigned* const* count_out,
                             unsigned* const* adjusted_out, double* const* lp_out, double* const* bow_out, long long* n_distinct,
                             long long* coc, double* D, int* fell_back, double* unk_log10);
+
+/* Evaluation and pruning of such models (csrc/ngram_prune.h; restated in fp64 by tests/ngram_prune_oracle.py;
+ * asr_amd/decoders/lm_train.py: NgramEstimate.perplexity / .prune, prune_arpa).  The pruning rule is the project's own: parity with
+ * SRILM's -prune and with lmplz's --prune is not pinned (neither tool was at hand).  Interpolation of several models is not offered.
+ * The model M: per order n = 1..N, cnt[n-1] rows of keys (u64 as above, ASCENDING), lp (fp64 log10 p) and lb (fp64 log10 backoff,
+ * NaN where none is listed).  The 1-grams list <unk> (key 0) as an ordinary row when the model has one.  Ids: 0 <unk>, 1 <s>, 2 </s>.
+ *  - p_M(w | h), h of m <= N - 1 tokens: the listed (m+1)-gram h w, else backoff(h) * p_M(w | h[1:]), backoff(h) = 1 where h is not
+ *    listed or lists none; at m = 0 an unlisted w is OOV: reported, not scored.  Every lookup is a binary search, at most
+ *    log2(cnt) + 1 steps; no loop spins, no shift is by 64 (keys of N * b = 64 bits are legal), nothing is added with an atomic.
+ *  - ds2_ngram_eval: sentences as in ds2_ngram_count (flat int32 ids, n_sent + 1 int64 offsets), but EVERY sentence is scored, an
+ *    empty one as </s> after <s>, and ids may be 0.  Sentence s owns the positions off[s] + s .. off[s+1] + s of the outputs (its
+ *    tokens, then </s>), n_tokens + n_sent in all, one lane each: out_lp = log10 p_M(token | the N - 1 framed tokens before it), out_order
+ *    = the order of the n-gram that was listed; OOV (or an id outside [0, n_vocab)): order 0 and NaN.  An id outside [0, n_vocab) in
+ *    the context ends the context there.  Nothing is accumulated: the caller sums.
+ *  - pruning marks n-grams of order >= 2; for a listed h w of order n: p its listed probability, q = p_M(w | h[1:]),
+ *    sp(h) / sq(h) = the sums of p / q over the listed children of h, num = 1 - sp, den = 1 - sq, alpha = h's listed backoff or 1,
+ *    alpha' = (num + p) / (den + q), P(h) = prod_i p_M(h_i | h_1 .. h_{i-1}) with a leading <s> scored as p_M(</s>), and in natural
+ *    logarithms  dH = -P(h) (p (ln q + ln alpha' - ln p) + num (ln alpha' - ln alpha));  val = exp(dH) - 1; marked when val < theta
+ *    (Stolcke 1998: each n-gram judged as if it alone left its context).  An n-gram whose context is not listed has val NaN, unmarked.
+ *  - ds2_ngram_prune_sums, one call per order n = 2..N: sp and sq per row of order n - 1 (NaN: no child) and q per row of order n
+ *    (q_out may be null).  A lane per n-gram, a segmented scan over the wave in lane order, and for contexts whose children cross
+ *    waves a second launch over one partial per wave: the order of the additions depends on the keys alone, so equal arrays give
+ *    equal bits.  scratch: 4 doubles per 64 rows of order n.  The host twin adds each context's children in row order.
+ *  - ds2_ngram_prune_entropy, one launch over all orders >= 2: q, sp, sq, val, mark are `order` pointers, entry n - 1 for the n-grams
+ *    of order n (entry 0 unused; sp / sq of entry n - 1 have the rows of order n - 1); val fp64, mark one byte per row.
+ *  - ds2_ngram_prune_closure, one call per order n = N down to 3: a row of order n with mark 0 clears the mark of its context, so
+ *    every kept n-gram's prefix is kept and kept sets are nested in theta.
+ *  - ds2_ngram_prune_backoff, one call per order bottom up, on the KEPT rows: lb = log10((1 - sp) / (1 - sq)) from ds2_ngram_prune_sums
+ *    over the kept children and the model already finished below; NaN where sp is NaN (a context left without children).
+ * The *_host twins run the same per-entry routines serially from host arrays. */
+int ds2_ngram_eval(const int* tokens, long long n_tokens, const long long* offsets, long long n_sent, int n_vocab, int order,
+                   const long long* cnt, void* const* keys, void* const* lp, void* const* lb, double* out_lp, int* out_order, void* stream);
+int ds2_ngram_eval_host(const int* tokens, long long n_tokens, const long long* offsets, long long n_sent, int n_vocab, int order,
+                        const long long* cnt, void* const* keys, void* const* lp, void* const* lb, double* out_lp, int* out_order);
+int ds2_ngram_prune_sums(int n_vocab, int order, const long long* cnt, void* const* keys, void* const* lp, void* const* lb, int n,
+                         double* q_out, double* sp, double* sq, double* scratch, long long scratch_doubles, void* stream);
+int ds2_ngram_prune_sums_host(int n_vocab, int order, const long long* cnt, void* const* keys, void* const* lp, void* const* lb, int n,
+                              double* q_out, double* sp, double* sq);
+int ds2_ngram_prune_entropy(int n_vocab, int order, const long long* cnt, void* const* keys, void* const* lp, void* const* lb,
+                            void* const* q, void* const* sp, void* const* sq, double theta, void* const* val, void* const* mark,
+                            void* stream);
+int ds2_ngram_prune_entropy_host(int n_vocab, int order, const long long* cnt, void* const* keys, void* const* lp, void* const* lb,
+                                 void* const* q, void* const* sp, void* const* sq, double theta, void* const* val, void* const* mark);
+int ds2_ngram_prune_closure(int n_vocab, int order, const long long* cnt, void* const* keys, void* const* lp, void* const* lb, int n,
+                            const unsigned char* mark, unsigned char* mark_ctx, void* stream);
+int ds2_ngram_prune_closure_host(int n_vocab, int order, const long long* cnt, void* const* keys, void* const* lp, void* const* lb, int n,
+                                 const unsigned char* mark, unsigned char* mark_ctx);
+int ds2_ngram_prune_backoff(long long cnt, const double* sp, const double* sq, double* lb, void* stream);
+int ds2_ngram_prune_backoff_host(long long cnt, const double* sp, const double* sq, double* lb);
 
 /* The same search with hotword boosting: the caller names a few phrases and the search prefers prefixes that spell them, with or
  * without the LM above (asr_amd/decoders/hotwords.py builds the automaton; restated by tests/ctc_beam_hot_oracle.py).  Parity with
